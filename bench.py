@@ -7,15 +7,21 @@ pass from a synthetic 1080p frame pair, reference default uniforms (noise on), f
 One "step" = one Tendrils.step() = one pass of the integrator over every particle this rank
 holds.  State, flow and frames are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode exact|fast] [--config c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode exact|fast] [--config c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, W warm-up steps, the pre-roll, ONE timed repetition of exactly K steps, the
+job's counters, the JSON line.  `--full` adds everything else this docstring describes - five timed repetitions (`--reps`),
+the PMC child passes, the kernel-only roofline passes, the other arithmetic mode, the flow-only launches, the frame loop, the
+strong-scaling and config-4 / config-5 legs, the fixed costs and the CPU baseline.  `--dump-outputs DIR` writes what the timed
+path computed in its last step (rank 0's share: dump_outputs() below) - the same arguments give the same inputs in every run.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself: the parent - before it touches
 the GPU - runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child, relays rank 0's
 JSON line and exits with the child's status.  Under a launcher (WORLD_SIZE set) every process is one rank.
 
-Timed region: W warm-up steps, then an untimed clock pre-roll (>= 50 ms of the same launches,
+Timed region: W warm-up steps, then an untimed clock pre-roll (a fixed number of the same launches, sized for >= 60 ms,
 disclosed as `preroll_ms`: a GPU that has idled for a few ms runs its first launches ~10 %
-slower, profiles/r2_a_*), then `--reps` (5) repetitions of: barrier + synchronize, EXACTLY K steps,
+slower, profiles/r2_a_*), then `--reps` (1; 5 with --full) repetitions of: barrier + synchronize, EXACTLY K steps,
 barrier + synchronize (the barrier: the ranks of one node meeting in shared memory - benchlib/job.py NodeBarrier; `barrier` in the
 line says which); max over ranks per repetition; `value` / `ms_per_step` are the MEDIAN repetition
 (`repetitions` carries all of them and their spread).  Every timed repetition contains the path's
@@ -84,13 +90,56 @@ from benchlib.roofline import bind, roofline_entry  # noqa: E402
 from benchlib.sidelegs import SideLegs, Stages, comm_deadline  # noqa: E402
 from benchlib.workload import (BYTES_PER_PARTICLE_STEP, CONFIGS, HBM_PEAK_GBS, MAX_FUSED, synth_rows, synth_state)  # noqa: E402,F401
 
+DUMP_PARTICLES = 1 << 20            # --dump-outputs: a seeded sample of the state this many particles large (16 MB)
+DUMP_FLOW_TEXELS = 1 << 21          # ... and the flow field whole up to this many texels (32 MB; 1920 x 1080 is whole)
+
+
+def sample_index(total, k, seed):
+    """a fixed, seeded, sorted choice of k of `total` flat indices (all of them when there are no more)"""
+    if total <= k:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(total, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, job, rank):
+    """--dump-outputs: what a caller of the timed path holds after its last step - rank 0's share of the job (every rank takes
+    the counters' collective).  state.npy: ring buffer 0 in texel order (readPixels), RGBA float32 of DUMP_PARTICLES particles
+    at the flat texel indices state_index.npy holds (float64); flow.npy: the flow field the optical-flow refresh left (float32,
+    [h, w, 4], or a seeded sample of DUMP_FLOW_TEXELS texels); counters.npy: the job's counter block (float64, in th_counters
+    order).  Under 64 MB in all.  Reading the state puts the slots back in texel order (the library re-sorts when it next steps)."""
+    stats = job.global_stats()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    width, rows, t = job.width, job.rows, job.t
+    idx = sample_index(width * rows, DUMP_PARTICLES, 20240611)
+    state = np.empty((idx.size, 4), np.float32)
+    band = max(1, (1 << 22) // width)                   # (downloaded in row bands of <= 64 MB)
+    for r0 in range(0, rows, band):
+        r1 = min(rows, r0 + band)
+        lo, hi = np.searchsorted(idx, [r0 * width, r1 * width])
+        if lo == hi:
+            continue
+        buf = np.empty((r1 - r0, width, 4), np.float32)
+        job.capi.call("th_download_state", job.ctx, 0, buf.ctypes.data_as(job.capi._fp), 0, r0, width, r1 - r0)
+        state[lo:hi] = buf.reshape(-1, 4)[idx[lo:hi] - r0 * width]
+    flow = t.flow.read()
+    if flow.shape[0] * flow.shape[1] > DUMP_FLOW_TEXELS:
+        flow = flow.reshape(-1, 4)[sample_index(flow.shape[0] * flow.shape[1], DUMP_FLOW_TEXELS, 20240612)]
+    counters = np.array([stats[k] for k, _ in job.capi.Counters._fields_], np.float64)
+    for name, a in (("state", state), ("state_index", idx.astype(np.float64)), ("flow", flow), ("counters", counters)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=128)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step region (value = the median)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region (value = the median; default 1, 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the roofline passes, PMC children, other mode, flow-only "
+                                                         "launches, frame loop, strong-scaling / config-4 / config-5 legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--mode", default="exact", choices=["exact", "fast"])
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS), help="BASELINE.json config (default c3: the metric's)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
@@ -109,7 +158,7 @@ def main():
     ap.add_argument("--in-view", action="store_true", help="experiment: keep every particle inside the view (|y*viewSize.y| < 1)")
     ap.add_argument("--flow-only", action="store_true", help="noiseWeight = 0 (preset 'Flow Only') in the timed region")
     args = ap.parse_args()
-    args.reps = max(args.reps, 1)
+    args.reps = max(args.reps if args.reps is not None else (5 if args.full else 1), 1)
 
     if args.flow_size:
         W.FLOW_W, W.FLOW_H = (int(v) for v in args.flow_size.lower().split("x"))
@@ -133,7 +182,7 @@ def main():
 
     pmc, pmc_note = {}, "not measured"
     under_profiler = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
-    if rank == 0 and world == 1 and not args.no_traffic and not args.force_dist and not under_profiler and not args.pmc_child:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic and not args.force_dist and not under_profiler and not args.pmc_child:
         extra = ["--mode", args.mode, "--config", args.config, "--state", state_fmt] + \
                 (["--in-view"] if args.in_view else []) + (["--flow-size", args.flow_size] if args.flow_size else [])
         stages.at("PMC child passes (rocprofv3)")
@@ -182,39 +231,44 @@ def main():
     job.reductions = 0
     walls = job.timed_region(args.steps, args.reps)
     reductions_per_rep = job.reductions // args.reps
+    if args.dump_outputs:
+        stages.at("outputs of the last timed step")
+        dump_outputs(args.dump_outputs, job, rank)
 
-    # c4: the same K steps with the counters reduced after EVERY step (BASELINE.md config 4 names both cadences)
     walls_every_step = None
-    if args.config == "c4":
-        walls_every_step = job.timed_region(args.steps, max(args.reps // 2, 2), every=1, refresh=False)
-
-    stages.at("kernel-only passes (roofline)")
-    # kernel-only pass for the roofline: the same K steps in the same launches as the timed region, a HIP event
-    # pair around every launch on the context's own stream
-    run_kernel_only(2 * launch_len, launch_len)
-    k_ms, k_n = timed_kernels(lambda: run_kernel_only(args.steps, launch_len))
-    # and the single-step kernel (one Tendrils.step() per launch: what a step() + draw() frame loop runs)
-    def singles():
-        for _ in range(64):             # one whole re-sort period of the tile-sorted slot order
-            t.timer.tick()
-            t.step()
-    singles()
-    s_ms, s_n = timed_kernels(singles)
-    # the other arithmetic mode on the same fused launches (exact <-> fast; tolerance of fast mode: DESIGN.md 4)
+    k_ms = k_n = s_ms = o_ms = 0
     other_mode = "exact" if args.mode == "fast" else "fast"
-    _capi.call("th_set_mode", ctx, ta.TH_MODE_EXACT if other_mode == "exact" else ta.TH_MODE_FAST)
-    run_kernel_only(2 * launch_len, launch_len)
-    o_ms, o_n = timed_kernels(lambda: run_kernel_only(8 * launch_len, launch_len))
-    _capi.call("th_set_mode", ctx, ta.TH_MODE_FAST if args.mode == "fast" else ta.TH_MODE_EXACT)
-    sync_all()
+    if args.full:
+        # c4: the same K steps with the counters reduced after EVERY step (BASELINE.md config 4 names both cadences)
+        if args.config == "c4":
+            walls_every_step = job.timed_region(args.steps, max(args.reps // 2, 2), every=1, refresh=False)
 
-    stages.at("statistics, flow-only launches")
+        stages.at("kernel-only passes (roofline)")
+        # kernel-only pass for the roofline: the same K steps in the same launches as the timed region, a HIP event
+        # pair around every launch on the context's own stream
+        run_kernel_only(2 * launch_len, launch_len)
+        k_ms, k_n = timed_kernels(lambda: run_kernel_only(args.steps, launch_len))
+        # and the single-step kernel (one Tendrils.step() per launch: what a step() + draw() frame loop runs)
+        def singles():
+            for _ in range(64):             # one whole re-sort period of the tile-sorted slot order
+                t.timer.tick()
+                t.step()
+        singles()
+        s_ms, s_n = timed_kernels(singles)
+        # the other arithmetic mode on the same fused launches (exact <-> fast; tolerance of fast mode: DESIGN.md 4)
+        _capi.call("th_set_mode", ctx, ta.TH_MODE_EXACT if other_mode == "exact" else ta.TH_MODE_FAST)
+        run_kernel_only(2 * launch_len, launch_len)
+        o_ms, o_n = timed_kernels(lambda: run_kernel_only(8 * launch_len, launch_len))
+        _capi.call("th_set_mode", ctx, ta.TH_MODE_FAST if args.mode == "fast" else ta.TH_MODE_EXACT)
+        sync_all()
+
+    stages.at("statistics, flow-only launches" if args.full else "statistics")
     stats = job.global_stats()          # (local pass + the library's all-reduce: every rank holds the job's counters)
 
     # second uniform set of BASELINE.md 3: flow only (noiseWeight = 0), same launches, after everything else
     # (it changes the state: without the wander term velocities decay towards 0/0 = NaN, as in the reference)
     f_ms = f_n = fs_ms = flow_only_nan = 0
-    if not args.flow_only:
+    if args.full and not args.flow_only:
         keep = t.state["noiseWeight"]
         t.state["noiseWeight"] = 0
         # few launches, straight from the live state: without the wander term the velocities decay by 0.72 per step and
@@ -228,7 +282,8 @@ def main():
 
     stages.at("max over ranks")
     walls = job.max_over_ranks(walls)
-    kern_s, single_s = job.max_over_ranks([k_ms / 1e3, s_ms / 1e3])
+    if args.full:
+        kern_s, single_s = job.max_over_ranks([k_ms / 1e3, s_ms / 1e3])
     if walls_every_step is not None:
         walls_every_step = job.max_over_ranks(walls_every_step)
     wall = median(walls)
@@ -237,43 +292,46 @@ def main():
     packed = state_fmt == "f16"
     bytes_per_step = BYTES_PER_PARTICLE_STEP // (2 if packed else 1)
     value = particles * args.steps / wall
-    launches = max(int(k_n), 1)
-    steps_per_launch = args.steps / launches
-    fused = steps_per_launch > 1
 
-    def rl(launch_s, steps_in_launch, counters):
-        return roofline_entry(job, launch_s, steps_in_launch, counters, bytes_per_step)
+    roofline = None
+    if args.full:
+        launches = max(int(k_n), 1)
+        steps_per_launch = args.steps / launches
+        fused = steps_per_launch > 1
 
-    main_cls = "fused" if fused else "single"
-    if args.flow_only:
-        main_cls += "_flow_only"
-    head = bind(rl(kern_s, steps_per_launch, pmc.get(main_cls)), fused)
-    kernel_name = ("logic_fused_packed_kernel" if packed else "logic_fused_kernel") if fused else \
-        ("logic_packed_kernel" if packed else "logic_kernel")
-    roofline = {"kernel": kernel_name, "launches": launches,
-                "uniform_set": "flow only (noiseWeight = 0)" if args.flow_only else "default (simplex noise on)",
-                "achieved_is": "algorithmic bytes (SURVEY.md 8d: %d B per particle-step) / mean launch duration - an equivalent "
-                               "single-step bandwidth (hbm_equivalent_frac = equivalent_frac = achieved / peak); the fused launch streams "
-                               "48/n B per particle-step (hbm_physical) and runs out of VALU issue: `bound` / `frac` name THAT resource "
-                               "(`frac_is`)" % bytes_per_step,
-                "pmc_note": pmc_note}
-    # `bound` / `frac` are what bind() found - the resource the launch runs out of (VALU issue for a fused launch), never above 1;
-    # the contract's figure for the dominant kernel (algorithmic bytes / launch duration against the HBM peak) stands
-    # beside it under its own name: achieved / peak / hbm_equivalent_frac
-    head["hbm_equivalent_frac"] = head["equivalent_frac"]
-    roofline.update(head)
-    single = bind(rl(single_s, 1, pmc.get("single")), False)
-    single["kernel"] = "logic_packed_kernel" if packed else "logic_kernel over tile-sorted slots (gathered taps; every 64th launch re-sorts through logic_sorted_kernel)"
-    roofline["single_step_kernel"] = single
-    roofline["other_mode"] = {"mode": other_mode, "avg_launch_ms": o_ms, "steps_per_launch": launch_len,
-                              "achieved": bytes_per_step * particles_rank * launch_len / max(o_ms, 1e-9) / 1e6,
-                              "note": "fast mode is toleranced for ONE step only (DESIGN.md 4): not a headline"}
-    if f_n:
-        fo = bind(rl(f_ms / 1e3, launch_len, pmc.get("fused_flow_only" if launch_len > 1 else "single_flow_only")), launch_len > 1)
-        fo["uniform_set"] = "flow only (noiseWeight = 0)"
-        fo["single_step_kernel_ms"] = fs_ms
-        fo["nan_particles_after"] = flow_only_nan
-        roofline["flow_only"] = fo
+        def rl(launch_s, steps_in_launch, counters):
+            return roofline_entry(job, launch_s, steps_in_launch, counters, bytes_per_step)
+
+        main_cls = "fused" if fused else "single"
+        if args.flow_only:
+            main_cls += "_flow_only"
+        head = bind(rl(kern_s, steps_per_launch, pmc.get(main_cls)), fused)
+        kernel_name = ("logic_fused_packed_kernel" if packed else "logic_fused_kernel") if fused else \
+            ("logic_packed_kernel" if packed else "logic_kernel")
+        roofline = {"kernel": kernel_name, "launches": launches,
+                    "uniform_set": "flow only (noiseWeight = 0)" if args.flow_only else "default (simplex noise on)",
+                    "achieved_is": "algorithmic bytes (SURVEY.md 8d: %d B per particle-step) / mean launch duration - an equivalent "
+                                   "single-step bandwidth (hbm_equivalent_frac = equivalent_frac = achieved / peak); the fused launch streams "
+                                   "48/n B per particle-step (hbm_physical) and runs out of VALU issue: `bound` / `frac` name THAT resource "
+                                   "(`frac_is`)" % bytes_per_step,
+                    "pmc_note": pmc_note}
+        # `bound` / `frac` are what bind() found - the resource the launch runs out of (VALU issue for a fused launch), never above 1;
+        # the contract's figure for the dominant kernel (algorithmic bytes / launch duration against the HBM peak) stands
+        # beside it under its own name: achieved / peak / hbm_equivalent_frac
+        head["hbm_equivalent_frac"] = head["equivalent_frac"]
+        roofline.update(head)
+        single = bind(rl(single_s, 1, pmc.get("single")), False)
+        single["kernel"] = "logic_packed_kernel" if packed else "logic_kernel over tile-sorted slots (gathered taps; every 64th launch re-sorts through logic_sorted_kernel)"
+        roofline["single_step_kernel"] = single
+        roofline["other_mode"] = {"mode": other_mode, "avg_launch_ms": o_ms, "steps_per_launch": launch_len,
+                                  "achieved": bytes_per_step * particles_rank * launch_len / max(o_ms, 1e-9) / 1e6,
+                                  "note": "fast mode is toleranced for ONE step only (DESIGN.md 4): not a headline"}
+        if f_n:
+            fo = bind(rl(f_ms / 1e3, launch_len, pmc.get("fused_flow_only" if launch_len > 1 else "single_flow_only")), launch_len > 1)
+            fo["uniform_set"] = "flow only (noiseWeight = 0)"
+            fo["single_step_kernel_ms"] = fs_ms
+            fo["nan_particles_after"] = flow_only_nan
+            roofline["flow_only"] = fo
 
     storage = "packed 8-B (SNORM16 pos + fp16 vel)" if packed else "RGBA32F"
     line = {
@@ -292,7 +350,7 @@ def main():
                                  "(+ the library's RCCL all-reduce of the counters) after every launch" % launch_len,
                    "mode": args.mode, "state_storage": state_fmt, "particles_per_gpu": particles_rank,
                    "parallelism": "row-band shard x%d, flow replicated" % world},
-        "roofline": roofline,
+        **({"roofline": roofline} if args.full else {}),
         "rccl": job.rccl_block(stats, reductions_per_rep),
         "counters": stats,
         "barrier": job.barrier.kind if job.barrier is not None else "none (one rank)",
@@ -302,7 +360,7 @@ def main():
         line["counters_every_step"] = {"value": particles * args.steps / wes, "ms_per_step": wes / args.steps * 1e3,
                                        "note": "same K steps, one launch and one counter reduction per step"}
 
-    if cfg["scaling"] == "strong":
+    if args.full and cfg["scaling"] == "strong":
         # what a launch group costs beside its kernel: the part of a strong-scaling point that does not shrink with the band
         from benchlib.legs import fixed_costs, short_frame_loop
         try:
@@ -317,20 +375,21 @@ def main():
 
     # (the side legs must not cost the line: whatever goes wrong in them is reported in their place, and one that never comes
     # back - a collective some rank does not reach - ends the job with the line as it stands: benchlib/sidelegs.py)
-    stages.at("side legs")
+    stages.at("side legs" if args.full else "shutdown")
     stages.done()                       # (the headline stands: from here on every leg has its own deadline)
     legs = SideLegs(line, rank)
     c3 = args.config == "c3"
-    want_c3s = c3 and not args.no_c3_strong and not args.flow_size and not under_profiler
-    want_c4 = c3 and not args.no_c4 and not args.flow_size and not under_profiler
-    want_c5 = c3 and not args.no_c5 and not args.flow_size and not under_profiler
+    full_c3 = args.full and c3
+    want_c3s = full_c3 and not args.no_c3_strong and not args.flow_size and not under_profiler
+    want_c4 = full_c3 and not args.no_c4 and not args.flow_size and not under_profiler
+    want_c5 = full_c3 and not args.no_c5 and not args.flow_size and not under_profiler
     after = (["c3_strong"] if want_c3s else []) + (["c4"] if want_c4 else []) + (["c5"] if want_c5 else [])
-    if world == 1 and c3 and not args.no_frame_loop:
+    if world == 1 and full_c3 and not args.no_frame_loop:
         legs.run("frame_loop", lambda: frame_loop(t, ctx, synth_state(rank)), after)
-    if (world > 1 or args.force_dist) and c3 and not args.no_frame_loop:
+    if (world > 1 or args.force_dist) and full_c3 and not args.no_frame_loop:
         # (collective: every rank runs it; a rank-local failure inside th_draw_sharded ends the draw on every rank - th_shard.hip)
         legs.run("frame_loop_sharded", lambda: frame_loop_sharded(job), after)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             line["cpu_baseline"] = cpu_baseline(t, width, min(rows, W.N))
         except Exception as e:            # noqa: BLE001
@@ -339,14 +398,14 @@ def main():
     job.dispose()
     if want_c3s:
         legs.run("c3_strong", lambda: c3_strong_leg(args, rank, local_rank, world, dist), after[1:])
-    if under_profiler and c3 and not args.no_c4:
+    if under_profiler and full_c3 and not args.no_c4:
         # (a kernel-trace of this command should average the headline's launches, not mix them with config 4's)
         line["c4"] = {"skipped": "under a profiler: run without it (or --config c4) for the config-4 leg"}
     elif want_c4:
         # (every rank takes part; the leg runs the same code path as the headline, so what it can still fail on - memory -
         # fails on every rank alike)
         legs.run("c4", lambda: c4_leg(args, rank, local_rank, world, dist), ["c5"] if want_c5 else [])
-    if under_profiler and c3 and not args.no_c5:
+    if under_profiler and full_c3 and not args.no_c5:
         line["c5"] = {"skipped": "under a profiler: run without it (or --config c5) for the config-5 leg"}
     elif want_c5:
         legs.run("c5", lambda: c5_leg(args, rank, local_rank, world, dist))
@@ -363,7 +422,6 @@ def main():
         except OSError:
             pass
         print(json.dumps(line), flush=True)
-
 
 if __name__ == "__main__":
     main()

@@ -1,11 +1,12 @@
 """One rank's share of a configuration and the timed region of bench.py."""
 import ctypes as C
+import math
 import time
 
 import numpy as np
 
 from . import workload as W
-from .workload import CONFIGS, PREROLL_MS, synth_flow, synth_frames, synth_rows, synth_state
+from .workload import CONFIGS, PREROLL_MS, PREROLL_RATE, synth_flow, synth_frames, synth_rows, synth_state
 
 
 def median(xs):
@@ -270,13 +271,11 @@ class Job:
         return ms.value, n.value
 
     def preroll(self):
-        """clock pre-roll: the launches of the timed region, untimed, until >= PREROLL_MS have run on the device"""
+        """clock pre-roll: the launches of the timed region, untimed - a fixed number of them, sized by PREROLL_RATE for >= PREROLL_MS
+        on the device (a count taken from a clock would step the state a different number of times in every run)"""
         self.sync_all()
-        p0 = time.perf_counter()
-        self.run_kernel_only(self.launch_len, self.launch_len)
-        self.sync_all()
-        est = max(time.perf_counter() - p0, 1e-4)
-        pre_launches = int(min(max(PREROLL_MS * 1e-3 / est, 1), 4096))
+        per_launch = self.particles_rank * self.launch_len / PREROLL_RATE
+        pre_launches = int(min(max(math.ceil(PREROLL_MS * 1e-3 / per_launch), 1), 4096))
         p0 = time.perf_counter()
         self.run_kernel_only(pre_launches * self.launch_len, self.launch_len)
         self.sync_all()

@@ -110,6 +110,11 @@ def dry_run(args, rank, world):
         run(args.steps)
         barrier()
         walls.append(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:                    # (rank 0's band after the last timed step, and the job's counters)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "state.npy"), state["band"].reshape(-1, 4))
+        np.save(os.path.join(args.dump_outputs, "counters.npy"), np.array([float(state["red"][k]) for k in
+                ("particles", "live", "nan", "capped", "respawned", "sum_speed", "max_speed")], np.float64))
     v = torch.tensor(walls, dtype=torch.float64)
     dist.all_reduce(v, op=dist.ReduceOp.MAX)
     walls = [float(x) for x in v]
@@ -136,9 +141,10 @@ def dry_run(args, rank, world):
                 time.sleep(1e6)
             return fn()
         return body
-    legs.run("c3_strong", leg("c3_strong", lambda: dry_strong(args, rank, world, dist, O, packed=False)), ["c5", "frame_loop_sharded"])
-    legs.run("c5", leg("c5", lambda: dry_strong(args, rank, world, dist, O, packed=True)), ["frame_loop_sharded"])
-    legs.run("frame_loop_sharded", leg("frame_loop_sharded", lambda: dry_frame_loop_sharded(rank, world, dist, O, state["band"], fl, row0, gheight)))
+    if args.full:                                          # (the legs of a --full run; a plain run ends with its headline)
+        legs.run("c3_strong", leg("c3_strong", lambda: dry_strong(args, rank, world, dist, O, packed=False)), ["c5", "frame_loop_sharded"])
+        legs.run("c5", leg("c5", lambda: dry_strong(args, rank, world, dist, O, packed=True)), ["frame_loop_sharded"])
+        legs.run("frame_loop_sharded", leg("frame_loop_sharded", lambda: dry_frame_loop_sharded(rank, world, dist, O, state["band"], fl, row0, gheight)))
 
     def finish():
         dist.barrier()

@@ -13,6 +13,7 @@ HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
 VALU_PEAK = 256 * 4 * 2.4e9 / 2     # wave64 VALU instructions per second: 2 cycles each on a SIMD-32
 MAX_FUSED = 32                  # th::kMaxFusedSteps
 PREROLL_MS = 60.0
+PREROLL_RATE = 2.5e11          # particle-steps/s the pre-roll's launch count is sized by: above every rate measured on MI355X
 
 CONFIGS = {
     # name: (width, global height as a function of world, rows per rank, state, steps per group, scaling)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_self_launch_two_ranks_dry_run(oracle):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "6", "--warmup", "2",
-                        "--reps", "3"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--reps", "3", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout                      # rank 0's line, relayed by the parent, and nothing else
@@ -47,6 +47,31 @@ def test_a_rank_without_shared_memory_sends_every_rank_to_the_torch_barrier(orac
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert line["barrier"] == "torch.distributed barrier" and line["value"] > 0 and line["legs_failed"] == []
+
+
+def test_plain_run_times_its_steps_once_and_dumps_the_same_outputs_every_time(oracle, tmp_path):
+    """A plain run (no --full) is the headline alone: ONE repetition of exactly --steps steps and no side legs; --dump-outputs
+    writes what the timed path left after its last step, and the same arguments give the same arrays in every run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "5", "--warmup", "1",
+                            "--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 5 and line["repetitions"]["n"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert not {"c3_strong", "c4", "c5", "frame_loop_sharded"} & set(line) and line["legs_failed"] == []
+        arrays = {p.name: np.load(p) for p in sorted(out.iterdir())}
+        assert set(arrays) == {"state.npy", "counters.npy"}
+        assert arrays["state.npy"].dtype == np.float32 and arrays["state.npy"].shape == (48 * 48, 4)
+        assert arrays["counters.npy"].dtype == np.float64 and arrays["counters.npy"][0] == 2 * 48 * 48
+        got.append(arrays)
+    for name in got[0]:
+        assert got[0][name].tobytes() == got[1][name].tobytes(), name
 
 
 def test_child_failure_is_the_parents_status():
@@ -85,7 +110,7 @@ def test_a_leg_that_never_comes_back_does_not_cost_the_line(oracle):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TH_BENCH_TEST_HANG="c5:1", TH_BENCH_LEG_TIMEOUT="8")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1",
-                        "--reps", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--reps", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -104,7 +129,7 @@ def test_a_communicator_that_never_comes_up_ends_in_a_fresh_child_with_the_line(
     env.update(TH_BENCH_TEST_HANG="comm_init:1", TH_BENCH_COMM_TIMEOUT="6", TH_BENCH_TIMEOUT="400")
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "4", "--warmup", "1",
-                        "--reps", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--reps", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert time.time() - t0 < 300
     lines = [l for l in r.stdout.splitlines() if l.strip()]

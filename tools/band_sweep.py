@@ -2,7 +2,7 @@
 """What an 8-GPU strong-scaling run of the metric's 16 M particles is made of, measured on ONE GPU.
 
 For the per-GPU share each point of the 1 / 2 / 4 / 8 curve implies - 4096, 2048, 1024, 512 rows of the 4096-wide texture -
-run the bench's own timed region (`bench.py --config c3_strong --pretend-world P --force-dist`: the driver's K and W, the
+run the bench's own timed region (`bench.py --config c3_strong --pretend-world P --force-dist --full`: the driver's K and W, the
 library's RCCL communicator up at world 1, statistics fold + counter all-reduce after every launch) and print, per point:
 particle-steps/s of the band, the wall per step, the integrator launch, and what a launch group costs beside its kernel
 (host enqueue, statistics fold, all-reduce enqueue-to-done).  The ratio of a band's rate x P to the whole texture's rate is
@@ -29,7 +29,7 @@ def main():
     rows, base = [], None
     for p in (int(v) for v in args.worlds.split(",")):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c3_strong", "--pretend-world", str(p), "--force-dist",
-               "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu", "--no-traffic", "--no-frame-loop"] + extra
+               "--steps", str(args.steps), "--warmup", str(args.warmup), "--full", "--no-cpu", "--no-traffic", "--no-frame-loop"] + extra
         env = dict(os.environ, MASTER_PORT=str(29600 + p))
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         line = None

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_${1:-r6}
 rm -rf $OUT; mkdir -p $OUT
-ARGS="--gpus 1 --steps 20 --warmup 5 --no-cpu --no-traffic"
+ARGS="--gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-traffic"
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/trace.log 2>&1
 run_pmc () { name=$1; shift; timeout 300 rocprofv3 --pmc $* --kernel-trace --output-format csv -d $OUT/pmc_$name -- python3 $ROOT/bench.py $ARGS > $OUT/pmc_$name.log 2>&1 || echo "pmc $name failed"; }
@@ -20,8 +20,8 @@ run_pmc ea TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum T
 run_pmc grbm GRBM_GUI_ACTIVE GRBM_COUNT
 cd $ROOT
 python3 tools/summarize_pmc.py $OUT > $OUT/summary.txt 2>&1
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2>$OUT/bench_driver.err
-timeout 900 python3 bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2>$OUT/bench_driver.err
+timeout 900 python3 bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err
 head -30 $OUT/summary.txt
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/draw_both_trace -- python3 $ROOT/tools/deposit_bench.py 40 --both > $OUT/draw_both_trace.log 2>&1
