@@ -60,8 +60,9 @@ struct th_options {
 
 // One captured th_step_n sequence (see th_step_n).
 struct GraphEntry {
-    int32_t n = 0, mode = 0;
-    uint32_t flags = 0;
+    int32_t n = 0;
+    th::LogicVariant variant{};          // the kernels the sequence launches
+    bool generic = false;
     std::vector<float4 *> ring;          // ring order at capture time
     th::LogicParams key{};               // launch parameters (the fields same_key() compares)
     hipGraphExec_t exec = nullptr;

@@ -60,77 +60,80 @@ int hash_table_vectors() { return kHashVec; }
 
 
 
+// The two formats of a state ring as the integrator loops see them: a Word per texel in memory, the decoded float4 in
+// registers, and what the ring holds of a state (`quantize`: the state a fused step hands the next one).
+struct F32Texel {                   // RGBA32F, 16 B per texel
+    using Word = float4;
+    static constexpr bool packed = false;
+    TH_D static Word empty() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    TH_D static Word load(const float4 *buf, uint32_t i) { return load_stream(&buf[i]); }
+    TH_D static void store(float4 *buf, uint32_t i, Word w) { store_stream(&buf[i], w); }
+    TH_D static float4 decode(Word w) { return w; }
+    TH_D static Word encode(float4 s) { return s; }
+    TH_D static float4 quantize(float4 s) { return s; }
+};
+struct PackedTexel {                // TH_STATE_F16, 8 B per texel (th_logic.hpp: pack_state)
+    using Word = v2u;
+    static constexpr bool packed = true;
+    TH_D static Word empty() { return Word{0x80008000u, 0u}; }
+    TH_D static Word load(const float4 *buf, uint32_t i) { return __builtin_nontemporal_load(&reinterpret_cast<const v2u *>(buf)[i]); }
+    TH_D static void store(float4 *buf, uint32_t i, Word w) { __builtin_nontemporal_store(w, &reinterpret_cast<v2u *>(buf)[i]); }
+    TH_D static float4 decode(Word w) { return unpack_state(make_uint2(w.x, w.y)); }
+    TH_D static Word encode(float4 s) { const uint2 q = pack_state(s); return Word{q.x, q.y}; }
+    TH_D static float4 quantize(float4 s) { return quantize_state(s); }
+};
+
+// The integrator loops are written once for both formats and expanded into the body of every kernel that runs them.  They are
+// macros, not __device__ functions: hipcc optimises a function on its own before it inlines it, and a kernel that calls its
+// loop comes out scheduled otherwise than one that holds it (commuted operands, other registers; fused kernels with more
+// VGPRs).  The kernel's template parameters and `p` are in scope.
+
 // Plain grid-stride, the next state texel of each lane prefetched one iteration ahead.  Slots are in texel order (slot ==
 // particle id) or - p.perm - in a tile-sorted order (the particle of slot s is perm[s]): a wave's taps then fall into
 // one neighbourhood of the decoded field, and the gather costs what a staged window would.  The hash
-// stages of the noise run through the LDS tables of the fused kernel.
+// stages of the noise run through the LDS tables of the fused kernel.  PTAB (sorted slots, with NOISE): hash stages from
+// LDS tables.  In texel order the pass waits for its random taps, not for arithmetic, and the tables' LDS traffic only
+// costs (0.188 vs 0.197 ms at C3).  `time`: captured-graph replays keep it in device memory.  LogicParams::seen (a frame
+// loop; uniform): a line is hidden for sure when both its ends lie beyond one edge (a NaN compares false: seen).
+#define TH_LOGIC_PLAIN_LOOP(Fmt)                                                                                              \
+    const float time = p.time_dev ? *p.time_dev : p.u.time;                                                                   \
+    __shared__ float4 smem[NOISE ? (PTAB ? kHashVec : 0) + kLutSize : 1];                                                     \
+    const float4 *lut = smem + (NOISE && PTAB ? kHashVec : 0);                                                                \
+    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};       \
+    if constexpr (NOISE) {                                                                                                    \
+        if constexpr (PTAB) fill_hash_tables(smem, p.lut);                                                                    \
+        else for (int k = threadIdx.x; k < kLutSize; k += 256) smem[k] = p.lut[k];                                            \
+        __syncthreads();                                                                                                      \
+    }                                                                                                                         \
+    const uint32_t stride = gridDim.x * 256u, end = p.count;                                                                  \
+    uint32_t idx = blockIdx.x * 256u + threadIdx.x;                                                                           \
+    typename Fmt::Word nxt = Fmt::empty();                                                                                    \
+    const uint32_t *perm = p.perm;                                                                                            \
+    uint32_t pnxt = idx;                                                                                                      \
+    if (idx < end) { nxt = Fmt::load(p.in, idx); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx]); }                   \
+    for (; idx < end; idx += stride) {                                                                                        \
+        const typename Fmt::Word w = nxt;                                                                                     \
+        const uint32_t pid = perm ? pnxt : idx;                                                                               \
+        if (idx + stride < end) { nxt = Fmt::load(p.in, idx + stride); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx + stride]); } \
+        const float4 st = Fmt::decode(w);                                                                                     \
+        const float4 r = integrate<FAST, NOISE, TARGET, POW2, DECODED, NOISE && PTAB>(p, lut, st, pid, time, &tabs);          \
+        Fmt::store(p.out, idx, Fmt::encode(r));                                                                               \
+        if constexpr (!Fmt::packed) {                                                                                         \
+            if (p.seen) {                                                                                                     \
+                const bool hidden = (st.x < p.seen_xlo && r.x < p.seen_xlo) || (st.x > p.seen_xhi && r.x > p.seen_xhi) ||     \
+                                    (st.y < p.seen_ylo && r.y < p.seen_ylo) || (st.y > p.seen_yhi && r.y > p.seen_yhi);       \
+                const unsigned long long any = __ballot(!hidden);                                                             \
+                if (__lane_id() == (uint32_t)__builtin_ctzll(__ballot(true))) p.seen[idx >> 6] = any ? 1u : 0u;               \
+            }                                                                                                                 \
+        }                                                                                                                     \
+    }
+
 template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB>
-__global__ __launch_bounds__(256) void logic_kernel(const LogicParams p)
-{
-    const float time = p.time_dev ? *p.time_dev : p.u.time;     // captured-graph replays keep `time` in device memory
-    // PTAB (sorted slots): hash stages from LDS tables.  In texel order the pass waits for its random taps, not for
-    // arithmetic, and the tables' LDS traffic only costs (0.188 vs 0.197 ms at C3)
-    __shared__ float4 smem[NOISE ? (PTAB ? kHashVec : 0) + kLutSize : 1];
-    const float4 *lut = smem + (NOISE && PTAB ? kHashVec : 0);
-    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};
-    if constexpr (NOISE) {
-        if constexpr (PTAB) fill_hash_tables(smem, p.lut);
-        else for (int k = threadIdx.x; k < kLutSize; k += 256) smem[k] = p.lut[k];
-        __syncthreads();
-    }
-    const uint32_t stride = gridDim.x * 256u, end = p.count;
-    uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    float4 nxt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const uint32_t *perm = p.perm;
-    uint32_t pnxt = idx;
-    if (idx < end) { nxt = load_stream(&p.in[idx]); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx]); }
-    for (; idx < end; idx += stride) {
-        float4 st = nxt;
-        const uint32_t pid = perm ? pnxt : idx;
-        if (idx + stride < end) { nxt = load_stream(&p.in[idx + stride]); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx + stride]); }
-        const float4 r = integrate<FAST, NOISE, TARGET, POW2, DECODED, NOISE && PTAB>(p, lut, st, pid, time, &tabs);
-        store_stream(&p.out[idx], r);
-        if (p.seen) {           // (uniform; a frame loop: LogicParams::seen)
-            // hidden for sure: both ends beyond one edge (a NaN compares false: seen)
-            const bool hidden = (st.x < p.seen_xlo && r.x < p.seen_xlo) || (st.x > p.seen_xhi && r.x > p.seen_xhi) ||
-                                (st.y < p.seen_ylo && r.y < p.seen_ylo) || (st.y > p.seen_yhi && r.y > p.seen_yhi);
-            const unsigned long long any = __ballot(!hidden);
-            if (__lane_id() == (uint32_t)__builtin_ctzll(__ballot(true))) p.seen[idx >> 6] = any ? 1u : 0u;
-        }
-    }
-}
+__global__ __launch_bounds__(256) void logic_kernel(const LogicParams p) { TH_LOGIC_PLAIN_LOOP(F32Texel) }
 
 // Packed-state integrator (TH_STATE_F16): same per-particle arithmetic on the decoded texel, 8 B in / 8 B out.
 template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB>
-__global__ __launch_bounds__(256) void logic_packed_kernel(const LogicParams p)
-{
-    const float time = p.time_dev ? *p.time_dev : p.u.time;
-    __shared__ float4 smem[NOISE ? (PTAB ? kHashVec : 0) + kLutSize : 1];      // (PTAB: sorted slots, as logic_kernel)
-    const float4 *lut = smem + (NOISE && PTAB ? kHashVec : 0);
-    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};
-    if constexpr (NOISE) {
-        if constexpr (PTAB) fill_hash_tables(smem, p.lut);
-        else for (int k = threadIdx.x; k < kLutSize; k += 256) smem[k] = p.lut[k];
-        __syncthreads();
-    }
-    const v2u *in = reinterpret_cast<const v2u *>(p.in);
-    v2u *out = reinterpret_cast<v2u *>(p.out);
-    const uint32_t stride = gridDim.x * 256u;
-    uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    v2u nxt = {0x80008000u, 0u};
-    const uint32_t *perm = p.perm;          // tile-sorted slots: the particle of slot s is perm[s] (as logic_kernel)
-    uint32_t pnxt = idx;
-    if (idx < p.count) { nxt = __builtin_nontemporal_load(&in[idx]); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx]); }
-    for (; idx < p.count; idx += stride) {
-        v2u w = nxt;
-        const uint32_t pid = perm ? pnxt : idx;
-        if (idx + stride < p.count) { nxt = __builtin_nontemporal_load(&in[idx + stride]); if (perm) pnxt = __builtin_nontemporal_load(&perm[idx + stride]); }
-        float4 r = integrate<FAST, NOISE, TARGET, POW2, DECODED, NOISE && PTAB>(p, lut, unpack_state(make_uint2(w.x, w.y)), pid, time, &tabs);
-        uint2 q = pack_state(r);
-        v2u qq = {q.x, q.y};
-        __builtin_nontemporal_store(qq, &out[idx]);
-    }
-}
+__global__ __launch_bounds__(256) void logic_packed_kernel(const LogicParams p) { TH_LOGIC_PLAIN_LOOP(PackedTexel) }
 
 // Generic kernel: reference-order evaluation of every texel (used when the host
 // cannot establish the fast path's preconditions, e.g. non-finite uniforms).
@@ -145,51 +148,34 @@ __global__ __launch_bounds__(256) void logic_generic_kernel(const LogicParams p)
     }
 }
 
-template <bool FAST, bool NOISE, bool TARGET>
-static void launch_logic_p2(const LogicParams &p, bool pow2, bool decoded, hipStream_t s)
+// Runtime flags as template arguments: lift(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).
+// Every combination of the flags is instantiated: pass only flags that act (LogicVariant, launch_logic's PTAB).
+template <class F>
+static void lift(F &&f) { f(); }
+template <class F, class... R>
+static void lift(F &&f, bool b, R... rest)
 {
-    // 7 workgroups per CU are resident: 2048 workgroups (8 per CU) ran as 1792 + a second round of 256; 20 per CU ends evenly
-    const int grid = grid_for(p.count, 20);
-#define TH_GO(P2, DEC) do { if (p.perm) hipLaunchKernelGGL((logic_kernel<FAST, NOISE, TARGET, P2, DEC, true>), dim3(grid), dim3(256), 0, s, p); \
-                            else hipLaunchKernelGGL((logic_kernel<FAST, NOISE, TARGET, P2, DEC, false>), dim3(grid), dim3(256), 0, s, p); } while (0)
-    if (pow2) { if (decoded) TH_GO(true, true); else TH_GO(true, false); }
-    else { if (decoded) TH_GO(false, true); else TH_GO(false, false); }
-#undef TH_GO
+    if (b) lift([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else lift([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-template <bool FAST, bool NOISE, bool TARGET>
-static void launch_packed_p2(const LogicParams &p, bool pow2, bool decoded, hipStream_t s)
+void launch_logic(const LogicParams &p, const LogicVariant &v, hipStream_t s)
 {
-    // 64 VGPRs in texel order (8 workgroups per CU resident: a grid of 8 per CU), 68 with the hash tables over sorted slots (7)
-    int grid = grid_for(p.count, p.perm ? 20 : 8);
-#define TH_GO(P2, DEC) do { if (p.perm) hipLaunchKernelGGL((logic_packed_kernel<FAST, NOISE, TARGET, P2, DEC, true>), dim3(grid), dim3(256), 0, s, p); \
-                            else hipLaunchKernelGGL((logic_packed_kernel<FAST, NOISE, TARGET, P2, DEC, false>), dim3(grid), dim3(256), 0, s, p); } while (0)
-    if (pow2) { if (decoded) TH_GO(true, true); else TH_GO(true, false); }
-    else { if (decoded) TH_GO(false, true); else TH_GO(false, false); }
-#undef TH_GO
+    const bool packed = v.format == StateFormat::packed;
+    // f32: 7 workgroups per CU are resident: 2048 workgroups (8 per CU) ran as 1792 + a second round of 256; 20 per CU ends
+    // evenly.  packed: 64 VGPRs in texel order (8 workgroups per CU resident: a grid of 8 per CU), 68 with the hash tables
+    // over sorted slots (7)
+    const int grid = packed ? grid_for(p.count, p.perm ? 20 : 8) : grid_for(p.count, 20);
+    lift([&](auto fast, auto noise, auto target, auto pow2, auto decoded, auto perm) {
+        constexpr bool ptab = noise && perm;            // (PTAB acts under NOISE only)
+        hipLaunchKernelGGL((packed ? logic_packed_kernel<fast, noise, target, pow2, decoded, ptab>
+                                   : logic_kernel<fast, noise, target, pow2, decoded, ptab>), dim3(grid), dim3(256), 0, s, p);
+    }, v.mode == TH_MODE_FAST, v.noise, v.target, v.pow2, v.decoded, p.perm != nullptr);
 }
 
-void launch_logic(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool decoded,
-                  bool generic, bool packed, hipStream_t s)
+void launch_logic_generic(const LogicParams &p, hipStream_t s)
 {
-    if (generic) {          // texel-order f32 only (the host unpacks around it)
-        hipLaunchKernelGGL(logic_generic_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
-        return;
-    }
-    const bool fast = mode == TH_MODE_FAST;
-#define TH_DISPATCH(F, N, T)                                             \
-    do {                                                                 \
-        if (packed) launch_packed_p2<F, N, T>(p, pow2, decoded, s);      \
-        else launch_logic_p2<F, N, T>(p, pow2, decoded, s);              \
-    } while (0)
-    if (fast) {
-        if (noise) { if (target) TH_DISPATCH(true, true, true); else TH_DISPATCH(true, true, false); }
-        else { if (target) TH_DISPATCH(true, false, true); else TH_DISPATCH(true, false, false); }
-    } else {
-        if (noise) { if (target) TH_DISPATCH(false, true, true); else TH_DISPATCH(false, true, false); }
-        else { if (target) TH_DISPATCH(false, false, true); else TH_DISPATCH(false, false, false); }
-    }
-#undef TH_DISPATCH
+    hipLaunchKernelGGL(logic_generic_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
 }
 
 // ---------------------------------------------------------------------------
@@ -203,8 +189,6 @@ void launch_logic(const LogicParams &p, int mode, bool noise, bool target, bool 
 // The flow tap reads the RGBA32F texel and decodes per particle (one decoded plane per step time
 // would multiply the gather footprint by nsteps).
 // ---------------------------------------------------------------------------
-constexpr bool kFusedPermTable = true;      // hash stages through the LDS tables (snoise_corners_tab)
-
 // The statistics of th_stats (stats_kernel below: same classification, same arithmetic per particle) taken by the launch that
 // has the state in registers: a lane's share, then one StatsPartial per workgroup (plain store; folded in a fixed order by
 // launch_stats_fold) - instead of a pass that reads the whole state again (268 MB at C3).
@@ -247,113 +231,68 @@ TH_D void stats_none(StatsPartial *slot, bool first)
     if (__ballot(!first) == 0ull && __lane_id() == 0u) *slot = StatsPartial{0ull, 0ull, 0ull, 0.0, 0.0};
 }
 
-template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS>
-__global__ __launch_bounds__(256) void logic_fused_kernel(const LogicParams p)
-{
-    // one LDS block: [permA | permB | gradient table], the hash tables first so that their reads need no base offset
-    __shared__ float4 smem[NOISE ? kHashVec + kLutSize : 1];
-    const float4 *lut = smem + (NOISE ? kHashVec : 0);
-    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};
-    if constexpr (NOISE) {
-        fill_hash_tables(smem, p.lut);
-        __syncthreads();
-    }
-    uint32_t idx, stride, end;
-    if constexpr (!BUCKETED) {
-        idx = blockIdx.x * 256u + threadIdx.x;
-        stride = gridDim.x * 256u;
-        end = p.count;
-    } else {
-        const uint32_t group = blockIdx.x & 7u, rank = blockIdx.x >> 3, per = (p.count + 7u) >> 3;
-        const uint32_t lo = group * per;
-        idx = lo + rank * 256u + threadIdx.x;
-        stride = (gridDim.x >> 3) * 256u;
-        end = lo + per < p.count ? lo + per : p.count;
-    }
-    float4 nxt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    uint32_t npid = idx;
-    [[maybe_unused]] bool first = true;
-    if (idx < end) {
-        nxt = load_stream(&p.in[idx]);
-        if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx]);
-    }
-    for (; idx < end; idx += stride) {
-        float4 st = nxt, prev = nxt;
-        uint32_t pid = BUCKETED ? npid : idx;
-        if (idx + stride < end) {
-            nxt = load_stream(&p.in[idx + stride]);
-            if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx + stride]);
-        }
-        for (uint32_t k = 0; k < p.nsteps; ++k) {
-            prev = st;
-            st = integrate<FAST, NOISE, TARGET, POW2, false, kFusedPermTable>(p, lut, st, pid, p.times[k], &tabs);
-        }
-        store_stream(&p.out_prev[idx], prev);
-        store_stream(&p.out[idx], st);
-        if constexpr (STATS) { stats_take(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], st, p.u.speedLimit, first); first = false; }
-    }
+// The fused loop.  One LDS block: [permA | permB | gradient table], the hash tables first so that their reads need no base
+// offset.  BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step (to
+// out_prev): f32 carries it along, a register copy per step; a packed ring makes its words at once at the last step (carried
+// through the loop as four more floats the kernel had 101 VGPRs - four waves per SIMD instead of five), and after one step
+// it is the word that came in, whatever that decodes to.  The statistics of a packed ring are those of what its texels
+// decode to - what th_stats reads through its f32 view.
+#define TH_LOGIC_FUSED_LOOP(Fmt)                                                                                              \
+    __shared__ float4 smem[NOISE ? kHashVec + kLutSize : 1];                                                                  \
+    const float4 *lut = smem + (NOISE ? kHashVec : 0);                                                                        \
+    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};       \
+    if constexpr (NOISE) {                                                                                                    \
+        fill_hash_tables(smem, p.lut);                                                                                        \
+        __syncthreads();                                                                                                      \
+    }                                                                                                                         \
+    uint32_t idx, stride, end;                                                                                                \
+    if constexpr (!BUCKETED) {                                                                                                \
+        idx = blockIdx.x * 256u + threadIdx.x;                                                                                \
+        stride = gridDim.x * 256u;                                                                                            \
+        end = p.count;                                                                                                        \
+    } else {                                                                                                                  \
+        const uint32_t group = blockIdx.x & 7u, rank = blockIdx.x >> 3, per = (p.count + 7u) >> 3;                            \
+        const uint32_t lo = group * per;                                                                                      \
+        idx = lo + rank * 256u + threadIdx.x;                                                                                 \
+        stride = (gridDim.x >> 3) * 256u;                                                                                     \
+        end = lo + per < p.count ? lo + per : p.count;                                                                        \
+    }                                                                                                                         \
+    typename Fmt::Word nxt = Fmt::empty();                                                                                    \
+    uint32_t npid = idx;                                                                                                      \
+    [[maybe_unused]] bool first = true;                                                                                       \
+    if (idx < end) {                                                                                                          \
+        nxt = Fmt::load(p.in, idx);                                                                                           \
+        if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx]);                                              \
+    }                                                                                                                         \
+    for (; idx < end; idx += stride) {                                                                                        \
+        typename Fmt::Word w = nxt, wprev = w;                                                                                \
+        const uint32_t pid = BUCKETED ? npid : idx;                                                                           \
+        if (idx + stride < end) {                                                                                             \
+            nxt = Fmt::load(p.in, idx + stride);                                                                              \
+            if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx + stride]);                                 \
+        }                                                                                                                     \
+        float4 st = Fmt::decode(w);                                                                                           \
+        for (uint32_t k = 0; k < p.nsteps; ++k) {                                                                             \
+            if constexpr (!Fmt::packed) wprev = Fmt::encode(st);                                                              \
+            else if (k + 1u == p.nsteps && k) wprev = Fmt::encode(st);                                                        \
+            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true>(p, lut, st, pid, p.times[k], &tabs));        \
+        }                                                                                                                     \
+        if (!Fmt::packed || p.nsteps) w = Fmt::encode(st);                                                                    \
+        Fmt::store(p.out_prev, idx, wprev);                                                                                   \
+        Fmt::store(p.out, idx, w);                                                                                            \
+        if constexpr (STATS) { stats_take(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], st, p.u.speedLimit, first); first = false; } \
+    }                                                                                                                         \
     if constexpr (STATS) stats_none(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], first);
-}
 
-// Packed ring (TH_STATE_F16): the same fusion on 8-B texels.  The storage quantisation is part of every step
-// (a step reads what the previous one stored), so each intermediate state goes through pack -> unpack in
-// registers: bit-identical to nsteps logic_packed_kernel launches.
 template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS>
-__global__ __launch_bounds__(256, 5) void logic_fused_packed_kernel(const LogicParams p)
-{
-    __shared__ float4 smem[NOISE ? kHashVec + kLutSize : 1];
-    const float4 *lut = smem + (NOISE ? kHashVec : 0);
-    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};
-    if constexpr (NOISE) {
-        fill_hash_tables(smem, p.lut);
-        __syncthreads();
-    }
-    const v2u *in = reinterpret_cast<const v2u *>(p.in);
-    v2u *out = reinterpret_cast<v2u *>(p.out), *out_prev = reinterpret_cast<v2u *>(p.out_prev);
-    uint32_t idx, stride, end;
-    if constexpr (!BUCKETED) {
-        idx = blockIdx.x * 256u + threadIdx.x;
-        stride = gridDim.x * 256u;
-        end = p.count;
-    } else {            // tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths like the f32 pass
-        const uint32_t group = blockIdx.x & 7u, rank = blockIdx.x >> 3, per = (p.count + 7u) >> 3;
-        const uint32_t lo = group * per;
-        idx = lo + rank * 256u + threadIdx.x;
-        stride = (gridDim.x >> 3) * 256u;
-        end = lo + per < p.count ? lo + per : p.count;
-    }
-    v2u nxt = {0x80008000u, 0u};
-    uint32_t npid = idx;
-    [[maybe_unused]] bool first = true;
-    if (idx < end) {
-        nxt = __builtin_nontemporal_load(&in[idx]);
-        if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx]);
-    }
-    for (; idx < end; idx += stride) {
-        uint2 w = make_uint2(nxt.x, nxt.y), wprev = w;
-        const uint32_t pid = BUCKETED ? npid : idx;
-        if (idx + stride < end) {
-            nxt = __builtin_nontemporal_load(&in[idx + stride]);
-            if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx + stride]);
-        }
-        // (between two fused steps the state is what the ring WOULD hold of it - quantize_state = unpack of pack - in registers as
-        // floats; the words are made once, for the two states that leave)
-        float4 st = unpack_state(w);
-        for (uint32_t k = 0; k < p.nsteps; ++k) {
-            // (the state before the last step leaves as words at once: carried through the loop as four more floats the kernel
-            // had 101 VGPRs - four waves per SIMD instead of five)
-            if (k + 1u == p.nsteps && k) wprev = pack_state(st);
-            st = quantize_state(integrate<FAST, NOISE, TARGET, POW2, false, kFusedPermTable>(p, lut, st, pid, p.times[k], &tabs));
-        }
-        if (p.nsteps) w = pack_state(st);                         // (one step: wprev stays the word that came in, whatever it decodes to)
-        v2u a = {wprev.x, wprev.y}, b = {w.x, w.y};
-        __builtin_nontemporal_store(a, &out_prev[idx]);
-        __builtin_nontemporal_store(b, &out[idx]);
-        // (the statistics of a packed ring are those of what its texels decode to - what th_stats reads through its f32 view)
-        if constexpr (STATS) { stats_take(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], st, p.u.speedLimit, first); first = false; }
-    }
-    if constexpr (STATS) stats_none(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], first);
-}
+__global__ __launch_bounds__(256) void logic_fused_kernel(const LogicParams p) { TH_LOGIC_FUSED_LOOP(F32Texel) }
+
+// Packed ring (TH_STATE_F16): the same fusion on 8-B texels.  The storage quantisation is part of every step (a step reads
+// what the previous one stored), so between two fused steps the state is what the ring WOULD hold of it - quantize_state =
+// unpack of pack - in registers as floats; the words are made once, for the two states that leave.  Bit-identical to
+// nsteps logic_packed_kernel launches.
+template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS>
+__global__ __launch_bounds__(256, 5) void logic_fused_packed_kernel(const LogicParams p) { TH_LOGIC_FUSED_LOOP(PackedTexel) }
 
 // Launch shape of the fused passes: one 256-slot workgroup per 256 particles (no persistent grid).  A fused pass
 // is issue-bound and runs 5 workgroups per CU (82 VGPRs): a persistent grid of 2048 workgroups left the CUs
@@ -368,46 +307,14 @@ static int fused_grid(uint32_t count, bool bucketed)
     return (int)(grid ? grid : 1u);
 }
 
-template <bool FAST, bool NOISE, bool TARGET>
-static void launch_fused_p2(const LogicParams &p, bool pow2, bool packed, hipStream_t s)
+void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t s)
 {
-    if (packed) {
-        const bool sorted = p.perm != nullptr;
-        const int pgrid = fused_grid(p.count, sorted);
-#define TH_GO(P2, BK)                                                                                                                 \
-    do {                                                                                                                              \
-        if (p.stats_part) hipLaunchKernelGGL((logic_fused_packed_kernel<FAST, NOISE, TARGET, P2, BK, true>), dim3(pgrid), dim3(256), 0, s, p);   \
-        else hipLaunchKernelGGL((logic_fused_packed_kernel<FAST, NOISE, TARGET, P2, BK, false>), dim3(pgrid), dim3(256), 0, s, p);               \
-    } while (0)
-        if (pow2) { if (sorted) TH_GO(true, true); else TH_GO(true, false); }
-        else { if (sorted) TH_GO(false, true); else TH_GO(false, false); }
-#undef TH_GO
-        return;
-    }
-    const bool bucketed = p.perm != nullptr;
+    const bool packed = v.format == StateFormat::packed, bucketed = p.perm != nullptr;
     const int grid = fused_grid(p.count, bucketed);
-#define TH_GO(P2, BK)                                                                                                         \
-    do {                                                                                                                      \
-        if (p.stats_part) hipLaunchKernelGGL((logic_fused_kernel<FAST, NOISE, TARGET, P2, BK, true>), dim3(grid), dim3(256), 0, s, p);   \
-        else hipLaunchKernelGGL((logic_fused_kernel<FAST, NOISE, TARGET, P2, BK, false>), dim3(grid), dim3(256), 0, s, p);               \
-    } while (0)
-    if (pow2) { if (bucketed) TH_GO(true, true); else TH_GO(true, false); }
-    else { if (bucketed) TH_GO(false, true); else TH_GO(false, false); }
-#undef TH_GO
-}
-
-void launch_logic_fused(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool packed, hipStream_t s)
-{
-    const bool fast = mode == TH_MODE_FAST;
-#define TH_DISPATCH(F, N, T) launch_fused_p2<F, N, T>(p, pow2, packed, s)
-    if (fast) {
-        if (noise) { if (target) TH_DISPATCH(true, true, true); else TH_DISPATCH(true, true, false); }
-        else { if (target) TH_DISPATCH(true, false, true); else TH_DISPATCH(true, false, false); }
-    } else {
-        if (noise) { if (target) TH_DISPATCH(false, true, true); else TH_DISPATCH(false, true, false); }
-        else { if (target) TH_DISPATCH(false, false, true); else TH_DISPATCH(false, false, false); }
-    }
-#undef TH_DISPATCH
+    lift([&](auto fast, auto noise, auto target, auto pow2, auto bk, auto stats) {
+        hipLaunchKernelGGL((packed ? logic_fused_packed_kernel<fast, noise, target, pow2, bk, stats>
+                                   : logic_fused_kernel<fast, noise, target, pow2, bk, stats>), dim3(grid), dim3(256), 0, s, p);
+    }, v.mode == TH_MODE_FAST, v.noise, v.target, v.pow2, bucketed, p.stats_part != nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -856,34 +763,20 @@ __global__ __launch_bounds__(256, 5) void logic_sorted_kernel(const LogicParams 
     }
 }
 
-template <bool FAST, bool NOISE, bool TARGET>
-static void launch_sorted_p2(const LogicParams &p, bool pow2, bool in_tiled, bool scatter, bool count, uint32_t max_chunks, hipStream_t s)
+void launch_logic_sorted(const LogicParams &p, const LogicVariant &v, SortedPass pass, uint32_t max_chunks, hipStream_t s)
 {
-    // IN_TILED: an upper bound of the chunk count (the real one lives on the device), rounded up to the 8 XCD groups
-    const int grid = in_tiled ? (int)(((max_chunks + 7u) & ~7u)) : tile_grid(p.count);
-#define TH_GO(P2, IT, SC, CN) hipLaunchKernelGGL((logic_sorted_kernel<FAST, NOISE, TARGET, P2, IT, SC, CN>), dim3(grid), dim3(256), 0, s, p)
-#define TH_GO_P2(IT, SC, CN) do { if (pow2) TH_GO(true, IT, SC, CN); else TH_GO(false, IT, SC, CN); } while (0)
-    if (in_tiled) {
-        if (scatter) TH_GO_P2(true, true, false);
-        else TH_GO_P2(true, false, true);        // (in place: the counting pass before a re-sort; plain passes run logic_kernel)
-    } else TH_GO_P2(false, true, false);
-#undef TH_GO_P2
-#undef TH_GO
-}
-
-void launch_logic_sorted(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool in_tiled, bool scatter,
-                         bool count, uint32_t max_chunks, hipStream_t s)
-{
-    const bool fast = mode == TH_MODE_FAST;
-#define TH_DISPATCH(F, N, T) launch_sorted_p2<F, N, T>(p, pow2, in_tiled, scatter, count, max_chunks, s)
-    if (fast) {
-        if (noise) { if (target) TH_DISPATCH(true, true, true); else TH_DISPATCH(true, true, false); }
-        else { if (target) TH_DISPATCH(true, false, true); else TH_DISPATCH(true, false, false); }
-    } else {
-        if (noise) { if (target) TH_DISPATCH(false, true, true); else TH_DISPATCH(false, true, false); }
-        else { if (target) TH_DISPATCH(false, false, true); else TH_DISPATCH(false, false, false); }
-    }
-#undef TH_DISPATCH
+    // sorted input: an upper bound of the chunk count (the real one lives on the device), rounded up to the 8 XCD groups
+    const int grid = pass == SortedPass::first_sort ? tile_grid(p.count) : (int)((max_chunks + 7u) & ~7u);
+    lift([&](auto fast, auto noise, auto target, auto pow2) {
+        switch (pass) {         // <.., IN_TILED, SCATTER, COUNT>
+        case SortedPass::first_sort:
+            hipLaunchKernelGGL((logic_sorted_kernel<fast, noise, target, pow2, false, true, false>), dim3(grid), dim3(256), 0, s, p); break;
+        case SortedPass::resort:
+            hipLaunchKernelGGL((logic_sorted_kernel<fast, noise, target, pow2, true, true, false>), dim3(grid), dim3(256), 0, s, p); break;
+        case SortedPass::count_in_place:
+            hipLaunchKernelGGL((logic_sorted_kernel<fast, noise, target, pow2, true, false, true>), dim3(grid), dim3(256), 0, s, p); break;
+        }
+    }, v.mode == TH_MODE_FAST, v.noise, v.target, v.pow2);
 }
 
 // Per-texel flow decode for one step (src/flow/get.glsl:3-5).  Sampling is NEAREST and get() is

@@ -228,17 +228,40 @@ struct StatsPartial {
     double sum_speed, max_speed;
 };
 
+enum class StateFormat { f32, packed };      // the state ring's texels: RGBA32F, or the packed 8-byte form (TH_STATE_F16)
+
+// Which specialised integrator a pass runs (th_step.hip: plan_step); the launchers make template arguments of it.  The
+// generic kernel is not one of them: launch_logic_generic.
+struct LogicVariant {
+    int32_t mode = TH_MODE_EXACT;  // TH_MODE_*
+    bool noise = false;            // noiseWeight != 0
+    bool target = false;           // the targets texture is read
+    bool pow2 = false;             // W and H are powers of two (LogicParams::log2w, inv_*)
+    bool decoded = false;          // taps from the decoded plane (LogicParams::flow_dec); the fused passes decode per particle
+    StateFormat format = StateFormat::f32;
+    bool operator==(const LogicVariant &o) const
+    {
+        return mode == o.mode && noise == o.noise && target == o.target && pow2 == o.pow2 && decoded == o.decoded && format == o.format;
+    }
+};
+
+// The passes of logic_sorted_kernel (th_kernels.hip "The single-step integrator over sorted slots"); f32 state only
+enum class SortedPass {
+    first_sort,         // input in texel order, output at the slots of the first sort
+    resort,             // input in a sorted order, output at the slots of a new sort
+    count_in_place,     // input in a sorted order, output at the same slots; the tiles of the output counted for a re-sort
+};
+
 // launchers (defined in th_kernels.hip)
-void launch_logic(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool decoded,
-                  bool generic, bool packed, hipStream_t stream);
-void launch_logic_fused(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool packed, hipStream_t stream);
+void launch_logic(const LogicParams &p, const LogicVariant &v, hipStream_t stream);        // over texel order or p.perm's slots
+void launch_logic_generic(const LogicParams &p, hipStream_t stream);                       // texel-order f32 only (the host unpacks around it)
+void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t stream);  // p.nsteps steps in one pass
 void launch_pack_state(void *dst, const float4 *src, uint32_t n, hipStream_t stream);      // f32 texels -> TH_STATE_F16
 void launch_unpack_state(float4 *dst, const void *src, uint32_t n, hipStream_t stream);
 void launch_flow_pack3(const float4 *flow, float *xyz, size_t n, hipStream_t stream);
 void launch_flow_decode(const float4 *flow, float2 *dec, size_t n, float time, const float *time_dev, float decay,
                         hipStream_t stream);
-void launch_logic_sorted(const LogicParams &p, int mode, bool noise, bool target, bool pow2, bool in_tiled, bool scatter,
-                         bool count, uint32_t max_chunks, hipStream_t stream);
+void launch_logic_sorted(const LogicParams &p, const LogicVariant &v, SortedPass pass, uint32_t max_chunks, hipStream_t stream);
 void launch_tile_hist(const TileSortParams &b, hipStream_t stream);
 void launch_tile_scan(const TileSortParams &b, hipStream_t stream);
 void launch_tile_scatter(const TileSortParams &b, hipStream_t stream);

@@ -38,7 +38,8 @@ bool finite_uniforms(const th_logic_uniforms &u)
 // ---- one integrator pass = plan (host decisions, may synchronise) + enqueue (launches only) -------
 struct StepPlan {
     th::LogicParams p{};         // everything except in / out / perm / time_dev
-    bool noise = false, use_targets = false, pow2 = false, decoded = false, generic = false;
+    th::LogicVariant v;          // the specialised kernel's variant ...
+    bool generic = false;        // ... unless the pass runs the generic kernel
     bool may_sort = false;       // this pass may run on (and produce) tile-sorted slots
 };
 
@@ -54,8 +55,11 @@ static th_status plan_step(th_context *c, const th_logic_uniforms &u, int32_t ta
     p.width = W;
     p.row0 = (uint32_t)c->cfg.row0;
     p.wf = (float)W; p.hf = (float)H;
-    plan.pow2 = is_pow2(W) && is_pow2(H);
-    p.log2w = plan.pow2 ? ilog2(W) : 0;
+    th::LogicVariant &v = plan.v;
+    v = th::LogicVariant{};
+    v.mode = c->cfg.mode;
+    v.pow2 = is_pow2(W) && is_pow2(H);
+    p.log2w = v.pow2 ? ilog2(W) : 0;
     p.inv_w = 1.0f / p.wf; p.inv_h = 1.0f / p.hf; p.inv_wh = 1.0f / (p.wf * p.hf);
     p.fw = c->fw; p.fh = c->fh;
     p.fwf = (float)c->fw; p.fhf = (float)c->fh;
@@ -66,8 +70,8 @@ static th_status plan_step(th_context *c, const th_logic_uniforms &u, int32_t ta
 
     // Preconditions of the specialised path (DESIGN.md "fast-path domain").
     plan.generic = c->opt.force_generic || !finite_uniforms(u);
-    plan.noise = u.noiseWeight != 0.0f;
-    plan.use_targets = u.target != 0.0f;
+    v.noise = u.noiseWeight != 0.0f;
+    v.target = u.target != 0.0f;
     if (!plan.generic) {
         // i = (x+.5 + (y+.5)W)/(WH) lies in (0, 1]; bound |vary(base, i, v)| <= |base|(1+|v|)
         double nscale = std::fabs((double)u.noiseScale) * (1.0 + std::fabs((double)u.varyNoiseScale)) * 1.001;
@@ -80,7 +84,7 @@ static th_status plan_step(th_context *c, const th_logic_uniforms &u, int32_t ta
         p.pos_bound = (float)std::fmin(bound * 0.999, 999999.0);
         if (!(p.pos_bound > 0.0f)) plan.generic = true;
     }
-    if (!plan.generic && !plan.use_targets) {
+    if (!plan.generic && !v.target) {
         // target == 0 multiplies (targets - pos) by an exact zero; dropping the read is only
         // value-preserving when the texture holds no NaN/Inf.
         if (!c->targets_checked) {
@@ -92,16 +96,19 @@ static th_status plan_step(th_context *c, const th_logic_uniforms &u, int32_t ta
             c->targets_nonfinite = flag != 0;
             c->targets_checked = true;
         }
-        plan.use_targets = c->targets_nonfinite;
+        v.target = c->targets_nonfinite;
     }
     // Decode the flow once per step when that is cheaper than decoding per particle: it shrinks the
     // random-gather footprint (the L2/Infinity-Fabric miss traffic is what bounds this kernel).
     const size_t flow_texels = (size_t)c->fw * c->fh;
-    plan.decoded = !plan.generic && c->texels() >= 2 * flow_texels;
+    v.decoded = !plan.generic && c->texels() >= 2 * flow_texels;
+    // A packed (TH_STATE_F16) ring runs the packed kernel on the default path (ring -> ring, specialised kernel); explicit
+    // targets and the generic kernel go through f32 staging.
+    v.format = c->packed && target == TH_TARGET_RING && !plan.generic ? th::StateFormat::packed : th::StateFormat::f32;
 
     // Slot layout (texel order or a tile-sorted order): only ring -> ring passes of the specialised f32 kernels run on
     // sorted slots; the callers bring the layout up to date.
-    plan.may_sort = plan.decoded && target == TH_TARGET_RING && sorting_possible(c) &&
+    plan.may_sort = v.decoded && target == TH_TARGET_RING && sorting_possible(c) &&
                     c->total_steps >= c->hold_texel_order_until;
     return TH_OK;
 }
@@ -116,12 +123,6 @@ static bool same_key(const th::LogicParams &a, const th::LogicParams &b)
            a.count == b.count && a.width == b.width && a.log2w == b.log2w && a.row0 == b.row0 &&
            a.wf == b.wf && a.hf == b.hf && a.fw == b.fw && a.fh == b.fh &&
            memcmp(&ua, &ub, sizeof ua) == 0 && a.s2_cap == b.s2_cap && a.pos_bound == b.pos_bound;
-}
-
-static uint32_t plan_flags(const StepPlan &plan)
-{
-    return (plan.noise ? 1u : 0u) | (plan.use_targets ? 2u : 0u) | (plan.pow2 ? 4u : 0u) | (plan.decoded ? 8u : 0u) |
-           (plan.generic ? 16u : 0u);
 }
 
 static th_status timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1)
@@ -145,9 +146,7 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
     th::LogicParams p = plan.p;
     float4 *out = nullptr;
     if (th_status s = resolve_target(c, target, true, &out)) return s;
-    // A packed (TH_STATE_F16) ring runs the packed kernel on the default path (ring -> ring, specialised
-    // kernel); explicit targets and the generic kernel go through f32 staging.
-    const bool packed_kernel = c->packed && target == TH_TARGET_RING && !plan.generic;
+    const bool packed_kernel = plan.v.format == th::StateFormat::packed;      // (else a packed ring goes through f32 staging)
     float4 *in = c->ring[1], *rt = out;     // Particles.step binds buffers[1] as `particles` (src/particles.js:139)
     if (c->packed && !packed_kernel) {
         if (th_status s = unpacked_view(c, c->ring[1], 1, &in)) return s;
@@ -204,7 +203,7 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
         // The re-sort of a frame loop (th_order.hip: asort_start): while draws over the slot order are going on, no step counts
         // or scatters - the order laid out beside the last draw is taken up here, its copy of this step's input in the input's
         // place - and the next one is started behind the step that is `resort_steps` launches on.
-        async = c->opt.async_sort && in_order >= 0 && plan.decoded && c->side && in == c->ring[1] && target == TH_TARGET_RING &&
+        async = c->opt.async_sort && in_order >= 0 && plan.v.decoded && c->side && in == c->ring[1] && target == TH_TARGET_RING &&
                 c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps;
         if (c->asort.pending) {
             const bool take = async && c->asort.valid && c->asort.src == in && c->asort.src_order == in_order && c->asort.at_step == c->total_steps &&
@@ -229,7 +228,7 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
         use_sorted = true;
         // between two sorts the pass is the plain grid-stride kernel over the sorted slots (taps gathered from the
         // decoded plane: a wave's taps fall into one neighbourhood); the chunk kernel counts and scatters around a re-sort
-        gather = !scatter && plan.decoded && (async || c->steps_since_sort + 1 < c->opt.resort_steps);
+        gather = !scatter && plan.v.decoded && (async || c->steps_since_sort + 1 < c->opt.resort_steps);
         p.geom = g;
         if (in_order >= 0) {
             const th_context::SlotOrder &o = c->orders[(size_t)in_order];
@@ -258,7 +257,7 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
         }
     }
 
-    if (plan.decoded)
+    if (plan.v.decoded)
         th::launch_flow_decode(c->flow, c->flow_dec, (size_t)c->fw * c->fh, time, time_dev, p.u.flowDecay, c->stream);
 
     // A frame loop: the plain kernel notes per 64 slots whether any of their lines - input position to output position - may
@@ -288,13 +287,13 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
         if (th_status s = timing_events(c, &k0, &k1)) return s;
         TH_HIP(hipEventRecord(k0, c->stream));
     }
-    if (gather) {
-        th::launch_logic(p, c->cfg.mode, plan.noise, plan.use_targets, plan.pow2, plan.decoded, plan.generic, packed_kernel, c->stream);
-    } else if (use_sorted)
-        th::launch_logic_sorted(p, c->cfg.mode, plan.noise, plan.use_targets, plan.pow2, in_order >= 0, scatter, count, c->max_chunks, c->stream);
+    if (use_sorted && !gather) {
+        const th::SortedPass pass = in_order < 0 ? th::SortedPass::first_sort : scatter ? th::SortedPass::resort : th::SortedPass::count_in_place;
+        th::launch_logic_sorted(p, plan.v, pass, c->max_chunks, c->stream);
+    } else if (plan.generic)
+        th::launch_logic_generic(p, c->stream);
     else
-        th::launch_logic(p, c->cfg.mode, plan.noise, plan.use_targets, plan.pow2, plan.decoded, plan.generic, packed_kernel,
-                         c->stream);
+        th::launch_logic(p, plan.v, c->stream);
     if (k1) TH_HIP(hipEventRecord(k1, c->stream));
     TH_HIP(hipGetLastError());
     if (target == TH_TARGET_RING || (target >= 0 && target < (int32_t)c->ring.size())) set_order(c, out, out_order);
@@ -390,7 +389,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
         // step): the field's x, y, z packed 12 B apart once per call - three quarters of the footprint, and the band one
         // XCD taps fits its L2 (0.574 -> 0.546 ms per 20-step launch at C3; with the noise on the pass is bound by its
         // arithmetic and the packing pass only costs: 1.829 against 1.818 + 0.01)
-        const bool pack3 = !plan.noise;
+        const bool pack3 = !plan.v.noise;
         if (pack3) {
             if (!c->flow3) TH_HIP(hipMalloc((void **)&c->flow3, (size_t)c->fw * c->fh * 3 * sizeof(float)));
             th::launch_flow_pack3(c->flow, c->flow3, (size_t)c->fw * c->fh, c->stream);
@@ -432,7 +431,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
                     if (th_status s = timing_events(c, &k0, &k1)) return s;
                     TH_HIP(hipEventRecord(k0, c->stream));
                 }
-                th::launch_logic_fused(p, c->cfg.mode, plan.noise, plan.use_targets, plan.pow2, c->packed, c->stream);
+                th::launch_logic_fused(p, plan.v, c->stream);
                 if (k1) TH_HIP(hipEventRecord(k1, c->stream));
                 TH_HIP(hipGetLastError());
                 set_order(c, other, order);                // both outputs sit at the input's slots
@@ -461,12 +460,11 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
     key.u.time = 0.0f;
     GraphEntry *hit = nullptr;
     for (GraphEntry &g : c->graphs)
-        if (g.n == n && g.mode == c->cfg.mode && g.ring == c->ring && g.flags == plan_flags(plan) && same_key(g.key, key)) { hit = &g; break; }
+        if (g.n == n && g.variant == plan.v && g.generic == plan.generic && g.ring == c->ring && same_key(g.key, key)) { hit = &g; break; }
     if (!hit) {
         if (c->graphs.size() >= 8) { destroy_graph(c->graphs.front()); c->graphs.erase(c->graphs.begin()); }
         GraphEntry g;
-        g.n = n; g.mode = c->cfg.mode; g.ring = c->ring;
-        g.flags = plan_flags(plan); g.key = key;
+        g.n = n; g.variant = plan.v; g.generic = plan.generic; g.ring = c->ring; g.key = key;
         TH_HIP(hipMalloc((void **)&g.times_dev, (size_t)n * sizeof(float)));
         TH_HIP(hipHostMalloc((void **)&g.times_host, (size_t)n * sizeof(float)));
         TH_HIP(hipEventCreate(&g.copied));
