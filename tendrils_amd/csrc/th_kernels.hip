@@ -235,8 +235,9 @@ TH_D void stats_none(StatsPartial *slot, bool first)
 // offset.  BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step (to
 // out_prev): f32 carries it along, a register copy per step; a packed ring makes its words at once at the last step (carried
 // through the loop as four more floats the kernel had 101 VGPRs - four waves per SIMD instead of five), and after one step
-// it is the word that came in, whatever that decodes to.  The statistics of a packed ring are those of what its texels
-// decode to - what th_stats reads through its f32 view.
+// it is the word that came in, whatever that decodes to.  (Peeling the last step off the loop instead leaves the step loop's
+// VALU count as it is (349) and inlines integrate twice: 90 VGPRs against 80 for the f32 kernel, profiles/r7_b_isa.txt.)
+// The statistics of a packed ring are those of what its texels decode to - what th_stats reads through its f32 view.
 #define TH_LOGIC_FUSED_LOOP(Fmt)                                                                                              \
     __shared__ float4 smem[NOISE ? kHashVec + kLutSize : 1];                                                                  \
     const float4 *lut = smem + (NOISE ? kHashVec : 0);                                                                        \
@@ -275,7 +276,7 @@ TH_D void stats_none(StatsPartial *slot, bool first)
         for (uint32_t k = 0; k < p.nsteps; ++k) {                                                                             \
             if constexpr (!Fmt::packed) wprev = Fmt::encode(st);                                                              \
             else if (k + 1u == p.nsteps && k) wprev = Fmt::encode(st);                                                        \
-            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true>(p, lut, st, pid, p.times[k], &tabs));        \
+            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true, !NOISE>(p, lut, st, pid, p.times[k], &tabs)); \
         }                                                                                                                     \
         if (!Fmt::packed || p.nsteps) w = Fmt::encode(st);                                                                    \
         Fmt::store(p.out_prev, idx, wprev);                                                                                   \

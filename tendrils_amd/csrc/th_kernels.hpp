@@ -256,6 +256,9 @@ enum class SortedPass {
 void launch_logic(const LogicParams &p, const LogicVariant &v, hipStream_t stream);        // over texel order or p.perm's slots
 void launch_logic_generic(const LogicParams &p, hipStream_t stream);                       // texel-order f32 only (the host unpacks around it)
 void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t stream);  // p.nsteps steps in one pass
+// Which flow copy a fused pass taps, fixed by its variant at compile time: p.flow3 (12 B per texel) without the noise,
+// p.flow (RGBA32F) with it.  The caller sets p.flow3 on the same condition.
+inline bool fused_taps_flow3(const LogicVariant &v) { return !v.noise; }
 void launch_pack_state(void *dst, const float4 *src, uint32_t n, hipStream_t stream);      // f32 texels -> TH_STATE_F16
 void launch_unpack_state(float4 *dst, const void *src, uint32_t n, hipStream_t stream);
 void launch_flow_pack3(const float4 *flow, float *xyz, size_t n, hipStream_t stream);

@@ -13,6 +13,15 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+// v_mad_u32_u24: a[23:0] * b[23:0] + c in one instruction, `b` wave-uniform (an SGPR operand).  As asm: hipcc emits
+// v_mul_lo_u32 for a 32-bit product whose operands it cannot bound.
+TH_D uint32_t mad_u24_s(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+
 // streaming (read-once / write-once) 16-byte accesses of the state ring
 TH_D float4 load_stream(const float4 *p)
 {
@@ -321,10 +330,11 @@ TH_D float snoise_finish(const NoiseCorners &n, float4 g0, float4 g1, float4 g2,
 //   TARGET target != 0 or the targets texture holds a non-finite value
 //   POW2   dataRes.x, dataRes.y powers of two: `/dataRes` == `*(1/dataRes)` exactly
 //   DECODED the flow tap reads the per-step decoded float2 plane (8 B) instead of RGBA32F (16 B)
+//   FLOW3  (fused passes without the noise: fused_taps_flow3) the flow tap reads p.flow3, 12 B per texel, instead of p.flow
 // ---------------------------------------------------------------------------
 // One particle: state texel `st` of particle `pid` (= texel index in this context's rows).
 constexpr int kTileShift = 5;            // 32 x 32-texel tiles of the flow field: the key of the tile-sorted slot order
-template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB = false>
+template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB = false, bool FLOW3 = false>
 TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32_t pid, float time,
                       const HashTables *tabs = nullptr)
 {
@@ -352,7 +362,16 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
             const float q = __builtin_nanf("");
             return make_float4(q, q, q, q);
         }
-        return logic_texel_ref(p, x, y, st, pid, time);
+        // An opaque copy of the particle id, and the texel coordinates again from it: what logic_texel_ref derives from them
+        // alone - three divisions, the five vary() under its `i`, the targets address - is then computed here, when a lane
+        // takes this branch, and not hoisted out of a fused loop into registers held live through every step of the fast
+        // path below.
+        uint32_t rpid = pid;
+        asm volatile("" : "+v"(rpid));
+        uint32_t rx, ry;
+        if constexpr (POW2) { rx = rpid & (p.width - 1u); ry = rpid >> p.log2w; }
+        else { ry = rpid / p.width; rx = rpid - ry * p.width; }
+        return logic_texel_ref(p, rx, ry + p.row0, st, rpid, time);
     }
 
     float fcx = (float)x + 0.5f, fcy = (float)y + 0.5f;
@@ -374,12 +393,21 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
     // either way (half_fw = 0.5*fw from the host; a denormal (v+1)/2 lands in texel 0 on both routes)
     int tx = (int)__builtin_amdgcn_fmed3f((sx + 1.0f) * p.half_fw, 0.0f, p.fwm1);      // trunc == floor on [0, n-1]
     int ty = (int)__builtin_amdgcn_fmed3f((sy + 1.0f) * p.half_fh, 0.0f, p.fhm1);
-    const int texel = ty * p.fw + tx;
     float ffx, ffy;      // getFlow(): data.xy * max(0, 1 - (time - data.z)*decay), src/flow/get.glsl:4
     float4 ft;
-    if constexpr (DECODED) { float2 d = p.flow_dec[texel]; ffx = d.x; ffy = d.y; }
-    else if (p.flow3) { const float *f3 = p.flow3 + 3u * (uint32_t)texel; ft = make_float4(f3[0], f3[1], f3[2], 0.0f); }     // (uniform branch)
-    else ft = p.flow[texel];
+    if constexpr (DECODED) { float2 d = p.flow_dec[ty * p.fw + tx]; ffx = d.x; ffy = d.y; }
+    else {
+        // The texel's byte offset in 32 bits, from the field's base (uniform: the load takes it as its scalar address):
+        // fw, tx, ty < 2^24 and fw * fh < 2^28 (th_flow_resize), so ty * fw + tx is exact in v_mad_u32_u24 and the offset
+        // stays below 2^32 at 12 or 16 bytes per texel.
+        const uint32_t texel = mad_u24_s((uint32_t)ty, (uint32_t)p.fw, (uint32_t)tx);
+        if constexpr (FLOW3) {
+            const float *f3 = reinterpret_cast<const float *>(reinterpret_cast<const char *>(p.flow3) + ((texel + (texel << 1)) << 2));
+            ft = make_float4(f3[0], f3[1], f3[2], 0.0f);
+        } else {
+            ft = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.flow) + (texel << 4));
+        }
+    }
 
     float wxs = 0.0f, wys = 0.0f;   // (wander * dt) * vary(noiseWeight)
     if constexpr (NOISE) {

@@ -389,7 +389,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
         // step): the field's x, y, z packed 12 B apart once per call - three quarters of the footprint, and the band one
         // XCD taps fits its L2 (0.574 -> 0.546 ms per 20-step launch at C3; with the noise on the pass is bound by its
         // arithmetic and the packing pass only costs: 1.829 against 1.818 + 0.01)
-        const bool pack3 = !plan.v.noise;
+        const bool pack3 = th::fused_taps_flow3(plan.v);
         if (pack3) {
             if (!c->flow3) TH_HIP(hipMalloc((void **)&c->flow3, (size_t)c->fw * c->fh * 3 * sizeof(float)));
             th::launch_flow_pack3(c->flow, c->flow3, (size_t)c->fw * c->fh, c->stream);
