@@ -439,6 +439,30 @@ typedef struct th_draw_info {
 } th_draw_info;
 th_status th_draw_query(th_context *ctx, th_draw_info *out);
 
+/* -- flow lines: FlowLine / FlowLines (src/flow-line/index.js, multi.js) drawn into the flow texture ----------------------
+ * Uniforms of src/flow-line/index.vert / index.frag; FlowLine's defaults are speed 3, rad 0.1, crestShape 0.6,
+ * speedLimit 0.01, viewSize [1, 1] (the demo assigns Tendrils.state over them, which overrides speedLimit only). */
+typedef struct th_flow_line_uniforms {
+    float speed, rad, crestShape, speedLimit;
+    float viewSize[2];
+} th_flow_line_uniforms;
+
+/* Line.update() + FlowLine.setAttributes (src/geom/line/index.js:76-117, src/flow-line/index.js:57-72) of one line: n points
+ * ([n][2] f32, the path) with their times (ms, double), closed or not.  No context, no GPU work.  *nverts = the strip's
+ * vertex count (0 when n < 2; else 2 * (n + closed)); capacity 0 asks for that count alone; with capacity >= *nverts the
+ * attribute arrays are written (a smaller capacity: TH_ERR_INVALID), per vertex:
+ * position[2], normal[2], miter[1] (sign flipped on even vertices), previous[2], time[1], dt[1] - the reference's f32 arrays. */
+th_status th_flow_line_attributes(const float *points, const double *times, int32_t n, int32_t closed, int32_t capacity,
+                                  int32_t *nverts, float *position, float *normal, float *miter, float *previous,
+                                  float *time, float *dt);
+/* Draws nlines lines into the context's flow, in the given order, as triangle strips blended SRC_ALPHA / ONE_MINUS_SRC_ALPHA
+ * (what Tendrils.step() leaves enabled, src/index.js:267-268).  Line i owns points[offsets[i] .. offsets[i+1]) and the
+ * times of the same indices; closed[i] != 0 closes it.  Lines of fewer than 2 points and nlines == 0 draw nothing.  Enqueues
+ * on the context's stream (a pinned staging copy; no wait on the GPU except for the previous call's upload, or when the
+ * call's scratch grows).  On a row-band shard every rank draws every line into its copy of the flow. */
+th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const float *points, const double *times,
+                        const int32_t *offsets, const int32_t *closed, int32_t nlines);
+
 /* Per-context switches between equivalent paths (build-defined; no switch changes a result - the parity suites rerun under
  * each, tests/conftest.py).  A context starts from the environment variables of the same names, read by th_create
  * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN;

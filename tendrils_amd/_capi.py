@@ -98,6 +98,11 @@ class CommInfo(C.Structure):
     _fields_ = [("active", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32), ("rccl_version", C.c_int32)]
 
 
+class FlowLineUniforms(C.Structure):
+    _fields_ = [("speed", C.c_float), ("rad", C.c_float), ("crestShape", C.c_float), ("speedLimit", C.c_float),
+                ("viewSize", C.c_float * 2)]
+
+
 COMM_ID_BYTES = 128         # TH_COMM_ID_BYTES
 
 _ctx = C.c_void_p
@@ -186,6 +191,10 @@ PROTOTYPES = {
     "th_view_step_buffers": (C.c_int32, [_ctx]),
     "th_colormap_upload": (C.c_int32, [_ctx, _fp, C.c_int32, C.c_int32]),
     "th_export_view_lines": (C.c_int32, [_ctx, C.POINTER(RenderUniforms), _fp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                            _fp, _fp, _fp, _fp, _fp, _fp]),
+    "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32), C.c_int32]),
 }
 
 _NO_STATUS = {"th_abi_version", "th_last_error"}

@@ -24,6 +24,7 @@
 #include "th_math.hpp"
 
 namespace thi {
+struct FlowLineScratch;                   // th_flowline.hip
 th_status fail(th_status code, const char *fmt, ...);      // records the message th_last_error() returns; returns `code`
 std::string &last_error();
 }  // namespace thi
@@ -243,6 +244,8 @@ struct th_context {
     // a COUNT pass has histogrammed the tiles of the state it wrote: valid for a SCATTER pass that reads exactly that
     struct { const float4 *buf = nullptr; int order = -1; th::TileGeom geom{}; long long at_step = -1; } counted;
 
+    thi::FlowLineScratch *flow_lines = nullptr;   // th_flow_lines: staging and scratch (grow-only)
+
     size_t texels() const { return (size_t)cfg.width * cfg.height; }
     size_t state_bytes() const { return texels() * (packed ? sizeof(uint2) : sizeof(float4)); }
 };
@@ -253,6 +256,7 @@ namespace thi {
 inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1)); }
 inline uint32_t ilog2(uint32_t v) { uint32_t r = 0; while (v >>= 1) ++r; return r; }
 th_status use(th_context *c, bool keeps_lines = false);
+void flow_lines_free(th_context *c);      // th_flowline.hip
 th_status alloc_state(th_context *c, float4 **out);
 th_status resolve_target(th_context *c, int32_t target, bool rotate_ok, float4 **out);
 th_status rect_ok(th_context *c, int32_t x0, int32_t y0, int32_t w, int32_t h);

@@ -46,6 +46,7 @@ class FlowTexture {
     return px;
   }
   clear() { native.flowClear(this.owner.particles.handle); }
+  bind() { return require('./flow-line').bind(this); }      // the target of FlowLine / FlowLines draws that name none
   sourceIndex() { return native.SOURCE_FLOW; }
 }
 
@@ -340,4 +341,8 @@ class Tendrils {
   }
 }
 
-module.exports = { defaults, glSettings, Tendrils, Particles, Program, Timer, default: Tendrils };
+module.exports = {
+  defaults, glSettings, Tendrils, Particles, Program, Timer, default: Tendrils,
+  get FlowLine() { return require('./flow-line').FlowLine; },
+  get FlowLines() { return require('./flow-line').FlowLines; }
+};

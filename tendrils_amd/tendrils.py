@@ -83,6 +83,11 @@ class FlowTexture:
     def clear(self):
         call("th_flow_clear", self._o.particles._ctx)
 
+    def bind(self):
+        """tendrils.flow.bind(): the target of the FlowLine / FlowLines draws that name none (tendrils_amd/flow_line.py)."""
+        from . import flow_line
+        return flow_line.bind(self)
+
     def source_index(self):
         return _capi.TH_SOURCE_FLOW
 
