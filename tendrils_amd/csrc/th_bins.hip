@@ -185,23 +185,6 @@ TH_D uint32_t place_single(const DepositParams &p, uint32_t bin, uint32_t rep)
     return place_of<true>(p, bin * kBinReplicas + rep, v);
 }
 
-// all threads of a 1024-thread workgroup: `mine` -> its exclusive prefix over the workgroup; `total` (same on every thread)
-TH_D unsigned long long block_scan_1024(unsigned long long *lds, unsigned long long mine, unsigned long long &total)
-{
-    const uint32_t t = threadIdx.x;
-    __syncthreads();
-    lds[t] = mine;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {
-        const unsigned long long a = t >= off ? lds[t - off] : 0ull;
-        __syncthreads();
-        lds[t] += a;
-        __syncthreads();
-    }
-    total = lds[1023];
-    return lds[t] - mine;
-}
-
 // The blocks of 256 slots in which some slot's line can draw at all (a property of the slot order and the shape alone: found
 // once per order), in rising order.
 // (the same walk over a new slot order notes where the texels lie that other lines' vertices read - LineSources, shapes whose
@@ -229,7 +212,7 @@ __global__ __launch_bounds__(1024) void bins_block_list_kernel(const uint8_t *fl
     const uint32_t per = (blocks + 1023u) / 1024u, lo = threadIdx.x * per < blocks ? threadIdx.x * per : blocks, hi = lo + per < blocks ? lo + per : blocks;
     unsigned long long n = 0, total = 0;
     for (uint32_t b = lo; b < hi; ++b) n += flags[b];
-    uint32_t at = (uint32_t)block_scan_1024(lds, n, total);
+    uint32_t at = (uint32_t)block_scan<1024>(lds, n, total);
     for (uint32_t b = lo; b < hi; ++b) if (flags[b]) list[at++] = b;
     if (threadIdx.x == 0u) *count = (uint32_t)total;
 }
@@ -1268,21 +1251,14 @@ __global__ __launch_bounds__(1024) void crowd_plan_kernel(const DepositParams p)
     const uint32_t lo = threadIdx.x * per < nlarge ? threadIdx.x * per : nlarge, hi = lo + per < nlarge ? lo + per : nlarge;
     unsigned long long kn = 0;
     for (uint32_t i = lo; i < hi; ++i) kn += bin_places(p, p.large_bins[i]);
-    kpart[threadIdx.x] = kn;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {
-        const unsigned long long ka = threadIdx.x >= off ? kpart[threadIdx.x - off] : 0ull;
-        __syncthreads();
-        kpart[threadIdx.x] += ka;
-        __syncthreads();
-    }
-    unsigned long long krun = kpart[threadIdx.x] - kn;
+    unsigned long long ktotal;
+    unsigned long long krun = block_scan<1024>(kpart, kn, ktotal);
     for (uint32_t i = lo; i < hi; ++i) {
         p.large_key0[i] = (uint32_t)(krun > 0xffffffffull ? 0xffffffffull : krun);
         krun += bin_places(p, p.large_bins[i]);
     }
     if (threadIdx.x == 1023u) {
-        const uint32_t keys = (uint32_t)(kpart[1023] > 0xffffffffull ? 0xffffffffull : kpart[1023]);      // (saturated: the host refuses it)
+        const uint32_t keys = (uint32_t)(ktotal > 0xffffffffull ? 0xffffffffull : ktotal);      // (saturated: the host refuses it)
         p.totals[kTotCrowdKeys] = keys;
         // the pass's totals straight into the host's memory, a sequence number behind them: the host polls that word instead of
         // waiting for a copy on another stream to be scheduled, run and signalled (a draw's only round trip: 43 -> ~10 us)
@@ -1845,7 +1821,7 @@ __global__ __launch_bounds__(1024) void owner_counts_kernel(const DepositParams 
     const uint32_t per = (p.nbins + 1023u) / 1024u, lo = threadIdx.x * per < p.nbins ? threadIdx.x * per : p.nbins, hi = lo + per < p.nbins ? lo + per : p.nbins;
     unsigned long long n = 0, total = 0;
     for (uint32_t b = lo; b < hi; ++b) n += o.counts[b];
-    unsigned long long run = block_scan_1024(lds, n, total);
+    unsigned long long run = block_scan<1024>(lds, n, total);
     for (uint32_t b = lo; b < hi; ++b) {
         for (uint32_t r = 0; r < o.world; ++r) if (o.bin_lo[r] == b) o.owner_bounds[r] = run;
         o.offsets[b] = run;
@@ -1899,7 +1875,7 @@ __global__ __launch_bounds__(1024) void owner_prefix_kernel(const OwnerParams o)
     const uint32_t *row = o.table + (size_t)s * o.nb;
     unsigned long long n = 0, total = 0;
     for (uint32_t b = lo; b < hi; ++b) n += row[b];
-    unsigned long long run = block_scan_1024(lds, n, total);
+    unsigned long long run = block_scan<1024>(lds, n, total);
     for (uint32_t b = lo; b < hi; ++b) { o.src_prefix[(size_t)s * o.nb + b] = run; run += row[b]; }
 }
 
@@ -1951,7 +1927,7 @@ __global__ __launch_bounds__(1024) void owner_pages_kernel(const DepositParams p
     };
     unsigned long long pages = 0, all = 0;
     for (uint32_t b = lo; b < hi; ++b) pages += pages_of(b);
-    unsigned long long first = block_scan_1024(lds, pages, all);
+    unsigned long long first = block_scan<1024>(lds, pages, all);
     for (uint32_t b = lo; b < hi; ++b) {
         o.bin_page[b] = (uint32_t)(first > 0xffffffffull ? 0xffffffffull : first);
         first += pages_of(b);

@@ -396,25 +396,13 @@ __global__ __launch_bounds__(256) void colscan_prefix_kernel(uint32_t *part, uin
 __global__ __launch_bounds__(1024) void colscan_bases_kernel(uint32_t W, uint32_t *colbase, uint32_t *total)
 {
     __shared__ unsigned long long sh[1024];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0ull;
-    __syncthreads();
+    unsigned long long carry = 0;
     for (uint32_t c0 = 0; c0 < W; c0 += 1024u) {
         const uint32_t col = c0 + threadIdx.x;
-        const unsigned long long s = col < W ? colbase[col] : 0ull;
-        sh[threadIdx.x] = s;
-        __syncthreads();
-        for (uint32_t o = 1; o < 1024u; o <<= 1) {
-            unsigned long long add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
-            __syncthreads();
-            sh[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const unsigned long long excl = carry + sh[threadIdx.x] - s;
+        unsigned long long window;
+        const unsigned long long excl = carry + block_scan<1024>(sh, col < W ? (unsigned long long)colbase[col] : 0ull, window);
         if (col < W) colbase[col] = (uint32_t)(excl > 0xffffffffull ? 0xffffffffull : excl);
-        __syncthreads();
-        if (threadIdx.x == 0) carry += sh[1023];
-        __syncthreads();
+        carry += window;
     }
     if (threadIdx.x == 0) *total = (uint32_t)(carry > 0xffffffffull ? 0xffffffffull : carry);
 }
@@ -466,58 +454,16 @@ __global__ void triangle_setup_kernel(const float *positions, int ntri, float vi
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
-    const float wx16 = 8.0f * (float)w, wy16 = 8.0f * (float)h;
-    const float x0 = wx16 - 8.0f, y0 = wy16 - 8.0f;
-    float cx[12], cy[12], tx[12], ty[12];
-    int n = 3;
+    float cx[12], cy[12];
     for (int k = 0; k < 3; ++k) {
         cx[k] = positions[6 * t + 2 * k] * view_x;
         cy[k] = positions[6 * t + 2 * k + 1] * view_y;
     }
-    for (int plane = 0; plane < 4 && n >= 3; ++plane) {
-        int q = 0;
-        for (int k = 0; k < n; ++k) {
-            const int j = k == n - 1 ? 0 : k + 1;
-            float di, dj;
-            switch (plane) {
-            case 0: di = 1.0f + cx[k]; dj = 1.0f + cx[j]; break;
-            case 1: di = 1.0f - cx[k]; dj = 1.0f - cx[j]; break;
-            case 2: di = 1.0f - cy[k]; dj = 1.0f - cy[j]; break;
-            default: di = 1.0f + cy[k]; dj = 1.0f + cy[j]; break;
-            }
-            if (di >= 0.0f) {
-                tx[q] = cx[k]; ty[q] = cy[k]; ++q;
-                if (dj < 0.0f) {
-                    const float D = 1.0f / (dj - di);
-                    tx[q] = (dj * cx[k] - di * cx[j]) * D; ty[q] = (dj * cy[k] - di * cy[j]) * D; ++q;
-                }
-            } else if (dj > 0.0f) {
-                const float D = 1.0f / (di - dj);
-                tx[q] = (di * cx[j] - dj * cx[k]) * D; ty[q] = (di * cy[j] - dj * cy[k]) * D; ++q;
-            }
-        }
-        n = q;
-        for (int k = 0; k < n; ++k) { cx[k] = tx[k]; cy[k] = ty[k]; }
-    }
-    TrianglePoly P;
-    P.n = 0;
-    if (n >= 3) {
-        for (int k = 0; k < n; ++k) { P.x[k] = dep_snap(cx[k], wx16, x0); P.y[k] = dep_snap(cy[k], wy16, y0); }
-        long long area2 = 0;
-        for (int k = 0; k < n; ++k) {
-            const int j = k + 1 == n ? 0 : k + 1;
-            area2 += (long long)P.x[k] * P.y[j] - (long long)P.x[j] * P.y[k];
-        }
-        if (area2 != 0) {
-            if (area2 > 0)
-                for (int a = 0, b = n - 1; a < b; ++a, --b) {
-                    int tmp = P.x[a]; P.x[a] = P.x[b]; P.x[b] = tmp;
-                    tmp = P.y[a]; P.y[a] = P.y[b]; P.y[b] = tmp;
-                }
-            P.n = n;
-        }
-    }
-    polys[t] = P;
+    int X[7], Y[7];
+    const int n = tri_clip_snap(cx, cy, 3, w, h, X, Y);
+    TrianglePoly &P = polys[t];
+    P.n = n;
+    for (int k = 0; k < n; ++k) { P.x[k] = X[k]; P.y[k] = Y[k]; }
 }
 
 __global__ __launch_bounds__(256) void triangle_fill_kernel(const TrianglePoly *polys, int ntri, float4 color, float4 *img, int w, int h)
@@ -529,20 +475,8 @@ __global__ __launch_bounds__(256) void triangle_fill_kernel(const TrianglePoly *
         bool touched = false;
         for (int t = 0; t < ntri; ++t) {
             const TrianglePoly &P = polys[t];
-            int left = w, right = 0;
-            for (int k = 0; k < P.n; ++k) {
-                const int kn = k + 1 == P.n ? 0 : k + 1;
-                const int Xa = P.x[k], Ya = P.y[k], Xb = P.x[kn], Yb = P.y[kn];
-                if (Ya == Yb) continue;
-                const bool swap = Yb < Ya;
-                const int X1 = swap ? Xb : Xa, Y1 = swap ? Yb : Ya, X2 = swap ? Xa : Xb, Y2 = swap ? Ya : Yb;
-                if (y < ((Y1 + 15) >> 4) || y >= ((Y2 + 15) >> 4)) continue;
-                const long long DX = X2 - X1, DY = Y2 - Y1;
-                long long e = dep_ceil_div(DX * (((long long)y << 4) - Y1) + (long long)X1 * DY, 16 * DY);
-                if (e < 0) e = 0;
-                if (e > w) e = w;
-                if (swap) right = (int)e; else left = (int)e;
-            }
+            int left, right;
+            tri_span(P.n, P.x, P.y, y, w, left, right);
             if (x >= left && x < right) { dep_blend_rgba(d, color); touched = true; }
         }
         if (touched) img[texel] = d;

@@ -5,19 +5,21 @@
 // reference's JS computes it, stored as f32 attributes).  th_flow_lines packs one record per drawn path point (a strip
 // vertex pair shares it) and uploads them through a pinned staging buffer.
 //
-// Device side, all on the context's stream (DESIGN.md 2.7):
+// Device side, all on the context's stream (DESIGN.md 3.6):
 //   fl_setup_kernel   one thread per strip triangle: the vertex stage of src/flow-line/index.vert in fp32 for its three
-//                     vertices, clip / snap / orient as the GeometrySpawner triangles (th_deposit.hip:triangle_setup_kernel),
+//                     vertices, clip / snap / orient as the GeometrySpawner triangles (th_raster.hpp:tri_clip_snap),
 //                     the barycentric set-up of the varyings, the triangle's 16 x 16-texel tile box; counts its tiles
 //                     per (tile, chunk of triangles)
-//   fl_scan_*         exclusive scan of those counts (tile-major, chunk-minor): where every chunk's run of a tile's list starts
+//   (scan)            exclusive scan of those counts (th_sort.hip:launch_exclusive_scan_u32; tile-major, chunk-minor):
+//                     where every chunk's run of a tile's list starts
 //   fl_fill_kernel    one workgroup per chunk, one thread per (triangle, tile) pair: the triangle's rank among the chunk's
 //                     earlier triangles on that tile, so that each tile's list is in primitive order
 //   fl_raster_kernel  one workgroup per tile, one thread per texel: reads its texel once, walks the tile's list in order,
-//                     64 triangles at a time staged in LDS (their row spans and varying set-ups), shades
+//                     64 triangles at a time staged in LDS (their row spans, th_raster.hpp:tri_span, and varying set-ups), shades
 //                     (src/flow-line/index.frag) and blends SRC_ALPHA / ONE_MINUS_SRC_ALPHA in registers, writes back once
 //                     if anything covered it.
 #include "th_ctx.hpp"
+#include "th_raster.hpp"
 
 namespace {
 
@@ -35,8 +37,7 @@ struct FlTri {                             // a set-up triangle
     // dx = 16 x - X0, dy = 16 y - Y0, l1 = (dx e2y - dy e2x) inv, l2 = (dy e1x - dx e1y) inv
     double X0, Y0, e1x, e1y, e2x, e2y, inv;
     float v0[7], d1[7], d2[7];             // varyings (values.rgba, crest.xy, sdf) at vertex 0 and their differences to 1 and 2
-    int n;                                 // clipped polygon vertices (0: draws nothing)
-    int x[7], y[7];                        // snapped, 1/16 texel, texel centres at multiples of 16
+    th::TrianglePoly P;                    // the clipped, snapped polygon (P.n 0: draws nothing)
 };
 
 struct FlParams {
@@ -54,15 +55,6 @@ struct FlParams {
     uint32_t list_cap;                     // its capacity (the host's bound; a write past it is dropped, never made)
     float4 *flow;
 };
-
-__device__ __forceinline__ long long fl_ceil_div(long long a, long long b)     // b > 0
-{
-    long long q = a / b;
-    if (a % b > 0) ++q;
-    return q;
-}
-
-__device__ __forceinline__ int fl_snap(float ndc, float scale, float offset) { return (int)__builtin_rintf(ndc * scale + offset); }
 
 // src/flow-line/index.vert (+ src/flow/apply/state.glsl, src/geom/line/expand/index.glsl), in the shader's order
 __device__ __forceinline__ void fl_vertex(const FlParams &p, const FlPoint &q, int side, float &cx, float &cy, float (&v)[7])
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(256) void fl_setup_kernel(const FlParams p)
         if (p.line_tri[mid] <= t) lo = mid; else hi = mid - 1;
     }
     const int j = t - p.line_tri[lo];                     // strip vertices j, j+1, j+2 of the line
-    float cx[12], cy[12], tx[12], ty[12], v[3][7];
+    float cx[12], cy[12], v[3][7];
     for (int k = 0; k < 3; ++k) {
         const int vert = j + k;
         fl_vertex(p, p.pts[p.line_pt[lo] + (vert >> 1)], vert & 1, cx[k], cy[k], v[k]);
@@ -99,68 +91,30 @@ __global__ __launch_bounds__(256) void fl_setup_kernel(const FlParams p)
     uint32_t bx = 0xffffu, by = 0xffffu;                   // (empty box: x0 = 0xffff > x1 = 0)
     bool finite = true;
     for (int k = 0; k < 3; ++k) finite = finite && __builtin_isfinite(cx[k]) && __builtin_isfinite(cy[k]);
-    int n = finite ? 3 : 0;
     const float wx16 = 8.0f * (float)p.w, wy16 = 8.0f * (float)p.h;
     const float ox = wx16 - 8.0f, oy = wy16 - 8.0f;
     // the snapped unclipped vertices: the varyings' barycentric set-up
     double SX[3], SY[3];
     for (int k = 0; k < 3; ++k) { SX[k] = (double)__builtin_rintf(cx[k] * wx16 + ox); SY[k] = (double)__builtin_rintf(cy[k] * wy16 + oy); }
-    for (int plane = 0; plane < 4 && n >= 3; ++plane) {
-        int q = 0;
+    int X[7], Y[7];
+    const int n = th::tri_clip_snap(cx, cy, finite ? 3 : 0, p.w, p.h, X, Y);
+    T.P.n = 0;
+    if (n) {
+        int minx = X[0], maxx = X[0], miny = Y[0], maxy = Y[0];
         for (int k = 0; k < n; ++k) {
-            const int jn = k == n - 1 ? 0 : k + 1;
-            float di, dj;
-            switch (plane) {
-            case 0: di = 1.0f + cx[k]; dj = 1.0f + cx[jn]; break;
-            case 1: di = 1.0f - cx[k]; dj = 1.0f - cx[jn]; break;
-            case 2: di = 1.0f - cy[k]; dj = 1.0f - cy[jn]; break;
-            default: di = 1.0f + cy[k]; dj = 1.0f + cy[jn]; break;
-            }
-            if (di >= 0.0f) {
-                tx[q] = cx[k]; ty[q] = cy[k]; ++q;
-                if (dj < 0.0f) {
-                    const float Dn = 1.0f / (dj - di);
-                    tx[q] = (dj * cx[k] - di * cx[jn]) * Dn; ty[q] = (dj * cy[k] - di * cy[jn]) * Dn; ++q;
-                }
-            } else if (dj > 0.0f) {
-                const float Dn = 1.0f / (di - dj);
-                tx[q] = (di * cx[jn] - dj * cx[k]) * Dn; ty[q] = (di * cy[jn] - dj * cy[k]) * Dn; ++q;
-            }
+            T.P.x[k] = X[k]; T.P.y[k] = Y[k];
+            minx = min(minx, X[k]); maxx = max(maxx, X[k]); miny = min(miny, Y[k]); maxy = max(maxy, Y[k]);
         }
-        n = q;
-        for (int k = 0; k < n; ++k) { cx[k] = tx[k]; cy[k] = ty[k]; }
-    }
-    T.n = 0;
-    if (n >= 3) {
-        int X[7], Y[7];
-        for (int k = 0; k < n; ++k) { X[k] = fl_snap(cx[k], wx16, ox); Y[k] = fl_snap(cy[k], wy16, oy); }
-        long long area2 = 0;
-        for (int k = 0; k < n; ++k) {
-            const int jn = k + 1 == n ? 0 : k + 1;
-            area2 += (long long)X[k] * Y[jn] - (long long)X[jn] * Y[k];
-        }
-        if (area2 != 0) {
-            if (area2 > 0)
-                for (int a = 0, b = n - 1; a < b; ++a, --b) {
-                    int tmp = X[a]; X[a] = X[b]; X[b] = tmp;
-                    tmp = Y[a]; Y[a] = Y[b]; Y[b] = tmp;
-                }
-            int minx = X[0], maxx = X[0], miny = Y[0], maxy = Y[0];
-            for (int k = 0; k < n; ++k) {
-                T.x[k] = X[k]; T.y[k] = Y[k];
-                minx = min(minx, X[k]); maxx = max(maxx, X[k]); miny = min(miny, Y[k]); maxy = max(maxy, Y[k]);
-            }
-            // texels the spans can reach: ceil(X / 16) <= x < ceil(maxX / 16), the same for rows
-            const int x0 = max((minx + 15) >> 4, 0), x1 = min(((maxx + 15) >> 4) - 1, p.w - 1);
-            const int y0 = max((miny + 15) >> 4, 0), y1 = min(((maxy + 15) >> 4) - 1, p.h - 1);
-            if (x0 <= x1 && y0 <= y1) {
-                T.n = n;
-                bx = (uint32_t)(x0 / kTile) | ((uint32_t)(x1 / kTile) << 16);
-                by = (uint32_t)(y0 / kTile) | ((uint32_t)(y1 / kTile) << 16);
-            }
+        // texels the spans can reach: ceil(X / 16) <= x < ceil(maxX / 16), the same for rows
+        const int x0 = max((minx + 15) >> 4, 0), x1 = min(((maxx + 15) >> 4) - 1, p.w - 1);
+        const int y0 = max((miny + 15) >> 4, 0), y1 = min(((maxy + 15) >> 4) - 1, p.h - 1);
+        if (x0 <= x1 && y0 <= y1) {
+            T.P.n = n;
+            bx = (uint32_t)(x0 / kTile) | ((uint32_t)(x1 / kTile) << 16);
+            by = (uint32_t)(y0 / kTile) | ((uint32_t)(y1 / kTile) << 16);
         }
     }
-    if (T.n) {
+    if (T.P.n) {
         const double e1x = SX[1] - SX[0], e1y = SY[1] - SY[0], e2x = SX[2] - SX[0], e2y = SY[2] - SY[0];
         const double det = e1x * e2y - e2x * e1y;
         T.X0 = SX[0]; T.Y0 = SY[0]; T.e1x = e1x; T.e1y = e1y; T.e2x = e2x; T.e2y = e2y;
@@ -168,7 +122,7 @@ __global__ __launch_bounds__(256) void fl_setup_kernel(const FlParams p)
         for (int k = 0; k < 7; ++k) { T.v0[k] = v[0][k]; T.d1[k] = v[1][k] - v[0][k]; T.d2[k] = v[2][k] - v[0][k]; }
     }
     p.box[2 * t] = bx; p.box[2 * t + 1] = by;
-    if (!T.n) return;
+    if (!T.P.n) return;
     const uint32_t chunk = (uint32_t)t / p.chunk;
     for (uint32_t ty = by & 0xffffu; ty <= (by >> 16); ++ty)
         for (uint32_t tx = bx & 0xffffu; tx <= (bx >> 16); ++tx)
@@ -193,25 +147,6 @@ __device__ __forceinline__ void fl_shade_blend(float4 &d, const double *g, const
     d.x = ox * ow + d.x * da; d.y = oy * ow + d.y * da; d.z = oz * ow + d.z * da; d.w = ow * ow + d.w * da;
 }
 
-// the span of a set-up triangle on one row (the GeometrySpawner triangles' scanline rule): left <= x < right
-__device__ __forceinline__ void fl_span(const FlTri &T, int row, int w, int &left, int &right)
-{
-    left = w; right = 0;
-    for (int e = 0; e < T.n; ++e) {
-        const int en = e + 1 == T.n ? 0 : e + 1;
-        const int Xa = T.x[e], Ya = T.y[e], Xb = T.x[en], Yb = T.y[en];
-        if (Ya == Yb) continue;
-        const bool swap = Yb < Ya;
-        const int X1 = swap ? Xb : Xa, Y1 = swap ? Yb : Ya, X2 = swap ? Xa : Xb, Y2 = swap ? Ya : Yb;
-        if (row < ((Y1 + 15) >> 4) || row >= ((Y2 + 15) >> 4)) continue;
-        const long long DX = X2 - X1, DY = Y2 - Y1;
-        long long ex = fl_ceil_div(DX * (((long long)row << 4) - Y1) + (long long)X1 * DY, 16 * DY);
-        if (ex < 0) ex = 0;
-        if (ex > w) ex = w;
-        if (swap) right = (int)ex; else left = (int)ex;
-    }
-}
-
 // The comparison arm of tools/flow_line_bench.py (TH_FLOWLINE_NAIVE=1): no bins, every texel walks every triangle in
 // order, as the GeometrySpawner's triangle_fill_kernel does.  Same results as the binned path.
 __global__ __launch_bounds__(256) void fl_naive_kernel(const FlParams p)
@@ -223,63 +158,14 @@ __global__ __launch_bounds__(256) void fl_naive_kernel(const FlParams p)
         bool touched = false;
         for (int t = 0; t < p.ntri; ++t) {
             const FlTri &T = p.tris[t];
-            if (!T.n) continue;
             int left, right;
-            fl_span(T, y, p.w, left, right);
+            th::tri_span(T.P.n, T.P.x, T.P.y, y, p.w, left, right);
             if (x < left || x >= right) continue;
             fl_shade_blend(d, &T.X0, T.v0, 16.0 * (double)x, 16.0 * (double)y, p.crest_shape);
             touched = true;
         }
         if (touched) p.flow[texel] = d;
     }
-}
-
-// ---- exclusive scan of a flat u32 array (1024 per block; the block sums by one workgroup) ---------------------------
-constexpr uint32_t kScanBlock = 1024;
-
-__global__ __launch_bounds__(256) void fl_scan_local_kernel(uint32_t *data, uint32_t *sums, uint32_t n)
-{
-    __shared__ uint32_t sh[256];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * 4u;
-    uint32_t v[4], s = 0;
-    for (int k = 0; k < 4; ++k) { v[k] = base + k < n ? data[base + k] : 0u; s += v[k]; }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256u; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - s;
-    for (int k = 0; k < 4; ++k) { if (base + k < n) data[base + k] = run; run += v[k]; }
-    if (threadIdx.x == 255) sums[blockIdx.x] = sh[255];
-}
-
-__global__ __launch_bounds__(1024) void fl_scan_sums_kernel(uint32_t *sums, uint32_t nblocks)
-{
-    __shared__ uint32_t sh[1024];
-    const uint32_t per = (nblocks + 1023u) / 1024u;
-    const uint32_t lo = min(threadIdx.x * per, nblocks), hi = min(lo + per, nblocks);
-    uint32_t s = 0;
-    for (uint32_t k = lo; k < hi; ++k) s += sums[k];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - s;
-    for (uint32_t k = lo; k < hi; ++k) { const uint32_t v = sums[k]; sums[k] = run; run += v; }
-}
-
-__global__ __launch_bounds__(256) void fl_scan_add_kernel(uint32_t *data, const uint32_t *sums, uint32_t n)
-{
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * 4u;
-    const uint32_t add = sums[blockIdx.x];
-    for (int k = 0; k < 4; ++k) if (base + k < n) data[base + k] += add;
 }
 
 // ---- stable fill: a triangle's place on each of its tiles = the chunk's run start + its earlier chunk-mates there --------
@@ -301,18 +187,10 @@ __global__ __launch_bounds__(256) void fl_fill_kernel(const FlParams p)
         run += x0 > x1 ? 0u : (x1 - x0 + 1u) * (y1 - y0 + 1u);
         sarea[k] = run;
     }
-    part[threadIdx.x] = run;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256u; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const uint32_t before = threadIdx.x ? part[threadIdx.x - 1] : 0u;
+    uint32_t pairs;                                        // (the chunk's pairs: the sum of its boxes' areas)
+    const uint32_t before = th::block_scan<256>(part, run, pairs);
     for (uint32_t k = threadIdx.x * per; k < min(m, (threadIdx.x + 1u) * per); ++k) sarea[k] += before;
     __syncthreads();
-    const uint32_t pairs = m ? sarea[m - 1] : 0u;
     for (uint32_t q = threadIdx.x; q < pairs; q += 256u) {
         uint32_t lo = 0, hi = m - 1;                       // the first triangle whose inclusive area sum exceeds q
         while (lo < hi) {
@@ -356,8 +234,9 @@ __global__ __launch_bounds__(256) void fl_raster_kernel(const FlParams p)
         for (uint32_t q = threadIdx.x; q < m * kTile; q += 256u) {
             const uint32_t k = q >> 4;
             const int row = ty * kTile + (int)(q & 15u);
+            const th::TrianglePoly &P = p.tris[p.list[base + k]].P;
             int left, right;
-            fl_span(p.tris[p.list[base + k]], row, p.w, left, right);
+            th::tri_span(P.n, P.x, P.y, row, p.w, left, right);
             span_l[k][q & 15u] = left;
             span_r[k][q & 15u] = right;
         }
@@ -611,9 +490,8 @@ th_status th_flow_lines(th_context *c, const th_flow_line_uniforms *u, const flo
 
     // device scratch: records | table | triangles | boxes | counts | list
     const uint32_t ncount = (uint32_t)(ntiles * nchunks) + 1u;
-    const uint32_t scan_blocks = (ncount + kScanBlock - 1) / kScanBlock;
     const size_t tri_bytes = align256((size_t)ntri * sizeof(FlTri)), box_bytes = align256((size_t)ntri * 8);
-    const size_t cnt_bytes = align256((size_t)ncount * 4), sum_bytes = align256((size_t)scan_blocks * 4);
+    const size_t cnt_bytes = align256((size_t)ncount * 4), sum_bytes = align256((size_t)th::exclusive_scan_sum_words(ncount) * 4);
     const size_t list_bytes = align256((size_t)std::max<uint64_t>(pairs, 1) * 4);
     const size_t need = up_bytes + tri_bytes + box_bytes + cnt_bytes + sum_bytes + list_bytes;
     if (s->dev_bytes < need) {
@@ -656,9 +534,7 @@ th_status th_flow_lines(th_context *c, const th_flow_line_uniforms *u, const flo
         TH_HIP(hipGetLastError());
         return TH_OK;
     }
-    hipLaunchKernelGGL(fl_scan_local_kernel, dim3(scan_blocks), dim3(256), 0, c->stream, p.counts, sums, ncount);
-    hipLaunchKernelGGL(fl_scan_sums_kernel, dim3(1), dim3(1024), 0, c->stream, sums, scan_blocks);
-    hipLaunchKernelGGL(fl_scan_add_kernel, dim3(scan_blocks), dim3(256), 0, c->stream, p.counts, sums, ncount);
+    th::launch_exclusive_scan_u32(p.counts, sums, ncount, c->stream);
     hipLaunchKernelGGL(fl_fill_kernel, dim3(nchunks), dim3(256), (size_t)chunk * 12, c->stream, p);
     hipLaunchKernelGGL(fl_raster_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, p);
     TH_HIP(hipGetLastError());

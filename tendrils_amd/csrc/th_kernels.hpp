@@ -348,6 +348,9 @@ bool loopback_id(const void *id_bytes);
 // joins the communicator `id` names - an RCCL one or an in-process one - as `rank` of `world`
 int comm_init(void **comm, const Transport **transport, const void *id_bytes, size_t bytes, int rank, int world);
 int loopback_init(void **comm, const Transport **transport, const void *id_bytes, size_t bytes, int rank, int world);
+// exclusive scan of n u32 words in place (th_sort.hip: three launches); block_sums: exclusive_scan_sum_words(n) words of scratch
+uint32_t exclusive_scan_sum_words(uint32_t n);
+void launch_exclusive_scan_u32(uint32_t *data, uint32_t *block_sums, uint32_t n, hipStream_t stream);
 // stable LSD radix sort of (key, u32 value) pairs by key bits [begin_bit, end_bit) (th_sort.hip): the passes ping-pong
 // between the (a) and (b) buffers; returns 0 when the result is in (a), 1 when it is in (b)
 constexpr uint32_t kRadixBits = 8;

@@ -1,5 +1,6 @@
 // th_math.hpp - fp32 building blocks of the integrator, shared by host (table
-// construction) and device (kernels).  The translation units that include this
+// construction) and device (kernels), and the workgroup-wide scan every unit's
+// kernels use (block_scan).  The translation units that include this
 // are compiled with -ffp-contract=off: `a * b + c` below is two correctly
 // rounded fp32 operations (what the reference's shader compiler emits); a fused
 // multiply-add appears only where written as th_fma().
@@ -122,5 +123,26 @@ TH_HD float permute_int(float x)
     return th_fma(-289.0f, th_floor(t * kInv289), t);
 }
 TH_HD float mod289_int(float x) { return th_fma(-289.0f, th_floor(x * kInv289), x); }
+
+// ---- workgroup-wide scan ------------------------------------------------------
+// All N threads of the workgroup: `mine` -> its exclusive prefix over the
+// workgroup; `total` (the same on every thread).  lds: N words.  The leading
+// barrier makes the words free to reuse (a loop may call this again at once).
+template <uint32_t N, typename T>
+TH_D T block_scan(T *lds, T mine, T &total)
+{
+    const uint32_t t = threadIdx.x;
+    __syncthreads();
+    lds[t] = mine;
+    __syncthreads();
+    for (uint32_t off = 1; off < N; off <<= 1) {
+        const T a = t >= off ? lds[t - off] : T(0);
+        __syncthreads();
+        lds[t] += a;
+        __syncthreads();
+    }
+    total = lds[N - 1];
+    return lds[t] - mine;
+}
 
 }  // namespace th

@@ -3,6 +3,8 @@
 // (src/particles.js:147-158, src/state/state-at-frame.glsl:12-22), the width-1 line rasteriser, the varyings of the flow
 // pass (src/flow/vert/main.vert:10-17, apply/state.glsl:5-16) and of the view pass (src/render/index.vert:58-100), the
 // per-line records and slow / long line lists, and the two blend targets.  Semantics as pinned in th_deposit.hip.
+// Also the triangle rules that the GeometrySpawner (th_deposit.hip) and the flow lines (th_flowline.hip) share: clip / snap /
+// orient (tri_clip_snap) and the scanline span (tri_span).
 #pragma once
 #include "th_kernels.hpp"
 #include "th_logic.hpp"
@@ -172,6 +174,77 @@ TH_D long long dep_ceil_div(long long a, long long b)     // b > 0
 }
 
 TH_D int dep_snap(float ndc, float scale, float offset) { return (int)__builtin_rintf(ndc * scale + offset); }
+
+// ---- triangles (the GeometrySpawner's, th_deposit.hip; the flow lines', th_flowline.hip) --------------------------------
+// Clip-space vertices 0..n-1 of (cx, cy) (n: 3, or 0 for a triangle the caller rejects) clipped against x >= -1, x <= 1,
+// y <= 1, y >= -1 in that order (cx, cy are the clipper's work space), snapped to 1/16 texel of a w x h target (texel
+// centres at multiples of 16) into X, Y, and put in the one winding the span rule reads (reversed when its doubled area
+// is > 0).  Returns the polygon's vertex count (at most 7): 0 when it draws nothing (clipped away or of zero area).
+TH_D int tri_clip_snap(float (&cx)[12], float (&cy)[12], int n, int w, int h, int (&X)[7], int (&Y)[7])
+{
+    const float wx16 = 8.0f * (float)w, wy16 = 8.0f * (float)h;
+    const float ox = wx16 - 8.0f, oy = wy16 - 8.0f;
+    float tx[12], ty[12];
+    for (int plane = 0; plane < 4 && n >= 3; ++plane) {
+        int q = 0;
+        for (int k = 0; k < n; ++k) {
+            const int j = k == n - 1 ? 0 : k + 1;
+            float di, dj;
+            switch (plane) {
+            case 0: di = 1.0f + cx[k]; dj = 1.0f + cx[j]; break;
+            case 1: di = 1.0f - cx[k]; dj = 1.0f - cx[j]; break;
+            case 2: di = 1.0f - cy[k]; dj = 1.0f - cy[j]; break;
+            default: di = 1.0f + cy[k]; dj = 1.0f + cy[j]; break;
+            }
+            if (di >= 0.0f) {
+                tx[q] = cx[k]; ty[q] = cy[k]; ++q;
+                if (dj < 0.0f) {
+                    const float D = 1.0f / (dj - di);
+                    tx[q] = (dj * cx[k] - di * cx[j]) * D; ty[q] = (dj * cy[k] - di * cy[j]) * D; ++q;
+                }
+            } else if (dj > 0.0f) {
+                const float D = 1.0f / (di - dj);
+                tx[q] = (di * cx[j] - dj * cx[k]) * D; ty[q] = (di * cy[j] - dj * cy[k]) * D; ++q;
+            }
+        }
+        n = q;
+        for (int k = 0; k < n; ++k) { cx[k] = tx[k]; cy[k] = ty[k]; }
+    }
+    if (n < 3) return 0;
+    for (int k = 0; k < n; ++k) { X[k] = dep_snap(cx[k], wx16, ox); Y[k] = dep_snap(cy[k], wy16, oy); }
+    long long area2 = 0;
+    for (int k = 0; k < n; ++k) {
+        const int j = k + 1 == n ? 0 : k + 1;
+        area2 += (long long)X[k] * Y[j] - (long long)X[j] * Y[k];
+    }
+    if (area2 == 0) return 0;
+    if (area2 > 0)
+        for (int a = 0, b = n - 1; a < b; ++a, --b) {
+            int tmp = X[a]; X[a] = X[b]; X[b] = tmp;
+            tmp = Y[a]; Y[a] = Y[b]; Y[b] = tmp;
+        }
+    return n;
+}
+
+// The scanline rule of a snapped polygon (n vertices X, Y as tri_clip_snap leaves them) on texel row `row` of a target
+// w texels wide: it covers left <= x < right.
+TH_D void tri_span(int n, const int *X, const int *Y, int row, int w, int &left, int &right)
+{
+    left = w; right = 0;
+    for (int k = 0; k < n; ++k) {
+        const int kn = k + 1 == n ? 0 : k + 1;
+        const int Xa = X[k], Ya = Y[k], Xb = X[kn], Yb = Y[kn];
+        if (Ya == Yb) continue;
+        const bool swap = Yb < Ya;
+        const int X1 = swap ? Xb : Xa, Y1 = swap ? Yb : Ya, X2 = swap ? Xa : Xb, Y2 = swap ? Ya : Yb;
+        if (row < ((Y1 + 15) >> 4) || row >= ((Y2 + 15) >> 4)) continue;
+        const long long DX = X2 - X1, DY = Y2 - Y1;
+        long long e = dep_ceil_div(DX * (((long long)row << 4) - Y1) + (long long)X1 * DY, 16 * DY);
+        if (e < 0) e = 0;
+        if (e > w) e = w;
+        if (swap) right = (int)e; else left = (int)e;
+    }
+}
 
 struct DepositLine {
     bool draws;

@@ -162,18 +162,11 @@ __global__ __launch_bounds__(256) void sort_scan_local_kernel(uint32_t *data, ui
     uint32_t v[4], s = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { v[k] = base + k < n ? data[base + k] : 0u; s += v[k]; }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256u; o <<= 1) {
-        uint32_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - s;
+    uint32_t total;
+    uint32_t run = block_scan<256>(sh, s, total);
 #pragma unroll
     for (int k = 0; k < 4; ++k) { if (base + k < n) data[base + k] = run; run += v[k]; }
-    if (threadIdx.x == 255) block_sums[blockIdx.x] = sh[255];
+    if (threadIdx.x == 255) block_sums[blockIdx.x] = total;
 }
 
 // exclusive scan of the block sums by ONE workgroup of 1024 threads (each walks a contiguous share)
@@ -184,15 +177,8 @@ __global__ __launch_bounds__(1024) void sort_scan_sums_kernel(uint32_t *block_su
     const uint32_t lo = threadIdx.x * per < nblocks ? threadIdx.x * per : nblocks, hi = lo + per < nblocks ? lo + per : nblocks;
     uint32_t s = 0;
     for (uint32_t k = lo; k < hi; ++k) s += block_sums[k];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-        uint32_t add = threadIdx.x >= o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - s;
+    uint32_t total;
+    uint32_t run = block_scan<1024>(sh, s, total);
     for (uint32_t k = lo; k < hi; ++k) { const uint32_t v = block_sums[k]; block_sums[k] = run; run += v; }
 }
 
@@ -225,13 +211,22 @@ uint32_t radix_blocks(uint32_t n) { return (n + kRadixBlock - 1) / kRadixBlock; 
 
 }  // namespace
 
+uint32_t exclusive_scan_sum_words(uint32_t n) { return (n + kScanBlock - 1) / kScanBlock; }
+
+void launch_exclusive_scan_u32(uint32_t *data, uint32_t *block_sums, uint32_t n, hipStream_t s)
+{
+    const uint32_t blocks = exclusive_scan_sum_words(n);
+    hipLaunchKernelGGL(sort_scan_local_kernel, dim3(blocks), dim3(256), 0, s, data, block_sums, n);
+    hipLaunchKernelGGL(sort_scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, blocks);
+    hipLaunchKernelGGL(sort_scan_add_kernel, dim3(blocks), dim3(256), 0, s, data, block_sums, n);
+}
+
 size_t radix_sort_temp_bytes(uint32_t n, int begin_bit, int end_bit)
 {
     const RadixPlan p = make_plan(begin_bit, end_bit);
     const size_t per_pass = ((size_t)1 << kRadixBits) * radix_blocks(n);
-    const size_t sums = (per_pass + kScanBlock - 1) / kScanBlock;
     (void)p;
-    return (per_pass + sums + 64) * sizeof(uint32_t);
+    return (per_pass + exclusive_scan_sum_words((uint32_t)per_pass) + 64) * sizeof(uint32_t);
 }
 
 // Sorts n pairs by key bits [begin_bit, end_bit), stable.  The passes ping-pong between the (a) and (b) buffers;
@@ -252,11 +247,8 @@ static int radix_sort_pairs(K *keys_a, uint32_t *vals_a, K *keys_b, uint32_t *va
         const uint32_t *vi = (q & 1) ? vals_b : (q == 0 && iota ? nullptr : vals_a);
         uint32_t *vo = (q & 1) ? vals_a : vals_b;
         const uint32_t used = (1u << plan.bits[q]) * nblocks;
-        const uint32_t scan_blocks = (used + kScanBlock - 1) / kScanBlock;
         hipLaunchKernelGGL((radix_hist_kernel<K>), dim3(nblocks), dim3(256), 0, s, ki, n, plan.shift[q], plan.bits[q], nblocks, counts);
-        hipLaunchKernelGGL(sort_scan_local_kernel, dim3(scan_blocks), dim3(256), 0, s, counts, sums, used);
-        hipLaunchKernelGGL(sort_scan_sums_kernel, dim3(1), dim3(1024), 0, s, sums, scan_blocks);
-        hipLaunchKernelGGL(sort_scan_add_kernel, dim3(scan_blocks), dim3(256), 0, s, counts, sums, used);
+        launch_exclusive_scan_u32(counts, sums, used, s);
         hipLaunchKernelGGL((radix_scatter_kernel<K>), dim3(nblocks), dim3(256), 0, s, ki, vi, ko, vo, n, plan.shift[q], plan.bits[q],
                            nblocks, counts);
     }
