@@ -147,7 +147,8 @@ typedef struct th_counters {
     uint64_t particles;      /* texels examined */
     uint64_t live;           /* pos != inert */
     uint64_t nan;            /* any component NaN */
-    uint64_t capped;         /* live and |vel| >= speedLimit*(1 - 2^-20) */
+    uint64_t capped;         /* live, finite and |vel| >= speedLimit*(1 - 2^-20); finite: no component NaN and |vel|, as
+                                fp32 sqrt(z*z + w*w), not infinite - an overflowed speed counts in `live` alone */
     uint64_t respawned;      /* particles (re)spawned into the state ring on this context since th_create: every texel
                                 of a th_spawn_ball pass, the accepted candidates of a th_spawn_sample pass */
     double sum_speed;        /* sum of |vel| over live, finite particles */

@@ -352,7 +352,9 @@ int loopback_init(void **comm, const Transport **transport, const void *id_bytes
 uint32_t exclusive_scan_sum_words(uint32_t n);
 void launch_exclusive_scan_u32(uint32_t *data, uint32_t *block_sums, uint32_t n, hipStream_t stream);
 // stable LSD radix sort of (key, u32 value) pairs by key bits [begin_bit, end_bit) (th_sort.hip): the passes ping-pong
-// between the (a) and (b) buffers; returns 0 when the result is in (a), 1 when it is in (b)
+// between the (a) and (b) buffers; returns 0 when the result is in (a), 1 when it is in (b).  n = 0 returns 0 and writes
+// nothing.  end_bit > begin_bit: an empty range is outside the contract (no caller passes one; the plan would sort by one
+// bit outside the range).
 constexpr uint32_t kRadixBits = 8;
 size_t radix_sort_temp_bytes(uint32_t n, int begin_bit, int end_bit);
 // iota: the values are the elements' positions 0..n-1 (vals_a need not be filled)

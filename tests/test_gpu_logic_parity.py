@@ -4,6 +4,7 @@ EXACT mode: bit-for-bit.  FAST mode: absolute tolerance for one step and a drift
 import numpy as np
 import pytest
 
+import prims
 from helpers import bits_equal, golden, load, state_overrides
 
 pytestmark = pytest.mark.gpu
@@ -314,6 +315,10 @@ def test_statistics_taken_by_the_fused_launch_equal_the_statistics_pass(n, steps
         assert fused["max_speed"] == again["max_speed"] == float(speed[live].max())
         assert abs(fused["sum_speed"] - again["sum_speed"]) <= 1e-12 * again["sum_speed"]
         assert fused["particles"] == n * n
+        # ... and both against the reference of th_counters: `capped`, `nan` and sum_speed too (bound: prims.sum_speed_bound)
+        want = prims.stats_reference(got, limit)
+        prims.assert_counters(again, want, "the statistics pass")
+        prims.assert_counters(fused, want, "the fused launch's statistics")
     t.dispose()
 
 
