@@ -11,7 +11,7 @@
  * th_spawn_image_download and th_slot_order.  Both hosts run row-band-sharded jobs, one process per GPU: the ranks join the
  * library's own communicator (th_comm_unique_id -> th_comm_init; JS: Particles.commUniqueId / commInit) and from then on
  * the path's collectives - the counter all-reduce, the draw()'s exchange, the state gather - are issued by the library over
- * RCCL (th_stats_allreduce, th_draw_sharded, th_state_gather); the host only carries the 128-byte id between its processes.
+ * RCCL (th_stats_allreduce, th_draw_sharded, th_spawn_sample_sharded, th_state_gather); the host only carries the 128-byte id between its processes.
  * The exchange primitives underneath (th_deposit_emit / _merge / _set_halo / _set_owners, th_flow_device_ptr,
  * th_state_device_ptr; device addresses reach JS as BigInt) stay exported for hosts with a transport of their own - the
  * Python host's torch.distributed path, tendrils_amd/sharding.py:draw_sharded - INTEGRATION.md.
@@ -286,6 +286,26 @@ th_status th_flow_device_ptr(th_context *ctx, void **dptr);
  *                       contexts on one device). */
 th_status th_state_gather(th_context *ctx, int32_t buffer);
 th_status th_state_gather_ptr(th_context *ctx, int32_t buffer, void **dptr);
+/* th_spawn_sample on a row-band shard whose source is ring buffer `source` (>= 0), every rank collectively: the taps'
+ * texels are fetched from the ranks that own them; no copy of the whole texture is made or needed.
+ * Candidate n of a particle is seeded with baseSeed + n (frag/best-sample-main.frag:34-38), and baseSeed is made of the
+ * particle's own state, its uv and the time: every tap is known before one is read.  The band is walked in chunks of whole
+ * rows (TH_OPT_SPAWN_CHUNK_ROWS); per chunk every rank computes its taps, parts the ones in other bands by owner, sends
+ * each owner the texel indices (4 bytes a tap), receives the texels (16 bytes a tap) and runs the unchanged apply / test /
+ * pick rounds over them - the band of the unsharded th_spawn_sample (and of the gathered path above), bit for bit, for
+ * every apply mode, sample count, state format and target, the respawned counter included.  Needs balanced bands (as
+ * th_state_gather) and the same uniforms, source, target and TH_OPT_SPAWN_CHUNK_ROWS on every rank.  A rank that fails on
+ * its own (no memory for its scratch; a request outside the band of the rank it went to) makes every rank return an error;
+ * the target's content is then unspecified.  When source and target are the same storage the pass still reads the texels
+ * as they were before it: it renders into a staging band, copied once the last chunk's requests have been answered.
+ * A context without a communicator, or a world of one, runs th_spawn_sample (taps = local_taps, no bytes); so does a
+ * negative source (TH_SOURCE_FLOW, TH_SOURCE_IMAGE: replicated on every rank).  th_spawn_direct stays on the gathered path. */
+th_status th_spawn_sample_sharded(th_context *ctx, const th_spawn_sample_uniforms *u, int32_t source, int32_t target);
+/* What the last th_spawn_sample_sharded of this context did: taps = samples x the band's particles; local_taps of them
+ * fell into this rank's own band; sent_bytes = 4 x the taps it asked other ranks for + 16 x the taps it answered,
+ * received_bytes the mirror image (the count words are not included); chunks = how many pieces the band was walked in. */
+typedef struct th_spawn_info { uint64_t taps, local_taps, sent_bytes, received_bytes; int32_t chunks, reserved; } th_spawn_info;
+th_status th_spawn_query(th_context *ctx, th_spawn_info *out);   /* what the last th_spawn_sample_sharded did */
 
 /* -- statistics, sync, interop ---------------------------------------------- */
 th_status th_stats(th_context *ctx, float speed_limit, th_counters *out);   /* of buffers[0]; synchronises */
@@ -466,7 +486,7 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
 
 /* Per-context switches between equivalent paths (build-defined; no switch changes a result - the parity suites rerun under
  * each, tests/conftest.py).  A context starts from the environment variables of the same names, read by th_create
- * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN;
+ * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS;
  * TH_DRAW=stream|bins sets what TH_DRAW_AUTO means).
  *   TH_OPT_BUCKET          tile-sorted slot order never (0) / always (1) / when it pays (-1, default)
  *   TH_OPT_RESORT_STEPS    re-sort period of single-step launches (default 64)
@@ -488,14 +508,17 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
  *   TH_OPT_INJECT_FAILURE  (TH_TESTING builds only - a release build answers "unknown option"; the one switch that DOES change what a
  *                          call returns) the next th_draw_sharded of THIS context fails on its own at stage 1 (its edge rows; packed rings), 2
  *                          (rasterising its lines) or 3 (making room for what it owns); 4: its binned pass gives up (every rank takes the stream-ordered pass, the draw succeeds);
+ *                          5: the next th_spawn_sample_sharded of THIS context asks another rank for a texel outside that rank's band;
  *                          the switch resets itself.  What is
- *                          tested: every other rank of the job returns an error too instead of waiting in a collective */
+ *                          tested: every other rank of the job returns an error too instead of waiting in a collective
+ *   TH_OPT_SPAWN_CHUNK_ROWS (TH_SPAWN_CHUNK_ROWS) rows of its band that th_spawn_sample_sharded computes, fetches and spawns at a time
+ *                          (default 0: as many as keep every scratch array of the exchange under about 64 MiB); the same on every rank */
 enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH_OPT_FUSE = 3, TH_OPT_GRAPH = 4,
        TH_OPT_FORCE_GENERIC = 5, TH_OPT_DRAW_REUSE = 6, TH_OPT_BINS_POOL = 7,
 #ifdef TH_TESTING
        TH_OPT_INJECT_FAILURE = 8,
 #endif
-       TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11 };
+       TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12 };
 th_status th_option_set(th_context *ctx, int32_t option, int64_t value);
 th_status th_option_get(th_context *ctx, int32_t option, int64_t *value);
 

@@ -94,6 +94,11 @@ class DrawInfo(C.Structure):
                 ("sent_bytes", C.c_uint64), ("received_bytes", C.c_uint64)]
 
 
+class SpawnInfo(C.Structure):
+    _fields_ = [("taps", C.c_uint64), ("local_taps", C.c_uint64), ("sent_bytes", C.c_uint64), ("received_bytes", C.c_uint64),
+                ("chunks", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CommInfo(C.Structure):
     _fields_ = [("active", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32), ("rccl_version", C.c_int32)]
 
@@ -155,6 +160,8 @@ PROTOTYPES = {
     "th_view_device_ptr": (C.c_int32, [_ctx, C.POINTER(C.c_void_p)]),
     "th_state_gather": (C.c_int32, [_ctx, C.c_int32]),
     "th_state_gather_ptr": (C.c_int32, [_ctx, C.c_int32, C.POINTER(C.c_void_p)]),
+    "th_spawn_sample_sharded": (C.c_int32, [_ctx, C.POINTER(SpawnSampleUniforms), C.c_int32, C.c_int32]),
+    "th_spawn_query": (C.c_int32, [_ctx, C.POINTER(SpawnInfo)]),
     "th_stats": (C.c_int32, [_ctx, C.c_float, C.POINTER(Counters)]),
     "th_stats_async": (C.c_int32, [_ctx, C.c_float, C.POINTER(C.c_void_p)]),
     "th_comm_unique_id": (C.c_int32, [C.c_void_p]),

@@ -45,6 +45,7 @@ void options_from_environment(th_options &o)
     o.draw_reuse = number("TH_DRAW_REUSE", 1) != 0;
     o.async_sort = number("TH_ASYNC_SORT", 1) != 0;
     o.skip_unseen = number("TH_SKIP_UNSEEN", 1) != 0;
+    o.spawn_chunk_rows = (int)number("TH_SPAWN_CHUNK_ROWS", 0); if (o.spawn_chunk_rows < 0) o.spawn_chunk_rows = 0;
     o.bins_pool = (uint32_t)number("TH_BINS_POOL", 0);
     o.bins_pages = (int)number("TH_BINS_PAGES", 0); if (o.bins_pages > (int)th::kBinPagesLimit || o.bins_pages < -(int)th::kBinPagesLimit) o.bins_pages = 0;
 }
@@ -256,6 +257,7 @@ th_status th_destroy(th_context *c)
     if (c->side2) (void)hipStreamSynchronize(c->side2);
     if (c->comm) { (void)c->transport->destroy(c->comm); c->comm = nullptr; }
     (void)hipFree(c->d_status); (void)hipFree(c->own_mem);
+    (void)hipFree(c->sp_taps); (void)hipFree(c->sp_asked); (void)hipFree(c->sp_answers); (void)hipFree(c->sp_words);
     thi::flow_lines_free(c);
     for (float4 *b : c->ring) (void)hipFree(b);
     (void)hipFree(c->flow); (void)hipFree(c->flow_dec); (void)hipFree(c->flow3); (void)hipFree(c->targets); (void)hipFree(c->lut_block);
@@ -627,8 +629,9 @@ th_status th_option_set(th_context *c, int32_t option, int64_t value)
     case TH_OPT_ASYNC_SORT: o.async_sort = value != 0; if (!o.async_sort) { if (th_status s = asort_drop(c)) return s; } break;
     case TH_OPT_BINS_POOL: TH_REQUIRE(value >= 0 && value < (1ll << 32), "TH_OPT_BINS_POOL out of range"); o.bins_pool = (uint32_t)value; break;
 #ifdef TH_TESTING
-    case TH_OPT_INJECT_FAILURE: TH_REQUIRE(value >= 0 && value <= 4, "TH_OPT_INJECT_FAILURE takes 0..4"); o.inject_failure = (int)value; break;
+    case TH_OPT_INJECT_FAILURE: TH_REQUIRE(value >= 0 && value <= 5, "TH_OPT_INJECT_FAILURE takes 0..5"); o.inject_failure = (int)value; break;
 #endif
+    case TH_OPT_SPAWN_CHUNK_ROWS: TH_REQUIRE(value >= 0 && value < (1 << 30), "TH_OPT_SPAWN_CHUNK_ROWS takes 0 (by the scratch budget) or a number of rows"); o.spawn_chunk_rows = (int)value; break;
     case TH_OPT_BINS_PAGES:
         TH_REQUIRE(value >= -(int64_t)th::kBinPagesLimit && value <= (int64_t)th::kBinPagesLimit && value != 1 && value != -1, "TH_OPT_BINS_PAGES takes 0, or 2..%u (negative: never widened)", th::kBinPagesLimit);
         o.bins_pages = (int)value;
@@ -662,6 +665,7 @@ th_status th_option_get(th_context *c, int32_t option, int64_t *value)
     case TH_OPT_INJECT_FAILURE: *value = o.inject_failure; break;
 #endif
     case TH_OPT_BINS_PAGES: *value = o.bins_pages; break;
+    case TH_OPT_SPAWN_CHUNK_ROWS: *value = o.spawn_chunk_rows; break;
     default: return fail(TH_ERR_INVALID, "unknown option %d", option);
     }
     return TH_OK;

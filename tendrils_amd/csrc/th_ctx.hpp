@@ -5,7 +5,7 @@
 //   th_step.hip   Particles.step: th_step / th_step_n
 //   th_spawn.hip  the spawners
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
-//   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce
+//   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,8 +54,10 @@ struct th_options {
     bool draw_reuse = true;              // TH_DRAW_REUSE: the stream-ordered view pass reuses the flow pass's geometry
     uint32_t bins_pool = 0;              // TH_BINS_POOL: first size of the binned pipeline's page pool (0: by the target's size)
     int bins_pages = 0;                  // TH_BINS_PAGES: pages a bin's list can grow to at first (0: kBinFirstPages); negative: that many and never more
-    int inject_failure = 0;              // (tests) the next th_draw_sharded fails on THIS rank at stage 1 / 2 / 3: the ranks must all leave
+    int inject_failure = 0;              // (tests) the next th_draw_sharded fails on THIS rank at stage 1 / 2 / 3 (5: the next
+                                         // th_spawn_sample_sharded asks for a texel outside its owner's band): the ranks must all leave
     bool skip_unseen = true;             // TH_SKIP_UNSEEN: draw() skips the blocks of slots whose lines the step saw end up outside the view (th_step.hip)
+    int spawn_chunk_rows = 0;            // TH_SPAWN_CHUNK_ROWS: rows of a band that th_spawn_sample_sharded fetches at a time (0: by the scratch budget)
     bool async_sort = true;              // TH_ASYNC_SORT: a frame loop's re-sort runs beside its draw() instead of inside two of its steps (th_step.hip)
 };
 
@@ -103,6 +105,15 @@ struct th_context {
     size_t x_capacity = 0;
     float4 *gathered = nullptr;          // row-band shard: a copy of the WHOLE particle texture (th_state_gather / _ptr) ...
     const void *gathered_of = nullptr;   // ... of this ring buffer, for the spawners that sample arbitrary particles
+    // th_spawn_sample_sharded (th_shard.hip): per tap of a chunk four u32 arrays and the fetched texels; what the other ranks
+    // ask this one for, and its answers; the counts' words (send 32 | receive 32 | the out-of-band flag)
+    void *sp_taps = nullptr;
+    size_t sp_taps_cap = 0;
+    uint32_t *sp_asked = nullptr;
+    float4 *sp_answers = nullptr;
+    size_t sp_asked_cap = 0;
+    unsigned long long *sp_words = nullptr;
+    th_spawn_info last_spawn{};          // th_spawn_query
     void *comm = nullptr;                // communicator of the job's ranks (th_comm_init), one rank per context ...
     const th::Transport *transport = nullptr;   // ... and how its ranks exchange bytes (RCCL; in-process for tests)
     uint32_t *d_status = nullptr;        // the word the ranks agree on (agree_status)

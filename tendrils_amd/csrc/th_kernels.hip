@@ -1104,46 +1104,74 @@ void launch_spawn_direct(const SpawnSampleParams &p, hipStream_t s)
     if (p.count) hipLaunchKernelGGL(spawn_direct_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
 }
 
-// src/spawn/pixels/frag/best-sample-main.frag:21-46 with head.frag:28-34
+// src/spawn/pixels/frag/best-sample-main.frag:21-46 with head.frag:28-34, in two parts: WHERE candidate n of a particle taps
+// the spawn data (its seed is baseSeed + n, and baseSeed is made of the particle's own state, its uv and the time - no tap
+// depends on which candidate won before it), and what the particle makes of the texel found there.  spawn_sample_kernel is
+// the two in a row; a row-band shard (spawn_shard_*_kernel below) fetches the texels from their owners in between.
+struct SpawnSeed { float b0, b1, b2, b3, tt; };
+
+TH_D SpawnSeed spawn_sample_seed(const th_spawn_sample_uniforms &u, float4 st, uint32_t idx, uint32_t width, uint32_t row0, float wf, float hf)
+{
+    uint32_t y = idx / width, x = idx - y * width;
+    float uvx = ((float)x + 0.5f) / wf, uvy = ((float)(y + row0) + 0.5f) / hf;
+    SpawnSeed s;
+    s.tt = u.time * 0.001f;
+    float add = 1.2345f + s.tt;
+    s.b0 = st.x + uvx + add; s.b1 = st.y + uvy + add; s.b2 = st.z + uvx + add; s.b3 = st.w + uvy + add;
+    return s;
+}
+
+// candidate n's tap: the sample position and the texel of the dw x dh spawn data it reads (row ty, column tx: ty * dw + tx)
+TH_D void spawn_sample_tap(const SpawnSeed &s, int n, float dwf, float dhf, float dwm1, float dhm1, float &su, float &sv, int &tx, int &ty)
+{
+    float fn = (float)n;
+    su = mod_glsl(random_glsl(s.b0 + fn, s.b1 + fn), 1.0f);
+    sv = mod_glsl(random_glsl(s.b2 + fn, s.b3 + fn), 1.0f);
+    tx = nearest_texel_f32(su, dwf, dwm1);
+    ty = nearest_texel_f32(sv, dhf, dhm1);
+}
+
+// ... and the rest of the round: spawnToPos, the apply, the test; true when the candidate replaced `st`
+TH_D bool spawn_sample_pick(const th_spawn_sample_uniforms &u, float tt, float su, float sv, float4 t, float4 &st)
+{
+    float px, py;
+    spawn_to_pos(u, su, sv, tt, px, py);
+    float4 other;
+    if (u.apply == 3) {            // bright-sample.frag -> apply/brightest.glsl:11-15 (GeometrySpawner)
+        float sc = t.x * t.z + t.y * t.w;
+        float ang = mod_glsl(random_glsl(su * sc, sv * sc), 1.0f) * 6.28318530717958647692f;
+        float sn, cs;
+        sincos_pinned(ang, sn, cs);
+        float lum = (t.x * 0.299f + t.y * 0.587f) + t.z * 0.114f;
+        other = make_float4(px, py, (cs * lum) * t.w, (sn * lum) * t.w);
+    } else if (u.apply == 2) {     // best-sample.frag: colour apply over the vignette pass
+        other = spawn_apply_color(t, spawn_vignette(su, sv), u.time, px, py);
+    } else if (u.apply == 0) {     // apply/flow.glsl: vec4(pos, getFlow(pixel, time, decay))
+        float k = __builtin_fmaxf(0.0f, 1.0f - ((u.time - t.z) * u.flowDecay));
+        other = make_float4(px, py, t.x * k, t.y * k);
+    } else {                       // data-sample: identity after the vignette pass
+        float vg = spawn_vignette(su, sv);
+        other = make_float4(t.x * vg, t.y * vg, t.z * vg, t.w * vg);
+    }
+    float4 cand = make_float4(other.x, other.y, other.z * u.speed, other.w * u.speed);
+    float tc = st.z * st.z + st.w * st.w, tn = cand.z * cand.z + cand.w * cand.w;
+    if (!(tc > u.bias * tn)) { st = cand; return true; }
+    return false;
+}
+
 __global__ __launch_bounds__(256) void spawn_sample_kernel(const SpawnSampleParams p)
 {
     const th_spawn_sample_uniforms &u = p.u;
     const float dwf = (float)p.dw, dhf = (float)p.dh, dwm1 = (float)(p.dw - 1), dhm1 = (float)(p.dh - 1);
     for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < p.count; idx += gridDim.x * 256u) {
-        uint32_t y = idx / p.width, x = idx - y * p.width;
-        float uvx = ((float)x + 0.5f) / p.wf, uvy = ((float)(y + p.row0) + 0.5f) / p.hf;
         float4 st = p.particles[idx];
-        float tt = u.time * 0.001f;
-        float add = 1.2345f + tt;
-        float b0 = st.x + uvx + add, b1 = st.y + uvy + add, b2 = st.z + uvx + add, b3 = st.w + uvy + add;
+        const SpawnSeed seed = spawn_sample_seed(u, st, idx, p.width, p.row0, p.wf, p.hf);
         bool took = false;
         for (int n = 0; n < u.samples; ++n) {
-            float fn = (float)n;
-            float su = mod_glsl(random_glsl(b0 + fn, b1 + fn), 1.0f);
-            float sv = mod_glsl(random_glsl(b2 + fn, b3 + fn), 1.0f);
-            float px, py;
-            spawn_to_pos(u, su, sv, tt, px, py);
-            float4 t = p.data[nearest_texel_f32(sv, dhf, dhm1) * p.dw + nearest_texel_f32(su, dwf, dwm1)];
-            float4 other;
-            if (u.apply == 3) {            // bright-sample.frag -> apply/brightest.glsl:11-15 (GeometrySpawner)
-                float sc = t.x * t.z + t.y * t.w;
-                float ang = mod_glsl(random_glsl(su * sc, sv * sc), 1.0f) * 6.28318530717958647692f;
-                float sn, cs;
-                sincos_pinned(ang, sn, cs);
-                float lum = (t.x * 0.299f + t.y * 0.587f) + t.z * 0.114f;
-                other = make_float4(px, py, (cs * lum) * t.w, (sn * lum) * t.w);
-            } else if (u.apply == 2) {     // best-sample.frag: colour apply over the vignette pass
-                other = spawn_apply_color(t, spawn_vignette(su, sv), u.time, px, py);
-            } else if (u.apply == 0) {     // apply/flow.glsl: vec4(pos, getFlow(pixel, time, decay))
-                float k = __builtin_fmaxf(0.0f, 1.0f - ((u.time - t.z) * u.flowDecay));
-                other = make_float4(px, py, t.x * k, t.y * k);
-            } else {                       // data-sample: identity after the vignette pass
-                float vg = spawn_vignette(su, sv);
-                other = make_float4(t.x * vg, t.y * vg, t.z * vg, t.w * vg);
-            }
-            float4 cand = make_float4(other.x, other.y, other.z * u.speed, other.w * u.speed);
-            float tc = st.z * st.z + st.w * st.w, tn = cand.z * cand.z + cand.w * cand.w;
-            if (!(tc > u.bias * tn)) { st = cand; took = true; }
+            float su, sv;
+            int tx, ty;
+            spawn_sample_tap(seed, n, dwf, dhf, dwm1, dhm1, su, sv, tx, ty);
+            took |= spawn_sample_pick(u, seed.tt, su, sv, p.data[ty * p.dw + tx], st);
         }
         p.out[idx] = st;
         const unsigned long long wave = __ballot(took);                 // statistics only: one atomic per wave
@@ -1155,6 +1183,120 @@ __global__ __launch_bounds__(256) void spawn_sample_kernel(const SpawnSamplePara
 void launch_spawn_sample(const SpawnSampleParams &p, hipStream_t s)
 {
     if (p.count) hipLaunchKernelGGL(spawn_sample_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
+}
+
+// ---- the same pass on a row-band shard whose spawn data is the particle texture (th_shard.hip: th_spawn_sample_sharded) ------
+// The band is walked in chunks of whole rows; tap (k, n) of a chunk - particle k of the chunk, candidate n - has the ordinal
+// n * count + k.  A texel of row ty belongs to the rank that holds that row: the balanced bands of sharding.shard_rows.
+TH_D uint32_t shard_owner_of_row(uint32_t row, uint32_t base, uint32_t extra)
+{
+    const uint32_t wide = extra * (base + 1u);                           // rows held by the ranks with one row more
+    return row < wide ? row / (base + 1u) : extra + (row - wide) / (base ? base : 1u);
+}
+
+// 1 - every tap's owner and texel; how many taps each owner is asked for (this rank's own share among them)
+__global__ __launch_bounds__(256) void spawn_shard_tap_kernel(const SpawnShardParams p)
+{
+    const th_spawn_sample_uniforms &u = p.u;
+    const float dwf = (float)p.width, dhf = (float)p.global_rows, dwm1 = (float)(p.width - 1u), dhm1 = (float)(p.global_rows - 1u);
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long mine = 0;                                         // lane r: taps of this wave that rank r owns
+    // (every lane of a wave walks the same rounds: the ballots below want all 64 of them)
+    for (uint32_t first = blockIdx.x * 256u; first < p.count; first += gridDim.x * 256u) {
+        const uint32_t k = first + threadIdx.x;
+        const bool valid = k < p.count;
+        const uint32_t idx = p.first + (valid ? k : 0u);
+        const SpawnSeed seed = spawn_sample_seed(u, p.particles[idx], idx, p.width, p.row0, p.wf, p.hf);
+        for (int n = 0; n < u.samples; ++n) {
+            float su, sv;
+            int tx, ty;
+            spawn_sample_tap(seed, n, dwf, dhf, dwm1, dhm1, su, sv, tx, ty);
+            // (an owner is a rank: whatever the arithmetic makes of a row, the request goes to somebody who checks it against its band)
+            const uint32_t owner = valid ? min(shard_owner_of_row((uint32_t)ty, p.base, p.extra), p.world - 1u) : 0xffffffffu;
+            if (valid) {
+                const size_t t = (size_t)n * p.count + k;
+                p.owner[t] = owner;
+                p.texel[t] = (uint32_t)ty * p.width + (uint32_t)tx;
+            }
+            for (uint32_t r = 0; r < p.world; ++r) {
+                const unsigned long long theirs = __ballot(owner == r);     // 64 lanes: a 64-bit mask
+                if (lane == r) mine += (unsigned long long)__builtin_popcountll(theirs);
+            }
+        }
+    }
+    if (lane < p.world && mine) atomicAdd(&p.counts[lane], mine);
+}
+
+// 2 - behind the stable partition by owner (one pass of the radix sort over the owner bits, the values the taps' ordinals):
+// the texel asked for at every place of the parted order, and every tap's place in it
+__global__ __launch_bounds__(256) void spawn_shard_request_kernel(const uint32_t *ordinal, const uint32_t *texel, uint32_t *request, uint32_t *place, uint32_t n)
+{
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
+        const uint32_t t = ordinal[j];
+        request[j] = texel[t];
+        place[t] = j;
+    }
+}
+
+// 3 - on the owner: the texels the other ranks asked for, out of this rank's band of the source buffer (texel order, f32)
+__global__ __launch_bounds__(256) void spawn_shard_answer_kernel(const float4 *band, uint32_t first_texel, uint32_t texels, const uint32_t *request,
+                                                                  float4 *answer, uint32_t n, uint32_t *outside)
+{
+    bool bad = false;
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < n; j += gridDim.x * 256u) {
+        const uint32_t at = request[j] - first_texel;                    // (below the band: wraps to something large)
+        const bool in = at < texels;
+        bad |= !in;
+        answer[j] = in ? band[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(outside, 1u);
+}
+
+// 4 - the rounds of the pass over the fetched texels (this rank's own straight from its band), candidate by candidate
+__global__ __launch_bounds__(256) void spawn_shard_pick_kernel(const SpawnShardParams p)
+{
+    const th_spawn_sample_uniforms &u = p.u;
+    const float dwf = (float)p.width, dhf = (float)p.global_rows, dwm1 = (float)(p.width - 1u), dhm1 = (float)(p.global_rows - 1u);
+    const uint32_t band_first = p.row0 * p.width, band_texels = p.rows * p.width;
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < p.count; k += gridDim.x * 256u) {
+        const uint32_t idx = p.first + k;
+        float4 st = p.particles[idx];
+        const SpawnSeed seed = spawn_sample_seed(u, st, idx, p.width, p.row0, p.wf, p.hf);
+        bool took = false;
+        for (int n = 0; n < u.samples; ++n) {
+            float su, sv;
+            int tx, ty;
+            spawn_sample_tap(seed, n, dwf, dhf, dwm1, dhm1, su, sv, tx, ty);
+            const uint32_t at = ((uint32_t)ty * p.width + (uint32_t)tx) - band_first;
+            const float4 t = at < band_texels ? p.data[at] : p.fetched[p.place[(size_t)n * p.count + k]];
+            took |= spawn_sample_pick(u, seed.tt, su, sv, t, st);
+        }
+        p.out[idx] = st;
+        const unsigned long long wave = __ballot(took);                 // statistics only: one atomic per wave
+        if (wave != 0ull && (threadIdx.x & 63u) == (unsigned)__builtin_ctzll(wave))
+            atomicAdd(p.accepted, (unsigned long long)__builtin_popcountll(wave));
+    }
+}
+
+void launch_spawn_shard_taps(const SpawnShardParams &p, hipStream_t s)
+{
+    if (p.count) hipLaunchKernelGGL(spawn_shard_tap_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
+}
+
+void launch_spawn_shard_requests(const uint32_t *ordinal, const uint32_t *texel, uint32_t *request, uint32_t *place, uint32_t n, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(spawn_shard_request_kernel, dim3(grid_for(n, 8)), dim3(256), 0, s, ordinal, texel, request, place, n);
+}
+
+void launch_spawn_shard_answers(const float4 *band, uint32_t first_texel, uint32_t texels, const uint32_t *request, float4 *answer, uint32_t n,
+                                uint32_t *outside, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(spawn_shard_answer_kernel, dim3(grid_for(n, 8)), dim3(256), 0, s, band, first_texel, texels, request, answer, n, outside);
+}
+
+void launch_spawn_shard_pick(const SpawnShardParams &p, hipStream_t s)
+{
+    if (p.count) hipLaunchKernelGGL(spawn_shard_pick_kernel, dim3(grid_for(p.count, 8)), dim3(256), 0, s, p);
 }
 
 // ---------------------------------------------------------------------------

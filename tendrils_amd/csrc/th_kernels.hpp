@@ -116,6 +116,24 @@ struct SpawnSampleParams {
     unsigned long long *accepted;   // += particles that took a candidate
 };
 
+// th_spawn_sample on a row-band shard whose spawn data is the particle texture (th_kernels.hip: spawn_shard_*_kernel): one
+// chunk of whole rows of the band, its taps fetched from the ranks that own them
+struct SpawnShardParams {
+    const float4 *particles;     // buffers[1], this band, texel order
+    float4 *out;                 // the target, this band
+    const float4 *data;          // this band of the source buffer (texel order, f32)
+    uint32_t first, count;       // the chunk: particles [first, first + count) of the band
+    uint32_t width, row0, rows, global_rows;
+    float wf, hf;
+    uint32_t world, base, extra; // balanced bands: global_rows / world rows each, the first global_rows % world ranks one more
+    th_spawn_sample_uniforms u;
+    unsigned long long *accepted;
+    uint32_t *owner, *texel;     // per tap (ordinal n * count + k): the rank that holds its texel, the texel (global index)
+    unsigned long long *counts;  // [world] taps per owner
+    const uint32_t *place;       // per tap: its place in the order parted by owner - and in `fetched`
+    const float4 *fetched;       // the texels the owners sent back
+};
+
 // flow deposit (th_deposit.hip): draw()'s flow pass
 // key of a fragment in the sharded deposit: 24 texel bits above the 32-bit stream index, the owner rank above them
 constexpr int kOwnerShift = 56;
@@ -377,6 +395,11 @@ void launch_draw_blend64(float4 *flow, uchar4 *view, const unsigned long long *k
 void launch_spawn_ball(const SpawnBallParams &p, hipStream_t stream);
 void launch_spawn_sample(const SpawnSampleParams &p, hipStream_t stream);
 void launch_spawn_direct(const SpawnSampleParams &p, hipStream_t stream);
+void launch_spawn_shard_taps(const SpawnShardParams &p, hipStream_t stream);
+void launch_spawn_shard_requests(const uint32_t *ordinal, const uint32_t *texel, uint32_t *request, uint32_t *place, uint32_t n, hipStream_t stream);
+void launch_spawn_shard_answers(const float4 *band, uint32_t first_texel, uint32_t texels, const uint32_t *request, float4 *answer, uint32_t n,
+                                uint32_t *outside, hipStream_t stream);      // *outside |= 1: a request beyond [first_texel, first_texel + texels)
+void launch_spawn_shard_pick(const SpawnShardParams &p, hipStream_t stream);
 constexpr int kStatsBlocks = 1024;
 
 }  // namespace th

@@ -1,5 +1,5 @@
 // th_shard.hip - row-band shards: the draw() exchange (emit by owner, merge, th_draw_sharded), the job's
-// communicator, the particle-texture gather of the spawners, the counter all-reduce.
+// communicator, the particle-texture gather of the spawners, the counter all-reduce, the sampled spawn that fetches its taps.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -180,13 +180,14 @@ static th_status injected(th_context *, int) { return TH_OK; }
 static bool injected_give_up(th_context *) { return false; }
 #endif
 
-static th_status peer_failure(th_context *c, int who, const char *stage)
+static th_status peer_failure(th_context *c, int who, const char *stage, bool spawn = false)
 {
+    if (spawn) return fail(TH_ERR_UNSUPPORTED, "sharded spawn: rank %d failed while %s (this rank, %d, had no error of its own)", who, stage, c->comm_rank);
     return fail(TH_ERR_UNSUPPORTED, "sharded draw: rank %d failed while %s (this rank, %d, had no error of its own); nothing was blended", who, stage, c->comm_rank);
 }
 
 // every rank hands in its status; all of them return TH_OK, or none does (a failing rank returns its own error)
-static th_status agree_status(th_context *c, th_status mine, const char *stage)
+static th_status agree_status(th_context *c, th_status mine, const char *stage, bool spawn = false)
 {
     if (c->comm_world <= 1) return mine;
     const std::string why = mine != TH_OK ? last_error() : std::string();
@@ -200,7 +201,7 @@ static th_status agree_status(th_context *c, th_status mine, const char *stage)
     TH_HIP(e);
     if ((worst >> 16) == 1u) return kRetryInStreamOrder;              // (every rank returns this together)
     if (mine != TH_OK) { last_error() = why; return mine; }
-    if (worst) return peer_failure(c, c->comm_world - (int)(worst & 0xffffu), stage);
+    if (worst) return peer_failure(c, c->comm_world - (int)(worst & 0xffffu), stage, spawn);
     return TH_OK;
 }
 
@@ -678,6 +679,205 @@ th_status th_state_gather(th_context *c, int32_t buffer)
     if (c->transport->allgather_bytes(c->comm, data, c->gathered, bytes.data(), offset.data(), c->comm_rank, world, c->stream))
         return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
     c->gathered_of = c->ring[(size_t)buffer];
+    return TH_OK;
+}
+
+// ---- th_spawn_sample on a row-band shard, the taps' texels fetched from the ranks that own them ------------------------------
+// (th_kernels.hip: spawn_shard_*_kernel.)  Per chunk of whole rows: taps -> stable partition by owner -> counts, texel indices
+// and texels change hands over the context's transport -> the pass's rounds.  What can fail on one rank alone - its scratch,
+// a request outside the band of the rank it went to - is agreed on before the next exchange (agree_status): all leave together.
+constexpr size_t kSpawnArrayBudget = (size_t)64 << 20;      // bytes of the largest per-tap array (the fetched texels) of one chunk
+constexpr size_t kSpawnTapBytes = 4 * sizeof(uint32_t) + sizeof(float4);
+
+// rows of a band fetched at a time: the same on every rank (made of the texture's width, the sample count and the option alone)
+static uint32_t spawn_chunk_rows(const th_context *c, int samples)
+{
+    const size_t per_row = (size_t)c->cfg.width * (size_t)std::max(samples, 1);
+    size_t rows = c->opt.spawn_chunk_rows > 0 ? (size_t)c->opt.spawn_chunk_rows : kSpawnArrayBudget / sizeof(float4) / per_row;
+    rows = std::min(rows, (((size_t)1 << 30) / per_row));          // (ordinals and sort sizes are 32-bit)
+    return (uint32_t)std::max<size_t>(rows, 1);
+}
+
+static void spawn_info_local(th_context *c, int samples)
+{
+    c->last_spawn = th_spawn_info{};
+    c->last_spawn.taps = c->last_spawn.local_taps = (uint64_t)std::max(samples, 0) * c->texels();
+    c->last_spawn.chunks = 1;
+}
+
+th_status th_spawn_sample_sharded(th_context *c, const th_spawn_sample_uniforms *u, int32_t source, int32_t target)
+{
+    if (th_status s = use(c)) return s;
+    TH_REQUIRE(u, "null uniforms");
+    if (source < 0 || !c->comm || c->comm_world <= 1) {
+        // the spawn data is replicated (flow, image), or the band is the whole texture: the plain pass
+        if (th_status s = th_spawn_sample(c, u, source, target)) return s;
+        spawn_info_local(c, u->samples);
+        return TH_OK;
+    }
+    // what follows is the same on every rank (a host error is not agreed on: every rank makes it)
+    TH_REQUIRE(u->samples >= 0 && u->samples <= 64, "samples out of range");
+    TH_REQUIRE(u->apply >= 0 && u->apply <= 3, "unknown apply mode %d", u->apply);
+    TH_REQUIRE(c->ring.size() >= 2, "spawn pass needs at least 2 state buffers (have %zu)", c->ring.size());
+    TH_REQUIRE(source < (int32_t)c->ring.size(), "bad spawnData source %d", source);
+    TH_REQUIRE(target == TH_TARGET_RING || target == TH_TARGET_TARGETS || (target >= 0 && target < (int32_t)c->ring.size()),
+               "bad render target %d (ring has %zu buffers)", target, c->ring.size());
+    const int world = c->comm_world, rank = c->comm_rank, W = c->cfg.width, H = c->cfg.global_height, samples = u->samples;
+    TH_REQUIRE(world <= 32, "the taps are parted for up to 32 ranks");
+    TH_REQUIRE((uint64_t)W * (uint64_t)H < (1ull << 32), "a texel index travels in 32 bits: %dx%d is too large", W, H);
+    const int base = H / world, extra = H % world;
+    {   // the bands of sharding.shard_rows, as th_state_gather checks them
+        const int rows = base + (rank < extra ? 1 : 0), row0 = rank * base + std::min(rank, extra);
+        TH_REQUIRE(rows == c->cfg.height && row0 == c->cfg.row0, "this context holds rows %d..%d, rank %d of %d balanced bands holds %d..%d",
+                   c->cfg.row0, c->cfg.row0 + c->cfg.height, rank, world, row0, row0 + rows);
+    }
+    const uint32_t chunk_rows = spawn_chunk_rows(c, samples), longest = (uint32_t)(base + (extra ? 1 : 0));
+    const uint32_t chunks = std::max(1u, (longest + chunk_rows - 1u) / chunk_rows);
+    const uint32_t my_rows = (uint32_t)c->cfg.height;
+    c->last_spawn = th_spawn_info{};
+    c->last_spawn.chunks = (int32_t)chunks;
+
+    // ---- this rank's buffers: the pass's views of the ring, the target (a staging band when it is the source's storage),
+    // scratch for the longest chunk - rank-local, agreed on
+    float4 *out = nullptr, *rt = nullptr, *particles = nullptr, *data = nullptr;
+    uint32_t *tap_owner = nullptr, *tap_texel = nullptr, *sorted_owner = nullptr, *sorted_ordinal = nullptr;
+    float4 *fetched = nullptr;
+    bool staged = false;
+    auto prepare = [&]() -> th_status {
+        if (th_status s = ensure_identity(c)) return s;          // bands are read, asked for and answered in texel order
+        if (th_status s = resolve_target(c, target, true, &out)) return s;
+        if (th_status s = render_target(c, out, 0, &rt)) return s;
+        // (`source` names the buffer in the ring order the pass sees: after the rotation)
+        staged = rt == out && out == c->ring[(size_t)source];
+        if (staged) { if (th_status s = staging(c, 0, &rt)) return s; }
+        if (th_status s = unpacked_view(c, c->ring[1], 1, &particles)) return s;
+        if (source == 1) data = particles;
+        else if (th_status s = unpacked_view(c, c->ring[(size_t)source], 2, &data)) return s;
+        const size_t taps = (size_t)std::min(chunk_rows, my_rows) * (size_t)W * (size_t)samples;
+        if (c->sp_taps_cap < taps) {
+            TH_HIP(hipStreamSynchronize(c->stream));
+            (void)hipFree(c->sp_taps); c->sp_taps = nullptr; c->sp_taps_cap = 0;
+            TH_HIP(hipMalloc(&c->sp_taps, taps * kSpawnTapBytes));
+            c->sp_taps_cap = taps;
+        }
+        fetched = static_cast<float4 *>(c->sp_taps);                // (the 16-byte array first)
+        tap_owner = reinterpret_cast<uint32_t *>(fetched + c->sp_taps_cap);
+        tap_texel = tap_owner + c->sp_taps_cap; sorted_owner = tap_texel + c->sp_taps_cap; sorted_ordinal = sorted_owner + c->sp_taps_cap;
+        if (!c->sp_words) TH_HIP(hipMalloc((void **)&c->sp_words, 66 * sizeof(unsigned long long)));
+        if (taps) if (th_status s = deposit_temp(c, th::radix_sort_temp_bytes((uint32_t)taps, 0, 5))) return s;
+        return TH_OK;
+    };
+    if (th_status s = agree_status(c, prepare(), "preparing its band", true)) return s;
+    unsigned long long *sendc = c->sp_words, *recvc = c->sp_words + 32;
+    uint32_t *outside = reinterpret_cast<uint32_t *>(c->sp_words + 64);
+    int owner_bits = 1;
+    while ((1 << owner_bits) < world) ++owner_bits;
+
+    th::SpawnShardParams p{};
+    p.particles = particles; p.out = rt; p.data = data;
+    p.width = (uint32_t)W; p.row0 = (uint32_t)c->cfg.row0; p.rows = my_rows; p.global_rows = (uint32_t)H;
+    p.wf = (float)W; p.hf = (float)H;
+    p.world = (uint32_t)world; p.base = (uint32_t)base; p.extra = (uint32_t)extra;
+    p.u = *u;
+    p.accepted = c->d_respawned + (target == TH_TARGET_TARGETS ? 1 : 0);
+    p.owner = tap_owner; p.texel = tap_texel; p.counts = sendc;
+    p.fetched = fetched;
+
+    std::vector<size_t> scount((size_t)world), soff((size_t)world), rcount((size_t)world), roff((size_t)world), one((size_t)world, 1), idx((size_t)world);
+    for (int r = 0; r < world; ++r) idx[(size_t)r] = (size_t)r;
+    for (uint32_t chunk = 0; chunk < chunks; ++chunk) {
+        // (a rank with a shorter band joins the last chunks' exchanges with nothing to ask for)
+        const uint32_t row_lo = std::min(my_rows, chunk * chunk_rows), row_hi = std::min(my_rows, row_lo + chunk_rows);
+        p.first = row_lo * (uint32_t)W; p.count = (row_hi - row_lo) * (uint32_t)W;
+        const uint32_t taps = p.count * (uint32_t)samples;
+        // stage 1 - the chunk's taps, parted by owner (stable: every owner's part in ordinal order); the counts change hands
+        uint32_t *request = tap_owner, *place = sorted_owner;        // (the sort's key buffers, free once it has run)
+        auto stage1 = [&]() -> th_status {
+            TH_HIP(hipMemsetAsync(c->sp_words, 0, 66 * sizeof(unsigned long long), c->stream));
+            if (!taps) return TH_OK;
+            th::launch_spawn_shard_taps(p, c->stream);
+            // one pass over the owner bits: the result lands in the second pair of buffers
+            (void)th::launch_radix_sort_u32(tap_owner, nullptr, sorted_owner, sorted_ordinal, taps, 0, owner_bits, c->dep_temp, true, c->stream);
+            th::launch_spawn_shard_requests(sorted_ordinal, tap_texel, request, place, taps, c->stream);
+            TH_HIP(hipGetLastError());
+            return TH_OK;
+        };
+        th_status mine = stage1();
+        if (c->transport->alltoallv(c->comm, sendc, one.data(), idx.data(), recvc, one.data(), idx.data(), sizeof(unsigned long long), world, c->stream))
+            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+        std::vector<unsigned long long> words(64, 0ull);
+        {
+            const std::string why = mine != TH_OK ? last_error() : std::string();
+            if (th_status s = read_back(c, words.data(), c->sp_words, words.size() * sizeof(unsigned long long))) return s;
+            if (mine != TH_OK) last_error() = why;
+        }
+        size_t at = 0, arriving = 0, asked = 0;
+        for (int r = 0; r < world; ++r) {
+            const size_t mine_for_r = mine == TH_OK ? (size_t)words[(size_t)r] : 0, theirs = (size_t)words[32 + (size_t)r];
+            soff[(size_t)r] = at; at += mine_for_r;
+            scount[(size_t)r] = r == rank ? 0 : mine_for_r;
+            rcount[(size_t)r] = r == rank ? 0 : theirs;
+            roff[(size_t)r] = arriving; arriving += rcount[(size_t)r];
+            asked += scount[(size_t)r];
+        }
+        // stage 2 - room for what the others ask of this rank; the last thing before the requests travel that can fail here alone
+        auto stage2 = [&]() -> th_status {
+            if (at != (size_t)taps) return fail(TH_ERR_HIP, "the owners' counts (%zu) do not add up to the chunk's %u taps", at, taps);
+            if (arriving >= ((size_t)1 << 31)) return fail(TH_ERR_UNSUPPORTED, "too many requests for one owner");
+            if (c->sp_asked_cap < arriving) {
+                (void)hipFree(c->sp_asked); (void)hipFree(c->sp_answers);
+                c->sp_asked = nullptr; c->sp_answers = nullptr; c->sp_asked_cap = 0;
+                const size_t cap = arriving + arriving / 4 + 1024;
+                TH_HIP(hipMalloc((void **)&c->sp_asked, cap * sizeof(uint32_t)));
+                TH_HIP(hipMalloc((void **)&c->sp_answers, cap * sizeof(float4)));
+                c->sp_asked_cap = cap;
+            }
+#ifdef TH_TESTING
+            if (c->opt.inject_failure == 5 && asked) {          // the first request that leaves: a texel of THIS rank's band
+                c->opt.inject_failure = 0;
+                size_t first = 0;
+                for (int r = 0; r < world; ++r) if (scount[(size_t)r]) { first = soff[(size_t)r]; break; }
+                th::launch_exchange_word(request + first, (uint32_t)c->cfg.row0 * (uint32_t)W, c->stream);
+                TH_HIP(hipGetLastError());
+            }
+#endif
+            return TH_OK;
+        };
+        if (mine == TH_OK) mine = stage2();
+        if (th_status s = agree_status(c, mine, "parting its taps and making room for the requests", true)) return s;
+        // stage 3 - the requests travel; every owner answers out of its band, and says so when it was asked for something else
+        if (c->transport->alltoallv(c->comm, request, scount.data(), soff.data(), c->sp_asked, rcount.data(), roff.data(), sizeof(uint32_t), world, c->stream))
+            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+        auto stage3 = [&]() -> th_status {
+            th::launch_spawn_shard_answers(data, (uint32_t)c->cfg.row0 * (uint32_t)W, my_rows * (uint32_t)W, c->sp_asked, c->sp_answers, (uint32_t)arriving, outside, c->stream);
+            TH_HIP(hipGetLastError());
+            uint32_t flag = 0;
+            if (arriving) if (th_status s = read_back(c, &flag, outside, sizeof flag)) return s;
+            if (flag) return fail(TH_ERR_INVALID, "sharded spawn: rank %d was asked for a texel outside its band (rows %d..%d): the ranks do not hold the balanced bands of one texture",
+                                  rank, c->cfg.row0, c->cfg.row0 + c->cfg.height);
+            return TH_OK;
+        };
+        if (th_status s = agree_status(c, stage3(), "answering the requests for its band", true)) return s;
+        // stage 4 - the texels come back to the places their requests left from; the pass's rounds over them
+        if (c->transport->alltoallv(c->comm, c->sp_answers, rcount.data(), roff.data(), fetched, scount.data(), soff.data(), sizeof(float4), world, c->stream))
+            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+        p.place = place;
+        th::launch_spawn_shard_pick(p, c->stream);
+        TH_HIP(hipGetLastError());
+        c->last_spawn.taps += taps;
+        c->last_spawn.local_taps += taps - asked;
+        c->last_spawn.sent_bytes += asked * sizeof(uint32_t) + arriving * sizeof(float4);
+        c->last_spawn.received_bytes += arriving * sizeof(uint32_t) + asked * sizeof(float4);
+    }
+    // (every rank has answered the last chunk's requests by now: the source may be written)
+    if (staged) TH_HIP(hipMemcpyAsync(out, rt, c->texels() * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    return staged ? TH_OK : commit_target(c, out, rt);
+}
+
+th_status th_spawn_query(th_context *c, th_spawn_info *out)
+{
+    TH_REQUIRE(c && out, "null argument");
+    *out = c->last_spawn;
     return TH_OK;
 }
 

@@ -4,7 +4,10 @@
 // HIP library through the N-API shim instead of WebGL.  `logic` is an opaque program object
 // naming the kernel family a pass runs (the reference swaps gl-shader objects:
 // src/index.js:250,435,451).
+const path = require('path');
 const native = require('./native');
+// the sharded best-sample spawn lives in a small addon of its own (th_napi_spawn.cc), over the main addon's context handle
+const spawnAddon = require(path.join(__dirname, '..', 'lib', 'tendrils_spawn_sharded.node'));
 const { step } = require('./utils');
 
 const defaults = () => ({
@@ -81,6 +84,7 @@ function runPass(particles, program, uniforms, target) {
         source = (source + 1) % particles.buffers.length;
       }
       if (program.kind === 'spawn-direct') native.spawnDirect(h, f, source, target);
+      else if (particles.fetchesTaps(source)) particles.spawnSampleSharded(f, program.fixed.samples, program.fixed.apply, source, target);
       else native.spawnSample(h, f, program.fixed.samples, program.fixed.apply, source, target);
       break;
     }
@@ -105,6 +109,10 @@ class Particles {
       shape: [this.shape[0], this.shape[1], 4]
     };
     this.nextId = 0;
+    // best-sample spawning from the particle texture on a row-band shard (PixelSpawner): 'auto' - through
+    // spawnSampleSharded when the context holds the job's communicator, else the gathered path; true / false force one
+    this.shardedSpawn = 'auto';
+    this.globalHeight = (params.globalHeight | 0) || this.shape[1];
     this.handle = native.create(params.device | 0, this.shape[0], this.shape[1],
       params.globalHeight | 0, params.row0 | 0, 0, params.mode | 0, params.stateFormat | 0);
   }
@@ -188,7 +196,8 @@ class Particles {
   // a switch between equivalent paths of the library (th_option_set / _get; no switch changes a result):
   // option('bucket') reads, option('bucket', 1) sets and returns the value
   option(name, value) {
-    const key = native['OPT_' + name.replace(/[A-Z]/g, (ch) => '_' + ch).toUpperCase()];
+    const constant = 'OPT_' + name.replace(/[A-Z]/g, (ch) => '_' + ch).toUpperCase();
+    const key = (native[constant] !== undefined) ? native[constant] : spawnAddon[constant];
     if (key === undefined) throw new Error('unknown option ' + name);
     return (value === undefined) ? native.option(this.handle, key) : native.option(this.handle, key, +value);
   }
@@ -205,6 +214,18 @@ class Particles {
   commDestroy() { native.commDestroy(this.handle); return this; }
   commQuery() { return native.commQuery(this.handle); }
   statsGlobal(speedLimit) { return native.statsGlobal(this.handle, speedLimit); }
+  // th_spawn_sample on a row-band shard whose spawn data is ring buffer `source`, every rank collectively: the taps' texels
+  // are fetched from the ranks that own them - no copy of the whole texture (uniforms: the 17 floats of runPass)
+  spawnSampleSharded(uniforms, samples, apply, source, target) {
+    spawnAddon.spawnSampleSharded(this.handle, uniforms, samples | 0, apply | 0, source | 0, target | 0);
+    return this;
+  }
+  spawnQuery() { return spawnAddon.spawnQuery(this.handle); }   // {taps, localTaps, sentBytes, receivedBytes, chunks} of the last one
+  // does a sample pass from `source` (as the library sees it) go through spawnSampleSharded?
+  fetchesTaps(source) {
+    if (this.shardedSpawn !== 'auto') return !!this.shardedSpawn;
+    return source >= 0 && this.globalHeight !== this.shape[1] && !!native.commQuery(this.handle).active;
+  }
 
   dispose() {
     if (this.handle) { native.destroy(this.handle); this.handle = null; }

@@ -82,6 +82,8 @@ class PixelSpawner {
     });
   }
 
+  // (on a row-band shard with a particle buffer for `buffer` and the job's communicator, the pass fetches its taps from
+  // the ranks that own them - Particles.shardedSpawn, spawnSampleSharded - instead of reading a gathered copy)
   spawn(tendrils, update = this.update.bind(this), ...rest) {
     return tendrils.spawnShader(this.shader, update, ...rest);
   }

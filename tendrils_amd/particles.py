@@ -81,6 +81,9 @@ class Particles:
         self._row0 = int(params.get("row0", 0))
         self._global_height = int(params.get("globalHeight", 0))
         self._next_id = 0
+        # best-sample spawning from the particle texture on a row-band shard (PixelSpawner): "auto" - through
+        # th_spawn_sample_sharded when the context holds the job's communicator, else the gathered path; True / False force one
+        self.sharded_spawn = "auto"
         cfg = _capi.Config(device=self._device, width=self.shape[0], height=self.shape[1],
                            global_height=self._global_height, row0=self._row0, num_buffers=0,
                            mode=self._mode, state_format=int(params.get("stateFormat", 0)))
@@ -192,7 +195,7 @@ class Particles:
         call("th_draw_pipeline", self._ctx, {"auto": -1, "stream": 0, "bins": 1}[which])
 
     OPTIONS = dict(bucket=0, resort_steps=1, rebucket_steps=2, fuse=3, graph=4, force_generic=5, draw_reuse=6, bins_pool=7,
-                   inject_failure=8, bins_pages=9, async_sort=10, skip_unseen=11)
+                   inject_failure=8, bins_pages=9, async_sort=10, skip_unseen=11, spawn_chunk_rows=12)
 
     def option(self, name, value=None):
         """A switch between equivalent paths of the library (th_option_set / _get; no switch changes a result): returns the
@@ -202,6 +205,16 @@ class Particles:
         out = C.c_int64(0)
         call("th_option_get", self._ctx, self.OPTIONS[name], C.byref(out))
         return out.value
+
+    def fetches_taps(self, source):
+        """does a sample pass from `source` (as the library sees it) go through th_spawn_sample_sharded?"""
+        if self.sharded_spawn != "auto":
+            return bool(self.sharded_spawn)
+        if source < 0 or self._global_height in (0, self.shape[1]):
+            return False
+        q = _capi.CommInfo()
+        call("th_comm_query", self._ctx, C.byref(q))
+        return bool(q.active)
 
     def deposit_flow(self, view_size, time, speed_limit):
         """The flow pass of Tendrils.draw(): (previous -> current) lines blended into the flow texture
@@ -294,7 +307,10 @@ def run_pass(particles, program, uniforms, target):
             # the C side resolves ring indices AFTER utils.step() rotated the ring (the order the
             # pass sees); `source` was taken from the pre-rotation list
             source = (source + 1) % len(particles.buffers)
-        call("th_spawn_sample" if kind == "spawn-sample" else "th_spawn_direct", ctx, C.byref(s), source, target)
+        if kind == "spawn-sample" and particles.fetches_taps(source):
+            call("th_spawn_sample_sharded", ctx, C.byref(s), source, target)      # every rank, collectively
+        else:
+            call("th_spawn_sample" if kind == "spawn-sample" else "th_spawn_direct", ctx, C.byref(s), source, target)
     else:
         raise ValueError("unknown program kind %r" % (kind,))
 

@@ -18,6 +18,15 @@ def shard_rows(global_height, world, rank):
     return row0, rows
 
 
+def owner_of_row(global_height, world, row):
+    """The rank whose band of shard_rows holds `row` (the arithmetic of the library's sharded spawn)."""
+    if not (0 <= row < global_height):
+        raise ValueError("row %d outside height %d" % (row, global_height))
+    base, extra = divmod(int(global_height), int(world))
+    wide = extra * (base + 1)                  # rows held by the ranks with one row more
+    return row // (base + 1) if row < wide else extra + (row - wide) // base
+
+
 COUNT_FIELDS = ("particles", "live", "nan", "capped", "respawned")
 
 
@@ -274,6 +283,29 @@ def gather_state(tendrils, buffer=0):
     from . import _capi
     index = buffer.index if hasattr(buffer, "index") else int(buffer)
     _capi.call("th_state_gather", tendrils.particles._ctx, index)
+
+
+def spawn_sample_sharded(tendrils, spawner, update=None, *rest):
+    """spawner.spawn(tendrils) of a row-band shard, every rank collectively, through th_spawn_sample_sharded whatever
+    Particles.sharded_spawn says: the taps' texels are fetched from the ranks that own them, no rank holds more than its
+    band (needs sharding.comm_init / comm_join; without a communicator the band must be the whole texture).  Returns
+    spawn_query()."""
+    p = tendrils.particles
+    before, p.sharded_spawn = p.sharded_spawn, True
+    try:
+        spawner.spawn(tendrils, update, *rest)
+    finally:
+        p.sharded_spawn = before
+    return spawn_query(tendrils)
+
+
+def spawn_query(tendrils):
+    """th_spawn_query: what the last th_spawn_sample_sharded of this context did - taps, local_taps, sent_bytes,
+    received_bytes, chunks"""
+    from . import _capi
+    q = _capi.SpawnInfo()
+    _capi.call("th_spawn_query", tendrils.particles._ctx, C.byref(q))
+    return {k: int(getattr(q, k)) for k in ("taps", "local_taps", "sent_bytes", "received_bytes", "chunks")}
 
 
 def _exchange(dist, keys, colors, texels):

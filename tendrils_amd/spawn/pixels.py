@@ -101,6 +101,8 @@ class PixelSpawner:
         return uniforms
 
     def spawn(self, tendrils, update=None, *rest):           # :58-60
+        """(on a row-band shard with a particle buffer for `buffer` and the job's communicator, the pass fetches its taps
+        from the ranks that own them - Particles.sharded_spawn, th_spawn_sample_sharded - instead of reading a gathered copy)"""
         return tendrils.spawnShader(self.shader, update or self.update, *rest)
 
     def setPixels(self, pixels):                             # :62-64
