@@ -52,8 +52,8 @@ void launch_unpack_state(float4 *dst, const void *src, uint32_t n, hipStream_t s
 __global__ __launch_bounds__(256) void hash_tables_kernel(float4 *block)
 {
     uint32_t *a = reinterpret_cast<uint32_t *>(block), *b = a + kPermA;
-    for (int k = threadIdx.x; k < kPermA; k += 256) a[k] = 4u * (uint32_t)permute_int((float)k);
-    for (int k = threadIdx.x; k < kPermB; k += 256) b[k] = 16u * (uint32_t)((int)permute_int((float)k) - kLutMin);
+    for (int k = threadIdx.x; k < kPermA; k += 256) a[k] = 4u * (uint32_t)permute_int((float)k) - kBiasBitsA;
+    for (int k = threadIdx.x; k < kPermB; k += 256) b[k] = 16u * (uint32_t)((int)permute_int((float)k) - kLutMin) - kBiasBitsB;
 }
 void launch_hash_tables(float4 *block, hipStream_t s) { hipLaunchKernelGGL(hash_tables_kernel, dim3(1), dim3(256), 0, s, block); }
 int hash_table_vectors() { return kHashVec; }

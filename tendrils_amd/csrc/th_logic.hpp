@@ -151,10 +151,19 @@ struct NoiseCorners {
 
 // ---- hash stages through LDS tables (issue-bound launches: the fused integrator) --------------------------
 // The first two permutation stages read the polynomial's own values from LDS instead of evaluating them, and the
-// whole index chain runs on integers that already are byte offsets, so no stage needs an offset multiply:
-//   permA[k] = 4 * permute_int(k)               k in [0, 290]: stage z (argument iz, iz + 1), 4 * value = offset unit of permB
-//   permB[k] = 16 * (permute_int(k) - kLutMin)  k in [0, 580]: stage y; + 16 * (ix + i) = byte offset of the gradient entry
-// Both are filled by the kernel with permute_int itself; mod289_int() results are exact integers in [0, 289].
+// whole index chain runs on integers that already are byte offsets.  They come straight from the float bits: mod289_int()
+// returns an exact integer r in [0, 289], and added to a power of two whose ulp is the reciprocal of the offset unit, r sits
+// in the mantissa already scaled - no float -> int conversion, no shift (both half rate on gfx950):
+//   bits(r + 2^21) = 0x4A000000 + (r << 2)      one ulp = 1/4:  r << 2 <= 1156
+//   bits(r + 2^19) = 0x49000000 + (r << 4)      one ulp = 1/16: r << 4 <= 4624 < 2^23, inside the mantissa (-0.0 gives r = 0)
+// The constant high bits are taken off by the tables' entries, in uint32 arithmetic (wrap-around: sums mod 2^32 are exact):
+//   permA[k] = 4 * permute_int(k) - 0x4A000000                k in [0, 290]: stage z (argument iz, iz + 1);
+//              + bits(iy + 2^21) = 4 * (permute(iz) + iy) = byte offset into permB
+//   permB[k] = 16 * (permute_int(k) - kLutMin) - 0x49000000   k in [0, 580]: stage y;
+//              + bits(ix + 2^19) = 16 * (permute(..) + ix - kLutMin) = byte offset of the gradient entry
+// Only the first-stage index addresses a table directly and masks its own high bits (& 0xffc).  The corner steps (+4, +16)
+// are added to the sums as before.  Both tables are filled with permute_int itself (hash_tables_kernel).
+constexpr uint32_t kBiasBitsA = 0x4A000000u, kBiasBitsB = 0x49000000u;      // bits(2^21), bits(2^19)
 constexpr int kPermA = 292, kPermB = 584;                    // entries (multiples of 4)
 constexpr int kHashVec = (kPermA + kPermB) / 4;              // float4 slots in front of the gradient table
 struct HashTables {
@@ -209,18 +218,21 @@ TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, co
     n.cx = cx + kC3; n.cy = cy + kC3; n.cz = cz + kC3;
     n.dx = ax - 0.5f; n.dy = ay - 0.5f; n.dz = az - 0.5f;
 
-    const uint32_t xi = (uint32_t)mod289_int(ix), yi = (uint32_t)mod289_int(iy), zi = (uint32_t)mod289_int(iz);
-    const uint32_t *pa = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permA) + (zi << 2));
-    const uint32_t pz0 = pa[0], pz1 = pa[1];                    // 4 * permute(iz), 4 * permute(iz + 1)
+    // r + 2^21, r + 2^19: the sums' bits are the offsets.  As asm: left to the compiler, the same three adds schedule into
+    // five more VGPRs (a wave per SIMD less) in one packed fused kernel.
+    uint32_t zb, yb, xb;
+    asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(zb) : "v"(mod289_int(iz)));       // kBiasBitsA + 4 * iz
+    asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(yb) : "v"(mod289_int(iy)));       // kBiasBitsA + 4 * iy
+    asm("v_add_f32 %0, 0x49000000, %1" : "=v"(xb) : "v"(mod289_int(ix)));       // kBiasBitsB + 16 * ix
+    zb &= 0xffcu;                                                               // byte offset into permA
+    const uint32_t *pa = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permA) + zb);
+    const uint32_t a0 = pa[0] + yb, a1 = pa[1] + yb;            // 4 * (permute(iz) + iy), 4 * (permute(iz + 1) + iy)
     uint32_t sel1, sel2;
     asm("v_cndmask_b32 %0, %2, %3, %4\n\tv_cndmask_b32 %1, %2, %3, %5"
-        : "=&v"(sel1), "=&v"(sel2) : "v"(pz0), "v"(pz1), "s"(mz1), "s"(mz2));
-    const uint32_t y4 = yi << 2;
+        : "=&v"(sel1), "=&v"(sel2) : "v"(a0), "v"(a1), "s"(mz1), "s"(mz2));
     auto stage_y = [&](uint32_t off) { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permB) + off); };
-    const uint32_t q0 = stage_y(pz0 + y4), q1 = stage_y(sel1 + y4 + e1y), q2 = stage_y(sel2 + y4 + e2y),
-                   q3 = stage_y(pz1 + y4 + 4u);
-    const uint32_t x16 = xi << 4;
-    n.j0 = (int)(q0 + x16); n.j1 = (int)(q1 + x16 + e1x); n.j2 = (int)(q2 + x16 + e2x); n.j3 = (int)(q3 + x16 + 16u);
+    const uint32_t q0 = stage_y(a0), q1 = stage_y(sel1 + e1y), q2 = stage_y(sel2 + e2y), q3 = stage_y(a1 + 4u);
+    n.j0 = (int)(q0 + xb); n.j1 = (int)(q1 + (xb + e1x)); n.j2 = (int)(q2 + (xb + e2x)); n.j3 = (int)(q3 + xb + 16u);
     return n;
 }
 

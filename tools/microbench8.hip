@@ -1,6 +1,7 @@
 // microbench8: issue rate of the integer / conversion VALU forms the fused integrator's index chain and flow-tap address can be
 // built from (v_cvt_u32_f32, v_floor_f32, the 24-bit multiplies, v_bfe_u32, v_lshl_add_u32, v_add3_u32, the 64-bit address
-// forms) and the plain shift / mask a biased-float index would use, against f32 mul / add.  Eight independent chains per lane
+// forms) and the plain shift / mask a biased-float index would use, against f32 mul / add; then the literal / SGPR-operand forms
+// of the biased-float hash chain (profiles/hash_chain_rates.txt).  Eight independent chains per lane
 // (no dependent issue back to back), 64 instructions per loop iteration (beside three scalar ones of the loop itself), every CU filled
 // with 2, 5 or 8 waves per SIMD.  Rates in lane-ops/s (wave-instructions * 64 per second).
 //   hipcc --offload-arch=gfx950 -O3 -o tools/bin/microbench8 tools/microbench8.hip
@@ -15,19 +16,24 @@ constexpr int kIters = 512;          // x 64 instructions per lane
                      TEXT("%4") "\n\t" TEXT("%5") "\n\t" TEXT("%6") "\n\t" TEXT("%7") "\n\t"
 #define X8(S) S S S S S S S S
 
-// 32-bit forms: one instruction per chain, chain register %0..%7, a loop-invariant operand in %8
-#define OP32(NAME, TEXT)                                                                                              \
+// 32-bit forms: one instruction per chain, chain register %0..%7, the loop-invariant inputs from %8 on: `b` in a VGPR
+// (OP32), in an SGPR (OP32S), or `b` in a VGPR and a wave-uniform 64-bit lane mask `m` in an SGPR pair as %9 (OP32M)
+#define OP32_IN(NAME, TEXT, ...)                                                                                      \
     __global__ __launch_bounds__(256) void k_##NAME(unsigned *out, unsigned seed)                                    \
     {                                                                                                                 \
         unsigned i = blockIdx.x * 256u + threadIdx.x;                                                                 \
         unsigned a0 = i ^ seed, a1 = a0 + 1u, a2 = a0 + 2u, a3 = a0 + 3u, a4 = a0 + 4u, a5 = a0 + 5u, a6 = a0 + 6u,    \
                  a7 = a0 + 7u, b = seed | 1u;                                                                         \
+        [[maybe_unused]] const unsigned long long m = ((unsigned long long)(seed * 0x9e3779b9u) << 32) | (seed * 0x85ebca6bu); \
         _Pragma("unroll 1") for (int it = 0; it < kIters; ++it)                                                       \
             asm volatile(X8(ROUND8(TEXT))                                                                              \
-                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b));   \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : __VA_ARGS__); \
         unsigned s = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;                                                           \
         if (s == 0x9e3779b9u) out[i] = s;                                                                             \
     }
+#define OP32(NAME, TEXT) OP32_IN(NAME, TEXT, "v"(b))
+#define OP32S(NAME, TEXT) OP32_IN(NAME, TEXT, "s"(b))
+#define OP32M(NAME, TEXT) OP32_IN(NAME, TEXT, "v"(b), "s"(m))
 
 #define T_CVT(r) "v_cvt_u32_f32 " r ", " r
 #define T_FLOOR(r) "v_floor_f32 " r ", " r
@@ -55,6 +61,22 @@ OP32(add3_u32, T_ADD3)
 OP32(add_u32, T_ADDU)
 OP32(lshlrev_b32, T_LSHL)
 OP32(and_b32, T_AND)
+// the forms the biased-float hash index chain is made of (32-bit literals, SGPR operands, the mask select) and ops of the
+// step loop the first table left out
+#define T_ADDF_LIT(r) "v_add_f32 " r ", 0x4a000000, " r
+#define T_ADDF_S(r) "v_add_f32 " r ", %8, " r
+#define T_AND_LIT(r) "v_and_b32 " r ", 0xffc, " r
+#define T_CNDMASK(r) "v_cndmask_b32 " r ", " r ", %8, %9"
+#define T_MAXF(r) "v_max_f32 " r ", " r ", %8"
+#define T_FMAC_LIT(r) "v_fmac_f32 " r ", 0xc3908000, %8"
+#define T_SUBF(r) "v_sub_f32 " r ", " r ", %8"
+OP32(add_f32_lit, T_ADDF_LIT)
+OP32S(add_f32_sgpr, T_ADDF_S)
+OP32(and_b32_lit, T_AND_LIT)
+OP32M(cndmask_b32_sgpr, T_CNDMASK)
+OP32(max_f32, T_MAXF)
+OP32(fmac_f32_lit, T_FMAC_LIT)
+OP32(sub_f32, T_SUBF)
 
 // 64-bit forms: eight 64-bit chains; v_mad_u64_u32 writes its carry to an SGPR pair of its own per chain
 __global__ __launch_bounds__(256) void k_mad_u64_u32(unsigned *out, unsigned seed)
@@ -111,7 +133,7 @@ static void run(const char *name, Kern k, unsigned *out, int cus, int waves_per_
     CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double lane_ops = 5.0 * blocks * 256.0 * kIters * 64.0;
-    printf("%-18s waves/SIMD %d: %7.3f ms  %6.2f T lane-ops/s\n", name, waves_per_simd, ms, lane_ops / ms / 1e9);
+    printf("%-20s waves/SIMD %d: %7.3f ms  %6.2f T lane-ops/s\n", name, waves_per_simd, ms, lane_ops / ms / 1e9);
     CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
 }
 
@@ -129,6 +151,9 @@ int main()
         {"v_mul_u32_u24", k_mul_u32_u24}, {"v_mul_hi_u32_u24", k_mul_hi_u32_u24}, {"v_mad_u32_u24", k_mad_u32_u24},
         {"v_bfe_u32", k_bfe_u32}, {"v_lshl_add_u32", k_lshl_add_u32}, {"v_add3_u32", k_add3_u32},
         {"v_mad_u64_u32", k_mad_u64_u32}, {"v_lshl_add_u64", k_lshl_add_u64},
+        {"v_add_f32 literal", k_add_f32_lit}, {"v_add_f32 sgpr", k_add_f32_sgpr}, {"v_and_b32 literal", k_and_b32_lit},
+        {"v_cndmask_b32 sgpr", k_cndmask_b32_sgpr}, {"v_max_f32", k_max_f32}, {"v_fmac_f32 literal", k_fmac_f32_lit},
+        {"v_sub_f32", k_sub_f32},
     };
     for (int w : {2, 5, 8})
         for (const auto &o : ops) run(o.n, o.k, out, prop.multiProcessorCount, w);
