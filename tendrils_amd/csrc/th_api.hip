@@ -117,7 +117,7 @@ th_status rect_ok(th_context *c, int32_t x0, int32_t y0, int32_t w, int32_t h)
 // ---- packed ring: f32 staging for everything except the hot step ---------------------------------
 th_status staging(th_context *c, int k, float4 **out)
 {
-    if (!c->tmp[k]) TH_HIP(hipMalloc((void **)&c->tmp[k], c->texels() * sizeof(float4)));
+    if (!c->tmp[k]) if (th_status s = c->tmp[k].alloc(c->texels())) return s;
     *out = c->tmp[k];
     return TH_OK;
 }
@@ -152,7 +152,7 @@ th_status commit_target(th_context *c, float4 *buf, float4 *rendered)
 th_status read_back(th_context *c, void *host, const void *dev, size_t bytes)
 {
     TH_REQUIRE(bytes <= kPinnedBytes, "read_back of %zu bytes", bytes);
-    if (!c->pinned) TH_HIP(hipHostMalloc(&c->pinned, kPinnedBytes, hipHostMallocDefault));
+    if (th_status s = c->pinned.reserve(kPinnedBytes, kPinnedBytes)) return s;
     TH_HIP(hipMemcpyAsync(c->pinned, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     TH_HIP(hipStreamSynchronize(c->stream));
     memcpy(host, c->pinned, bytes);
@@ -212,26 +212,26 @@ th_status th_create(const th_config *cfg, th_context **out)
         TH_HIP(hipEventCreate(&c->ev1));
         // one block: [hash tables (filled on the device) | gradient table]; c->lut points at the gradient table
         const size_t hv = (size_t)th::hash_table_vectors();
-        TH_HIP(hipMalloc((void **)&c->lut_block, (hv + th::kLutSize) * sizeof(float4)));
+        if (th_status s = c->lut_block.alloc(hv + th::kLutSize)) return s;
         c->lut = c->lut_block + hv;
         std::vector<float4> lut(th::kLutSize);
         build_gradient_table(lut.data());
         TH_HIP(hipMemcpy(c->lut, lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
         th::launch_hash_tables(c->lut_block, c->stream);
         TH_HIP(hipGetLastError());
-        TH_HIP(hipMalloc((void **)&c->d_flag, sizeof(unsigned int)));
-        TH_HIP(hipMalloc((void **)&c->partials, th::kStatsBlocks * sizeof(th::StatsPartial)));
-        TH_HIP(hipMalloc((void **)&c->d_counters, sizeof(th_counters)));
-        TH_HIP(hipMalloc((void **)&c->d_respawned, 2 * sizeof(unsigned long long)));
+        if (th_status s = c->d_flag.alloc(1)) return s;
+        if (th_status s = c->partials.alloc(th::kStatsBlocks)) return s;
+        if (th_status s = c->d_counters.alloc(1)) return s;
+        if (th_status s = c->d_respawned.alloc(2)) return s;
         TH_HIP(hipMemset(c->d_respawned, 0, 2 * sizeof(unsigned long long)));
         // Tendrils ctor: flow and targets start as 1x1 float FBOs (src/index.js:102-105);
         // setupParticles gives targets the particle shape (src/index.js:207).
         c->fw = c->fh = 1;
-        TH_HIP(hipMalloc((void **)&c->flow, sizeof(float4)));
+        if (th_status s = c->flow.alloc(1)) return s;
         TH_HIP(hipMemsetAsync(c->flow, 0, sizeof(float4), c->stream));
-        TH_HIP(hipMalloc((void **)&c->flow_dec, sizeof(float2)));
+        if (th_status s = c->flow_dec.alloc(1)) return s;
         // targets is an RGBA32F texture in every state format
-        TH_HIP(hipMalloc((void **)&c->targets, c->texels() * sizeof(float4)));
+        if (th_status s = c->targets.alloc(c->texels())) return s;
         TH_HIP(hipMemsetAsync(c->targets, 0, c->texels() * sizeof(float4), c->stream));
         for (int k = 0; k < c->cfg.num_buffers; ++k) {
             float4 *b = nullptr;
@@ -256,43 +256,15 @@ th_status th_destroy(th_context *c)
     if (c->side) (void)hipStreamSynchronize(c->side);          // (a re-sort beside the last draw may still be running there)
     if (c->side2) (void)hipStreamSynchronize(c->side2);
     if (c->comm) { (void)c->transport->destroy(c->comm); c->comm = nullptr; }
-    (void)hipFree(c->d_status); (void)hipFree(c->own_mem);
-    (void)hipFree(c->sp_taps); (void)hipFree(c->sp_asked); (void)hipFree(c->sp_answers); (void)hipFree(c->sp_words);
     thi::flow_lines_free(c);
-    for (float4 *b : c->ring) (void)hipFree(b);
-    (void)hipFree(c->flow); (void)hipFree(c->flow_dec); (void)hipFree(c->flow3); (void)hipFree(c->targets); (void)hipFree(c->lut_block);
-    (void)hipFree(c->frames[0]); (void)hipFree(c->frames[1]);
-    (void)hipFree(c->dep_count); (void)hipFree(c->dep_offset); (void)hipFree(c->dep_blocks); (void)hipFree(c->dep_total);
-    (void)hipFree(c->dep_record); (void)hipFree(c->dep_lists); (void)hipFree(c->mrg_keys2); (void)hipFree(c->mrg_colors);
-    (void)hipFree(c->bin_mem); (void)hipFree(c->draw_blocks); (void)hipFree(c->draw_block_flags); (void)hipFree(c->d_row_draws); (void)hipFree(c->src_row_index); (void)hipFree(c->src_col_index); (void)hipFree(c->src_slots); (void)hipFree(c->edge_rows); (void)hipFree(c->crowd_mem); (void)hipFree(c->chunk_table);
-    (void)hipFree(c->bins_keys); (void)hipFree(c->bins_colors); (void)hipFree(c->crowd_keys); (void)hipFree(c->crowd_sorted); (void)hipFree(c->crowd_parted); (void)hipFree(c->crowd_windows); (void)hipFree(c->gathered);
-    if (c->forked) (void)hipEventDestroy(c->forked);
-    if (c->joined) (void)hipEventDestroy(c->joined);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->joined2) (void)hipEventDestroy(c->joined2);
-    if (c->regrouped) (void)hipEventDestroy(c->regrouped);
-    if (c->side2) (void)hipStreamDestroy(c->side2);
-    if (c->bins_totals_host) (void)hipHostFree(c->bins_totals_host);
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    (void)hipFree(c->x_halo); (void)hipFree(c->x_counts); (void)hipFree(c->x_keys); (void)hipFree(c->x_colors);
-    for (uint32_t *q : c->dep_u32) (void)hipFree(q);
-    for (unsigned long long *q : c->dep_u64) (void)hipFree(q);
-    (void)hipFree(c->dep_colors_sorted); (void)hipFree(c->mrg_keys); (void)hipFree(c->mrg_vals[0]); (void)hipFree(c->mrg_vals[1]);
-    (void)hipFree(c->dep_colors); (void)hipFree(c->dep_temp);
-    (void)hipFree(c->image); (void)hipFree(c->view_screen); (void)hipFree(c->colormap);
-    for (uchar4 *b : c->view_ring) (void)hipFree(b);
-    (void)hipFree(c->d_flag); (void)hipFree(c->partials); (void)hipFree(c->fused_parts); (void)hipFree(c->d_counters); (void)hipFree(c->d_respawned);
     clear_graphs(c);
-    for (float4 *t : c->tmp) (void)hipFree(t);
-    for (th_context::SlotOrder &o : c->orders) { (void)hipFree(o.perm); (void)hipFree(o.chunks); (void)hipFree(o.records); (void)hipFree(o.nchunks); }
-    (void)hipFree(c->spare); (void)hipFree(c->tile_mem); (void)hipFree(c->block_records); (void)hipFree(c->asort.dst); (void)hipFree(c->seen.bytes);
-    if (c->asort.ready) (void)hipEventDestroy(c->asort.ready);
-    if (c->asort.done) (void)hipEventDestroy(c->asort.done);
-    if (c->miss_host) (void)hipHostFree(c->miss_host);
+    for (hipEvent_t e : {c->forked, c->joined, c->joined2, c->regrouped, c->asort.ready, c->asort.done, c->ev0, c->ev1}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->kt_events) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (hipStream_t q : {c->side, c->side2, c->stream}) if (q) (void)hipStreamDestroy(q);
+    // the ring elements, and the two buffers that trade places with them; every other buffer is a member and goes with the context
+    for (float4 *b : c->ring) (void)hipFree(b);
+    for (uchar4 *b : c->view_ring) (void)hipFree(b);
+    (void)hipFree(c->spare); (void)hipFree(c->asort.dst);
     delete c;
     return TH_OK;
 }
@@ -376,12 +348,9 @@ th_status th_flow_resize(th_context *c, int32_t w, int32_t h)
     if (w == c->fw && h == c->fh) return TH_OK;              // gl-fbo: same shape is a no-op
     TH_HIP(hipStreamSynchronize(c->stream));
     clear_graphs(c);
-    TH_HIP(hipFree(c->flow));
-    TH_HIP(hipFree(c->flow_dec));
-    (void)hipFree(c->flow3);
-    c->flow = nullptr; c->flow_dec = nullptr; c->flow3 = nullptr;
-    TH_HIP(hipMalloc((void **)&c->flow, (size_t)w * h * sizeof(float4)));
-    TH_HIP(hipMalloc((void **)&c->flow_dec, (size_t)w * h * sizeof(float2)));
+    c->flow.reset(); c->flow_dec.reset(); c->flow3.reset();
+    if (th_status s = c->flow.alloc((size_t)w * h)) return s;
+    if (th_status s = c->flow_dec.alloc((size_t)w * h)) return s;
     TH_HIP(hipMemsetAsync(c->flow, 0, (size_t)w * h * sizeof(float4), c->stream));
     c->fw = w; c->fh = h;
     return TH_OK;
@@ -463,9 +432,7 @@ th_status th_frames_resize(th_context *c, int32_t w, int32_t h)
     if (w == c->frw && h == c->frh) return TH_OK;
     TH_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k) {
-        TH_HIP(hipFree(c->frames[k]));
-        c->frames[k] = nullptr;
-        TH_HIP(hipMalloc((void **)&c->frames[k], (size_t)w * h * sizeof(uchar4)));
+        if (th_status s = c->frames[k].alloc((size_t)w * h)) return s;
         TH_HIP(hipMemsetAsync(c->frames[k], 0, (size_t)w * h * sizeof(uchar4), c->stream));
     }
     c->frw = w; c->frh = h;
@@ -484,7 +451,7 @@ th_status th_frames_upload(th_context *c, const uint8_t *rgba8)
 th_status th_frames_rotate(th_context *c)
 {
     TH_REQUIRE(c, "null context");
-    uchar4 *t = c->frames[1]; c->frames[1] = c->frames[0]; c->frames[0] = t;   // utils.step on 2 buffers
+    c->frames[0].swap(c->frames[1]);          // utils.step on 2 buffers
     return TH_OK;
 }
 
@@ -637,7 +604,7 @@ th_status th_option_set(th_context *c, int32_t option, int64_t value)
         o.bins_pages = (int)value;
         if (c->chunk_table) {           // (takes effect at once: the table is laid out again by the next binned pass)
             TH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->chunk_table); c->chunk_table = nullptr; (void)hipFree(c->bin_mem); c->bin_mem = nullptr; c->bin_capacity = 0; c->bin_max_pages = 0;
+            c->chunk_table.reset(); c->bin_mem.reset(); c->bin_capacity = 0; c->bin_max_pages = 0;
         }
         break;
     default: return fail(TH_ERR_INVALID, "unknown option %d", option);

@@ -1,5 +1,6 @@
 // th_ctx.hpp - what the translation units behind include/tendrils_hip.h share: the context, the error helpers and the
 // internal functions one unit offers the others (namespace thi).  Host side only; the kernels' interface is th_kernels.hpp.
+//   th_mem.hpp    DevBuf / HostBuf: the owner of every device / pinned buffer here (the ring elements apart)
 //   th_api.hip    context life cycle, textures, read-backs, timers, options
 //   th_order.hip  tile-sorted slot orders of the ring buffers, captured th_step_n graphs
 //   th_step.hip   Particles.step: th_step / th_step_n
@@ -41,6 +42,10 @@ std::string &last_error();
         if (!(cond)) return thi::fail(TH_ERR_INVALID, __VA_ARGS__); \
     } while (0)
 
+#include "th_mem.hpp"                     // thi::DevBuf / thi::HostBuf: every device and pinned buffer below is one of these
+using thi::DevBuf;
+using thi::HostBuf;
+
 // Per-context switches (th_option_set / th_option_get).  A context starts from the environment variables of the same
 // names, read when it is created - not once per process - so one process can hold contexts on different paths.
 struct th_options {
@@ -69,7 +74,8 @@ struct GraphEntry {
     std::vector<float4 *> ring;          // ring order at capture time
     th::LogicParams key{};               // launch parameters (the fields same_key() compares)
     hipGraphExec_t exec = nullptr;
-    float *times_dev = nullptr, *times_host = nullptr;
+    DevBuf<float> times_dev;
+    HostBuf<float> times_host;
     hipEvent_t copied = nullptr;         // times_host -> times_dev copy of the last replay
 };
 
@@ -79,52 +85,48 @@ struct th_context {
     hipStream_t stream = nullptr;
     std::vector<float4 *> ring;          // ring[0] = buffers[0] (most recent); TH_STATE_F16: packed, 8 B per texel
     bool packed = false;                 // cfg.state_format == TH_STATE_F16
-    float4 *tmp[3] = {nullptr, nullptr, nullptr};   // f32 staging for the non-hot operations on a packed ring
-    float4 *flow = nullptr;
-    float2 *flow_dec = nullptr;          // per-step decoded plane (launch_flow_decode)
-    float *flow3 = nullptr;              // the flow texels' x, y, z alone (fused passes: th_step_n packs them once per call)
+    DevBuf<float4> tmp[3];               // f32 staging for the non-hot operations on a packed ring
+    DevBuf<float4> flow;
+    DevBuf<float2> flow_dec;             // per-step decoded plane (launch_flow_decode)
+    DevBuf<float> flow3;                 // the flow texels' x, y, z alone (fused passes: th_step_n packs them once per call)
     int32_t fw = 0, fh = 0;
-    float4 *targets = nullptr;
+    DevBuf<float4> targets;
     bool targets_checked = true, targets_nonfinite = false;   // fresh texture = zeros
-    float4 *lut = nullptr, *lut_block = nullptr;      // gradient table (inside lut_block, behind the hash tables)
-    uchar4 *frames[2] = {nullptr, nullptr};
+    DevBuf<float4> lut_block;            // [hash tables | gradient table] ...
+    float4 *lut = nullptr;               // ... the gradient table inside it
+    DevBuf<uchar4> frames[2];
     int32_t frw = 0, frh = 0;
-    unsigned int *d_flag = nullptr;
-    th::StatsPartial *partials = nullptr;
+    DevBuf<unsigned int> d_flag;
+    DevBuf<th::StatsPartial> partials;
     // the statistics a fused th_step_n launch took of the state it wrote (LogicParams::stats_part): valid while ring[0] is
     // that buffer and nothing has written it (use() without keeps_lines drops them)
-    th::StatsPartial *fused_parts = nullptr;
-    uint32_t fused_parts_cap = 0;
+    DevBuf<th::StatsPartial> fused_parts;
     struct { bool valid = false; const float4 *buf = nullptr; float limit = 0.0f; uint32_t nparts = 0; } fused_stats;
-    th_counters *d_counters = nullptr;
+    DevBuf<th_counters> d_counters;
     // th_draw_sharded: the neighbours' edge rows, the owners' counts, what this rank received
-    float4 *x_halo = nullptr;            // [lo: cur row, prev row | hi: cur row, prev row], `width` texels each
-    unsigned long long *x_counts = nullptr;   // device: bounds (33) | send counts (32) | recv counts (32)
-    unsigned long long *x_keys = nullptr;
-    float4 *x_colors = nullptr;
-    size_t x_capacity = 0;
-    float4 *gathered = nullptr;          // row-band shard: a copy of the WHOLE particle texture (th_state_gather / _ptr) ...
+    DevBuf<float4> x_halo;               // [lo: cur row, prev row | hi: cur row, prev row], `width` texels each
+    DevBuf<unsigned long long> x_counts;   // device: bounds (33) | send counts (32) | recv counts (32)
+    DevBuf<unsigned long long> x_keys;   // (x_keys.size() is the capacity of both: exchange_room)
+    DevBuf<float4> x_colors;
+    DevBuf<float4> gathered;             // row-band shard: a copy of the WHOLE particle texture (th_state_gather / _ptr) ...
     const void *gathered_of = nullptr;   // ... of this ring buffer, for the spawners that sample arbitrary particles
     // th_spawn_sample_sharded (th_shard.hip): per tap of a chunk four u32 arrays and the fetched texels; what the other ranks
     // ask this one for, and its answers; the counts' words (send 32 | receive 32 | the out-of-band flag)
-    void *sp_taps = nullptr;
-    size_t sp_taps_cap = 0;
-    uint32_t *sp_asked = nullptr;
-    float4 *sp_answers = nullptr;
-    size_t sp_asked_cap = 0;
-    unsigned long long *sp_words = nullptr;
+    DevBuf<char> sp_taps;                // (kSpawnTapBytes per tap)
+    DevBuf<uint32_t> sp_asked;           // (sp_asked.size() is the capacity of both)
+    DevBuf<float4> sp_answers;
+    DevBuf<unsigned long long> sp_words;
     th_spawn_info last_spawn{};          // th_spawn_query
     void *comm = nullptr;                // communicator of the job's ranks (th_comm_init), one rank per context ...
     const th::Transport *transport = nullptr;   // ... and how its ranks exchange bytes (RCCL; in-process for tests)
-    uint32_t *d_status = nullptr;        // the word the ranks agree on (agree_status)
-    void *own_mem = nullptr;             // th_draw_sharded through the bins: counts, offsets, tables (th_bins.hip: OwnerParams)
-    uint32_t own_bins = 0;
+    DevBuf<uint32_t> d_status;           // the word the ranks agree on (agree_status)
+    DevBuf<uint32_t> own_mem;            // th_draw_sharded through the bins: counts, offsets, tables (th_bins.hip: OwnerParams)
     bool sharded_draw_ready = false;     // th_draw_sharded has allocated its fixed buffers (and the ranks agreed that all did)
     int32_t comm_rank = 0, comm_world = 1;
     // flow deposit scratch (grow-only): per-flow-texel counters and the fragment lists
-    uint32_t *dep_count = nullptr, *dep_offset = nullptr, *dep_blocks = nullptr, *dep_total = nullptr;   // per line; scan scratch
-    uint4 *dep_record = nullptr;         // per line: the texels of a short line
-    uint32_t *dep_lists = nullptr;       // slow / long line lists (counters first)
+    DevBuf<uint32_t> dep_count, dep_offset, dep_blocks, dep_total;   // per line; scan scratch
+    DevBuf<uint4> dep_record;            // per line: the texels of a short line
+    DevBuf<uint32_t> dep_lists;          // slow / long line lists (counters first)
     uint32_t dep_owners = 1;             // th_deposit_set_owners: ranks owning flow texels in the sharded deposit
     bool dep_pairs = false;              // the colour buffers hold two varyings per fragment (th_draw)
     // the geometry of the last draw pass (fragment counts, offsets, records, the sorted fragment order): the flow pass
@@ -133,75 +135,76 @@ struct th_context {
     struct { bool valid = false, binned = false; float view_x = 0, view_y = 0, line_half = 0; uint32_t total = 0, nlarge = 0, nblocks = 0; bool sorted_in_a = false; } drawn;
     uint32_t dep_list_cap = 0;
     // binned pipeline (th_bins.hip): the bins' cursors | the large bins | first block of each (+ 1) | first regrouped key of each (+ 1)
-    uint32_t *bin_mem = nullptr;
+    DevBuf<uint32_t> bin_mem;
     uint32_t bin_capacity = 0;
-    uint32_t *chunk_table = nullptr;     // per list x bin_max_pages: the pages a list has grown by
+    DevBuf<uint32_t> chunk_table;        // per list x bin_max_pages: the pages a list has grown by
     // the blocks of 256 slots with a line that can draw, for the slot order ring[0] is held in (th_bins.hip: bins_block_list_kernel)
-    uint32_t *draw_blocks = nullptr, draw_nblocks = 0;
-    uint8_t *draw_block_flags = nullptr;
+    DevBuf<uint32_t> draw_blocks;
+    uint32_t draw_nblocks = 0;
+    DevBuf<uint8_t> draw_block_flags;
     int draw_blocks_order = -2;
     unsigned long long draw_blocks_stamp = 0;
     uint32_t bin_max_pages = 0;          // (widened when a bin outgrows its lists: bins_table_widen)
     bool bins_dirty = false;             // an emitting pass filled the store and no blend has emptied it since (a sharded draw that ended
                                          // between the two): the next emitting pass wipes it first
-    unsigned long long *bins_keys = nullptr;   // the page store: (bins x kBinReplicas + bins_pool) pages of kBinPage places - keys (~0 = empty) ...
-    float4 *bins_colors = nullptr;       // ... and varyings (two per place once a th_draw has run)
+    DevBuf<unsigned long long> bins_keys;      // the page store: (bins x kBinReplicas + bins_pool) pages of kBinPage places - keys (~0 = empty) ...
+    DevBuf<float4> bins_colors;          // ... and varyings (two per place once a th_draw has run)
     uint32_t bins_pool = 0, bins_store_bins = 0;
     bool bins_pairs = false;
-    uint32_t *crowd_mem = nullptr;       // per large bin: fragments per texel, first fragment of every texel, fill cursors, long runs
-    uint32_t crowd_capacity = 0;
-    unsigned long long *crowd_keys = nullptr;  // the large bins' fragments regrouped by texel
-    uint32_t *crowd_sorted = nullptr;          // ... their places, run by run in blend order
-    unsigned long long *crowd_parted = nullptr;  // ... the giants' keys parted by stream index, and their windows (th_bins.hip: giant_*_kernel)
-    uint32_t *crowd_windows = nullptr;
+    DevBuf<uint32_t> crowd_mem;          // per large bin: fragments per texel, first fragment of every texel, fill cursors, long runs
+    uint32_t crowd_capacity = 0;         // (in bins: where the arrays inside crowd_mem begin)
+    DevBuf<unsigned long long> crowd_keys;     // the large bins' fragments regrouped by texel
+    DevBuf<uint32_t> crowd_sorted;             // ... their places, run by run in blend order
+    DevBuf<unsigned long long> crowd_parted;     // ... the giants' keys parted by stream index, and their windows (th_bins.hip: giant_*_kernel)
+    DevBuf<uint32_t> crowd_windows;
     size_t crowd_keys_cap = 0;
     hipStream_t side = nullptr;                // the long runs of a crowded target are blended beside everything else
     hipEvent_t forked = nullptr, joined = nullptr;
     hipStream_t side2 = nullptr;               // ... and the crowded bins' short runs beside both
     hipEvent_t joined2 = nullptr, regrouped = nullptr;
-    uint32_t *bins_totals_host = nullptr;      // (pinned, coherent; kTotWords + 1 words) the binned pass's totals, written by the plan's last kernel, and the sequence number behind them
+    HostBuf<uint32_t> bins_totals_host;        // (coherent, mapped; kTotWords + 1 words) the binned pass's totals, written by the plan's last kernel, and the sequence number behind them
     uint32_t *bins_totals_dev = nullptr;       // ... as the device addresses it
     uint32_t totals_seq = 0;
     bool mrg_pairs = false, x_pairs = false;   // the merge / exchange colour buffers hold two varyings per fragment (th_draw_emit / _merge)
-    void *pinned = nullptr;                    // (pinned, kPinnedBytes) small read-backs: a pageable hipMemcpyAsync costs ~0.15 ms per call
+    HostBuf<char> pinned;                      // (kPinnedBytes) small read-backs: a pageable hipMemcpyAsync costs ~0.15 ms per call
     int lines_local = -1;                // every vertex of every line reads the line's own particle (line_rows)
-    uint32_t *d_row_draws = nullptr;     // bit per global row: the row's lines can draw (line_rows)
+    DevBuf<uint32_t> d_row_draws;        // bit per global row: the row's lines can draw (line_rows)
     // ... and when not (lines_local == 0): the rows / columns whose texels some OTHER line's vertex reads, and - per slot order -
     // where those texels lie (th::LineSources; th_bins.hip: bins_block_flags_kernel)
-    uint16_t *src_row_index = nullptr, *src_col_index = nullptr;
+    DevBuf<uint16_t> src_row_index, src_col_index;
     uint32_t src_nrows = 0, src_ncols = 0;
     bool rows_cross_bands = false;       // some line of this band looks a row of a neighbouring band up (halo rows needed)
-    uint32_t *src_slots = nullptr;       // (allocated with draw_blocks; valid for draw_blocks_order / _stamp)
-    float4 *edge_rows = nullptr;         // th_draw_sharded through the bins: this band's edge rows gathered into texel order (4 x W)
+    DevBuf<uint32_t> src_slots;          // (allocated with draw_blocks; valid for draw_blocks_order / _stamp)
+    DevBuf<float4> edge_rows;            // th_draw_sharded through the bins: this band's edge rows gathered into texel order (4 x W)
     int draw_pipeline = TH_DRAW_AUTO;    // th_draw_pipeline
     th_draw_info last_draw{};            // th_draw_query
     long long draws = 0;                          // (`draws` counts frames: the passes drawn at one total_steps share a count ...
     long long draw_frame_step = -1;               //  ... and a pipeline: th_draw.hip, draw_uses_bins)
     int frame_bins = -1;
     long long last_binned_draw = -(1ll << 40);   // total_steps at the last draw over slot order
-    uint32_t *dep_u32[4] = {nullptr, nullptr, nullptr, nullptr};     // per fragment: keys, slots, and both sorted
-    unsigned long long *dep_u64[2] = {nullptr, nullptr};             // sharded form: (texel, stream index) keys, sorted
-    float4 *dep_colors_sorted = nullptr;
+    DevBuf<uint32_t> dep_u32[4];                                     // per fragment: keys, slots, and both sorted
+    DevBuf<unsigned long long> dep_u64[2];                           // sharded form: (texel, stream index) keys, sorted
+    DevBuf<float4> dep_colors_sorted;
     bool dep_wide = false;
     const float4 *halo_lo = nullptr, *halo_hi = nullptr;             // caller-owned neighbour rows (th_deposit_set_halo)
-    unsigned long long *mrg_keys = nullptr, *mrg_keys2 = nullptr;    // th_deposit_merge scratch (sort ping-pong)
-    uint32_t *mrg_vals[2] = {nullptr, nullptr};
+    DevBuf<unsigned long long> mrg_keys, mrg_keys2;                  // th_deposit_merge scratch (sort ping-pong)
+    DevBuf<uint32_t> mrg_vals[2];
     size_t mrg_capacity = 0;
-    float4 *mrg_colors = nullptr;        // the received varyings gathered into texel order
-    float4 *dep_colors = nullptr;
-    void *dep_temp = nullptr;
-    size_t dep_lines = 0, dep_capacity = 0, dep_temp_bytes = 0;
+    DevBuf<float4> mrg_colors;           // the received varyings gathered into texel order
+    DevBuf<float4> dep_colors;
+    DevBuf<char> dep_temp;
+    size_t dep_lines = 0, dep_capacity = 0;   // (set once all of their buffers are there: prepare_pass, deposit_reserve)
     uchar4 *view = nullptr;              // the BOUND view image (RGBA8, flow shape): what the view pass, fills, clears and read-backs touch
     int32_t view_w = 0, view_h = 0;
-    uchar4 *view_screen = nullptr;       // the drawing buffer (bound unless th_view_bind chose a buffer), lazily allocated
+    DevBuf<uchar4> view_screen;          // the drawing buffer (bound unless th_view_bind chose a buffer), lazily allocated
     std::vector<uchar4 *> view_ring;     // Tendrils.buffers (src/index.js:172-184): off-screen view images, in ring order
     int32_t view_buffers = 0;            // how many the host asked for (th_view_buffers)
     int32_t view_bound = -1;             // ring position of the bound image when it was bound; -1: the screen (the pointer `view` is what counts)
-    float4 *colormap = nullptr;          // tendrils.colorMap (nullptr = the 1x1 zero texture)
+    DevBuf<float4> colormap;             // tendrils.colorMap (nullptr = the 1x1 zero texture)
     int32_t cmap_w = 0, cmap_h = 0;
-    float4 *image = nullptr;             // PixelSpawner's own buffer (TH_SOURCE_IMAGE)
+    DevBuf<float4> image;                // PixelSpawner's own buffer (TH_SOURCE_IMAGE)
     int32_t iw = 0, ih = 0;
-    unsigned long long *d_respawned = nullptr;   // [0]: particles replaced by respawn passes, [1]: scratch (passes into `targets`)
+    DevBuf<unsigned long long> d_respawned;      // [0]: particles replaced by respawn passes, [1]: scratch (passes into `targets`)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool kernel_timing = false;          // th_kernel_timing: event pair around every logic launch
     std::vector<hipEvent_t> kt_events;   // pairs (start, stop); kt_used of them recorded
@@ -212,10 +215,10 @@ struct th_context {
     // texel order or in one of `orders` (a step that re-sorts writes its output in a new order while its input keeps
     // the old one, so two orders can be alive at a time).
     struct SlotOrder {
-        uint32_t *perm = nullptr;            // slot -> particle id
-        th::TileChunk *chunks = nullptr;     // chunk table
-        th::ChunkRecord *records = nullptr;  // per chunk: tiles of the next positions (written by a COUNT pass)
-        uint32_t *nchunks = nullptr;
+        DevBuf<uint32_t> perm;               // slot -> particle id
+        DevBuf<th::TileChunk> chunks;        // chunk table
+        DevBuf<th::ChunkRecord> records;     // per chunk: tiles of the next positions (written by a COUNT pass)
+        DevBuf<uint32_t> nchunks;
         th::TileGeom geom{};                 // key function the order was sorted with
         int32_t fw = 0, fh = 0;
         int refs = 0;                        // ring buffers stored in this order
@@ -223,14 +226,14 @@ struct th_context {
     };
     std::vector<SlotOrder> orders;
     std::vector<std::pair<float4 *, int>> buf_order;   // ring buffers held in a sorted order (absent = texel order)
-    float4 *spare = nullptr;             // spare state buffer (ensure_identity moves through it)
-    uint32_t *tile_mem = nullptr;        // hist | cursor (kSortReplicas x kMaxTileBins words each) | misses (8 words) | totals | starts (kMaxTileBins each)
-    th::ChunkRecord *block_records = nullptr;   // per 4096-slot block: tile_hist's table for tile_scatter
+    float4 *spare = nullptr;             // spare state buffer (ensure_identity moves through it: it trades places with ring elements - raw, like them)
+    DevBuf<uint32_t> tile_mem;           // hist | cursor (kSortReplicas x kMaxTileBins words each) | misses (8 words) | totals | starts (kMaxTileBins each)
+    DevBuf<th::ChunkRecord> block_records;      // per 4096-slot block: tile_hist's table for tile_scatter
     uint32_t max_chunks = 0;
     int steps_since_sort = 0;
     unsigned long long sorts = 0;
     long long total_steps = 0, hold_texel_order_until = 0;   // texel-order consumers (draw) keep the layout off for a period
-    uint32_t *miss_host = nullptr;       // pinned: window misses since the last sort, as of some recent launch
+    HostBuf<uint32_t> miss_host;         // window misses since the last sort, as of some recent launch
     // A re-sort under way beside a draw() (th_step.hip "the re-sort of a frame loop"): the step's output `src` (held in order
     // `src_order`) is being copied into `dst` in the new order `order` on the side stream; the next step takes the copy for
     // its input when nothing has touched `src` since (state_written / state_moved), anything else drops it.
@@ -238,14 +241,14 @@ struct th_context {
         bool pending = false, valid = false;
         const float4 *src = nullptr;
         int src_order = -1, order = -1;
-        float4 *dst = nullptr;               // (allocated once)
+        float4 *dst = nullptr;               // (allocated once; trades places with ring[1]: raw, like the ring elements)
         hipEvent_t ready = nullptr, done = nullptr;
         long long at_step = -1;              // total_steps when it was started
     } asort;
     // what a single step saw of its lines (LogicParams::seen): valid for a draw() that reads exactly these two buffers in this
     // order through this view
     struct {
-        uint8_t *bytes = nullptr;            // texels / 64 of them (a multiple of 4)
+        DevBuf<uint8_t> bytes;               // texels / 64 of them (a multiple of 4)
         const float4 *cur = nullptr, *prev = nullptr;
         int order = -1;
         unsigned long long stamp = 0;

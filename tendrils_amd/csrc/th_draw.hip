@@ -108,15 +108,14 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
     TH_REQUIRE((size_t)c->fw * c->fh > 0 && (uint64_t)c->cfg.width * c->cfg.global_height < (1ull << 32), "bad shapes");
     if (c->dep_lines != lines) {
         TH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->dep_count); (void)hipFree(c->dep_offset); (void)hipFree(c->dep_blocks); (void)hipFree(c->dep_record);
-        (void)hipFree(c->dep_lists);
-        c->dep_count = c->dep_offset = c->dep_blocks = c->dep_lists = nullptr; c->dep_record = nullptr;
-        TH_HIP(hipMalloc((void **)&c->dep_count, lines * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->dep_offset, lines * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->dep_record, 2 * lines * sizeof(uint4)));
-        TH_HIP(hipMalloc((void **)&c->dep_lists, th::deposit_list_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, &c->dep_list_cap) * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->dep_blocks, (size_t)th::deposit_scan_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height) * sizeof(uint32_t)));
-        if (!c->dep_total) TH_HIP(hipMalloc((void **)&c->dep_total, th::kTotWords * sizeof(uint32_t)));      // [0] total, [1] out-of-band flag, [2] largest bin, [3] large bins, [4] their blocks
+        c->dep_lines = 0;                   // (all five per-line buffers and `lines`, or nothing: a failure below leaves the next call to start over)
+        c->dep_count.reset(); c->dep_offset.reset(); c->dep_blocks.reset(); c->dep_record.reset(); c->dep_lists.reset();
+        if (th_status s = c->dep_count.alloc(lines)) return s;
+        if (th_status s = c->dep_offset.alloc(lines)) return s;
+        if (th_status s = c->dep_record.alloc(2 * lines)) return s;
+        if (th_status s = c->dep_lists.alloc(th::deposit_list_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, &c->dep_list_cap))) return s;
+        if (th_status s = c->dep_blocks.alloc(th::deposit_scan_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height))) return s;
+        if (th_status s = c->dep_total.reserve(th::kTotWords, th::kTotWords)) return s;      // [0] total, [1] out-of-band flag, [2] largest bin, [3] large bins, [4] their blocks
         c->dep_lines = lines;
     }
     p = th::DepositParams{};
@@ -154,16 +153,14 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
         p.nbins = p.bins_x * (((uint32_t)c->fh + (1u << th::kBinShift) - 1u) >> th::kBinShift);
         if (c->bin_capacity < p.nbins) {
             TH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->bin_mem); c->bin_mem = nullptr; c->bin_capacity = 0;
-            (void)hipFree(c->chunk_table); c->chunk_table = nullptr;
+            c->bin_capacity = 0; c->bin_mem.reset(); c->chunk_table.reset();
             const size_t stride = ((size_t)p.nbins + 255) / 256 * 256 + 64;      // (the lists' cursors of one bin on different memory channels)
-            TH_HIP(hipMalloc((void **)&c->bin_mem, (th::kBinReplicas * stride + 2 * (size_t)p.nbins + 2) * sizeof(uint32_t)));
+            if (th_status s = c->bin_mem.alloc(th::kBinReplicas * stride + 2 * (size_t)p.nbins + 2)) return s;
             // (TH_OPT_BINS_PAGES: how far a list can grow at first - tests make it small to run the widening path)
             const int first = c->opt.bins_pages;
             c->bin_max_pages = first > 0 ? (uint32_t)first : (first < 0 ? (uint32_t)-first : th::kBinFirstPages);
-            const size_t table = (size_t)p.nbins * th::kBinReplicas * c->bin_max_pages * sizeof(uint32_t);
-            TH_HIP(hipMalloc((void **)&c->chunk_table, table));
-            TH_HIP(hipMemsetAsync(c->chunk_table, 0, table, c->stream));        // (every reader of a list leaves its entries empty)
+            if (th_status s = c->chunk_table.alloc((size_t)p.nbins * th::kBinReplicas * c->bin_max_pages)) return s;
+            TH_HIP(hipMemsetAsync(c->chunk_table, 0, c->chunk_table.bytes(), c->stream));        // (every reader of a list leaves its entries empty)
             c->bin_capacity = p.nbins;
         }
         p.bin_stride = (uint32_t)(((size_t)c->bin_capacity + 255) / 256 * 256 + 64);
@@ -178,14 +175,14 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
         if (c->opt.skip_unseen && c->lines_local == 1 && c->seen.bytes && c->seen.cur == c->ring[0] && c->seen.prev == c->ring[1] && p.cur == c->ring[0] && p.prev == c->ring[1] &&
             c->seen.order == o && c->seen.stamp == stamp && c->seen.view_x == p.view_x && c->seen.view_y == p.view_y && c->seen.fw == c->fw && c->seen.fh == c->fh &&
             drawn_line_width(c, TH_PASS_FLOW) <= 2.0f && drawn_line_width(c, TH_PASS_VIEW) <= 2.0f)
-            p.block_seen = reinterpret_cast<const uint32_t *>(c->seen.bytes);
+            p.block_seen = reinterpret_cast<const uint32_t *>(c->seen.bytes.get());
         if (!c->draw_blocks || c->draw_blocks_order != o || c->draw_blocks_stamp != stamp) {
             const size_t blocks = (c->texels() + 255) / 256;
             if (!c->draw_blocks) {
-                TH_HIP(hipMalloc((void **)&c->draw_blocks, (blocks + 1) * sizeof(uint32_t)));
-                TH_HIP(hipMalloc((void **)&c->draw_block_flags, blocks));
+                if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
                 if (c->lines_local == 0)
-                    TH_HIP(hipMalloc((void **)&c->src_slots, ((size_t)c->src_nrows * c->cfg.width + (size_t)c->src_ncols * c->cfg.height + 1) * sizeof(uint32_t)));
+                    if (th_status s = c->src_slots.alloc((size_t)c->src_nrows * c->cfg.width + (size_t)c->src_ncols * c->cfg.height + 1)) return s;
+                if (th_status s = c->draw_blocks.alloc(blocks + 1)) return s;          // (last: the three are there when this one is)
             }
             th::launch_bins_block_list(p, c->draw_block_flags, c->draw_blocks + 1, c->draw_blocks, o >= 0 ? c->src_slots : nullptr, c->stream);
             TH_HIP(hipGetLastError());
@@ -222,39 +219,29 @@ th_status deposit_count(th_context *c, const th_deposit_uniforms *u, th::Deposit
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs)
 {
     if (pairs && !c->dep_pairs) {                 // two varyings per fragment: the colour buffers at twice the size
-        (void)hipFree(c->dep_colors); c->dep_colors = nullptr;
-        (void)hipFree(c->dep_colors_sorted); c->dep_colors_sorted = nullptr;
-        if (c->dep_capacity) TH_HIP(hipMalloc((void **)&c->dep_colors, 2 * c->dep_capacity * sizeof(float4)));
+        c->dep_colors.reset(); c->dep_colors_sorted.reset();
         c->dep_pairs = true;
+        if (c->dep_capacity) if (th_status s = c->dep_colors.alloc(2 * c->dep_capacity)) { c->dep_capacity = 0; return s; }
     }
     if (c->dep_capacity < total) {
-        for (uint32_t *&q : c->dep_u32) { (void)hipFree(q); q = nullptr; }
-        for (unsigned long long *&q : c->dep_u64) { (void)hipFree(q); q = nullptr; }
-        (void)hipFree(c->dep_colors); c->dep_colors = nullptr;
-        (void)hipFree(c->dep_colors_sorted); c->dep_colors_sorted = nullptr;
+        for (DevBuf<uint32_t> &q : c->dep_u32) q.reset();
+        for (DevBuf<unsigned long long> &q : c->dep_u64) q.reset();
+        c->dep_colors.reset(); c->dep_colors_sorted.reset();
         c->dep_capacity = 0; c->dep_wide = false;
         const size_t cap = (size_t)total + (size_t)total / 4 + 1024;
-        for (uint32_t *&q : c->dep_u32) TH_HIP(hipMalloc((void **)&q, cap * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->dep_colors, (c->dep_pairs ? 2 : 1) * cap * sizeof(float4)));
+        for (DevBuf<uint32_t> &q : c->dep_u32) if (th_status s = q.alloc(cap)) return s;
+        if (th_status s = c->dep_colors.alloc((c->dep_pairs ? 2 : 1) * cap)) return s;
         c->dep_capacity = cap;
     }
-    if (!c->dep_colors_sorted) TH_HIP(hipMalloc((void **)&c->dep_colors_sorted, (c->dep_pairs ? 2 : 1) * c->dep_capacity * sizeof(float4)));
+    if (!c->dep_colors_sorted) if (th_status s = c->dep_colors_sorted.alloc((c->dep_pairs ? 2 : 1) * c->dep_capacity)) return s;
     if (wide && !c->dep_wide) {
-        for (unsigned long long *&q : c->dep_u64) TH_HIP(hipMalloc((void **)&q, c->dep_capacity * sizeof(unsigned long long)));
+        for (DevBuf<unsigned long long> &q : c->dep_u64) if (th_status s = q.alloc(c->dep_capacity)) return s;
         c->dep_wide = true;
     }
     return TH_OK;
 }
 
-th_status deposit_temp(th_context *c, size_t need)
-{
-    if (c->dep_temp_bytes < need) {
-        (void)hipFree(c->dep_temp); c->dep_temp = nullptr; c->dep_temp_bytes = 0;
-        TH_HIP(hipMalloc(&c->dep_temp, need + need / 4));
-        c->dep_temp_bytes = need + need / 4;
-    }
-    return TH_OK;
-}
+th_status deposit_temp(th_context *c, size_t need) { return c->dep_temp.reserve(need, need + need / 4); }
 
 // ---- view pass ---------------------------------------------------------------------------------------------
 // The screen image and Tendrils.buffers at the target's shape (Tendrils.resize gives every buffer viewRes, src/index.js:404:
@@ -264,7 +251,7 @@ th_status view_storage(th_context *c)
     const bool shaped = c->view_w == c->fw && c->view_h == c->fh;
     if (c->view && shaped && (int32_t)c->view_ring.size() == c->view_buffers) return TH_OK;
     const size_t bytes = (size_t)c->fw * c->fh * sizeof(uchar4);
-    auto fresh = [&](uchar4 **img) -> th_status {
+    auto fresh = [&](uchar4 **img) -> th_status {            // (a view_ring element: raw, like the particle ring's)
         TH_HIP(hipMalloc((void **)img, bytes));
         TH_HIP(hipMemsetAsync(*img, 0, bytes, c->stream));       // a fresh drawing buffer is transparent black
         return TH_OK;
@@ -275,13 +262,16 @@ th_status view_storage(th_context *c)
     TH_HIP(hipStreamSynchronize(c->stream));
     c->view = nullptr;
     if (!shaped) {
-        (void)hipFree(c->view_screen); c->view_screen = nullptr;
+        c->view_screen.reset();
         for (uchar4 *&b : c->view_ring) { (void)hipFree(b); b = nullptr; }
         c->view_w = c->view_h = 0;
     }
     while ((int32_t)c->view_ring.size() > c->view_buffers) { (void)hipFree(c->view_ring.back()); c->view_ring.pop_back(); }
     while ((int32_t)c->view_ring.size() < c->view_buffers) c->view_ring.push_back(nullptr);
-    if (!c->view_screen) if (th_status s = fresh(&c->view_screen)) return s;
+    if (!c->view_screen) {
+        if (th_status s = c->view_screen.alloc((size_t)c->fw * c->fh)) return s;
+        TH_HIP(hipMemsetAsync(c->view_screen, 0, bytes, c->stream));
+    }
     for (uchar4 *&b : c->view_ring) if (!b) if (th_status s = fresh(&b)) return s;
     c->view_w = c->fw; c->view_h = c->fh;
     c->view = bound >= 0 && bound < (int32_t)c->view_ring.size() ? c->view_ring[(size_t)bound] : c->view_screen;   // (a bound buffer that was removed: the screen)
@@ -317,13 +307,12 @@ static th_status export_run(th_context *c, th::DepositParams &p, float *lines, u
     *count = total;
     if (!lines || total == 0) return TH_OK;                  // size query
     TH_REQUIRE(capacity >= total, "line buffer holds %llu of %u lines", (unsigned long long)capacity, total);
-    float *d_out = nullptr;
-    TH_HIP(hipMalloc((void **)&d_out, (size_t)total * 12 * sizeof(float)));
+    DevBuf<float> d_out;                     // (every way out frees it; the one that launched waits for the stream first)
+    if (th_status s = d_out.alloc((size_t)total * 12)) return s;
     th::launch_export_write(p, d_out, c->stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(lines, d_out, (size_t)total * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
     TH_HIP(e);
     return TH_OK;
 }
@@ -375,17 +364,17 @@ static th_status bins_store(th_context *c, uint32_t nbins, uint32_t pool, bool p
 {
     if (c->bins_keys && c->bins_store_bins == nbins && c->bins_pool >= pool && (c->bins_pairs || !pairs)) return TH_OK;
     TH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->bins_keys); (void)hipFree(c->bins_colors);
-    c->bins_keys = nullptr; c->bins_colors = nullptr;
+    c->bins_keys.reset(); c->bins_colors.reset();
     pool = pool > c->bins_pool ? pool : c->bins_pool;
     pairs = pairs || c->bins_pairs;
     c->bins_pool = 0; c->bins_store_bins = 0;
     const size_t places = ((size_t)nbins * th::kBinReplicas + pool) * th::kBinPage;
     TH_REQUIRE(places < ((size_t)1 << 32), "the binned draw's chunk store would hold 2^32 places or more");
-    if (hipMalloc((void **)&c->bins_keys, places * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->bins_colors, places * (pairs ? 2 : 1) * sizeof(float4)) != hipSuccess) {
+    const std::string said = last_error();          // (a store that cannot be had is no error: th_last_error() keeps what it said)
+    if (c->bins_colors.alloc(places * (pairs ? 2 : 1)) != TH_OK || c->bins_keys.alloc(places) != TH_OK) {      // (the keys last: the store is there when they are)
         (void)hipGetLastError();
-        (void)hipFree(c->bins_keys); c->bins_keys = nullptr; c->bins_colors = nullptr;
+        last_error() = said;
+        c->bins_colors.reset();
         return kRetryInStreamOrder;
     }
     TH_HIP(hipMemsetAsync(c->bins_keys, 0xff, places * sizeof(unsigned long long), c->stream));
@@ -406,7 +395,7 @@ th_status bins_streams(th_context *c)
     TH_HIP(hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking));
     TH_HIP(hipEventCreateWithFlags(&c->joined2, hipEventDisableTiming));
     TH_HIP(hipEventCreateWithFlags(&c->regrouped, hipEventDisableTiming));
-    TH_HIP(hipHostMalloc((void **)&c->bins_totals_host, (th::kTotWords + 1) * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+    if (th_status s = c->bins_totals_host.alloc(th::kTotWords + 1, hipHostMallocCoherent | hipHostMallocMapped)) return s;
     memset(c->bins_totals_host, 0, (th::kTotWords + 1) * sizeof(uint32_t));
     TH_HIP(hipHostGetDevicePointer((void **)&c->bins_totals_dev, c->bins_totals_host, 0));
     return TH_OK;
@@ -459,14 +448,14 @@ th_status bins_table_widen(th_context *c, th::DepositParams &p, bool keep)
     const uint32_t had = c->bin_max_pages, wide = had * 4u < th::kBinPagesLimit ? had * 4u : th::kBinPagesLimit;
     if (c->opt.bins_pages < 0 || wide <= had) return kRetryInStreamOrder;
     const size_t lists = (size_t)c->bin_capacity * th::kBinReplicas;
-    uint32_t *table = nullptr;
-    if (hipMalloc((void **)&table, lists * wide * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return kRetryInStreamOrder; }
-    TH_HIP(hipMemsetAsync(table, 0, lists * wide * sizeof(uint32_t), c->stream));
+    DevBuf<uint32_t> table;
+    const std::string said = last_error();          // (no memory for it is no error: th_last_error() keeps what it said)
+    if (table.alloc(lists * wide) != TH_OK) { (void)hipGetLastError(); last_error() = said; return kRetryInStreamOrder; }
+    TH_HIP(hipMemsetAsync(table, 0, table.bytes(), c->stream));
     if (keep) TH_HIP(hipMemcpy2DAsync(table, (size_t)wide * sizeof(uint32_t), c->chunk_table, (size_t)had * sizeof(uint32_t), (size_t)had * sizeof(uint32_t), lists, hipMemcpyDeviceToDevice, c->stream));
     TH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->chunk_table);
-    c->chunk_table = table; c->bin_max_pages = wide;
-    p.page_table = table; p.max_pages = wide;
+    c->chunk_table.swap(table); c->bin_max_pages = wide;          // (the narrow one goes with `table`)
+    p.page_table = c->chunk_table; p.max_pages = wide;
     return TH_OK;
 }
 
@@ -478,16 +467,15 @@ th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t poo
     const size_t had = ((size_t)c->bins_store_bins * th::kBinReplicas + c->bins_pool) * th::kBinPage;
     const size_t places = ((size_t)c->bins_store_bins * th::kBinReplicas + pool) * th::kBinPage, per = c->bins_pairs ? 2 : 1;
     TH_REQUIRE(places < ((size_t)1 << 32), "the binned draw's chunk store would hold 2^32 places or more");
-    unsigned long long *keys = nullptr;
-    float4 *colors = nullptr;
-    TH_HIP(hipMalloc((void **)&keys, places * sizeof(unsigned long long)));
-    if (hipMalloc((void **)&colors, places * per * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(keys); return fail(TH_ERR_HIP, "the binned store could not grow to %zu places", places); }
+    DevBuf<unsigned long long> keys;
+    DevBuf<float4> colors;
+    if (th_status s = keys.alloc(places)) return s;
+    if (colors.alloc(places * per) != TH_OK) { (void)hipGetLastError(); return fail(TH_ERR_HIP, "the binned store could not grow to %zu places", places); }
     TH_HIP(hipMemcpyAsync(keys, c->bins_keys, had * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
     TH_HIP(hipMemcpyAsync(colors, c->bins_colors, had * per * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     TH_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->bins_keys); (void)hipFree(c->bins_colors);
-    c->bins_keys = keys; c->bins_colors = colors; c->bins_pool = pool;
-    p.frag_keys = keys; p.colors = colors; p.pool_pages = pool;
+    c->bins_keys.swap(keys); c->bins_colors.swap(colors); c->bins_pool = pool;      // (the smaller ones go with the locals)
+    p.frag_keys = c->bins_keys; p.colors = c->bins_colors; p.pool_pages = pool;
     return TH_OK;
 }
 
@@ -547,25 +535,24 @@ th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragme
     c->last_draw.pipeline = TH_DRAW_BINS; c->last_draw.fragments = total; c->last_draw.crowded_fragments = host[th::kTotCrowdKeys];
     if (host[th::kTotCrowdKeys] == 0xffffffffu) return fail(TH_ERR_UNSUPPORTED, "too many fragments in crowded bins for one draw (2^32 or more places)");
     if (c->crowd_capacity < nlarge) {
-        (void)hipFree(c->crowd_mem); c->crowd_mem = nullptr; c->crowd_capacity = 0;
+        c->crowd_capacity = 0;
         const uint32_t cap = std::min(p.nbins, std::max(2u * nlarge + 256u, p.nbins / 4u));      // (a quarter of the bins at once: no growth step by step)
-        TH_HIP(hipMalloc((void **)&c->crowd_mem, (size_t)cap * th::crowd_words_per_bin() * sizeof(uint32_t)));
+        if (th_status s = c->crowd_mem.alloc((size_t)cap * th::crowd_words_per_bin())) return s;
         // (the fragment counts per texel - the first cap * 256 words - start from zero; crowd_scan_kernel leaves them so)
         TH_HIP(hipMemsetAsync(c->crowd_mem, 0, (size_t)cap * 256 * sizeof(uint32_t), c->stream));
         TH_HIP(hipStreamSynchronize(c->stream));         // (whichever stream the regroup runs on: a new buffer is rare)
         c->crowd_capacity = cap;
     }
     if (c->crowd_keys_cap < host[th::kTotCrowdKeys]) {
-        (void)hipFree(c->crowd_keys); (void)hipFree(c->crowd_sorted); (void)hipFree(c->crowd_parted); (void)hipFree(c->crowd_windows);
-        c->crowd_keys = nullptr; c->crowd_sorted = nullptr; c->crowd_parted = nullptr; c->crowd_windows = nullptr; c->crowd_keys_cap = 0;
+        c->crowd_keys.reset(); c->crowd_sorted.reset(); c->crowd_parted.reset(); c->crowd_windows.reset(); c->crowd_keys_cap = 0;
         // (room for every fragment of a pass like this one and a quarter more: the share of the crowded bins grows from a third
         // to three quarters over the first hundred frames of a loop - sized by what it is now, the four buffers were freed and
         // allocated again every few frames on the way, milliseconds each time)
         const size_t cap = std::max(2 * (size_t)host[th::kTotCrowdKeys], (size_t)total + total / 4) + ((size_t)1 << 20);
-        TH_HIP(hipMalloc((void **)&c->crowd_keys, cap * sizeof(unsigned long long)));
-        TH_HIP(hipMalloc((void **)&c->crowd_sorted, cap * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->crowd_parted, cap * sizeof(unsigned long long)));
-        TH_HIP(hipMalloc((void **)&c->crowd_windows, (cap / 512 + 2) * 3 * sizeof(uint32_t)));      // (th_bins.hip: giant_part_kernel)
+        if (th_status s = c->crowd_keys.alloc(cap)) return s;
+        if (th_status s = c->crowd_sorted.alloc(cap)) return s;
+        if (th_status s = c->crowd_parted.alloc(cap)) return s;
+        if (th_status s = c->crowd_windows.alloc((cap / 512 + 2) * 3)) return s;      // (th_bins.hip: giant_part_kernel)
         c->crowd_keys_cap = cap;
     }
     p.nlarge = nlarge;
@@ -801,9 +788,8 @@ th_status th_colormap_upload(th_context *c, const float *rgba, int32_t w, int32_
     TH_REQUIRE(rgba && w > 0 && h > 0 && (uint64_t)w * h < (1ull << 28), "bad colour map %dx%d", w, h);
     if (w != c->cmap_w || h != c->cmap_h) {
         TH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->colormap);
-        c->colormap = nullptr; c->cmap_w = c->cmap_h = 0;
-        TH_HIP(hipMalloc((void **)&c->colormap, (size_t)w * h * sizeof(float4)));
+        c->cmap_w = c->cmap_h = 0;
+        if (th_status s = c->colormap.alloc((size_t)w * h)) return s;
         c->cmap_w = w; c->cmap_h = h;
     }
     TH_HIP(hipMemcpyAsync(c->colormap, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice, c->stream));

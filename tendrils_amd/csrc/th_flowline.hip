@@ -333,10 +333,8 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 namespace thi {
 struct FlowLineScratch {
-    void *dev = nullptr;
-    size_t dev_bytes = 0;
-    void *pinned = nullptr;
-    size_t pinned_bytes = 0;
+    DevBuf<char> dev;
+    HostBuf<char> pinned;
     hipEvent_t uploaded = nullptr;             // the last copy out of `pinned`
     bool pending = false;
     std::vector<V2> nrm;
@@ -348,8 +346,6 @@ void flow_lines_free(th_context *c)
     thi::FlowLineScratch *s = c->flow_lines;
     if (!s) return;
     if (s->uploaded) (void)hipEventDestroy(s->uploaded);
-    (void)hipFree(s->dev);
-    if (s->pinned) (void)hipHostFree(s->pinned);
     delete s;
     c->flow_lines = nullptr;
 }
@@ -433,15 +429,10 @@ th_status th_flow_lines(th_context *c, const th_flow_line_uniforms *u, const flo
     const size_t tab_bytes = align256(sizeof(int32_t) * (size_t)(2 * nl + 1));
     const size_t up_bytes = rec_bytes + tab_bytes;
     if (s->pending) { TH_HIP(hipEventSynchronize(s->uploaded)); s->pending = false; }   // (the previous call's copy: long done)
-    if (s->pinned_bytes < up_bytes) {
-        if (s->pinned) TH_HIP(hipHostFree(s->pinned));
-        s->pinned = nullptr; s->pinned_bytes = 0;
-        TH_HIP(hipHostMalloc(&s->pinned, up_bytes * 2, hipHostMallocDefault));
-        s->pinned_bytes = up_bytes * 2;
-    }
+    if (th_status st = s->pinned.reserve(up_bytes, up_bytes * 2)) return st;
     if (!s->uploaded) TH_HIP(hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
 
-    FlPoint *rec = static_cast<FlPoint *>(s->pinned);
+    FlPoint *rec = reinterpret_cast<FlPoint *>(s->pinned.get());
     const bool bounded = u->speedLimit > 0.0f;
     const double vx = (double)u->viewSize[0], vy = (double)u->viewSize[1], rad = std::fabs((double)u->rad);
     uint64_t pairs = 0;
@@ -484,7 +475,7 @@ th_status th_flow_lines(th_context *c, const th_flow_line_uniforms *u, const flo
         }
     }
     TH_REQUIRE(pairs < (1ull << 31), "%llu tile entries: too many for one call", (unsigned long long)pairs);
-    int32_t *tab = reinterpret_cast<int32_t *>(static_cast<char *>(s->pinned) + rec_bytes);
+    int32_t *tab = reinterpret_cast<int32_t *>(s->pinned + rec_bytes);
     std::copy(line_tri.begin(), line_tri.end(), tab);
     std::copy(line_pt.begin(), line_pt.end(), tab + nl + 1);
 
@@ -494,15 +485,11 @@ th_status th_flow_lines(th_context *c, const th_flow_line_uniforms *u, const flo
     const size_t cnt_bytes = align256((size_t)ncount * 4), sum_bytes = align256((size_t)th::exclusive_scan_sum_words(ncount) * 4);
     const size_t list_bytes = align256((size_t)std::max<uint64_t>(pairs, 1) * 4);
     const size_t need = up_bytes + tri_bytes + box_bytes + cnt_bytes + sum_bytes + list_bytes;
-    if (s->dev_bytes < need) {
+    if (s->dev.size() < need) {
         TH_HIP(hipStreamSynchronize(c->stream));              // (growing: the old scratch may still be in use)
-        TH_HIP(hipFree(s->dev));
-        s->dev = nullptr; s->dev_bytes = 0;
-        const size_t want = need + need / 2;
-        TH_HIP(hipMalloc(&s->dev, want));
-        s->dev_bytes = want;
+        if (th_status st = s->dev.alloc(need + need / 2)) return st;
     }
-    char *base = static_cast<char *>(s->dev);
+    char *base = s->dev;
     TH_HIP(hipMemcpyAsync(base, s->pinned, up_bytes, hipMemcpyHostToDevice, c->stream));
     TH_HIP(hipEventRecord(s->uploaded, c->stream));
     s->pending = true;

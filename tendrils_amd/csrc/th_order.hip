@@ -10,10 +10,8 @@ namespace thi {
 void destroy_graph(GraphEntry &g)
 {
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (g.times_dev) (void)hipFree(g.times_dev);
-    if (g.times_host) (void)hipHostFree(g.times_host);
     if (g.copied) (void)hipEventDestroy(g.copied);
-    g = GraphEntry{};
+    g = GraphEntry{};                     // (frees its buffers)
 }
 
 void clear_graphs(th_context *c)
@@ -88,12 +86,12 @@ th_status line_rows(th_context *c)
         if (!(row[0] == row[1] && cur[0] == cur[1])) bits[(size_t)m >> 5] |= 1u << (m & 31);
     }
     if (rows_drift && rows != H) { source_row(row0); source_row(row0 + rows - 1); }
-    TH_HIP(hipMalloc((void **)&c->d_row_draws, bits.size() * sizeof(uint32_t)));
+    if (th_status s = c->d_row_draws.alloc(bits.size())) return s;
     TH_HIP(hipMemcpy(c->d_row_draws, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->src_nrows = c->src_ncols = 0; c->rows_cross_bands = false;
     if (!local && nrows < 0xfffeu && ncols < 0xfffeu && (size_t)nrows * (size_t)W + (size_t)ncols * (size_t)rows < ((size_t)1 << 31)) {
-        TH_HIP(hipMalloc((void **)&c->src_row_index, (size_t)rows * sizeof(uint16_t)));
-        TH_HIP(hipMalloc((void **)&c->src_col_index, (size_t)W * sizeof(uint16_t)));
+        if (th_status s = c->src_row_index.alloc((size_t)rows)) return s;
+        if (th_status s = c->src_col_index.alloc((size_t)W)) return s;
         TH_HIP(hipMemcpy(c->src_row_index, row_index.data(), (size_t)rows * sizeof(uint16_t), hipMemcpyHostToDevice));
         TH_HIP(hipMemcpy(c->src_col_index, col_index.data(), (size_t)W * sizeof(uint16_t), hipMemcpyHostToDevice));
         c->src_nrows = nrows; c->src_ncols = ncols; c->rows_cross_bands = rows_drift && rows != H;
@@ -136,13 +134,13 @@ bool any_sorted(const th_context *c) { return !c->buf_order.empty(); }
 th_status sort_storage(th_context *c)
 {
     if (th_status s = line_rows(c)) return s;
-    if (c->tile_mem) return TH_OK;
+    if (c->miss_host) return TH_OK;          // (the last of them to be allocated: all or nothing)
     const size_t n = c->texels();
-    TH_HIP(hipMalloc((void **)&c->spare, n * sizeof(float4)));
-    TH_HIP(hipMalloc((void **)&c->tile_mem, (kTileWords + 8 + 2 * th::kMaxTileBins) * sizeof(uint32_t)));
+    if (!c->spare) TH_HIP(hipMalloc((void **)&c->spare, n * sizeof(float4)));
+    if (th_status s = c->tile_mem.alloc(kTileWords + 8 + 2 * th::kMaxTileBins)) return s;
     TH_HIP(hipMemsetAsync(c->tile_mem, 0, (kTileWords + 8 + 2 * th::kMaxTileBins) * sizeof(uint32_t), c->stream));
-    TH_HIP(hipMalloc((void **)&c->block_records, ((n + th::kTileChunk - 1) / th::kTileChunk) * sizeof(th::ChunkRecord)));
-    TH_HIP(hipHostMalloc((void **)&c->miss_host, 2 * sizeof(uint32_t)));
+    if (th_status s = c->block_records.alloc((n + th::kTileChunk - 1) / th::kTileChunk)) return s;
+    if (th_status s = c->miss_host.alloc(2)) return s;
     c->miss_host[0] = c->miss_host[1] = 0;
     c->max_chunks = (uint32_t)(n / th::kTileChunk) + th::kMaxTileBins + 8u;
     return TH_OK;
@@ -153,11 +151,11 @@ th_status free_order(th_context *c, int *out)
 {
     for (size_t k = 0; k < c->orders.size(); ++k) if (c->orders[k].refs == 0) { *out = (int)k; return TH_OK; }
     th_context::SlotOrder o;
-    TH_HIP(hipMalloc((void **)&o.perm, c->texels() * sizeof(uint32_t)));
-    TH_HIP(hipMalloc((void **)&o.chunks, (size_t)c->max_chunks * sizeof(th::TileChunk)));
-    TH_HIP(hipMalloc((void **)&o.records, (size_t)c->max_chunks * sizeof(th::ChunkRecord)));
-    TH_HIP(hipMalloc((void **)&o.nchunks, sizeof(uint32_t)));
-    c->orders.push_back(o);
+    if (th_status s = o.perm.alloc(c->texels())) return s;
+    if (th_status s = o.chunks.alloc(c->max_chunks)) return s;
+    if (th_status s = o.records.alloc(c->max_chunks)) return s;
+    if (th_status s = o.nchunks.alloc(1)) return s;
+    c->orders.push_back(std::move(o));
     *out = (int)c->orders.size() - 1;
     return TH_OK;
 }

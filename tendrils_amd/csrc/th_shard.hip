@@ -209,24 +209,50 @@ static th_status agree_status(th_context *c, th_status mine, const char *stage, 
 static th_status merge_reserve(th_context *c, uint32_t total, int target)
 {
     if (target == 2 && !c->mrg_pairs) {
-        (void)hipFree(c->mrg_colors); c->mrg_colors = nullptr;
-        if (c->mrg_capacity) TH_HIP(hipMalloc((void **)&c->mrg_colors, 2 * c->mrg_capacity * sizeof(float4)));
         c->mrg_pairs = true;
+        if (c->mrg_capacity) if (th_status s = c->mrg_colors.alloc(2 * c->mrg_capacity)) { c->mrg_capacity = 0; return s; }
     }
     if (c->mrg_capacity < total) {
-        (void)hipFree(c->mrg_keys); (void)hipFree(c->mrg_keys2); (void)hipFree(c->mrg_vals[0]); (void)hipFree(c->mrg_vals[1]);
-        (void)hipFree(c->mrg_colors);
-        c->mrg_keys = c->mrg_keys2 = nullptr; c->mrg_vals[0] = c->mrg_vals[1] = nullptr; c->mrg_colors = nullptr; c->mrg_capacity = 0;
+        c->mrg_keys.reset(); c->mrg_keys2.reset(); c->mrg_vals[0].reset(); c->mrg_vals[1].reset(); c->mrg_colors.reset(); c->mrg_capacity = 0;
         const size_t cap = (size_t)total + (size_t)total / 4 + 1024;
-        TH_HIP(hipMalloc((void **)&c->mrg_keys, cap * sizeof(unsigned long long)));
-        TH_HIP(hipMalloc((void **)&c->mrg_keys2, cap * sizeof(unsigned long long)));
-        TH_HIP(hipMalloc((void **)&c->mrg_vals[0], cap * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->mrg_vals[1], cap * sizeof(uint32_t)));
-        TH_HIP(hipMalloc((void **)&c->mrg_colors, (c->mrg_pairs ? 2 : 1) * cap * sizeof(float4)));
+        if (th_status s = c->mrg_keys.alloc(cap)) return s;
+        if (th_status s = c->mrg_keys2.alloc(cap)) return s;
+        if (th_status s = c->mrg_vals[0].alloc(cap)) return s;
+        if (th_status s = c->mrg_vals[1].alloc(cap)) return s;
+        if (th_status s = c->mrg_colors.alloc((c->mrg_pairs ? 2 : 1) * cap)) return s;
         c->mrg_capacity = cap;
     }
     if (th_status s = deposit_temp(c, th::radix_sort_temp_bytes(total, 32, 32 + deposit_texel_bits(c)))) return s;
-    if (!c->dep_total) TH_HIP(hipMalloc((void **)&c->dep_total, th::kTotWords * sizeof(uint32_t)));
+    return c->dep_total.reserve(th::kTotWords, th::kTotWords);
+}
+
+// room for `total` received fragments (grow-only; both: two varyings each).  x_keys.size() is the capacity: the keys are
+// allocated last, so that they are only there when the varyings are
+static th_status exchange_room(th_context *c, size_t total, bool both)
+{
+    if (c->x_keys.size() >= total && (c->x_pairs || !both)) return TH_OK;
+    const size_t cap = std::max(total, c->x_keys.size()) + total / 4 + 1024;
+    c->x_keys.reset(); c->x_colors.reset();
+    c->x_pairs = c->x_pairs || both;
+    if (th_status s = c->x_colors.alloc((c->x_pairs ? 2 : 1) * cap)) return s;
+    return c->x_keys.alloc(cap);
+}
+
+// the owners' ranges [lo[r], hi[r]) - in texels - of the target(s) a pass drew to every rank, in place
+static th_status gather_owned(th_context *c, bool view, bool both, const std::vector<size_t> &lo, const std::vector<size_t> &hi)
+{
+    const int world = c->comm_world, rank = c->comm_rank;
+    for (int plane_of = 0; plane_of < 2; ++plane_of) {          // 0: the flow texture, 1: the view buffer
+        if (plane_of == 0 ? (view && !both) : !view) continue;
+        const size_t elem = plane_of ? sizeof(uchar4) : sizeof(float4);
+        std::vector<size_t> gb((size_t)world), go((size_t)world);
+        for (int r = 0; r < world; ++r) { gb[(size_t)r] = (hi[(size_t)r] - lo[(size_t)r]) * elem; go[(size_t)r] = lo[(size_t)r] * elem; }
+        char *plane = plane_of ? reinterpret_cast<char *>(c->view) : reinterpret_cast<char *>(c->flow.get());
+        if (c->transport->allgather_bytes(c->comm, plane + go[(size_t)rank], plane, gb.data(), go.data(), rank, world, c->stream))
+            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+        for (int r = 0; r < world; ++r) if (r != rank) c->last_draw.received_bytes += gb[(size_t)r];
+        if (world > 1) c->last_draw.sent_bytes += gb[(size_t)rank];
+    }
     return TH_OK;
 }
 
@@ -281,16 +307,7 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
     // stage 2 - room for what arrives and for its merge: the last thing that can fail on one rank alone
     mine = total < ((size_t)1 << 31) ? TH_OK : fail(TH_ERR_UNSUPPORTED, "too many fragments for one owner");
     auto room = [&]() -> th_status {
-        if (c->x_capacity < total || (both && !c->x_pairs)) {
-            (void)hipFree(c->x_keys); (void)hipFree(c->x_colors);
-            c->x_keys = nullptr; c->x_colors = nullptr;
-            const size_t cap = std::max(total, c->x_capacity) + total / 4 + 1024;
-            c->x_capacity = 0;
-            c->x_pairs = c->x_pairs || both;
-            TH_HIP(hipMalloc((void **)&c->x_keys, cap * sizeof(unsigned long long)));
-            TH_HIP(hipMalloc((void **)&c->x_colors, (c->x_pairs ? 2 : 1) * cap * sizeof(float4)));
-            c->x_capacity = cap;
-        }
+        if (th_status s = exchange_room(c, total, both)) return s;
         return merge_reserve(c, (uint32_t)total, both ? 2 : (view ? 1 : 0));
     };
     if (mine == TH_OK) mine = injected(c, 3);
@@ -304,21 +321,9 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
                            : (view ? th_view_merge(c, c->x_keys, c->x_colors, total) : th_deposit_merge(c, c->x_keys, c->x_colors, total))) return s;
     // the owners' texel ranges of the target(s) to every rank, in place
     const size_t texels = (size_t)c->fw * c->fh, chunk = (texels + (size_t)world - 1) / (size_t)world;
-    for (int plane_of = 0; plane_of < 2; ++plane_of) {          // 0: the flow texture, 1: the view buffer
-        if (plane_of == 0 ? (view && !both) : !view) continue;
-        const size_t elem = plane_of ? sizeof(uchar4) : sizeof(float4);
-        std::vector<size_t> gb((size_t)world), go((size_t)world);
-        for (int r = 0; r < world; ++r) {
-            const size_t lo = std::min(texels, (size_t)r * chunk), hi = std::min(texels, ((size_t)r + 1) * chunk);
-            gb[(size_t)r] = (hi - lo) * elem; go[(size_t)r] = lo * elem;
-        }
-        char *plane = plane_of ? reinterpret_cast<char *>(c->view) : reinterpret_cast<char *>(c->flow);
-        if (c->transport->allgather_bytes(c->comm, plane + go[(size_t)rank], plane, gb.data(), go.data(), rank, world, c->stream))
-            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-        for (int r = 0; r < world; ++r) if (r != rank) c->last_draw.received_bytes += gb[(size_t)r];
-        if (world > 1) c->last_draw.sent_bytes += gb[(size_t)rank];
-    }
-    return TH_OK;
+    std::vector<size_t> lo((size_t)world), hi((size_t)world);
+    for (int r = 0; r < world; ++r) { lo[(size_t)r] = std::min(texels, (size_t)r * chunk); hi[(size_t)r] = std::min(texels, ((size_t)r + 1) * chunk); }
+    return gather_owned(c, view, both, lo, hi);
 }
 
 // The same pass through the BINS (th_bins.hip "the bins travel to the ranks that own them"): every rank rasterises its band's
@@ -352,14 +357,12 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
         o.world = (uint32_t)world; o.rank = (uint32_t)rank;
         for (int r = 0; r <= world; ++r) o.bin_lo[r] = (uint32_t)((unsigned long long)bins_y * (unsigned)r / (unsigned)world) * p.bins_x;
         o.nb = o.bin_lo[rank + 1] - o.bin_lo[rank];
-        if (c->own_bins < p.nbins) {
+        const size_t words = (size_t)p.nbins * (1 + 2 + 1 + 1 + 32 * 1 + 32 * 2) + 2 * (2 + 33 + 32) + 64;
+        if (c->own_mem.size() < words) {
             TH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->own_mem); c->own_mem = nullptr; c->own_bins = 0;
-            const size_t words = (size_t)p.nbins * (1 + 2 + 1 + 1 + 32 * 1 + 32 * 2) + 2 * (2 + 33 + 32) + 64;
-            TH_HIP(hipMalloc(&c->own_mem, words * sizeof(uint32_t)));
-            c->own_bins = p.nbins;
+            if (th_status s = c->own_mem.alloc(words)) return s;
         }
-        unsigned long long *q = static_cast<unsigned long long *>(c->own_mem);           // (the 8-byte arrays first)
+        unsigned long long *q = reinterpret_cast<unsigned long long *>(c->own_mem.get());           // (the 8-byte arrays first)
         o.offsets = q; q += (size_t)p.nbins + 1;
         q += 33;                                               // (the owners' bounds lived here: they lie beside the counts now)
         o.owner_bounds = c->x_counts;
@@ -424,16 +427,7 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
     auto stage2 = [&]() -> th_status {
         if (th_status s = injected(c, 3)) return s;
         if (total >= ((size_t)1 << 31)) return fail(TH_ERR_UNSUPPORTED, "too many fragments for one owner");
-        if (world > 1 && (c->x_capacity < total || (both && !c->x_pairs))) {
-            (void)hipFree(c->x_keys); (void)hipFree(c->x_colors);
-            c->x_keys = nullptr; c->x_colors = nullptr;
-            const size_t cap = std::max(total, c->x_capacity) + total / 4 + 1024;
-            c->x_capacity = 0;
-            c->x_pairs = c->x_pairs || both;
-            TH_HIP(hipMalloc((void **)&c->x_keys, cap * sizeof(unsigned long long)));
-            TH_HIP(hipMalloc((void **)&c->x_colors, (c->x_pairs ? 2 : 1) * cap * sizeof(float4)));
-            c->x_capacity = cap;
-        }
+        if (world > 1) if (th_status s = exchange_room(c, total, both)) return s;
         // (where every source's part starts in what arrives: the running sum of the received counts, made on the device)
         th::launch_exchange_recv_base(recvc, (uint32_t)world, const_cast<unsigned long long *>(o.recv_base), c->stream);
         TH_HIP(hipGetLastError());
@@ -470,23 +464,13 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
     if (laid == TH_OK) laid = bins_pass_finish(c, p, nullptr, false);
     // (an owner that could not lay its bins out has blended nothing; the others have: the draw is lost, and everybody says so)
     if (th_status s = agree_status(c, laid == kRetryInStreamOrder ? fail(TH_ERR_HIP, "the owner's store could not be had") : laid, "laying out the bins it owns")) return s;
-    const uint32_t bins_y = p.nbins / p.bins_x;
-    for (int plane_of = 0; plane_of < 2; ++plane_of) {          // 0: the flow texture, 1: the view buffer
-        if (plane_of == 0 ? (view && !both) : !view) continue;
-        const size_t elem = plane_of ? sizeof(uchar4) : sizeof(float4);
-        std::vector<size_t> gb((size_t)world), go((size_t)world);
-        for (int r = 0; r < world; ++r) {
-            const size_t row_lo = std::min<size_t>((size_t)c->fh, ((size_t)bins_y * (size_t)r / (size_t)world) << th::kBinShift);
-            const size_t row_hi = std::min<size_t>((size_t)c->fh, ((size_t)bins_y * ((size_t)r + 1) / (size_t)world) << th::kBinShift);
-            gb[(size_t)r] = (row_hi - row_lo) * (size_t)c->fw * elem; go[(size_t)r] = row_lo * (size_t)c->fw * elem;
-        }
-        char *plane = plane_of ? reinterpret_cast<char *>(c->view) : reinterpret_cast<char *>(c->flow);
-        if (c->transport->allgather_bytes(c->comm, plane + go[(size_t)rank], plane, gb.data(), go.data(), rank, world, c->stream))
-            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-        for (int r = 0; r < world; ++r) if (r != rank) c->last_draw.received_bytes += gb[(size_t)r];
-        if (world > 1) c->last_draw.sent_bytes += gb[(size_t)rank];
+    const size_t bins_y = p.nbins / p.bins_x, fh = (size_t)c->fh, fw = (size_t)c->fw;
+    std::vector<size_t> lo((size_t)world), hi((size_t)world);          // (an owner owns whole bin rows)
+    for (int r = 0; r < world; ++r) {
+        lo[(size_t)r] = std::min(fh, (bins_y * (size_t)r / (size_t)world) << th::kBinShift) * fw;
+        hi[(size_t)r] = std::min(fh, (bins_y * ((size_t)r + 1) / (size_t)world) << th::kBinShift) * fw;
     }
-    return TH_OK;
+    return gather_owned(c, view, both, lo, hi);
 }
 
 th_status th_draw_sharded(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
@@ -503,10 +487,10 @@ th_status th_draw_sharded(th_context *c, const th_deposit_uniforms *du, const th
     if (!c->sharded_draw_ready) {
         // the fixed buffers of the exchange, once - and the ranks make sure that every one of them has them
         auto fixed = [&]() -> th_status {
-            if (!c->x_counts) TH_HIP(hipMalloc((void **)&c->x_counts, 97 * sizeof(unsigned long long)));
-            if (world > 1 && !c->x_halo) TH_HIP(hipMalloc((void **)&c->x_halo, (size_t)4 * W * sizeof(float4)));
+            if (th_status s = c->x_counts.reserve(97, 97)) return s;
+            if (world > 1) if (th_status s = c->x_halo.reserve((size_t)4 * W, (size_t)4 * W)) return s;
             if (th_status s = line_rows(c)) return s;
-            if (world > 1 && c->rows_cross_bands && !c->edge_rows) TH_HIP(hipMalloc((void **)&c->edge_rows, (size_t)4 * W * sizeof(float4)));
+            if (world > 1 && c->rows_cross_bands) if (th_status s = c->edge_rows.reserve((size_t)4 * W, (size_t)4 * W)) return s;
             return ru ? view_storage(c) : TH_OK;
         };
         if (th_status s = agree_status(c, fixed(), "allocating the exchange's buffers")) return s;
@@ -609,7 +593,7 @@ th_status th_comm_init(th_context *c, const void *id, int32_t rank, int32_t worl
     TH_REQUIRE(id, "null communicator id");
     TH_REQUIRE(world >= 1 && rank >= 0 && rank < world, "rank %d outside world %d", rank, world);
     TH_REQUIRE(!c->comm, "the context already holds a communicator (th_comm_destroy first)");
-    if (!c->d_status) TH_HIP(hipMalloc((void **)&c->d_status, 2 * sizeof(uint32_t)));
+    if (th_status s = c->d_status.reserve(2, 2)) return s;
     if (th::comm_init(&c->comm, &c->transport, id, TH_COMM_ID_BYTES, rank, world)) return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
     c->comm_rank = rank; c->comm_world = world;
     c->sharded_draw_ready = false;
@@ -641,7 +625,7 @@ th_status th_comm_query(th_context *c, th_comm_info *out)
 static th_status gather_storage(th_context *c, int32_t buffer)
 {
     TH_REQUIRE(buffer >= 0 && buffer < (int32_t)c->ring.size(), "bad buffer %d (ring has %zu)", buffer, c->ring.size());
-    if (!c->gathered) TH_HIP(hipMalloc((void **)&c->gathered, (size_t)c->cfg.width * c->cfg.global_height * sizeof(float4)));
+    if (!c->gathered) if (th_status s = c->gathered.alloc((size_t)c->cfg.width * c->cfg.global_height)) return s;
     c->gathered_of = nullptr;
     return TH_OK;
 }
@@ -754,16 +738,15 @@ th_status th_spawn_sample_sharded(th_context *c, const th_spawn_sample_uniforms 
         if (source == 1) data = particles;
         else if (th_status s = unpacked_view(c, c->ring[(size_t)source], 2, &data)) return s;
         const size_t taps = (size_t)std::min(chunk_rows, my_rows) * (size_t)W * (size_t)samples;
-        if (c->sp_taps_cap < taps) {
+        if (c->sp_taps.size() < taps * kSpawnTapBytes) {
             TH_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->sp_taps); c->sp_taps = nullptr; c->sp_taps_cap = 0;
-            TH_HIP(hipMalloc(&c->sp_taps, taps * kSpawnTapBytes));
-            c->sp_taps_cap = taps;
+            if (th_status s = c->sp_taps.alloc(taps * kSpawnTapBytes)) return s;
         }
-        fetched = static_cast<float4 *>(c->sp_taps);                // (the 16-byte array first)
-        tap_owner = reinterpret_cast<uint32_t *>(fetched + c->sp_taps_cap);
-        tap_texel = tap_owner + c->sp_taps_cap; sorted_owner = tap_texel + c->sp_taps_cap; sorted_ordinal = sorted_owner + c->sp_taps_cap;
-        if (!c->sp_words) TH_HIP(hipMalloc((void **)&c->sp_words, 66 * sizeof(unsigned long long)));
+        const size_t taps_cap = c->sp_taps.size() / kSpawnTapBytes;
+        fetched = reinterpret_cast<float4 *>(c->sp_taps.get());     // (the 16-byte array first)
+        tap_owner = reinterpret_cast<uint32_t *>(fetched + taps_cap);
+        tap_texel = tap_owner + taps_cap; sorted_owner = tap_texel + taps_cap; sorted_ordinal = sorted_owner + taps_cap;
+        if (th_status s = c->sp_words.reserve(66, 66)) return s;
         if (taps) if (th_status s = deposit_temp(c, th::radix_sort_temp_bytes((uint32_t)taps, 0, 5))) return s;
         return TH_OK;
     };
@@ -824,13 +807,11 @@ th_status th_spawn_sample_sharded(th_context *c, const th_spawn_sample_uniforms 
         auto stage2 = [&]() -> th_status {
             if (at != (size_t)taps) return fail(TH_ERR_HIP, "the owners' counts (%zu) do not add up to the chunk's %u taps", at, taps);
             if (arriving >= ((size_t)1 << 31)) return fail(TH_ERR_UNSUPPORTED, "too many requests for one owner");
-            if (c->sp_asked_cap < arriving) {
-                (void)hipFree(c->sp_asked); (void)hipFree(c->sp_answers);
-                c->sp_asked = nullptr; c->sp_answers = nullptr; c->sp_asked_cap = 0;
+            if (c->sp_asked.size() < arriving) {          // (the requests last: they are only there when the answers are)
+                c->sp_asked.reset();
                 const size_t cap = arriving + arriving / 4 + 1024;
-                TH_HIP(hipMalloc((void **)&c->sp_asked, cap * sizeof(uint32_t)));
-                TH_HIP(hipMalloc((void **)&c->sp_answers, cap * sizeof(float4)));
-                c->sp_asked_cap = cap;
+                if (th_status s = c->sp_answers.alloc(cap)) return s;
+                if (th_status s = c->sp_asked.alloc(cap)) return s;
             }
 #ifdef TH_TESTING
             if (c->opt.inject_failure == 5 && asked) {          // the first request that leaves: a texel of THIS rank's band

@@ -111,9 +111,8 @@ static th_status image_resize(th_context *c, int32_t w, int32_t h)
     TH_REQUIRE(w > 0 && h > 0 && w < (1 << 24) && h < (1 << 24) && (uint64_t)w * h < (1ull << 28), "bad image %dx%d", w, h);
     if (w != c->iw || h != c->ih) {
         TH_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->image);
-        c->image = nullptr; c->iw = c->ih = 0;
-        TH_HIP(hipMalloc((void **)&c->image, (size_t)w * h * sizeof(float4)));
+        c->iw = c->ih = 0;
+        if (th_status s = c->image.alloc((size_t)w * h)) return s;
         c->iw = w; c->ih = h;
     }
     return TH_OK;
@@ -127,16 +126,15 @@ th_status th_spawn_image_triangles(th_context *c, const float *positions, int32_
     if (th_status s = image_resize(c, w, h)) return s;
     TH_HIP(hipMemsetAsync(c->image, 0, (size_t)w * h * sizeof(float4), c->stream));      // gl.clear(COLOR_BUFFER_BIT)
     if (triangles == 0) return TH_OK;
-    float *d_pos = nullptr;
-    th::TrianglePoly *d_polys = nullptr;
-    TH_HIP(hipMalloc((void **)&d_pos, (size_t)triangles * 6 * sizeof(float)));
-    TH_HIP(hipMalloc((void **)&d_polys, (size_t)triangles * sizeof(th::TrianglePoly)));
+    DevBuf<float> d_pos;                      // (every way out frees them; the one that launched waits for the stream first)
+    DevBuf<th::TrianglePoly> d_polys;
+    if (th_status s = d_pos.alloc((size_t)triangles * 6)) return s;
+    if (th_status s = d_polys.alloc((size_t)triangles)) return s;
     TH_HIP(hipMemcpyAsync(d_pos, positions, (size_t)triangles * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     th::launch_triangles(d_pos, triangles, viewSize[0], viewSize[1], make_float4(color[0], color[1], color[2], color[3]),
                          d_polys, c->image, w, h, c->stream);
     hipError_t e = hipGetLastError();
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_pos); (void)hipFree(d_polys);
     TH_HIP(e);
     return TH_OK;
 }

@@ -272,7 +272,7 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
         c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps && vx > 0.0f && vy > 0.0f && std::isfinite(vx) && std::isfinite(vy)) {
         if (!c->seen.bytes) {
             const size_t bytes = ((c->texels() + 63) / 64 + 7) & ~(size_t)3;
-            TH_HIP(hipMalloc((void **)&c->seen.bytes, bytes));
+            if (th_status s = c->seen.bytes.alloc(bytes)) return s;
             TH_HIP(hipMemsetAsync(c->seen.bytes, 0, bytes, c->stream));
         }
         const float mx = 4.0f / (float)c->fw, my = 4.0f / (float)c->fh;
@@ -391,7 +391,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
         // arithmetic and the packing pass only costs: 1.829 against 1.818 + 0.01)
         const bool pack3 = th::fused_taps_flow3(plan.v);
         if (pack3) {
-            if (!c->flow3) TH_HIP(hipMalloc((void **)&c->flow3, (size_t)c->fw * c->fh * 3 * sizeof(float)));
+            if (!c->flow3) if (th_status s = c->flow3.alloc((size_t)c->fw * c->fh * 3)) return s;
             th::launch_flow_pack3(c->flow, c->flow3, (size_t)c->fw * c->fh, c->stream);
         }
         {
@@ -416,12 +416,10 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
                 const bool takes_stats = done + m == n;
                 if (takes_stats) {
                     const uint32_t parts = th::fused_stats_parts(p.count, p.perm != nullptr), need = parts + (parts + 255u) / 256u + 16u;
-                    if (c->fused_parts_cap < need) {
+                    if (c->fused_parts.size() < need) {
                         TH_HIP(hipStreamSynchronize(c->stream));
-                        (void)hipFree(c->fused_parts); c->fused_parts = nullptr; c->fused_parts_cap = 0;
-                        TH_HIP(hipMalloc((void **)&c->fused_parts, (size_t)need * sizeof(th::StatsPartial)));
                         // (no memset, here or in front of a launch: every wave writes its partial - an empty one where it met no particle)
-                        c->fused_parts_cap = need;
+                        if (th_status s = c->fused_parts.alloc(need)) return s;
                     }
                     p.stats_part = c->fused_parts;
                     c->fused_stats.nparts = parts; c->fused_stats.limit = p.u.speedLimit;
@@ -465,8 +463,8 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
         if (c->graphs.size() >= 8) { destroy_graph(c->graphs.front()); c->graphs.erase(c->graphs.begin()); }
         GraphEntry g;
         g.n = n; g.variant = plan.v; g.generic = plan.generic; g.ring = c->ring; g.key = key;
-        TH_HIP(hipMalloc((void **)&g.times_dev, (size_t)n * sizeof(float)));
-        TH_HIP(hipHostMalloc((void **)&g.times_host, (size_t)n * sizeof(float)));
+        if (th_status s = g.times_dev.alloc((size_t)n)) return s;
+        if (th_status s = g.times_host.alloc((size_t)n)) return s;
         TH_HIP(hipEventCreate(&g.copied));
         const std::vector<float4 *> ring_before = c->ring;
         const int since_before = c->steps_since_sort;
@@ -489,7 +487,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
             if (st != TH_OK) return st;
             return fail(TH_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e));
         }
-        c->graphs.push_back(g);
+        c->graphs.push_back(std::move(g));
         hit = &c->graphs.back();
     }
     TH_HIP(hipEventSynchronize(hit->copied));          // previous replay's copy out of times_host is done
