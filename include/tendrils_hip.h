@@ -486,7 +486,7 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
 
 /* Per-context switches between equivalent paths (build-defined; no switch changes a result - the parity suites rerun under
  * each, tests/conftest.py).  A context starts from the environment variables of the same names, read by th_create
- * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS;
+ * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS, TH_HASH_WINDOW;
  * TH_DRAW=stream|bins sets what TH_DRAW_AUTO means).
  *   TH_OPT_BUCKET          tile-sorted slot order never (0) / always (1) / when it pays (-1, default)
  *   TH_OPT_RESORT_STEPS    re-sort period of single-step launches (default 64)
@@ -512,13 +512,17 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
  *                          the switch resets itself.  What is
  *                          tested: every other rank of the job returns an error too instead of waiting in a collective
  *   TH_OPT_SPAWN_CHUNK_ROWS (TH_SPAWN_CHUNK_ROWS) rows of its band that th_spawn_sample_sharded computes, fetches and spawns at a time
- *                          (default 0: as many as keep every scratch array of the exchange under about 64 MiB); the same on every rank */
+ *                          (default 0: as many as keep every scratch array of the exchange under about 64 MiB); the same on every rank
+ *   TH_OPT_HASH_WINDOW     (TH_HASH_WINDOW) fused th_step_n launches hash the noise lattice over a window of it, without the
+ *                          mod 289 of every coordinate, whenever the launch's coordinates provably fit one (1, default); never (0)
+ *   TH_OPT_HASH_WINDOW_LAUNCHES  (read-only) fused launches of this context that ran over the window so far */
 enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH_OPT_FUSE = 3, TH_OPT_GRAPH = 4,
        TH_OPT_FORCE_GENERIC = 5, TH_OPT_DRAW_REUSE = 6, TH_OPT_BINS_POOL = 7,
 #ifdef TH_TESTING
        TH_OPT_INJECT_FAILURE = 8,
 #endif
-       TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12 };
+       TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12,
+       TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14 };
 th_status th_option_set(th_context *ctx, int32_t option, int64_t value);
 th_status th_option_get(th_context *ctx, int32_t option, int64_t *value);
 

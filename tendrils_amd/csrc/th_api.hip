@@ -45,6 +45,7 @@ void options_from_environment(th_options &o)
     o.draw_reuse = number("TH_DRAW_REUSE", 1) != 0;
     o.async_sort = number("TH_ASYNC_SORT", 1) != 0;
     o.skip_unseen = number("TH_SKIP_UNSEEN", 1) != 0;
+    o.hash_window = number("TH_HASH_WINDOW", 1) != 0;
     o.spawn_chunk_rows = (int)number("TH_SPAWN_CHUNK_ROWS", 0); if (o.spawn_chunk_rows < 0) o.spawn_chunk_rows = 0;
     o.bins_pool = (uint32_t)number("TH_BINS_POOL", 0);
     o.bins_pages = (int)number("TH_BINS_PAGES", 0); if (o.bins_pages > (int)th::kBinPagesLimit || o.bins_pages < -(int)th::kBinPagesLimit) o.bins_pages = 0;
@@ -218,6 +219,9 @@ th_status th_create(const th_config *cfg, th_context **out)
         build_gradient_table(lut.data());
         TH_HIP(hipMemcpy(c->lut, lut.data(), lut.size() * sizeof(float4), hipMemcpyHostToDevice));
         th::launch_hash_tables(c->lut_block, c->stream);
+        TH_HIP(hipGetLastError());
+        if (th_status s = c->win_block.alloc((size_t)th::win_table_vectors())) return s;
+        th::launch_win_tables(c->win_block, c->lut, c->stream);
         TH_HIP(hipGetLastError());
         if (th_status s = c->d_flag.alloc(1)) return s;
         if (th_status s = c->partials.alloc(th::kStatsBlocks)) return s;
@@ -593,6 +597,8 @@ th_status th_option_set(th_context *c, int32_t option, int64_t value)
     case TH_OPT_FORCE_GENERIC: o.force_generic = value != 0; break;
     case TH_OPT_DRAW_REUSE: o.draw_reuse = value != 0; break;
     case TH_OPT_SKIP_UNSEEN: o.skip_unseen = value != 0; break;
+    case TH_OPT_HASH_WINDOW: o.hash_window = value != 0; break;
+    case TH_OPT_HASH_WINDOW_LAUNCHES: return fail(TH_ERR_INVALID, "TH_OPT_HASH_WINDOW_LAUNCHES is read-only");
     case TH_OPT_ASYNC_SORT: o.async_sort = value != 0; if (!o.async_sort) { if (th_status s = asort_drop(c)) return s; } break;
     case TH_OPT_BINS_POOL: TH_REQUIRE(value >= 0 && value < (1ll << 32), "TH_OPT_BINS_POOL out of range"); o.bins_pool = (uint32_t)value; break;
 #ifdef TH_TESTING
@@ -627,6 +633,8 @@ th_status th_option_get(th_context *c, int32_t option, int64_t *value)
     case TH_OPT_DRAW_REUSE: *value = o.draw_reuse; break;
     case TH_OPT_ASYNC_SORT: *value = o.async_sort; break;
     case TH_OPT_SKIP_UNSEEN: *value = o.skip_unseen; break;
+    case TH_OPT_HASH_WINDOW: *value = o.hash_window; break;
+    case TH_OPT_HASH_WINDOW_LAUNCHES: *value = c->hash_window_launches; break;
     case TH_OPT_BINS_POOL: *value = o.bins_pool; break;
 #ifdef TH_TESTING
     case TH_OPT_INJECT_FAILURE: *value = o.inject_failure; break;

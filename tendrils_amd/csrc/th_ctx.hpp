@@ -64,6 +64,7 @@ struct th_options {
     bool skip_unseen = true;             // TH_SKIP_UNSEEN: draw() skips the blocks of slots whose lines the step saw end up outside the view (th_step.hip)
     int spawn_chunk_rows = 0;            // TH_SPAWN_CHUNK_ROWS: rows of a band that th_spawn_sample_sharded fetches at a time (0: by the scratch budget)
     bool async_sort = true;              // TH_ASYNC_SORT: a frame loop's re-sort runs beside its draw() instead of inside two of its steps (th_step.hip)
+    bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
 };
 
 // One captured th_step_n sequence (see th_step_n).
@@ -94,6 +95,8 @@ struct th_context {
     bool targets_checked = true, targets_nonfinite = false;   // fresh texture = zeros
     DevBuf<float4> lut_block;            // [hash tables | gradient table] ...
     float4 *lut = nullptr;               // ... the gradient table inside it
+    DevBuf<float4> win_block;            // [winA | winB | winG]: the same tables extended periodically (th_logic.hpp "over a window")
+    long long hash_window_launches = 0;  // fused launches that ran over the window tables (TH_OPT_HASH_WINDOW_LAUNCHES)
     DevBuf<uchar4> frames[2];
     int32_t frw = 0, frh = 0;
     DevBuf<unsigned int> d_flag;

@@ -58,6 +58,18 @@ __global__ __launch_bounds__(256) void hash_tables_kernel(float4 *block)
 void launch_hash_tables(float4 *block, hipStream_t s) { hipLaunchKernelGGL(hash_tables_kernel, dim3(1), dim3(256), 0, s, block); }
 int hash_table_vectors() { return kHashVec; }
 
+// the window tables (th_logic.hpp "over a window"): the same two polynomials and the gradient table, extended periodically
+__global__ __launch_bounds__(256) void win_tables_kernel(float4 *block, const float4 *lut)
+{
+    uint32_t *a = reinterpret_cast<uint32_t *>(block), *b = a + kWinA;
+    float4 *g = block + kWinVec;
+    for (int k = threadIdx.x; k < kWinA; k += 256) a[k] = 4u * (uint32_t)permute_int((float)(k % 289)) - kBiasBitsA;
+    for (int k = threadIdx.x; k < kWinB; k += 256) b[k] = 16u * (uint32_t)((int)permute_int((float)(k % 289)) - kLutMin) - kBiasBitsB;
+    for (int k = threadIdx.x; k < kWinG; k += 256) g[k] = lut[k % 289 - kLutMin];
+}
+void launch_win_tables(float4 *block, const float4 *lut, hipStream_t s) { hipLaunchKernelGGL(win_tables_kernel, dim3(1), dim3(256), 0, s, block, lut); }
+int win_table_vectors() { return kWinVec + kWinG; }
+
 
 
 // The two formats of a state ring as the integrator loops see them: a Word per texel in memory, the decoded float4 in
@@ -232,18 +244,22 @@ TH_D void stats_none(StatsPartial *slot, bool first)
 }
 
 // The fused loop.  One LDS block: [permA | permB | gradient table], the hash tables first so that their reads need no base
-// offset.  BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step (to
+// offset - or, WIN, the window tables [winA | winB | winG] (19 680 B: six workgroups per CU hold 118 of 160 KB); `lut` then
+// lies kLutMin entries in front of winG, the addressing the gradient reads have anyway.
+// BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step (to
 // out_prev): f32 carries it along, a register copy per step; a packed ring makes its words at once at the last step (carried
 // through the loop as four more floats the kernel had 101 VGPRs - four waves per SIMD instead of five), and after one step
 // it is the word that came in, whatever that decodes to.  (Peeling the last step off the loop instead leaves the step loop's
 // VALU count as it is (349) and inlines integrate twice: 90 VGPRs against 80 for the f32 kernel, profiles/r7_b_isa.txt.)
 // The statistics of a packed ring are those of what its texels decode to - what th_stats reads through its f32 view.
 #define TH_LOGIC_FUSED_LOOP(Fmt)                                                                                              \
-    __shared__ float4 smem[NOISE ? kHashVec + kLutSize : 1];                                                                  \
-    const float4 *lut = smem + (NOISE ? kHashVec : 0);                                                                        \
-    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + kPermA};       \
+    static_assert(!WIN || (NOISE && !FAST), "WIN: NOISE, exact");                                                              \
+    __shared__ float4 smem[WIN ? kWinVec + kWinG : NOISE ? kHashVec + kLutSize : 1];                                          \
+    const float4 *lut = smem + (WIN ? kWinVec + kLutMin : NOISE ? kHashVec : 0);                                              \
+    const HashTables tabs{reinterpret_cast<const uint32_t *>(smem), reinterpret_cast<const uint32_t *>(smem) + (WIN ? kWinA : kPermA)}; \
     if constexpr (NOISE) {                                                                                                    \
-        fill_hash_tables(smem, p.lut);                                                                                        \
+        if constexpr (WIN) fill_win_tables(smem, p.win);                                                                      \
+        else fill_hash_tables(smem, p.lut);                                                                                   \
         __syncthreads();                                                                                                      \
     }                                                                                                                         \
     uint32_t idx, stride, end;                                                                                                \
@@ -276,7 +292,7 @@ TH_D void stats_none(StatsPartial *slot, bool first)
         for (uint32_t k = 0; k < p.nsteps; ++k) {                                                                             \
             if constexpr (!Fmt::packed) wprev = Fmt::encode(st);                                                              \
             else if (k + 1u == p.nsteps && k) wprev = Fmt::encode(st);                                                        \
-            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true, !NOISE>(p, lut, st, pid, p.times[k], &tabs)); \
+            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true, !NOISE, WIN>(p, lut, st, pid, p.times[k], &tabs)); \
         }                                                                                                                     \
         if (!Fmt::packed || p.nsteps) w = Fmt::encode(st);                                                                    \
         Fmt::store(p.out_prev, idx, wprev);                                                                                   \
@@ -285,14 +301,14 @@ TH_D void stats_none(StatsPartial *slot, bool first)
     }                                                                                                                         \
     if constexpr (STATS) stats_none(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], first);
 
-template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS>
+template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS, bool WIN>
 __global__ __launch_bounds__(256) void logic_fused_kernel(const LogicParams p) { TH_LOGIC_FUSED_LOOP(F32Texel) }
 
 // Packed ring (TH_STATE_F16): the same fusion on 8-B texels.  The storage quantisation is part of every step (a step reads
 // what the previous one stored), so between two fused steps the state is what the ring WOULD hold of it - quantize_state =
 // unpack of pack - in registers as floats; the words are made once, for the two states that leave.  Bit-identical to
 // nsteps logic_packed_kernel launches.
-template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS>
+template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool BUCKETED, bool STATS, bool WIN>
 __global__ __launch_bounds__(256, 5) void logic_fused_packed_kernel(const LogicParams p) { TH_LOGIC_FUSED_LOOP(PackedTexel) }
 
 // Launch shape of the fused passes: one 256-slot workgroup per 256 particles (no persistent grid).  A fused pass
@@ -312,10 +328,11 @@ void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t
 {
     const bool packed = v.format == StateFormat::packed, bucketed = p.perm != nullptr;
     const int grid = fused_grid(p.count, bucketed);
-    lift([&](auto fast, auto noise, auto target, auto pow2, auto bk, auto stats) {
-        hipLaunchKernelGGL((packed ? logic_fused_packed_kernel<fast, noise, target, pow2, bk, stats>
-                                   : logic_fused_kernel<fast, noise, target, pow2, bk, stats>), dim3(grid), dim3(256), 0, s, p);
-    }, v.mode == TH_MODE_FAST, v.noise, v.target, v.pow2, bucketed, p.stats_part != nullptr);
+    lift([&](auto fast, auto noise, auto target, auto pow2, auto bk, auto stats, auto window) {
+        constexpr bool win = noise && !fast && window;  // (WIN acts under NOISE, in exact mode only)
+        hipLaunchKernelGGL((packed ? logic_fused_packed_kernel<fast, noise, target, pow2, bk, stats, win>
+                                   : logic_fused_kernel<fast, noise, target, pow2, bk, stats, win>), dim3(grid), dim3(256), 0, s, p);
+    }, v.mode == TH_MODE_FAST, v.noise, v.target, v.pow2, bucketed, p.stats_part != nullptr, p.win != nullptr);
 }
 
 // ---------------------------------------------------------------------------

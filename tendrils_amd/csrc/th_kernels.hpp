@@ -11,6 +11,9 @@
 namespace th {
 
 constexpr uint32_t kMaxFusedSteps = 32;
+// fused launches over a window of the noise lattice (th_logic.hpp "over a window"; th_step.hip: hash_window)
+constexpr int kWinSpan = 286;                // widest range hi - lo of lattice coordinates that a window takes
+constexpr int kWinMaxCell = 8958;            // mod289_int(i) is the true residue of every integer |i| up to here
 
 // Tile-sorted slot order (th_kernels.hip "Tile-sorted slot order")
 constexpr uint32_t kTileChunk = 4096;        // slots per workgroup (16 per thread), all of one tile
@@ -72,6 +75,10 @@ struct LogicParams {
     uint32_t nsteps;
     struct StatsPartial *stats_part;   // (optional) per workgroup: the statistics of state nsteps, taken while it is in registers
     float times[kMaxFusedSteps];   // `time` of each fused step
+    // (fused launches over a window of the noise lattice, th_logic.hpp "over a window"; behind the older fields, which keep their places)
+    const float4 *win;       // [winA | winB | winG]
+    float win_bound;         // |pos| below this (<= pos_bound) keeps both evaluations' lattice coordinates inside the launch's windows
+    float win_k[2][3];       // per evaluation: 2^21 - cz, 2^21 - cxy, 2^19 - cxy
 };
 
 struct TileSortParams {
@@ -273,7 +280,7 @@ enum class SortedPass {
 // launchers (defined in th_kernels.hip)
 void launch_logic(const LogicParams &p, const LogicVariant &v, hipStream_t stream);        // over texel order or p.perm's slots
 void launch_logic_generic(const LogicParams &p, hipStream_t stream);                       // texel-order f32 only (the host unpacks around it)
-void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t stream);  // p.nsteps steps in one pass
+void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t stream);  // p.nsteps steps in one pass; p.win set (with the noise, exact mode): over the window tables
 // Which flow copy a fused pass taps, fixed by its variant at compile time: p.flow3 (12 B per texel) without the noise,
 // p.flow (RGBA32F) with it.  The caller sets p.flow3 on the same condition.
 inline bool fused_taps_flow3(const LogicVariant &v) { return !v.noise; }
@@ -291,6 +298,8 @@ void launch_permute_state(float4 *dst, const float4 *src, const uint32_t *perm, 
 void launch_fill(float4 *dst, float4 value, size_t n, hipStream_t stream);
 void launch_hash_tables(float4 *block, hipStream_t stream);      // the hash tables in front of the gradient table (th_kernels.hip)
 int hash_table_vectors();
+void launch_win_tables(float4 *block, const float4 *lut, hipStream_t stream);   // [winA | winB | winG] from the gradient table `lut`
+int win_table_vectors();
 void launch_finite_check(const float4 *src, size_t n, unsigned int *flag, hipStream_t stream);
 // the fold of `nparts` per-workgroup partials a fused launch left (LogicParams::stats_part; fused_stats_parts() of them)
 void launch_stats_fold(const StatsPartial *parts, uint32_t nparts, StatsPartial *scratch, size_t n, const unsigned long long *respawned,

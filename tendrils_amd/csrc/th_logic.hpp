@@ -179,9 +179,31 @@ TH_D void fill_hash_tables(float4 *smem, const float4 *lut_global)
     for (int k = threadIdx.x; k < kHashVec + kLutSize; k += 256) smem[k] = block[k];
 }
 
+// ---- the same stages over a window of the lattice (WIN: the fused launches whose coordinates the host can bound) ------
+// Only the residue mod 289 of a lattice coordinate enters the hash, and the coordinates of one launch lie in a narrow
+// window the host knows (th_step.hip: hash_window).  With the tables extended periodically and indexed by i - c, c a
+// multiple of 289 below the window, mod289_int (v_mul, v_floor, v_fma per coordinate) leaves the step loop: the bias add
+// takes the raw coordinate and a constant that carries -c (LogicParams::win_k: 2^21 - cz, 2^21 - cxy, 2^19 - cxy per
+// evaluation; exact, the sums lie in [2^k, 2^k + 578]).  P[r] = permute_int(r):
+//   winA[u] = 4 * P[u mod 289] - 0x4A000000                u = iz - cz (+ 1) in [0, 579]
+//   winB[j] = 16 * (P[j mod 289] - kLutMin) - 0x49000000   j = P[..] + (iy - cxy) + e in [0, 867]
+//   winG[k] = gradient entry of argument k mod 289         k = P[..] + (ix - cxy) + e in [0, 867], at byte 16 * (k - kLutMin)
+// permute_int(k) == permute_int(k mod 289) on the old tables' arguments and mod289_int is the true residue for |i| <= 8958
+// (tests/test_hash_window.py), so every entry read is the one the unwindowed chain reads.
+constexpr int kWinA = 580, kWinB = 868, kWinG = 868;
+constexpr int kWinVec = (kWinA + kWinB) / 4;                 // float4 slots in front of winG
+static_assert(288 + kWinSpan + 2 < kWinA && 2 * 288 + kWinSpan + 1 < kWinB, "i - c <= 288 + kWinSpan (th_kernels.hpp) stays inside the tables");
 
-template <bool FAST>
-TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, const HashTables &T)
+TH_D void fill_win_tables(float4 *smem, const float4 *win_global)
+{
+    for (int k = threadIdx.x; k < kWinVec + kWinG; k += 256) smem[k] = win_global[k];
+}
+
+
+// WIN: T holds the window tables, K the evaluation's three bias constants (wave-uniform:
+// SGPR operands of the adds), and the coordinates go into the adds as they are.  Everything behind the adds is the same.
+template <bool FAST, bool WIN = false>
+TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, const HashTables &T, const float *K = nullptr)
 {
     NoiseCorners n;
     float s = mad<FAST>(vz, kC3, sxy);
@@ -221,9 +243,15 @@ TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, co
     // r + 2^21, r + 2^19: the sums' bits are the offsets.  As asm: left to the compiler, the same three adds schedule into
     // five more VGPRs (a wave per SIMD less) in one packed fused kernel.
     uint32_t zb, yb, xb;
-    asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(zb) : "v"(mod289_int(iz)));       // kBiasBitsA + 4 * iz
-    asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(yb) : "v"(mod289_int(iy)));       // kBiasBitsA + 4 * iy
-    asm("v_add_f32 %0, 0x49000000, %1" : "=v"(xb) : "v"(mod289_int(ix)));       // kBiasBitsB + 16 * ix
+    if constexpr (WIN) {
+        asm("v_add_f32 %0, %2, %1" : "=v"(zb) : "v"(iz), "s"(K[0]));            // kBiasBitsA + 4 * (iz - cz)
+        asm("v_add_f32 %0, %2, %1" : "=v"(yb) : "v"(iy), "s"(K[1]));            // kBiasBitsA + 4 * (iy - cxy)
+        asm("v_add_f32 %0, %2, %1" : "=v"(xb) : "v"(ix), "s"(K[2]));            // kBiasBitsB + 16 * (ix - cxy)
+    } else {
+        asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(zb) : "v"(mod289_int(iz)));   // kBiasBitsA + 4 * iz
+        asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(yb) : "v"(mod289_int(iy)));   // kBiasBitsA + 4 * iy
+        asm("v_add_f32 %0, 0x49000000, %1" : "=v"(xb) : "v"(mod289_int(ix)));   // kBiasBitsB + 16 * ix
+    }
     zb &= 0xffcu;                                                               // byte offset into permA
     const uint32_t *pa = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permA) + zb);
     const uint32_t a0 = pa[0] + yb, a1 = pa[1] + yb;            // 4 * (permute(iz) + iy), 4 * (permute(iz + 1) + iy)
@@ -346,7 +374,11 @@ TH_D float snoise_finish(const NoiseCorners &n, float4 g0, float4 g1, float4 g2,
 // ---------------------------------------------------------------------------
 // One particle: state texel `st` of particle `pid` (= texel index in this context's rows).
 constexpr int kTileShift = 5;            // 32 x 32-texel tiles of the flow field: the key of the tile-sorted slot order
-template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB = false, bool FLOW3 = false>
+//   WIN    (fused passes, with PTAB, exact mode) the hash stages run over the launch's window of the lattice: window tables,
+//          p.win_k, and p.win_bound as the domain guard - a lane outside it takes the reference-order branch like any lane
+//          outside pos_bound.  Not with FAST: between win_bound and pos_bound the fast arithmetic is the result, which the
+//          reference-order branch does not give (a second fast path in the cold branch cost the fast kernels 8 to 16 VGPRs)
+template <bool FAST, bool NOISE, bool TARGET, bool POW2, bool DECODED, bool PTAB = false, bool FLOW3 = false, bool WIN = false>
 TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32_t pid, float time,
                       const HashTables *tabs = nullptr)
 {
@@ -360,7 +392,9 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
 
     // two compares (not max): a NaN in either component must fail the test.  pos_bound < |inert| (host), so inert
     // particles (src/logic.frag:52) fail it too and are passed through by logic_texel_ref.
-    bool in_domain = __builtin_fabsf(posx) < p.pos_bound && __builtin_fabsf(posy) < p.pos_bound;
+    static_assert(!WIN || (PTAB && !FAST), "the window: fused passes in exact mode");
+    const float bound = WIN ? p.win_bound : p.pos_bound;
+    bool in_domain = __builtin_fabsf(posx) < bound && __builtin_fabsf(posy) < bound;
     if (__builtin_expect(!in_domain, 0)) {
         if (!(posx != kInert || posy != kInert)) return st;              // inert: pass through (src/logic.frag:52)
         // A NaN or infinite position component makes every output component NaN in the reference: the first noise
@@ -431,8 +465,8 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
         NoiseCorners na, nb;
         float4 a0, a1, a2, a3, b0, b1, b2, b3;
         if constexpr (PTAB) {
-            na = snoise_corners_tab<FAST>(nx, ny, uvx + ntime, sxy, *tabs);
-            nb = snoise_corners_tab<FAST>(nx, ny, (uvy + ntime) + 1234.5678f, sxy, *tabs);
+            na = snoise_corners_tab<FAST, WIN>(nx, ny, uvx + ntime, sxy, *tabs, p.win_k[0]);
+            nb = snoise_corners_tab<FAST, WIN>(nx, ny, (uvy + ntime) + 1234.5678f, sxy, *tabs, p.win_k[1]);
             a0 = lut_at_offset(lut, na.j0); a1 = lut_at_offset(lut, na.j1); a2 = lut_at_offset(lut, na.j2); a3 = lut_at_offset(lut, na.j3);
             b0 = lut_at_offset(lut, nb.j0); b1 = lut_at_offset(lut, nb.j1); b2 = lut_at_offset(lut, nb.j2); b3 = lut_at_offset(lut, nb.j3);
         } else {

@@ -32,6 +32,47 @@ bool finite_uniforms(const th_logic_uniforms &u)
     return true;
 }
 
+// The window of the noise lattice that one fused launch of m steps stays in (th_logic.hpp "over a window"):
+// the bound on |pos| that goes with it and the bias constants of both evaluations.  In double; hulls over the index i in
+// [0, 1] (vary() is linear in it) and uv in [0, 1]; every lattice range 2 cells wider each way than its hull, for the
+// kernel's fp32 rounding (below 0.01 cell at these magnitudes).  false: a range is wider than a window, or reaches beyond
+// the cells whose mod289_int is the true residue, or - a huge noiseScale - the bound on |pos| does not reach twice the view's
+// half-extent (pos * viewSize in [-1, 1] is in sight): particles in and near plain sight would take the reference-order
+// branch.  The launch then runs the kernel without the window, as every launch in fast mode does (th_logic.hpp: integrate, WIN).
+constexpr double kWinNoiseUnits = 64.0;      // N: |pos * noiseScale'| <= N inside win_bound
+constexpr double kWinMinViews = 2.0;         // win_bound * min|viewSize| at least this
+bool hash_window(const th_logic_uniforms &u, float pos_bound, const float *times, int32_t m, float *win_bound, float (*win_k)[3])
+{
+    const double N = kWinNoiseUnits;
+    const double scale0 = u.noiseScale, scale1 = scale0 + (double)u.varyNoiseScale * scale0;
+    const double scale = std::fmax(std::fabs(scale0), std::fabs(scale1));
+    *win_bound = (float)(scale > 0.0 ? std::fmin((double)pos_bound, N / scale) : (double)pos_bound);
+    if (!((double)*win_bound * std::fmin(std::fabs((double)u.viewSize[0]), std::fabs((double)u.viewSize[1])) >= kWinMinViews)) return false;
+    const double speed0 = u.noiseSpeed, speed1 = speed0 + (double)u.varyNoiseSpeed * speed0;
+    double tlo = std::numeric_limits<double>::infinity(), thi = -tlo;
+    for (int32_t k = 0; k < m; ++k)
+        for (double speed : {speed0, speed1}) {
+            const double nt = (double)times[k] * speed;
+            tlo = std::fmin(tlo, nt); thi = std::fmax(thi, nt);
+        }
+    for (int e = 0; e < 2; ++e) {
+        const double zlo = tlo + (e ? 1234.5678 : 0.0), zhi = thi + 1.0 + (e ? 1234.5678 : 0.0);    // z = uv + ntime (+ 1234.5678)
+        const double slo = zlo / 3.0 - 2.0 * N / 3.0, shi = zhi / 3.0 + 2.0 * N / 3.0;                // s = (nx + ny + z) / 3
+        const double lo[2] = {std::floor(-N + slo) - 2.0, std::floor(zlo + slo) - 2.0};               // ix, iy | iz
+        const double hi[2] = {std::floor(N + shi) + 2.0, std::floor(zhi + shi) + 2.0};
+        double c[2];
+        for (int a = 0; a < 2; ++a) {
+            if (!(hi[a] - lo[a] <= (double)th::kWinSpan)) return false;
+            if (!(std::fmax(std::fabs(lo[a]), std::fabs(hi[a])) + 1.0 <= (double)th::kWinMaxCell)) return false;
+            c[a] = 289.0 * std::floor(lo[a] / 289.0);
+        }
+        win_k[e][0] = (float)(2097152.0 - c[1]);      // 2^21 - cz
+        win_k[e][1] = (float)(2097152.0 - c[0]);      // 2^21 - cxy
+        win_k[e][2] = (float)(524288.0 - c[0]);       // 2^19 - cxy
+    }
+    return true;
+}
+
 }  // namespace
 
 // Build the launch parameters of one integrator pass and pick the kernel variant.
@@ -411,6 +452,8 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
                 p.perm = order >= 0 ? c->orders[(size_t)order].perm : nullptr;
                 p.nsteps = (uint32_t)m;
                 for (int32_t k = 0; k < m; ++k) p.times[k] = times[(size_t)(done + k)];
+                const bool window = plan.v.noise && plan.v.mode != TH_MODE_FAST && c->opt.hash_window && hash_window(p.u, p.pos_bound, p.times, m, &p.win_bound, p.win_k);
+                if (window) p.win = c->win_block;
                 // the last launch of the call takes the statistics of the state it leaves in buffers[0] (a packed ring's: of
                 // what the stored texels decode to)
                 const bool takes_stats = done + m == n;
@@ -432,6 +475,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
                 th::launch_logic_fused(p, plan.v, c->stream);
                 if (k1) TH_HIP(hipEventRecord(k1, c->stream));
                 TH_HIP(hipGetLastError());
+                if (window) ++c->hash_window_launches;
                 set_order(c, other, order);                // both outputs sit at the input's slots
                 c->counted.buf = nullptr;
                 if (m & 1) { c->ring[0] = other; c->ring[1] = cur; }
