@@ -75,7 +75,8 @@ enum {
     TH_TARGET_RING = -1,     /* rotate the ring, write buffers[0] (the default path) */
     TH_TARGET_TARGETS = -2,  /* tendrils.targets (src/index.js:105) */
     TH_SOURCE_FLOW = -3,     /* tendrils.flow as spawnData (src/demo.main.js:403-406) */
-    TH_SOURCE_IMAGE = -4     /* the spawner's own buffer: an RGBA image in a float texture (th_spawn_image_upload) */
+    TH_SOURCE_IMAGE = -4,    /* the spawner's own buffer: an RGBA image in a float texture (th_spawn_image_upload) */
+    TH_SOURCE_NONE = -5      /* th_program_run: the pass has no spawnData */
     /* values >= 0 name ring buffer k in its CURRENT order (buffers[k]) */
 };
 
@@ -218,6 +219,57 @@ th_status th_spawn_image_upload(th_context *ctx, const float *rgba, int32_t w, i
 th_status th_spawn_image_triangles(th_context *ctx, const float *positions, int32_t triangles, const float viewSize[2],
                                    const float color[4], int32_t w, int32_t h);
 th_status th_spawn_image_download(th_context *ctx, float *rgba);           /* read-back (tests) */
+
+/* -- user programs: a pass the CALLER wrote ------------------------------------------------------------------------
+ * The seam the reference is built around: Particles.step(update, buffer) runs whatever shader object sits in particles.logic
+ * as one full-screen pass over the state ring (src/particles.js:123-145), Tendrils.spawnShader(shader, update, buffer) swaps
+ * any gl-shader in for one pass (src/index.js:432-457), and new Tendrils(gl, { logicShader }) takes a caller's integrator.
+ * Here such a shader is HIP source defining one device function,
+ *     __device__ float4 th_main(const th_pass &p);        - main() of the fragment shader; the return value is gl_FragColor
+ * compiled for gfx950 at run time through hiprtc (bound at run time: the copy the process already holds, else by soname;
+ * TH_HIPRTC_LIB names another; a host that never compiles a program never loads it) with the library's arithmetic flags
+ * (-O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize) behind a prelude that declares (tendrils_amd/csrc/th_program_prelude.inc):
+ *   th_pass            x, y (this texel in the WHOLE texture: gl_FragCoord.xy - 0.5 of the unsharded run, also on a row band),
+ *                      index (y * dataRes.x + x), dataRes, geomRes (= dataRes.x, 2 dataRes.y: src/index.js:195-197),
+ *                      uv (gl_FragCoord.xy / dataRes in fp32, src/logic.frag:46), self (this texel of `particles` = buffers[1]
+ *                      as the pass sees the ring), uniforms (th_uniforms<T>(p): the caller's block as the caller's struct)
+ *   th_particles(p, x, y)      texel (x, y) of `particles`, whole-texture coordinates, clamped to the texture
+ *   th_data(p, u, v), th_flow(p, u, v)   texture2D(spawnData / flow, (u, v)): NEAREST, CLAMP_TO_EDGE, clamp(floor(u * n), 0, n - 1)
+ *                              in fp32; th_data_res(p) / th_flow_res(p) their resolutions; no spawnData reads as zeros
+ *   th_targets(p)              this texel of tendrils.targets
+ * Every accessor clamps its index: a program that reads through them alone cannot read out of bounds.
+ *  th_program_compile  no context, no device needed.  TH_ERR_INVALID when the source does not compile (a source without
+ *                      th_main included); th_program_log() then holds the compiler's whole output (per thread, like
+ *                      th_last_error()), with the line numbers of the caller's text under the name `name`
+ *  th_program_run      one pass: ring semantics of th_step / the spawn passes (target = TH_TARGET_RING rotates the ring and
+ *                      writes buffers[0]; TH_TARGET_TARGETS; a ring index), f32 and packed rings (a packed ring is read and
+ *                      written through the f32 staging of the spawn passes), whole textures and row bands; `source` names
+ *                      spawnData as for th_spawn_sample - TH_SOURCE_FLOW, TH_SOURCE_IMAGE, a ring index in the order the pass
+ *                      sees (on a row band: gathered first, th_state_gather), or TH_SOURCE_NONE.  uniforms: the caller's own
+ *                      struct of up to 1024 bytes (more: TH_ERR_INVALID), handed to the kernel with its launch - the call
+ *                      enqueues and returns.  Buffers held in tile-sorted slot order are brought back to texel order first, as
+ *                      by every spawn pass.  The pass does NOT touch the `respawned` counter (the library cannot know what a
+ *                      program spawns).  A context loads the program on its first run and keeps the module until th_destroy.
+ *                      On a row band a read of `particles` outside the band's rows fails the call with TH_ERR_UNSUPPORTED
+ *                      (the row is named; the target's content is then unspecified) - such a call waits for its pass.
+ *                      A target that is also read through th_particles / th_data at OTHER texels is GL's feedback loop: undefined.
+ *  th_program_query    registers, LDS, scratch (spills) and code size of the kernel as this context loaded it
+ *  th_program_destroy  frees the program; contexts that have run it keep running it (th_program_run / _query with the
+ *                      handle stay valid on THOSE contexts until they are destroyed) */
+typedef struct th_program th_program;
+typedef struct th_program_info {
+    uint32_t vgprs, sgprs;           /* registers per lane / per wave */
+    uint32_t lds_bytes;              /* static LDS of a workgroup */
+    uint32_t scratch_bytes;          /* private memory per lane: non-zero = the program spills */
+    uint32_t code_bytes;             /* machine code of the program's code object */
+    uint32_t reserved;
+} th_program_info;
+th_status th_program_compile(const char *source, const char *name, th_program **out);
+const char *th_program_log(void);
+th_status th_program_destroy(th_program *program);
+th_status th_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
+                         int32_t source, int32_t target);
+th_status th_program_query(th_context *ctx, th_program *program, th_program_info *out);
 
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */

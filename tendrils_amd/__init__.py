@@ -9,10 +9,10 @@ and bench.py; the Node host (tendrils_amd/js) binds the same C ABI through N-API
 from ._capi import (INERT, TH_MODE_EXACT, TH_MODE_FAST, TH_SOURCE_FLOW, TH_STATE_F16, TH_STATE_F32,
                     TH_TARGET_RING, TH_TARGET_TARGETS, TendrilsHipError)
 from .flow_line import FlowLine, FlowLines
-from .particles import Particles, defaults as particles_defaults
+from .particles import Particles, Program, defaults as particles_defaults
 from .tendrils import Tendrils, defaults, gl_settings
 from .timer import Timer
 
-__all__ = ["Particles", "FlowLine", "FlowLines", "Tendrils", "Timer", "defaults", "particles_defaults", "gl_settings",
+__all__ = ["Particles", "Program", "FlowLine", "FlowLines", "Tendrils", "Timer", "defaults", "particles_defaults", "gl_settings",
            "TendrilsHipError", "INERT", "TH_MODE_EXACT", "TH_MODE_FAST", "TH_STATE_F32", "TH_STATE_F16", "TH_TARGET_RING",
            "TH_TARGET_TARGETS", "TH_SOURCE_FLOW"]

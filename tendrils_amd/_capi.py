@@ -15,7 +15,8 @@ TH_MODE_EXACT, TH_MODE_FAST = 0, 1
 TH_STATE_F32, TH_STATE_F16 = 0, 1
 TH_PASS_FLOW, TH_PASS_VIEW = 0, 1
 TH_MAX_LINE_WIDTH = 64.0
-TH_TARGET_RING, TH_TARGET_TARGETS, TH_SOURCE_FLOW, TH_SOURCE_IMAGE = -1, -2, -3, -4
+TH_TARGET_RING, TH_TARGET_TARGETS, TH_SOURCE_FLOW, TH_SOURCE_IMAGE, TH_SOURCE_NONE = -1, -2, -3, -4, -5
+TH_ERR_INVALID, TH_ERR_HIP, TH_ERR_NO_DEVICE, TH_ERR_UNSUPPORTED = 1, 2, 3, 4
 INERT = -1000000.0
 
 
@@ -101,6 +102,11 @@ class SpawnInfo(C.Structure):
 
 class CommInfo(C.Structure):
     _fields_ = [("active", C.c_int32), ("rank", C.c_int32), ("world", C.c_int32), ("rccl_version", C.c_int32)]
+
+
+class ProgramInfo(C.Structure):
+    _fields_ = [("vgprs", C.c_uint32), ("sgprs", C.c_uint32), ("lds_bytes", C.c_uint32), ("scratch_bytes", C.c_uint32),
+                ("code_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class FlowLineUniforms(C.Structure):
@@ -198,13 +204,18 @@ PROTOTYPES = {
     "th_view_step_buffers": (C.c_int32, [_ctx]),
     "th_colormap_upload": (C.c_int32, [_ctx, _fp, C.c_int32, C.c_int32]),
     "th_export_view_lines": (C.c_int32, [_ctx, C.POINTER(RenderUniforms), _fp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "th_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "th_program_log": (C.c_char_p, []),
+    "th_program_destroy": (C.c_int32, [C.c_void_p]),
+    "th_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32]),
+    "th_program_query": (C.c_int32, [_ctx, C.c_void_p, C.POINTER(ProgramInfo)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), C.c_int32]),
 }
 
-_NO_STATUS = {"th_abi_version", "th_last_error"}
+_NO_STATUS = {"th_abi_version", "th_last_error", "th_program_log"}
 TEST_BUILD_ONLY = {"th_comm_loopback_id"}      # declared under TH_TESTING in include/tendrils_hip.h
 _lib = None
 

@@ -7,6 +7,7 @@
 //   th_spawn.hip  the spawners
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
 //   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
+//   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -66,6 +67,28 @@ struct th_options {
     bool async_sort = true;              // TH_ASYNC_SORT: a frame loop's re-sort runs beside its draw() instead of inside two of its steps (th_step.hip)
     bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
 };
+
+// A user program as one context has loaded it (th_program.hip): the context owns the module - unloaded when the context
+// goes - and a reference to the program's record, so that th_program_destroy of a program a context has run is safe.
+struct th_program;
+namespace thi {
+struct ProgramModule {
+    th_program *prog = nullptr;
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;          // th_program_kernel
+    ProgramModule() = default;
+    ProgramModule(const ProgramModule &) = delete;
+    ProgramModule &operator=(const ProgramModule &) = delete;
+    ProgramModule(ProgramModule &&o) noexcept : prog(o.prog), module(o.module), fn(o.fn) { o.prog = nullptr; o.module = nullptr; o.fn = nullptr; }
+    ProgramModule &operator=(ProgramModule &&o) noexcept
+    {
+        if (this != &o) { reset(); prog = o.prog; module = o.module; fn = o.fn; o.prog = nullptr; o.module = nullptr; o.fn = nullptr; }
+        return *this;
+    }
+    ~ProgramModule() { reset(); }
+    void reset();                        // th_program.hip
+};
+}  // namespace thi
 
 // One captured th_step_n sequence (see th_step_n).
 struct GraphEntry {
@@ -262,6 +285,9 @@ struct th_context {
     struct { const float4 *buf = nullptr; int order = -1; th::TileGeom geom{}; long long at_step = -1; } counted;
 
     thi::FlowLineScratch *flow_lines = nullptr;   // th_flow_lines: staging and scratch (grow-only)
+
+    std::vector<thi::ProgramModule> programs;     // th_program_run: the user programs this context has loaded
+    DevBuf<unsigned> prog_flag;                   // ... and the word a pass on a row band raises (th_particles outside the band)
 
     size_t texels() const { return (size_t)cfg.width * cfg.height; }
     size_t state_bytes() const { return texels() * (packed ? sizeof(uint2) : sizeof(float4)); }

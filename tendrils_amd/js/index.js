@@ -89,6 +89,7 @@ class Tendrils {
     this.targets = new TargetsTexture(this);
     this.buffers = [];
     this.logicShader = null;
+    this.logicOption = (params.logicShader || null);   // new Tendrils(gl, { logicShader }): the caller's integrator
     this.uniforms = { render: {}, update: {} };
     this.particles = null;
     this.viewRes = [0, 0];
@@ -169,7 +170,7 @@ class Tendrils {
       row0: this.band.row0,
       globalHeight: this.band.globalHeight || (this.band.rows ? rootNum : 0)
     });
-    this.logicShader = this.particles.logic;
+    this.logicShader = (this.logicOption || this.particles.logic);
     this.particles.setup(numBuffers);
     this.targets.shape = shape;
     this.flow.shape = this.flow.shape;            // (re)create on the new context
@@ -254,7 +255,7 @@ class Tendrils {
   // n x (timer.tick(); step()) for a fixed-step, unpaused timer, as one captured-graph replay
   stepN(n) {
     const tm = this.timer;
-    if (tm.paused || tm.step < 0 || tm.end >= 0) {
+    if (tm.paused || tm.step < 0 || tm.end >= 0 || this.logicShader.kind !== 'logic') {
       for (let k = 0; k < n; ++k) { tm.tick(); this.step(); }
       return this;
     }

@@ -8,6 +8,8 @@ const path = require('path');
 const native = require('./native');
 // the sharded best-sample spawn lives in a small addon of its own (th_napi_spawn.cc), over the main addon's context handle
 const spawnAddon = require(path.join(__dirname, '..', 'lib', 'tendrils_spawn_sharded.node'));
+// ... and so do user programs (th_napi_program.cc): passes the caller wrote, compiled through hiprtc
+const programAddon = require(path.join(__dirname, '..', 'lib', 'tendrils_program.node'));
 const { step } = require('./utils');
 
 const defaults = () => ({
@@ -26,6 +28,24 @@ class Program {
   }
   bind() { return this; }
 }
+
+// A user program (include/tendrils_hip.h "user programs") is any object { source, uniforms, name }: `source` is HIP text
+// defining `__device__ float4 th_main(const th_pass &p)`, `uniforms` the block the source reads through th_uniforms<T>(p) -
+// an ArrayBuffer (or a typed array) of at most 1024 bytes laid out as that struct, read at every pass - or nothing.  It is
+// compiled once, on its first pass (a source that does not compile throws with the compiler's output); disposeProgram frees it.
+const isUserProgram = (program) => (!!program && typeof program.source === 'string');
+const compiled = new WeakMap();
+function userProgramHandle(program) {
+  let handle = compiled.get(program);
+  if (!handle) compiled.set(program, handle = programAddon.programCompile(program.source, program.name || 'user_program'));
+  return handle;
+}
+function disposeProgram(program) {
+  const handle = compiled.get(program);
+  if (handle) { programAddon.programDestroy(handle); compiled.delete(program); }
+}
+const uniformBlock = (program) => (((program.uniforms instanceof ArrayBuffer) || ArrayBuffer.isView(program.uniforms))
+  ? program.uniforms : null);
 
 // Stand-in for one gl-fbo of the ring; identity survives ring rotation.
 class StateBuffer {
@@ -56,6 +76,18 @@ function packLogic(u) {
 
 function runPass(particles, program, uniforms, target) {
   const h = particles.handle;
+  if (isUserProgram(program)) {
+    const data = uniforms.spawnData;
+    let source = programAddon.SOURCE_NONE;
+    if (data !== undefined && data !== null) {
+      if (data.bindFor) data.bindFor(particles);   // a spawner's own image buffer
+      source = ((typeof data === 'number') ? data : data.sourceIndex());
+      // ring indices are resolved by the library after utils.step() rotated the ring
+      if (source >= 0 && target === native.TARGET_RING) source = (source + 1) % particles.buffers.length;
+    }
+    programAddon.programRun(h, userProgramHandle(program), uniformBlock(program), source, target);
+    return;
+  }
   switch (program.kind) {
     case 'logic':
       native.step(h, packLogic(uniforms), target);
@@ -164,7 +196,8 @@ class Particles {
     const target = ((!buffer) ? native.TARGET_RING
       : ((buffer instanceof StateBuffer) ? buffer.index : buffer.targetIndex()));
 
-    const uniforms = Particles.applyUpdate(Object.assign(this.logic.uniforms, {
+    // (a user program's `uniforms` is its own packed block: the pass's uniform object starts empty)
+    const uniforms = Particles.applyUpdate(Object.assign((isUserProgram(this.logic) ? {} : this.logic.uniforms), {
       dataRes: this.shape,
       geomRes: this.geomShape
     }), update);
@@ -189,7 +222,9 @@ class Particles {
 
   draw() {}                                       // no display on this path (src/particles.js:147-158)
 
-  updateLogic(logic) { this.logic = ((logic instanceof Program) ? logic : new Program('logic')); }
+  updateLogic(logic) { this.logic = (((logic instanceof Program) || isUserProgram(logic)) ? logic : new Program('logic')); }
+  // registers, LDS, scratch (non-zero: it spills) and code bytes of a user program's kernel as this context loaded it
+  programQuery(program) { return programAddon.programQuery(this.handle, userProgramHandle(program)); }
   updateRender() {}
 
   sync() { native.sync(this.handle); }
@@ -253,4 +288,4 @@ class Particles {
   }
 }
 
-module.exports = { defaults, Particles, Program, StateBuffer, runPass, default: Particles };
+module.exports = { defaults, Particles, Program, StateBuffer, runPass, isUserProgram, disposeProgram, default: Particles };

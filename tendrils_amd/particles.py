@@ -21,15 +21,71 @@ def defaults():
 
 
 class Program:
-    """Stand-in for a compiled gl-shader object: names a kernel family."""
+    """Stand-in for a compiled gl-shader object: names a kernel family - or, from_source(), holds a pass the caller wrote."""
 
     def __init__(self, kind, **fixed):
-        self.kind = kind          # 'logic' | 'spawn-init' | 'spawn-ball' | 'spawn-sample' | 'spawn-direct'
+        self.kind = kind          # 'logic' | 'spawn-init' | 'spawn-ball' | 'spawn-sample' | 'spawn-direct' | 'user'
         self.fixed = fixed        # compile-time constants of that shader (e.g. samples, apply)
         self.uniforms = {}
+        self.handle = None        # 'user': the compiled th_program
+        self.uniforms_struct = None
+
+    @classmethod
+    def from_source(cls, source, uniforms_struct=None, name="user_program"):
+        """A user program (include/tendrils_hip.h "user programs"): HIP source defining
+        `__device__ float4 th_main(const th_pass &p)`, compiled here, once, for gfx950 - no GPU needed.  uniforms_struct: the
+        ctypes.Structure that mirrors the struct the source reads through th_uniforms<T>(p) (at most 1024 bytes); a pass
+        fills it by field name from its uniforms.  A source that does not compile raises TendrilsHipError with the
+        compiler's output (the caller's own line numbers, under `name`)."""
+        if uniforms_struct is not None and C.sizeof(uniforms_struct) > 1024:
+            raise ValueError("a uniform block holds at most 1024 bytes (%d)" % C.sizeof(uniforms_struct))
+        lib = _capi.load()
+        handle = C.c_void_p()
+        status = lib.th_program_compile(source.encode(), name.encode(), C.byref(handle))
+        if status != _capi.TH_OK:
+            raise _capi.TendrilsHipError(status, lib.th_last_error().decode(errors="replace") + "\n" +
+                                         lib.th_program_log().decode(errors="replace"))
+        prog = cls("user", name=name)
+        prog.handle, prog.uniforms_struct = handle, uniforms_struct
+        return prog
+
+    def pack(self, uniforms):
+        """the uniform block of one pass: every field of uniforms_struct the dict names (gl.uniform*: the others stay zero)"""
+        if self.uniforms_struct is None:
+            return None
+        block = self.uniforms_struct()
+        for field in self.uniforms_struct._fields_:
+            name, ctype = field[0], field[1]
+            if name not in uniforms:
+                continue
+            value = uniforms[name]
+            if issubclass(ctype, C.Array):
+                array = getattr(block, name)
+                for k, v in enumerate(np.asarray(value).reshape(-1)[:len(array)]):
+                    array[k] = v.item()
+            else:
+                setattr(block, name, value.item() if isinstance(value, np.generic) else value)
+        return block
+
+    def query(self, particles):
+        """registers, LDS, scratch (non-zero: the program spills) and code bytes of the kernel as `particles` loaded it"""
+        info = _capi.ProgramInfo()
+        call("th_program_query", particles._ctx, self.handle, C.byref(info))
+        return {k: getattr(info, k) for k, _ in _capi.ProgramInfo._fields_ if k != "reserved"}
 
     def bind(self):
         return self
+
+    def dispose(self):
+        if self.handle:
+            call("th_program_destroy", self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.dispose()
+        except Exception:
+            pass
 
 
 LOGIC = "logic"
@@ -312,6 +368,21 @@ def run_pass(particles, program, uniforms, target):
             call("th_spawn_sample_sharded", ctx, C.byref(s), source, target)      # every rank, collectively
         else:
             call("th_spawn_sample" if kind == "spawn-sample" else "th_spawn_direct", ctx, C.byref(s), source, target)
+    elif kind == "user":
+        if not program.handle:
+            raise ValueError("user program %r was disposed" % (program.fixed.get("name"),))
+        block = program.pack(uniforms)
+        src = uniforms.get("spawnData")
+        if src is None:
+            source = _capi.TH_SOURCE_NONE
+        else:
+            if hasattr(src, "bind_for"):                  # a spawner's own image buffer: uploaded on use
+                src.bind_for(particles)
+            source = src if isinstance(src, int) else src.source_index()
+            if source >= 0 and target == _capi.TH_TARGET_RING:
+                source = (source + 1) % len(particles.buffers)      # (as above: the order the pass sees)
+        call("th_program_run", ctx, program.handle, C.byref(block) if block is not None else None,
+             C.sizeof(block) if block is not None else 0, source, target)
     else:
         raise ValueError("unknown program kind %r" % (kind,))
 

@@ -176,6 +176,7 @@ class Tendrils:
         self.renderView = bool(params.get("renderView", True))     # draw() also runs the view pass (as the reference's does)
         self.buffers = []
         self.logicShader = None
+        self._logic_option = params.get("logicShader")         # new Tendrils(gl, { logicShader }): the caller's integrator
         self.uniforms = dict(render={}, update={})
         self.viewRes = [0, 0]
         self.viewSize = [0, 0]
@@ -258,7 +259,7 @@ class Tendrils:
             shape=shape, geomShape=[shape[0], shape[1] * 2], logic=Program(LOGIC),
             device=self._device, mode=self._mode, stateFormat=self._state_format, row0=row0,
             globalHeight=(gh if gh else (rootNum if rows else 0))))
-        self.logicShader = self.particles.logic
+        self.logicShader = self._logic_option or self.particles.logic
         self.particles.setup(numBuffers)
         self.targets.shape = shape
         self.flow.shape = self.flow.shape          # (re)create on the new context
@@ -352,7 +353,7 @@ class Tendrils:
     def step_n(self, n):
         """n x (timer.tick(); step()) for a fixed-step, unpaused timer, as one captured-graph replay."""
         tm = self.timer
-        if tm.paused or tm.step < 0 or tm.end >= 0:
+        if tm.paused or tm.step < 0 or tm.end >= 0 or self.logicShader.kind != LOGIC:
             for _ in range(n):
                 tm.tick()
                 self.step()
