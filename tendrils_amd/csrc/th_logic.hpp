@@ -161,8 +161,17 @@ struct NoiseCorners {
 //              + bits(iy + 2^21) = 4 * (permute(iz) + iy) = byte offset into permB
 //   permB[k] = 16 * (permute_int(k) - kLutMin) - 0x49000000   k in [0, 580]: stage y;
 //              + bits(ix + 2^19) = 16 * (permute(..) + ix - kLutMin) = byte offset of the gradient entry
-// Only the first-stage index addresses a table directly and masks its own high bits (& 0xffc).  The corner steps (+4, +16)
-// are added to the sums as before.  Both tables are filled with permute_int itself (hash_tables_kernel).
+// Only the first-stage index addresses a table directly and masks its own high bits (& 0xffc; over the window the add
+// itself writes the low half of its bits alone).  Both tables are filled with permute_int itself (hash_tables_kernel).
+// Stage y: with a0 = permA[iz] + bits(iy), a1 = permA[iz + 1] + bits(iy), the four corners read B[a0], B[sel1 + 4 * i1.y],
+// B[sel2 + 4 * i2.y] and B[a1 + 4], sel = a1 where the corner's z step is set and a0 where not.  i1 has at most one
+// component set and i2 at least two, in every value of the three compares (ties included): i1.z implies !i1.y, and !i2.z
+// implies i2.y.  So the four reads only ever hit the two pairs u0, u1 = B[a0], B[a0 + 4] and w0, w1 = B[a1], B[a1 + 4] -
+// one ds_read2_b32 each, issued as soon as a0 / a1 are there - and the corners are picked from the words afterwards:
+//   q0 = u0     q1 = i1.z ? w0 : (i1.y ? u1 : u0)     q2 = i2.z ? (i2.y ? w1 : w0) : u1     q3 = w1
+// (four v_cndmask on the masks the order block hands out; no select or add in front of the reads, two LDS instructions
+// for four, the same dwords; a + 4 <= 4 * (288 + iy + 1) is the q3 read's offset, inside both tables: tests/test_corner_select.py).
+// The x steps (+16) are added to the last sums as before.
 constexpr uint32_t kBiasBitsA = 0x4A000000u, kBiasBitsB = 0x49000000u;      // bits(2^21), bits(2^19)
 constexpr int kPermA = 292, kPermB = 584;                    // entries (multiples of 4)
 constexpr int kHashVec = (kPermA + kPermB) / 4;              // float4 slots in front of the gradient table
@@ -213,25 +222,27 @@ TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, co
 
     // Traversal order masks as in snoise_corners.  Here the second and third corner offsets are selected instead of
     // subtracted: x0 - i1 with i1 in {0, 1} is x0 or x0 - 1 (exactly, signed zeros included), and x0 - 1 serves both
-    // corners; the x / y steps also come out as index increments (0 or one table entry) for the hash chain below.
+    // corners; the x steps also come out as index increments (0 or one gradient entry) and the y / z masks as SGPR pairs
+    // for the hash chain below.
     const float ax1 = ax - 1.0f, ay1 = ay - 1.0f, az1 = az - 1.0f;
     float bx, by, bz, cx, cy, cz;
-    uint32_t e1x, e2x, e1y, e2y;
-    unsigned long long mz1, mz2;
+    uint32_t e1x, e2x;
+    unsigned long long my1, my2, mz1, mz2;       // i1.y, i2.y, i1.z, i2.z as lane masks: they pick the stage-y words below
     {
         unsigned long long l1, l2, l3, m;
         asm("v_cmp_lt_f32 %[l1], %[ax], %[ay]\n\t"
             "v_cmp_lt_f32 %[l2], %[ay], %[az]\n\t"
             "v_cmp_lt_f32 %[l3], %[az], %[ax]\n\t"
             "s_andn2_b64 %[m], %[l3], %[l1]\n\t"     "v_cndmask_b32 %[bx], %[ax], %[ax1], %[m]\n\t"   "v_cndmask_b32 %[e1x], 0, 16, %[m]\n\t"
-            "s_andn2_b64 %[m], %[l1], %[l2]\n\t"     "v_cndmask_b32 %[by], %[ay], %[ay1], %[m]\n\t"   "v_cndmask_b32 %[e1y], 0, 4, %[m]\n\t"
+            "s_andn2_b64 %[my1], %[l1], %[l2]\n\t"   "v_cndmask_b32 %[by], %[ay], %[ay1], %[my1]\n\t"
             "s_andn2_b64 %[mz1], %[l2], %[l3]\n\t"   "v_cndmask_b32 %[bz], %[az], %[az1], %[mz1]\n\t"
             "s_orn2_b64 %[m], %[l3], %[l1]\n\t"      "v_cndmask_b32 %[cx], %[ax], %[ax1], %[m]\n\t"   "v_cndmask_b32 %[e2x], 0, 16, %[m]\n\t"
-            "s_orn2_b64 %[m], %[l1], %[l2]\n\t"      "v_cndmask_b32 %[cy], %[ay], %[ay1], %[m]\n\t"   "v_cndmask_b32 %[e2y], 0, 4, %[m]\n\t"
+            "s_orn2_b64 %[my2], %[l1], %[l2]\n\t"    "v_cndmask_b32 %[cy], %[ay], %[ay1], %[my2]\n\t"
             "s_orn2_b64 %[mz2], %[l2], %[l3]\n\t"    "v_cndmask_b32 %[cz], %[az], %[az1], %[mz2]"
-            : [l1] "=&s"(l1), [l2] "=&s"(l2), [l3] "=&s"(l3), [m] "=&s"(m), [mz1] "=&s"(mz1), [mz2] "=&s"(mz2),
+            : [l1] "=&s"(l1), [l2] "=&s"(l2), [l3] "=&s"(l3), [m] "=&s"(m),
+              [my1] "=&s"(my1), [my2] "=&s"(my2), [mz1] "=&s"(mz1), [mz2] "=&s"(mz2),
               [bx] "=&v"(bx), [by] "=&v"(by), [bz] "=&v"(bz), [cx] "=&v"(cx), [cy] "=&v"(cy), [cz] "=&v"(cz),
-              [e1x] "=&v"(e1x), [e2x] "=&v"(e2x), [e1y] "=&v"(e1y), [e2y] "=&v"(e2y)
+              [e1x] "=&v"(e1x), [e2x] "=&v"(e2x)
             : [ax] "v"(ax), [ay] "v"(ay), [az] "v"(az), [ax1] "v"(ax1), [ay1] "v"(ay1), [az1] "v"(az1)
             : "scc");
     }
@@ -244,23 +255,31 @@ TH_D NoiseCorners snoise_corners_tab(float vx, float vy, float vz, float sxy, co
     // five more VGPRs (a wave per SIMD less) in one packed fused kernel.
     uint32_t zb, yb, xb;
     if constexpr (WIN) {
-        asm("v_add_f32 %0, %2, %1" : "=v"(zb) : "v"(iz), "s"(K[0]));            // kBiasBitsA + 4 * (iz - cz)
+        // The z sum's offset 4 * (iz - cz) <= 2316 lies in the low half of its bits: the add writes that half alone and
+        // pads the rest with zeros (SDWA takes the SGPR operand), which is the mask.  The sum's one reader is the address
+        // of the LDS read below (the tables start the workgroup's LDS: no add in between), so no VALU instruction takes
+        // the half-written register in the next slot - the wait state gfx950 wants there, which nothing inserts behind asm.
+        asm("v_add_f32_sdwa %0, %2, %1 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD"
+            : "=v"(zb) : "v"(iz), "s"(K[0]));                                   // 4 * (iz - cz): byte offset into winA
         asm("v_add_f32 %0, %2, %1" : "=v"(yb) : "v"(iy), "s"(K[1]));            // kBiasBitsA + 4 * (iy - cxy)
         asm("v_add_f32 %0, %2, %1" : "=v"(xb) : "v"(ix), "s"(K[2]));            // kBiasBitsB + 16 * (ix - cxy)
     } else {
         asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(zb) : "v"(mod289_int(iz)));   // kBiasBitsA + 4 * iz
         asm("v_add_f32 %0, 0x4a000000, %1" : "=v"(yb) : "v"(mod289_int(iy)));   // kBiasBitsA + 4 * iy
         asm("v_add_f32 %0, 0x49000000, %1" : "=v"(xb) : "v"(mod289_int(ix)));   // kBiasBitsB + 16 * ix
+        zb &= 0xffcu;                                                           // byte offset into permA (SDWA takes no literal)
     }
-    zb &= 0xffcu;                                                               // byte offset into permA
     const uint32_t *pa = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permA) + zb);
     const uint32_t a0 = pa[0] + yb, a1 = pa[1] + yb;            // 4 * (permute(iz) + iy), 4 * (permute(iz + 1) + iy)
-    uint32_t sel1, sel2;
-    asm("v_cndmask_b32 %0, %2, %3, %4\n\tv_cndmask_b32 %1, %2, %3, %5"
-        : "=&v"(sel1), "=&v"(sel2) : "v"(a0), "v"(a1), "s"(mz1), "s"(mz2));
-    auto stage_y = [&](uint32_t off) { return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permB) + off); };
-    const uint32_t q0 = stage_y(a0), q1 = stage_y(sel1 + e1y), q2 = stage_y(sel2 + e2y), q3 = stage_y(a1 + 4u);
-    n.j0 = (int)(q0 + xb); n.j1 = (int)(q1 + (xb + e1x)); n.j2 = (int)(q2 + (xb + e2x)); n.j3 = (int)(q3 + xb + 16u);
+    const uint32_t *pu = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permB) + a0);
+    const uint32_t *pw = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(T.permB) + a1);
+    const uint32_t u0 = pu[0], u1 = pu[1], w0 = pw[0], w1 = pw[1];              // B[a0], B[a0 + 4], B[a1], B[a1 + 4]
+    uint32_t q1, q2, t1, t2;
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(t1) : "v"(u0), "v"(u1), "s"(my1));
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(q1) : "v"(t1), "v"(w0), "s"(mz1));
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(t2) : "v"(w0), "v"(w1), "s"(my2));
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(q2) : "v"(u1), "v"(t2), "s"(mz2));
+    n.j0 = (int)(u0 + xb); n.j1 = (int)(q1 + (xb + e1x)); n.j2 = (int)(q2 + (xb + e2x)); n.j3 = (int)(w1 + xb + 16u);
     return n;
 }
 
@@ -344,10 +363,14 @@ TH_D float4 lut_at(const float4 *lut, int magic)
 template <bool FAST>
 TH_D float snoise_finish(const NoiseCorners &n, float4 g0, float4 g1, float4 g2, float4 g3)
 {
-    float m0 = __builtin_fmaxf(0.6f - mad<FAST>(n.az, n.az, mad<FAST>(n.ay, n.ay, n.ax * n.ax)), 0.0f);
-    float m1 = __builtin_fmaxf(0.6f - mad<FAST>(n.bz, n.bz, mad<FAST>(n.by, n.by, n.bx * n.bx)), 0.0f);
-    float m2 = __builtin_fmaxf(0.6f - mad<FAST>(n.cz, n.cz, mad<FAST>(n.cy, n.cy, n.cx * n.cx)), 0.0f);
-    float m3 = __builtin_fmaxf(0.6f - mad<FAST>(n.dz, n.dz, mad<FAST>(n.dy, n.dy, n.dx * n.dx)), 0.0f);
+    // max(0.6 - d, 0) with d a sum of squares: 0.6 - d <= 0.6 < 1, so the value is med3(0.6 - d, 0, 1), which the compiler
+    // folds into the subtract's clamp modifier - one instruction per corner instead of v_sub_f32 + v_max_f32.  (As the
+    // builtin, not as asm: the asm form took six VGPRs more in the fused kernel.)
+    auto falloff = [](float d) { return __builtin_amdgcn_fmed3f(0.6f - d, 0.0f, 1.0f); };
+    float m0 = falloff(mad<FAST>(n.az, n.az, mad<FAST>(n.ay, n.ay, n.ax * n.ax)));
+    float m1 = falloff(mad<FAST>(n.bz, n.bz, mad<FAST>(n.by, n.by, n.bx * n.bx)));
+    float m2 = falloff(mad<FAST>(n.cz, n.cz, mad<FAST>(n.cy, n.cy, n.cx * n.cx)));
+    float m3 = falloff(mad<FAST>(n.dz, n.dz, mad<FAST>(n.dy, n.dy, n.dx * n.dx)));
     m0 *= m0; m1 *= m1; m2 *= m2; m3 *= m3;
     m0 *= m0; m1 *= m1; m2 *= m2; m3 *= m3;
     float d0 = mad<FAST>(g0.z, n.az, mad<FAST>(g0.y, n.ay, g0.x * n.ax));
