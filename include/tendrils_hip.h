@@ -8,7 +8,8 @@
  * 432-457) over WebGL FBO ping-pong.  Each entry point below replaces one of
  * those GL-backed operations; the ctypes binding (tendrils_amd/_capi.py) binds exactly these
  * symbols and the N-API shim (tendrils_amd/csrc/th_napi.cc) all of them except th_stream, th_stats_async,
- * th_spawn_image_download and th_slot_order.  Both hosts run row-band-sharded jobs, one process per GPU: the ranks join the
+ * th_spawn_image_download and th_slot_order (the flow lines, the sharded spawn, the user programs and the colour-map blend
+ * through small addons of their own beside it: th_napi_flowline.cc, th_napi_spawn.cc, th_napi_program.cc, th_napi_blend.cc).  Both hosts run row-band-sharded jobs, one process per GPU: the ranks join the
  * library's own communicator (th_comm_unique_id -> th_comm_init; JS: Particles.commUniqueId / commInit) and from then on
  * the path's collectives - the counter all-reduce, the draw()'s exchange, the state gather - are issued by the library over
  * RCCL (th_stats_allreduce, th_draw_sharded, th_spawn_sample_sharded, th_state_gather); the host only carries the 128-byte id between its processes.
@@ -456,6 +457,45 @@ th_status th_view_copy(th_context *ctx, int32_t index);
 th_status th_view_step_buffers(th_context *ctx);
 /* tendrils.colorMap (src/index.js:94-96: a 1x1 float FBO unless given): RGBA32F, NEAREST, CLAMP_TO_EDGE */
 th_status th_colormap_upload(th_context *ctx, const float *rgba, int32_t w, int32_t h);
+/* -- the demo's colour-map blend: Blend.draw(tendrils.colorMap) (src/screen/blend/index.js, main.frag; src/demo.main.js:541-560,
+ * 1068-1079), the pass the demo runs every frame before step() and draw(): the views - the two audio data textures and the
+ * camera frame or the image spawner's buffer - summed into the colour map, each with a global alpha:
+ *     uv = gl_FragCoord.xy / resolution;  sum += vec4(c.rgb * (c.a * alpha), c.a * alpha) for c = texture2D(view, uv)
+ * Every view is NEAREST / CLAMP_TO_EDGE and keeps its own shape; nothing is clamped (the view pass clamps what it looks up).
+ * A view is a caller's texture (th_texture_upload into one of TH_MAX_TEXTURES slots; a view list may name a slot more than
+ * once, as the demo does for mic and track) or one of the textures the context already holds:
+ *   TH_TEX_RGBA32F  a float FBO (gl-fbo {float: true}): 4 floats a texel
+ *   TH_TEX_RGBA8    a non-float FBO: 4 bytes a texel, read as UNORM8 the way th_optical_flow reads its frames, at most 65536 a side
+ *   TH_TEX_L32F     an AudioTexture (src/audio/data-texture.js: gl-texture2d of a float ndarray [n, 1]): w = n, h = 1, one
+ *                   float a texel, sampled as (L, L, L, 1)
+ *  th_texture_upload    texture.setPixels / AudioTexture.apply(): on the context's stream; the slot's memory is kept while its
+ *                       shape and format stay the same.  The caller's array is free again when the call returns.
+ *  th_colormap_resize   colorMap.shape = [w, h] (src/demo.main.js:504): a new shape gives a zero-filled map, the same shape nothing
+ *  th_colormap_blend    one pass over the colour map as it stands (1 x 1 until someone resizes or uploads it); enqueues and
+ *                       returns.  gl_blend = 1: the GL state Tendrils.step() leaves behind (BLEND, SRC_ALPHA /
+ *                       ONE_MINUS_SRC_ALPHA, src/index.js:267-268 - Blend.draw never touches it): the map receives
+ *                       sum * sum.a + dst * (1 - sum.a); gl_blend = 0 (before the first step()): sum.  clear = 0 keeps the
+ *                       destination (Blend.draw(target, resolution, false)), else it is cleared to zeros first.
+ *                       Touches the colour map only: the ring, its slot order and what a view pass reuses of the last flow
+ *                       pass stay.  On a row-band shard the colour map is replicated: every rank blends for itself.
+ *                       n outside 1..TH_MAX_BLEND_VIEWS, an empty slot, TH_VIEW_FRAMES before th_frames_resize,
+ *                       TH_VIEW_SPAWN_IMAGE before an image: TH_ERR_INVALID, nothing launched.
+ *  th_colormap_shape / _download, th_texture_download   read-backs (tests, checkpoints); the downloads synchronise */
+enum { TH_TEX_RGBA32F = 0, TH_TEX_RGBA8 = 1, TH_TEX_L32F = 2 };
+enum { TH_VIEW_TEXTURE = 0, TH_VIEW_FRAMES = 1, TH_VIEW_SPAWN_IMAGE = 2 };
+#define TH_MAX_TEXTURES 8
+#define TH_MAX_BLEND_VIEWS 8      /* GLSL ES 1.0's minimum MAX_TEXTURE_IMAGE_UNITS */
+typedef struct th_blend_view {
+    int32_t source;              /* TH_VIEW_* */
+    int32_t index;               /* TH_VIEW_TEXTURE: slot; TH_VIEW_FRAMES: 0 / 1 = OpticalFlow.buffers[k] as they stand; TH_VIEW_SPAWN_IMAGE: ignored */
+    float alpha;
+} th_blend_view;
+th_status th_texture_upload(th_context *ctx, int32_t slot, int32_t format, const void *texels, int32_t w, int32_t h);
+th_status th_texture_download(th_context *ctx, int32_t slot, void *texels);
+th_status th_colormap_resize(th_context *ctx, int32_t w, int32_t h);
+th_status th_colormap_shape(th_context *ctx, int32_t *w, int32_t *h);
+th_status th_colormap_blend(th_context *ctx, const th_blend_view *views, int32_t n, int32_t gl_blend, int32_t clear);
+th_status th_colormap_download(th_context *ctx, float *rgba);
 /* th_export_lines with the view pass's vertex colours in place of the flow varyings */
 th_status th_export_view_lines(th_context *ctx, const th_render_uniforms *u, float *lines, uint64_t capacity, uint64_t *count);
 /* The view pass of a row-band shard (src/index.js:315-337), the same way: th_view_emit = this band's fragments with the render

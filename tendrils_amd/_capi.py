@@ -114,7 +114,14 @@ class FlowLineUniforms(C.Structure):
                 ("viewSize", C.c_float * 2)]
 
 
+class BlendView(C.Structure):
+    _fields_ = [("source", C.c_int32), ("index", C.c_int32), ("alpha", C.c_float)]
+
+
 COMM_ID_BYTES = 128         # TH_COMM_ID_BYTES
+TEX_RGBA32F, TEX_RGBA8, TEX_L32F = 0, 1, 2                  # TH_TEX_*
+VIEW_TEXTURE, VIEW_FRAMES, VIEW_SPAWN_IMAGE = 0, 1, 2       # TH_VIEW_*
+MAX_TEXTURES = MAX_BLEND_VIEWS = 8                          # TH_MAX_TEXTURES, TH_MAX_BLEND_VIEWS
 
 _ctx = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -203,6 +210,12 @@ PROTOTYPES = {
     "th_view_copy": (C.c_int32, [_ctx, C.c_int32]),
     "th_view_step_buffers": (C.c_int32, [_ctx]),
     "th_colormap_upload": (C.c_int32, [_ctx, _fp, C.c_int32, C.c_int32]),
+    "th_texture_upload": (C.c_int32, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "th_texture_download": (C.c_int32, [_ctx, C.c_int32, C.c_void_p]),
+    "th_colormap_resize": (C.c_int32, [_ctx, C.c_int32, C.c_int32]),
+    "th_colormap_shape": (C.c_int32, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "th_colormap_blend": (C.c_int32, [_ctx, C.POINTER(BlendView), C.c_int32, C.c_int32, C.c_int32]),
+    "th_colormap_download": (C.c_int32, [_ctx, _fp]),
     "th_export_view_lines": (C.c_int32, [_ctx, C.POINTER(RenderUniforms), _fp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "th_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_program_log": (C.c_char_p, []),

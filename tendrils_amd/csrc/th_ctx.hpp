@@ -8,6 +8,7 @@
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
 //   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
 //   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run)
+//   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -230,6 +231,9 @@ struct th_context {
     int32_t cmap_w = 0, cmap_h = 0;
     DevBuf<float4> image;                // PixelSpawner's own buffer (TH_SOURCE_IMAGE)
     int32_t iw = 0, ih = 0;
+    // the caller's textures (th_texture_upload): what the colour-map blend sums beside the frames and the spawn image (th_blend.hip)
+    struct Texture { DevBuf<char> texels; int32_t w = 0, h = 0, format = -1; };      // TH_TEX_*: 16 / 4 / 4 bytes a texel
+    Texture textures[TH_MAX_TEXTURES];
     DevBuf<unsigned long long> d_respawned;      // [0]: particles replaced by respawn passes, [1]: scratch (passes into `targets`)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool kernel_timing = false;          // th_kernel_timing: event pair around every logic launch

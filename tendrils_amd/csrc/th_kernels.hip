@@ -838,23 +838,13 @@ void launch_flow_decode(const float4 *flow, float2 *dec, size_t n, float time, c
 // Ten NEAREST/CLAMP taps of the two RGBA8 frames; neighbouring lanes read neighbouring
 // texels, so every tap is a coalesced 4-byte-per-lane load served by L2.
 // ---------------------------------------------------------------------------
-// NEAREST + CLAMP_TO_EDGE index into an 8-bit-per-channel texture, with the coordinate
-// precision of the captured reference run: clamp to [0, 1), truncate to 16 fractional bits,
-// texel = (coord16 * size) >> 16 (equals floor(u*size) except within 2^-16 of a texel boundary).
-TH_D int nearest_texel_fx16(float u, unsigned n)
-{
-    float c = __builtin_amdgcn_fmed3f(u, 0.0f, 65535.0f / 65536.0f);
-    unsigned fx = (unsigned)(c * 65536.0f);
-    return (int)((fx * n) >> 16);
-}
-
+// (the taps: nearest_texel_fx16, th_math.hpp)
 // gray value of frame texel (tx, ty): texture2D on RGBA8 then grayScale() (src/utils/gray-scale.glsl:2).
 // UNORM8 -> float as (c*257) * (1/65535): what the captured reference run did; equals c/255 within 1 ulp.
 TH_D float gray_texel(const uchar4 *img, int w, int tx, int ty)
 {
     uchar4 t = img[ty * w + tx];
-    const float k = 1.0f / 65535.0f;
-    float r = ((float)t.x * 257.0f) * k, g = ((float)t.y * 257.0f) * k, b = ((float)t.z * 257.0f) * k;
+    float r = unorm8(t.x), g = unorm8(t.y), b = unorm8(t.z);
     return r * 0.3f + g * 0.59f + b * 0.11f;
 }
 

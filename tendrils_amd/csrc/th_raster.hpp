@@ -38,14 +38,6 @@ struct DepositVertex {
     float uvx, uvy;    // its coordinates in the vertex stream (the colour map is looked up there)
 };
 
-TH_D int dep_nearest(float u, int n)       // NEAREST + CLAMP_TO_EDGE on a float texture
-{
-    float f = th_floor(u * (float)n);
-    if (!(f > 0.0f)) return 0;
-    if (f > (float)(n - 1)) return n - 1;
-    return (int)f;
-}
-
 // The view pass's vertex colour (src/render/index.vert:58-100): base colour + colour map + flow-aligned colour, each
 // pre-multiplied and clamped, alpha scaled by the speed and a vignette.  Operation order as in the shader (and in the
 // checker's restatement); sin(time*flowDecay) - a uniform-only expression, implementation-defined in GLSL - comes from

@@ -106,6 +106,7 @@ class Tendrils {
     // (flowWidth: 5 then draws width-1 lines, as it does there); up to [1, 64] for the picture of a GL that honours widths
     this.lineWidthRange = (params.lineWidthRange || [1, 1]);
     this.bound = null;                             // the bound view image: null = the screen, else one of this.buffers
+    this.blending = false;                         // gl.isEnabled(gl.BLEND): what step() / spawnShader() leave enabled (Blend.draw inherits it)
     this.setupBuffers(params.numBuffers);          // src/index.js:109
   }
 
@@ -248,6 +249,7 @@ class Tendrils {
       });
 
       this.particles.step(this.uniforms.update);
+      this.blending = true;                        // src/index.js:267-268
     }
     return this;
   }
@@ -266,6 +268,7 @@ class Tendrils {
       viewSize: this.viewSize, viewRes: this.viewRes
     });
     this.particles.stepN(this.uniforms.update, tm.time, dt, n);
+    this.blending = this.blending || n > 0;
     for (let k = 0; k < n; ++k) tm.tick();
     return this;
   }
@@ -338,6 +341,7 @@ class Tendrils {
     }, update), ...rest);
 
     this.particles.logic = this.logicShader;
+    this.blending = true;                          // src/index.js:453-454
     return this;
   }
 }
@@ -345,5 +349,8 @@ class Tendrils {
 module.exports = {
   defaults, glSettings, Tendrils, Particles, Program, Timer, default: Tendrils,
   get FlowLine() { return require('./flow-line').FlowLine; },
-  get FlowLines() { return require('./flow-line').FlowLines; }
+  get FlowLines() { return require('./flow-line').FlowLines; },
+  get Blend() { return require('./blend').Blend; },
+  get AudioTexture() { return require('./blend').AudioTexture; },
+  get ColorMap() { return require('./blend').ColorMap; }
 };

@@ -15,7 +15,8 @@ class OpticalFlow {
   constructor(tendrils, options, uniforms) {
     const base = defaults();
     this.tendrils = tendrils;
-    this.buffers = [{ id: 0 }, { id: 1 }];
+    // (identities of the two frame textures; each names its owner, so that a Blend can take one for a view: js/blend.js)
+    this.buffers = [{ id: 0, opticalFlow: this }, { id: 1, opticalFlow: this }];
     this.uniforms = Object.assign(base.uniforms, uniforms);
     this.bound = { ...this.uniforms };
     this.shape = [1, 1];

@@ -44,6 +44,12 @@ class OpticalFlow:
         u.time, u.speed, u.speedLimit = float(b["time"]), float(b["speed"]), float(b["speedLimit"])
         call("th_optical_flow", self._ctx, C.byref(u))
 
+    def frame(self, k=0):
+        """buffers[k] as it stands now, as a view of a Blend (`video: opticalFlow.buffers[0]`, src/demo.main.js:552): the
+        view keeps naming that frame texture when step() rotates the pair"""
+        from .blend import FrameView
+        return FrameView(self, self.buffers[k])
+
     def step(self):                               # :60-62 utils.step(this.buffers)
         self.buffers.insert(0, self.buffers.pop())
         call("th_frames_rotate", self._ctx)

@@ -145,6 +145,7 @@ class Particles:
                            mode=self._mode, state_format=int(params.get("stateFormat", 0)))
         self._ctx = C.c_void_p()
         call("th_create", C.byref(cfg), C.byref(self._ctx))
+        self.textures = [None] * _capi.MAX_TEXTURES      # who last uploaded into each texture slot of the context (blend.py)
 
     # -- lifecycle -----------------------------------------------------------------
     def setup(self, numBuffers=1):                  # src/particles.js:81-92

@@ -93,24 +93,53 @@ class FlowTexture:
 
 
 class ColorMap:
-    """tendrils.colorMap (src/index.js:94-96): RGBA32F, a 1x1 zero texture until set."""
+    """tendrils.colorMap (src/index.js:94-96): RGBA32F, a 1x1 zero texture until set.  The host copy `set_pixels` keeps
+    (for a context made later) is dropped by whatever changes the map on the device: a Blend.draw into it, a new shape."""
 
     def __init__(self, owner):
         self._o = owner
-        self.shape = [1, 1]
+        self._shape = [1, 1]
         self._pixels = None
+
+    @property
+    def shape(self):
+        return list(self._shape)
+
+    @shape.setter
+    def shape(self, wh):                           # colorMap.shape = shape (src/demo.main.js:504): gl-fbo gives a new shape
+        wh = [int(wh[0]), int(wh[1])]              # zeroed attachments and leaves the same shape alone
+        if wh != self._shape:
+            self._shape, self._pixels = wh, None
+            self.bind_shape()
 
     def set_pixels(self, texels):
         t = np.ascontiguousarray(texels, np.float32)
         assert t.ndim == 3 and t.shape[2] == 4
-        self.shape = [t.shape[1], t.shape[0]]
+        self._shape = [t.shape[1], t.shape[0]]
         self._pixels = t
         self.bind()
 
     def bind(self):
         if self._pixels is not None and self._o.particles is not None:
             call("th_colormap_upload", self._o.particles._ctx, self._pixels.ctypes.data_as(_capi._fp),
-                 self.shape[0], self.shape[1])
+                 self._shape[0], self._shape[1])
+        elif self._pixels is None:
+            self.bind_shape()
+
+    def bind_shape(self):
+        """the device's map has this shape (a context made after the shape was set starts from a zeroed map of it)"""
+        if self._o.particles is not None and self._shape != [1, 1]:
+            call("th_colormap_resize", self._o.particles._ctx, self._shape[0], self._shape[1])
+
+    def blended(self):
+        """a pass on the device has written the map: the host copy is older than it"""
+        self._pixels = None
+
+    def read(self):
+        """[h, w, 4] float32: the map as the device holds it"""
+        out = np.empty((self._shape[1], self._shape[0], 4), np.float32)
+        call("th_colormap_download", self._o.particles._ctx, out.ctypes.data_as(_capi._fp))
+        return out
 
 
 class TargetsTexture:
@@ -190,6 +219,7 @@ class Tendrils:
         # (flowWidth: 5 then draws width-1 lines, as it does there); up to [1, 64] for the picture of a GL that honours widths
         self.lineWidthRange = tuple(params.get("lineWidthRange", (1, 1)))
         self._bound = None                       # the bound view image: None = the screen, else one of self.buffers
+        self.blending = False                    # gl.isEnabled(gl.BLEND): what step() / spawnShader() leave enabled (Blend.draw inherits it)
         self.setupBuffers(int(params.get("numBuffers", 0) or 0))      # src/index.js:109
 
     # -- setup ---------------------------------------------------------------------
@@ -348,6 +378,7 @@ class Tendrils:
                 flow=self.flow, targets=self.targets,
                 viewSize=self.viewSize, viewRes=self.viewRes)
             self.particles.step(self.uniforms["update"])
+            self.blending = True                                # src/index.js:267-268
         return self
 
     def step_n(self, n):
@@ -364,6 +395,7 @@ class Tendrils:
         self.uniforms["update"].update(dt=dt, time=tm.time, start=tm.since, flow=self.flow, targets=self.targets,
                                        viewSize=self.viewSize, viewRes=self.viewRes)
         self.particles.step_n(self.uniforms["update"], tm.time, dt, n)
+        self.blending = self.blending or n > 0
         for _ in range(n):
             tm.tick()
         return self
@@ -455,6 +487,7 @@ class Tendrils:
         base = dict(self.state, time=self.timer.time, viewSize=self.viewSize, viewRes=self.viewRes)
         self.particles.step(Particles.applyUpdate(base, update), *rest)
         self.particles.logic = self.logicShader
+        self.blending = True                                    # src/index.js:453-454
         return self
 
 
