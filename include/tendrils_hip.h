@@ -272,6 +272,58 @@ th_status th_program_run(th_context *ctx, th_program *program, const void *unifo
                          int32_t source, int32_t target);
 th_status th_program_query(th_context *ctx, th_program *program, th_program_info *out);
 
+/* -- screen programs: a full-screen pass the CALLER wrote, over the view images ---------------------------------------
+ * The reference's other seam: Screen.render() (src/screen/index.js) draws one full-screen triangle with whatever shader is
+ * bound, into whatever framebuffer is bound - the demo ends its frame with one, a shader of its own over tendrils.buffers[0]
+ * into the screen (src/demo.main.js:1084-1102).  Here such a shader is HIP source defining one device function,
+ *     __device__ float4 th_screen(const th_screen_pass &s);   - main() of the fragment shader; the return value is gl_FragColor
+ * compiled exactly as a user program is (same hiprtc, same flags, same `#line 1 "<name>"`, same th_program_log()) behind a
+ * prelude of its own (tendrils_amd/csrc/th_screen_prelude.inc) that declares:
+ *   th_screen_pass     x, y (the target texel: gl_FragCoord.xy - 0.5, rows in the order th_view_download / th_colormap_download
+ *                      give them), res (the target's shape), uv (gl_FragCoord.xy / res in fp32: ((float)x + 0.5f) / res.x,
+ *                      ((float)y + 0.5f) / res.y), uniforms (th_uniforms<T>(s): the caller's block, up to 1024 bytes)
+ *   th_tex(s, unit, u, v)      texture2D(unit, (u, v)): NEAREST, CLAMP_TO_EDGE, with the tap arithmetic of th_colormap_blend -
+ *                              RGBA32F / L32F at clamp(floor(u * n), 0, n - 1) in fp32, RGBA8 through the 16-bit fixed-point
+ *                              coordinate and read as UNORM8; L32F reads as (L, L, L, 1)
+ *   th_texel(s, unit, x, y)    texel (x, y) of a unit, integer coordinates clamped to the texture
+ *   th_tex_res(s, unit)        the unit's shape
+ * A unit at or beyond the number of bound units reads as zeros; every accessor clamps: a program that reads through them
+ * alone cannot read out of bounds.
+ *  th_screen_program_compile   as th_program_compile (a source without th_screen does not compile).  The handle is a th_program of
+ *                      the other kind: th_program_destroy / _query / _log serve both; th_program_run refuses a screen program and
+ *                      th_screen_run a state program (TH_ERR_INVALID, both kinds named, nothing launched).
+ *  th_screen_run       one pass over its target, enqueued on the context's stream.
+ *                      units: 0..TH_MAX_BLEND_VIEWS of them; TH_VIEW_TEXTURE / _FRAMES / _SPAWN_IMAGE as for th_colormap_blend,
+ *                      TH_VIEW_BUFFER (Tendrils.buffers[index] as the ring stands now, RGBA8), TH_VIEW_SCREEN (the screen image,
+ *                      RGBA8), TH_VIEW_COLORMAP (RGBA32F), TH_VIEW_FLOW (the flow field, RGBA32F) - th_colormap_blend takes
+ *                      none of these four.
+ *                      target: TH_SCREEN_TARGET_VIEW (the BOUND view image: the screen, or the buffer th_view_bind chose; RGBA8),
+ *                      TH_SCREEN_TARGET_COLORMAP (RGBA32F), TH_SCREEN_TARGET_TEXTURE (slot target_index, which must hold an
+ *                      RGBA32F or RGBA8 texture already: its shape is the pass's resolution).  The flow field is no target.
+ *                      gl_blend as for th_colormap_blend: 1 = SRC_ALPHA / ONE_MINUS_SRC_ALPHA over the destination - into RGBA8
+ *                      the blend of th_view_fill / th_view_copy (clamp, blend with c / 255, round), into a float target
+ *                      c * c.a + dst * (1 - c.a), unclamped; 0 = stored: RGBA8 as (unsigned char)(clamp(c, 0, 1) * 255 + 0.5),
+ *                      float as it is.  The destination is read only when gl_blend = 1.
+ *                      A unit that names the memory the pass writes (the bound buffer, the screen while it is bound, the colour
+ *                      map into itself, a slot as unit and target) is GL's feedback loop and here a race: TH_ERR_INVALID, the
+ *                      unit named.  Also TH_ERR_INVALID, nothing launched, the target untouched: n_units outside
+ *                      0..TH_MAX_BLEND_VIEWS, an empty slot, an L32F target slot, TH_VIEW_FRAMES before th_frames_resize,
+ *                      TH_VIEW_SPAWN_IMAGE before an image, TH_VIEW_BUFFER beyond the ring, more than 1024 uniform bytes, null
+ *                      uniforms with a size, a null program.
+ *                      Touches its target only: the ring, its slot order, the `respawned` counter and what a view pass reuses
+ *                      of the last flow pass stay.  On a row-band shard the colour map and the caller's textures are replicated:
+ *                      those targets work, every rank computes for itself; TH_SCREEN_TARGET_VIEW fails with TH_ERR_UNSUPPORTED
+ *                      (a band's view image holds only what it owns), and a unit that reads a view image or the flow field
+ *                      there reads what THAT context holds - its own share, not the job's picture. */
+enum { TH_SCREEN_TARGET_VIEW = 0, TH_SCREEN_TARGET_COLORMAP = 1, TH_SCREEN_TARGET_TEXTURE = 2 };
+typedef struct th_screen_unit {
+    int32_t source;              /* TH_VIEW_* */
+    int32_t index;               /* TH_VIEW_TEXTURE: slot; TH_VIEW_FRAMES: 0 / 1; TH_VIEW_BUFFER: ring position; else ignored */
+} th_screen_unit;
+th_status th_screen_program_compile(const char *source, const char *name, th_program **out);
+th_status th_screen_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
+                        const th_screen_unit *units, int32_t n_units, int32_t target, int32_t target_index, int32_t gl_blend);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */
 th_status th_frames_upload(th_context *ctx, const uint8_t *rgba8);     /* setPixels -> buffers[0] */
@@ -482,7 +534,8 @@ th_status th_colormap_upload(th_context *ctx, const float *rgba, int32_t w, int3
  *                       TH_VIEW_SPAWN_IMAGE before an image: TH_ERR_INVALID, nothing launched.
  *  th_colormap_shape / _download, th_texture_download   read-backs (tests, checkpoints); the downloads synchronise */
 enum { TH_TEX_RGBA32F = 0, TH_TEX_RGBA8 = 1, TH_TEX_L32F = 2 };
-enum { TH_VIEW_TEXTURE = 0, TH_VIEW_FRAMES = 1, TH_VIEW_SPAWN_IMAGE = 2 };
+enum { TH_VIEW_TEXTURE = 0, TH_VIEW_FRAMES = 1, TH_VIEW_SPAWN_IMAGE = 2,
+       TH_VIEW_BUFFER = 3, TH_VIEW_SCREEN = 4, TH_VIEW_COLORMAP = 5, TH_VIEW_FLOW = 6 };      /* (from 3 on: th_screen_run alone) */
 #define TH_MAX_TEXTURES 8
 #define TH_MAX_BLEND_VIEWS 8      /* GLSL ES 1.0's minimum MAX_TEXTURE_IMAGE_UNITS */
 typedef struct th_blend_view {

@@ -118,9 +118,15 @@ class BlendView(C.Structure):
     _fields_ = [("source", C.c_int32), ("index", C.c_int32), ("alpha", C.c_float)]
 
 
+class ScreenUnit(C.Structure):
+    _fields_ = [("source", C.c_int32), ("index", C.c_int32)]
+
+
 COMM_ID_BYTES = 128         # TH_COMM_ID_BYTES
 TEX_RGBA32F, TEX_RGBA8, TEX_L32F = 0, 1, 2                  # TH_TEX_*
 VIEW_TEXTURE, VIEW_FRAMES, VIEW_SPAWN_IMAGE = 0, 1, 2       # TH_VIEW_*
+VIEW_BUFFER, VIEW_SCREEN, VIEW_COLORMAP, VIEW_FLOW = 3, 4, 5, 6      # ... th_screen_run alone
+SCREEN_TARGET_VIEW, SCREEN_TARGET_COLORMAP, SCREEN_TARGET_TEXTURE = 0, 1, 2      # TH_SCREEN_TARGET_*
 MAX_TEXTURES = MAX_BLEND_VIEWS = 8                          # TH_MAX_TEXTURES, TH_MAX_BLEND_VIEWS
 
 _ctx = C.c_void_p
@@ -222,6 +228,9 @@ PROTOTYPES = {
     "th_program_destroy": (C.c_int32, [C.c_void_p]),
     "th_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32]),
     "th_program_query": (C.c_int32, [_ctx, C.c_void_p, C.POINTER(ProgramInfo)]),
+    "th_screen_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "th_screen_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ScreenUnit), C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

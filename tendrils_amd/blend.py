@@ -120,27 +120,37 @@ class Blend:
         table = (_capi.BlendView * n)()
         slots = []                                # the distinct audio textures of this draw, in order of appearance
         for i, view in enumerate(self.views):
-            view = getattr(view, "texture", view)
-            if isinstance(view, PixelSpawner):
-                view = view.buffer
-            if isinstance(view, AudioTexture):
-                if not any(view is s for s in slots):
-                    slots.append(view)
-                    _upload(particles, len(slots) - 1, view)
-                table[i].source, table[i].index = _capi.VIEW_TEXTURE, [view is s for s in slots].index(True)
-            elif isinstance(view, FrameView):
-                table[i].source, table[i].index = _capi.VIEW_FRAMES, view.index()
-            elif isinstance(view, ImageBuffer):
-                view.bind_for(particles)
-                table[i].source, table[i].index = _capi.VIEW_SPAWN_IMAGE, 0
-            else:
+            found = resolve_view(particles, view, slots)
+            if found is None:
                 raise TypeError("Blend.draw: view %d (%r) is no AudioTexture, OpticalFlow frame or image buffer" % (i, view))
+            table[i].source, table[i].index = found
             table[i].alpha = float(self.alphas[i])
         target.bind_shape()
         blending = tendrils.blending if gl_blend is None else bool(gl_blend)
         call("th_colormap_blend", particles._ctx, table, n, int(blending), int(bool(clear)))
         target.blended()
         return self
+
+
+def resolve_view(particles, view, slots, free=range(_capi.MAX_TEXTURES)):
+    """(TH_VIEW_* source, index) of one of the views a host hands to a pass over textures - an AudioTexture (or its .texture),
+    an OpticalFlow frame, the image spawner's buffer (a PixelSpawner, its .buffer or .buffer.color[0]) - or None for anything
+    else.  `slots`: the distinct audio textures of this pass so far, in order of appearance; the k-th of them travels in
+    texture slot free[k]."""
+    view = getattr(view, "texture", view)
+    if isinstance(view, PixelSpawner):
+        view = view.buffer
+    if isinstance(view, AudioTexture):
+        if not any(view is s for s in slots):
+            slots.append(view)
+            _upload(particles, free[len(slots) - 1], view)
+        return _capi.VIEW_TEXTURE, free[[view is s for s in slots].index(True)]
+    if isinstance(view, FrameView):
+        return _capi.VIEW_FRAMES, view.index()
+    if isinstance(view, ImageBuffer):
+        view.bind_for(particles)
+        return _capi.VIEW_SPAWN_IMAGE, 0
+    return None
 
 
 def _upload(particles, slot, texture):

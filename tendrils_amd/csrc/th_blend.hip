@@ -81,6 +81,10 @@ bool shape_ok(int32_t format, int32_t w, int32_t h)
     return w > 0 && h > 0 && w <= side && h <= side && (uint64_t)w * h < (1ull << 28);
 }
 
+}  // namespace
+
+namespace thi {
+
 // the colour map as the reference has it before anyone sets one: a 1 x 1 float FBO, zeros (src/index.js:94-96)
 th_status colormap_storage(th_context *c)
 {
@@ -91,7 +95,7 @@ th_status colormap_storage(th_context *c)
     return TH_OK;
 }
 
-}  // namespace
+}  // namespace thi
 
 extern "C" {
 

@@ -7,18 +7,22 @@
 //   th_spawn.hip  the spawners
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
 //   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
-//   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run)
+//   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run), and what both kinds of
+//                  program share: the hiprtc binding, the compile, the log, the per-context modules
+//   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -69,14 +73,27 @@ struct th_options {
     bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
 };
 
-// A user program as one context has loaded it (th_program.hip): the context owns the module - unloaded when the context
-// goes - and a reference to the program's record, so that th_program_destroy of a program a context has run is safe.
-struct th_program;
+// A compiled program of either kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
+// anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
+namespace thi {
+enum ProgramKind { kStateProgram = 0, kScreenProgram = 1 };      // th_program_compile / th_screen_program_compile
+}
+struct th_program {
+    thi::ProgramKind kind = thi::kStateProgram;
+    std::string name;
+    std::vector<char> code;
+    std::mutex lock;                     // `code` against a th_program_destroy on another thread
+    bool destroyed = false;
+    std::atomic<int> refs{1};
+    uint32_t sgprs = 0, code_bytes = 0;  // of the kind's kernel, read from the code object
+};
+// ... and as one context has loaded it (th_program.hip): the context owns the module - unloaded when the context goes - and
+// a reference to the program's record, so that th_program_destroy of a program a context has run is safe.
 namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel
+    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -290,7 +307,7 @@ struct th_context {
 
     thi::FlowLineScratch *flow_lines = nullptr;   // th_flow_lines: staging and scratch (grow-only)
 
-    std::vector<thi::ProgramModule> programs;     // th_program_run: the user programs this context has loaded
+    std::vector<thi::ProgramModule> programs;     // th_program_run / th_screen_run: the programs this context has loaded
     DevBuf<unsigned> prog_flag;                   // ... and the word a pass on a row band raises (th_particles outside the band)
 
     size_t texels() const { return (size_t)cfg.width * cfg.height; }
@@ -327,6 +344,18 @@ inline void state_moved(th_context *c, const float4 *from, const float4 *to)
     if (c->asort.src == from) c->asort.valid = false;
     if (c->seen.cur == from || c->seen.prev == from) c->seen.cur = c->seen.prev = nullptr;
 }
+
+// ---- th_program.hip --------------------------------------------------------------------------------------------------
+constexpr uint32_t kUniformBytes = 1024;        // a program's uniform block (th_program_uniform_block in both preludes)
+const char *program_kind_name(ProgramKind kind);
+// `prelude` + `#line 1 "<name>"` + `source` through hiprtc into a program of `kind`; th_program_log() holds the compiler's output
+th_status program_compile(ProgramKind kind, const std::string &prelude, const char *source, const char *name, th_program **out);
+// the checks every run of a program starts with: the handle, its kind (`entry`: the entry point asked), the uniform block
+th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes);
+// the context's module of `prog`, loaded on first use
+th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out);
+// ---- th_blend.hip ----------------------------------------------------------------------------------------------------
+th_status colormap_storage(th_context *c);
 
 // ---- th_order.hip ----------------------------------------------------------------------------------------------------
 void destroy_graph(GraphEntry &g);

@@ -146,24 +146,13 @@ TH_D T block_scan(T *lds, T mine, T &total)
 }
 
 // ---- texture taps shared by the passes that sample a texture at a uv (draw()'s colour map, optical flow, the colour-map
-// blend): NEAREST + CLAMP_TO_EDGE, as pinned against captures of the reference
-TH_D int dep_nearest(float u, int n)       // ... on a float texture: always inside [0, n - 1] (a NaN coordinate: 0)
-{
-    float f = th_floor(u * (float)n);
-    if (!(f > 0.0f)) return 0;
-    if (f > (float)(n - 1)) return n - 1;
-    return (int)f;
-}
-// ... on an 8-bit-per-channel texture (n <= 65536), with the coordinate
-// precision of the captured reference run: clamp to [0, 1), truncate to 16 fractional bits,
-// texel = (coord16 * size) >> 16 (equals floor(u*size) except within 2^-16 of a texel boundary).
-TH_D int nearest_texel_fx16(float u, unsigned n)
-{
-    float c = __builtin_amdgcn_fmed3f(u, 0.0f, 65535.0f / 65536.0f);
-    unsigned fx = (unsigned)(c * 65536.0f);
-    return (int)((fx * n) >> 16);
-}
-// UNORM8 -> float as (c*257) * (1/65535): what the captured reference run did; equals c/255 within 1 ulp.
-TH_D float unorm8(unsigned char c) { return ((float)c * 257.0f) * (1.0f / 65535.0f); }
+// blend, a caller's screen program): NEAREST + CLAMP_TO_EDGE, as pinned against captures of the reference.  The rules
+// themselves are in th_taps.inc, which a screen program's prelude carries as text: one copy for both.
+#define TH_TAPS(...) __VA_ARGS__
+#include "th_taps.inc"
+#undef TH_TAPS
+TH_D int dep_nearest(float u, int n) { return th_tap_nearest(u, n); }                    // a float texture
+TH_D int nearest_texel_fx16(float u, unsigned n) { return th_tap_fx16(u, n); }            // an 8-bit-per-channel one
+TH_D float unorm8(unsigned char c) { return th_tap_unorm8(c); }
 
 }  // namespace th

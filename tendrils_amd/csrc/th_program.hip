@@ -8,35 +8,23 @@
 // hiprtc is bound at run time like librccl in th_comm.hip: the copy the process already holds (torch's, in the Python host),
 // else by soname; TH_HIPRTC_LIB names another.  Nothing here is linked against it: a host that never compiles a program never
 // loads it, and compiling needs no device.
+//
+// What the two kinds of program share (th_screen.hip: screen programs) is here too: the hiprtc binding, the compile, the log,
+// what is read out of the code object, the per-context modules (thi::program_*).
 #include <dlfcn.h>
 #include <elf.h>
 #include <hip/hiprtc.h>
 
-#include <atomic>
-#include <mutex>
-
 #include "th_ctx.hpp"
 
 using namespace thi;
-
-// A compiled program: the gfx950 code object, until th_program_destroy; the record itself lives as long as anything names it -
-// the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
-struct th_program {
-    std::string name;
-    std::vector<char> code;
-    std::mutex lock;                     // `code` against a th_program_destroy on another thread
-    bool destroyed = false;
-    std::atomic<int> refs{1};
-    uint32_t sgprs = 0, code_bytes = 0;  // of th_program_kernel, read from the code object
-};
 
 namespace {
 
 const char kPrelude[] =
 #include "th_program_prelude.inc"
     ;
-const char kKernelName[] = "th_program_kernel";
-constexpr uint32_t kUniformBytes = 1024;
+const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel"};      // by ProgramKind
 
 // the launch record (th_program_prelude.inc: th_program_args, th_program_uniform_block - the same layout)
 struct ProgramArgs {
@@ -98,7 +86,7 @@ Hiprtc &hiprtc()
 
 thread_local std::string g_program_log;
 
-// What the code object says of th_program_kernel: the SGPR count is in its metadata note alone (msgpack: the kernel's map has
+// What the code object says of the kind's kernel: the SGPR count is in its metadata note alone (msgpack: the kernel's map has
 // its keys in order, .name before .sgpr_count), the code size is that of .text.
 void inspect_code_object(th_program *p)
 {
@@ -118,7 +106,7 @@ void inspect_code_object(th_program *p)
             }
         }
     }
-    const std::string name = std::string("\xb1") + kKernelName, key = "\xab.sgpr_count";
+    const std::string name = std::string(1, (char)(0xa0 + strlen(kKernelNames[p->kind]))) + kKernelNames[p->kind], key = "\xab.sgpr_count";
     auto at = std::search(b.begin(), b.end(), name.begin(), name.end());
     if (at != b.end()) at = std::search(at, b.end(), key.begin(), key.end());
     if (at == b.end() || (size_t)(b.end() - at) < key.size() + 5) return;
@@ -145,19 +133,25 @@ void ProgramModule::reset()
     module = nullptr; fn = nullptr; prog = nullptr;
 }
 
-}  // namespace thi
+const char *program_kind_name(ProgramKind kind) { return kind == kScreenProgram ? "screen program (th_screen_program_compile)" : "state program (th_program_compile)"; }
 
-namespace {
+th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes)
+{
+    TH_REQUIRE(prog, "null program");
+    TH_REQUIRE(prog->kind == kind, "%s runs a %s: '%s' is a %s", entry, program_kind_name(kind), prog->name.c_str(), program_kind_name(prog->kind));
+    TH_REQUIRE(uniform_bytes <= kUniformBytes, "uniform block of %u bytes (at most %u)", uniform_bytes, kUniformBytes);
+    TH_REQUIRE(uniforms || uniform_bytes == 0, "null uniforms");
+    return TH_OK;
+}
 
-// the context's module of `prog`, loaded on first use
-th_status loaded(th_context *c, th_program *prog, ProgramModule **out)
+th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
 {
     for (ProgramModule &m : c->programs) if (m.prog == prog) { *out = &m; return TH_OK; }
     std::lock_guard<std::mutex> hold(prog->lock);
     TH_REQUIRE(!prog->destroyed, "program '%s' was destroyed before this context had loaded it", prog->name.c_str());
     ProgramModule m;
     TH_HIP(hipModuleLoadData(&m.module, prog->code.data()));
-    TH_HIP(hipModuleGetFunction(&m.fn, m.module, kKernelName));
+    TH_HIP(hipModuleGetFunction(&m.fn, m.module, kKernelNames[prog->kind]));
     m.prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));
@@ -165,13 +159,7 @@ th_status loaded(th_context *c, th_program *prog, ProgramModule **out)
     return TH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char *th_program_log(void) { return g_program_log.c_str(); }
-
-th_status th_program_compile(const char *source, const char *name, th_program **out)
+th_status program_compile(ProgramKind kind, const std::string &prelude, const char *source, const char *name, th_program **out)
 {
     TH_REQUIRE(source && out, "null argument");
     *out = nullptr;
@@ -180,9 +168,9 @@ th_status th_program_compile(const char *source, const char *name, th_program **
     if (!R.lib) return fail(TH_ERR_UNSUPPORTED, "hiprtc is not loadable (%s); TH_HIPRTC_LIB names one", R.error.c_str());
     const std::string label = name && *name ? name : "user_program";
     // the user's text begins at line 1 of a file called `label`: a diagnostic names the line the user wrote
-    const std::string text = std::string(kPrelude) + "\n#line 1 \"" + label + "\"\n" + source + "\n";
+    const std::string text = prelude + "\n#line 1 \"" + label + "\"\n" + source + "\n";
     hiprtcProgram hp = nullptr;
-    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), "th_program_prelude", 0, nullptr, nullptr);
+    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), kind == kScreenProgram ? "th_screen_prelude" : "th_program_prelude", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) return fail(TH_ERR_INVALID, "hiprtcCreateProgram: %s", R.GetErrorString(r));
     // the product's arithmetic flags (csrc/Makefile: HIPFLAGS)
     const char *opts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950"};
@@ -202,6 +190,7 @@ th_status th_program_compile(const char *source, const char *name, th_program **
     } else if (!(p = new (std::nothrow) th_program)) {
         st = fail(TH_ERR_INVALID, "out of host memory");
     } else {
+        p->kind = kind;
         p->name = label;
         p->code.resize(n);
         if ((r = R.GetCode(hp, p->code.data())) != HIPRTC_SUCCESS) {
@@ -213,6 +202,17 @@ th_status th_program_compile(const char *source, const char *name, th_program **
     (void)R.DestroyProgram(&hp);
     *out = p;
     return st;
+}
+
+}  // namespace thi
+
+extern "C" {
+
+const char *th_program_log(void) { return g_program_log.c_str(); }
+
+th_status th_program_compile(const char *source, const char *name, th_program **out)
+{
+    return program_compile(kStateProgram, kPrelude, source, name, out);
 }
 
 th_status th_program_destroy(th_program *p)
@@ -231,11 +231,9 @@ th_status th_program_destroy(th_program *p)
 th_status th_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t source, int32_t target)
 {
     if (th_status s = use(c)) return s;
-    TH_REQUIRE(prog, "null program");
-    TH_REQUIRE(uniform_bytes <= kUniformBytes, "uniform block of %u bytes (at most %u)", uniform_bytes, kUniformBytes);
-    TH_REQUIRE(uniforms || uniform_bytes == 0, "null uniforms");
+    if (th_status s = program_run_args(prog, kStateProgram, "th_program_run", uniforms, uniform_bytes)) return s;
     ProgramModule *m = nullptr;
-    if (th_status s = loaded(c, prog, &m)) return s;
+    if (th_status s = program_loaded(c, prog, &m)) return s;
     if (th_status s = ensure_identity(c)) return s;      // a pass operates in texel order, like every spawn pass
     // the pass reads `particles` = buffers[1] like every Particles.step (src/particles.js:139)
     TH_REQUIRE(c->ring.size() >= 2, "a pass needs at least 2 state buffers (have %zu)", c->ring.size());
@@ -301,7 +299,7 @@ th_status th_program_query(th_context *c, th_program *prog, th_program_info *inf
     if (th_status s = use(c, true)) return s;
     TH_REQUIRE(prog && info, "null argument");
     ProgramModule *m = nullptr;
-    if (th_status s = loaded(c, prog, &m)) return s;
+    if (th_status s = program_loaded(c, prog, &m)) return s;
     int vgprs = 0, lds = 0, scratch = 0;
     TH_HIP(hipFuncGetAttribute(&vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, m->fn));
     TH_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m->fn));

@@ -683,17 +683,8 @@ TH_D void dep_blend_rgba(float4 &d, float4 c) { const float sa = c.w, da = 1.0f 
 
 // the view pass's blend: the RGBA8 drawing buffer - the fragment colour is clamped to [0, 1], blended with the stored
 // colour c/255 and stored as round(255 x), fragment after fragment (what the captured GL does)
-TH_D void dep_blend_rgba8(uchar4 &q, float4 c)
-{
-    c.x = __builtin_fminf(__builtin_fmaxf(c.x, 0.0f), 1.0f); c.y = __builtin_fminf(__builtin_fmaxf(c.y, 0.0f), 1.0f);
-    c.z = __builtin_fminf(__builtin_fmaxf(c.z, 0.0f), 1.0f); c.w = __builtin_fminf(__builtin_fmaxf(c.w, 0.0f), 1.0f);
-    const float sa = c.w, da = 1.0f - sa, k = 1.0f / 255.0f;
-    auto mix8 = [&](float src, unsigned char dst) {
-        const float o = src * sa + ((float)dst * k) * da;
-        return (unsigned char)(__builtin_fminf(__builtin_fmaxf(o, 0.0f), 1.0f) * 255.0f + 0.5f);
-    };
-    q = make_uchar4(mix8(c.x, q.x), mix8(c.y, q.y), mix8(c.z, q.z), mix8(c.w, q.w));
-}
+// (th_taps.inc: th_blend_rgba8 - the one definition, a caller's screen program blends through it too)
+TH_D void dep_blend_rgba8(uchar4 &q, float4 c) { th_blend_rgba8(q, c); }
 
 // pass 5: fragments sorted by texel (stable: stream order inside a texel).  The lane at the head of a texel's run blends
 // its first kShortRun fragments itself, four read ahead of the dependent blends - nearly every run ends there.  What

@@ -23,6 +23,8 @@ def defaults():
 class Program:
     """Stand-in for a compiled gl-shader object: names a kernel family - or, from_source(), holds a pass the caller wrote."""
 
+    COMPILE, SOURCE_KIND = "th_program_compile", "user"       # what from_source() compiles with, and into which kind
+
     def __init__(self, kind, **fixed):
         self.kind = kind          # 'logic' | 'spawn-init' | 'spawn-ball' | 'spawn-sample' | 'spawn-direct' | 'user'
         self.fixed = fixed        # compile-time constants of that shader (e.g. samples, apply)
@@ -41,11 +43,11 @@ class Program:
             raise ValueError("a uniform block holds at most 1024 bytes (%d)" % C.sizeof(uniforms_struct))
         lib = _capi.load()
         handle = C.c_void_p()
-        status = lib.th_program_compile(source.encode(), name.encode(), C.byref(handle))
+        status = getattr(lib, cls.COMPILE)(source.encode(), name.encode(), C.byref(handle))
         if status != _capi.TH_OK:
             raise _capi.TendrilsHipError(status, lib.th_last_error().decode(errors="replace") + "\n" +
                                          lib.th_program_log().decode(errors="replace"))
-        prog = cls("user", name=name)
+        prog = cls(cls.SOURCE_KIND, name=name)
         prog.handle, prog.uniforms_struct = handle, uniforms_struct
         return prog
 
@@ -86,6 +88,14 @@ class Program:
             self.dispose()
         except Exception:
             pass
+
+
+class ScreenProgram(Program):
+    """A screen program (include/tendrils_hip.h "screen programs"): from_source() takes HIP source defining
+    `__device__ float4 th_screen(const th_screen_pass &s)` - the shader of one Screen.render() - and is otherwise
+    Program.from_source: compiled once, for gfx950, no GPU needed; TendrilsHipError with the compiler's output; pack(),
+    query() and dispose() as there.  Tendrils.screenShader() runs it."""
+    COMPILE, SOURCE_KIND = "th_screen_program_compile", "screen"
 
 
 LOGIC = "logic"

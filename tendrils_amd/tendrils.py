@@ -2,7 +2,8 @@
 particle-update path: state uniforms, timer, flow/targets textures, step(), spawn(),
 spawnShader(), resize(), and draw() = the flow pass + the view pass (the particles' lines with the
 render shader's colours into an RGBA8 image of the drawing buffer: `view`, read with read_view()).
-The multi-buffer screen passes (blur / copy shaders, src/screen) are outside this build.
+The demo's last pass - a shader of its own over the finished view (src/screen) - is screenShader() with a caller's
+ScreenProgram; the reference's own blur shader is outside this build.
 """
 import ctypes as C
 import math
@@ -11,7 +12,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import LOGIC, Particles, Program, run_pass
+from .particles import LOGIC, Particles, Program, ScreenProgram, run_pass
 from .timer import Timer
 
 
@@ -193,6 +194,20 @@ class ViewBuffer:
         self._o = None
 
 
+class ScreenImage:
+    """The drawing buffer itself (gl.bindFramebuffer(gl.FRAMEBUFFER, null)) as a texture a screen pass samples."""
+
+    def __init__(self, owner):
+        self._o = owner
+
+    def bind(self):
+        self._o._bind_view(None)
+        return self
+
+    def read(self):
+        return self._o.read_view(None)
+
+
 class Tendrils:
     def __init__(self, gl=None, options=None):
         params = {**defaults(), **(options or {})}
@@ -204,6 +219,7 @@ class Tendrils:
         self.colorMap = params.get("colorMap") or ColorMap(self)
         self.renderView = bool(params.get("renderView", True))     # draw() also runs the view pass (as the reference's does)
         self.buffers = []
+        self.screen = ScreenImage(self)
         self.logicShader = None
         self._logic_option = params.get("logicShader")         # new Tendrils(gl, { logicShader }): the caller's integrator
         self.uniforms = dict(render={}, update={})
@@ -273,6 +289,58 @@ class Tendrils:
             self.buffers.insert(0, self.buffers.pop())         # src/utils/index.js:1-7
             if self.particles is not None:
                 call("th_view_step_buffers", self.particles._ctx)
+        return self
+
+    def screenShader(self, program, uniforms=None, views=(), target=None, blend=None):
+        """Screen.render() with a caller's shader bound (src/screen/index.js; the demo's last pass, src/demo.main.js:1084-1102):
+        `program` - a ScreenProgram - runs once per texel of `target`: None = the bound view image, tendrils.colorMap, or a
+        texture slot (an int: the slot's RGBA32F / RGBA8 texture).  views: the texture units in order - one of self.buffers,
+        self.screen, self.colorMap, self.flow, anything a Blend takes, or a texture slot (an int).  blend: gl.BLEND for this
+        pass; None = what the passes before left (as Blend.draw)."""
+        from .blend import resolve_view
+        if not isinstance(program, ScreenProgram) or not program.handle:
+            raise TypeError("screenShader: %r is no compiled ScreenProgram" % (program,))
+        particles, views = self.particles, list(views)
+        if len(views) > _capi.MAX_BLEND_VIEWS:
+            raise ValueError("screenShader: at most %d views (got %d)" % (_capi.MAX_BLEND_VIEWS, len(views)))
+        named = {int(v) for v in views + [target] if isinstance(v, (int, np.integer))}
+        free = [k for k in range(_capi.MAX_TEXTURES) if k not in named]      # (audio textures travel in slots nobody named)
+        table, slots = (_capi.ScreenUnit * max(1, len(views)))(), []
+        for i, view in enumerate(views):
+            if isinstance(view, (int, np.integer)):
+                found = _capi.VIEW_TEXTURE, int(view)
+                particles.textures[int(view)] = None           # (whatever audio texture the host thought it held)
+            elif isinstance(view, ViewBuffer):
+                found = _capi.VIEW_BUFFER, self.buffers.index(view)
+            elif isinstance(view, ScreenImage):
+                found = _capi.VIEW_SCREEN, 0
+            elif isinstance(view, ColorMap):
+                view.bind_shape()
+                found = _capi.VIEW_COLORMAP, 0
+            elif isinstance(view, FlowTexture):
+                found = _capi.VIEW_FLOW, 0
+            else:
+                found = resolve_view(particles, view, slots, free)
+            if found is None:
+                raise TypeError("screenShader: view %d (%r) is nothing a screen pass samples" % (i, view))
+            table[i].source, table[i].index = found
+        if target is None:
+            where, index = _capi.SCREEN_TARGET_VIEW, 0
+        elif isinstance(target, ColorMap):
+            target.bind_shape()
+            where, index = _capi.SCREEN_TARGET_COLORMAP, 0
+        elif isinstance(target, (int, np.integer)):
+            where, index = _capi.SCREEN_TARGET_TEXTURE, int(target)
+        else:
+            raise TypeError("screenShader: target %r is neither None (the bound view image), the colorMap nor a texture slot" % (target,))
+        block = program.pack(uniforms or {})
+        blending = self.blending if blend is None else bool(blend)
+        call("th_screen_run", particles._ctx, program.handle, None if block is None else C.byref(block),
+             0 if block is None else C.sizeof(block), table, len(views), where, index, int(blending))
+        if where == _capi.SCREEN_TARGET_COLORMAP:
+            target.blended()
+        elif where == _capi.SCREEN_TARGET_TEXTURE:
+            particles.textures[index] = None
         return self
 
     def viewport(self):                                        # src/index.js:410-419: gl.viewport(0, 0, ...viewRes) - every pass
