@@ -324,6 +324,43 @@ th_status th_screen_program_compile(const char *source, const char *name, th_pro
 th_status th_screen_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
                         const th_screen_unit *units, int32_t n_units, int32_t target, int32_t target_index, int32_t gl_blend);
 
+/* -- draw programs: the vertex stage of a draw() pass the CALLER wrote ------------------------------------------------
+ * The reference's third seam: new Tendrils(gl, { renderShader, flowShader }) (src/index.js:70-71, 114-120) - the shaders that
+ * particles.draw(..., gl.LINES) runs in the two passes of draw().  Their fragment stages are gl_FragColor = the varying;
+ * what differs is the vertex stage, and here such a vertex shader is HIP source defining one device function,
+ *     __device__ th_vertex th_vertex_main(const th_vertex_pass &v);   - main() of the vertex shader, once per stream vertex
+ * compiled exactly as a user program is (same hiprtc, same flags, same `#line 1 "<name>"`, same th_program_log()) behind a
+ * prelude of its own (tendrils_amd/csrc/th_draw_prelude.inc) that declares:
+ *   th_vertex_pass     uv (the attribute of the stream Particles.generateLUT([W, 2H]), fp32 of the doubles), state (what
+ *                      stateAtFrame(uv, dataRes, previous, particles) returns: the texel and the buffer the lookup selects -
+ *                      also for the shapes whose lookup lands beside the line's own texel), from_current, column, vertex (i, j
+ *                      of the stream), line (the stream index i * H + (j >> 1)), dataRes, geomRes, uniforms (th_uniforms<T>(v):
+ *                      the caller's block, up to 1024 bytes)
+ *   th_vertex          { float2 position; float4 color; } - gl_Position.xy (w = 1) and the vec4 varying
+ *   th_discard_vertex()        the vertex of an `if(state.xy != inert)` that was not taken: its line draws nothing
+ *   th_flow(v, u, w), th_flow_res(v)           texture2D(flow, (u, w)): NEAREST, CLAMP_TO_EDGE - the field as it was BEFORE this
+ *                              pass, also in a pass that draws into it (every vertex runs before anything blends)
+ *   th_colormap(v, u, w), th_colormap_res(v)   ... of the colour map; no map held: the 1 x 1 zero texture
+ * Every accessor clamps: a program that reads through them alone cannot read out of bounds.
+ * Everything behind the vertex stage is the library's and the same code as for its own stages: a line with a discarded vertex,
+ * of zero length, or with a non-finite position or one beyond 1024 draws nothing; the line's hexagon at the pass's width
+ * (th_line_width), clipping, 1/16-texel snapping, ceil() scan conversion, the varying along the snapped endpoints, the blend in
+ * primitive order (SRC_ALPHA / ONE_MINUS_SRC_ALPHA; the view's in RGBA8).
+ *  th_draw_program_compile    as th_program_compile (a source without th_vertex_main does not compile).  The handle is a
+ *                      th_program of a third kind: th_program_destroy / _query / _log serve all three; th_program_run, th_screen_run
+ *                      and th_draw_program_run refuse each other's programs (TH_ERR_INVALID, both kinds named, nothing launched).
+ *  th_draw_program_run one pass of draw() with the program as its vertex stage: pass = TH_PASS_FLOW blends into the flow field
+ *                      (as th_flow_deposit), TH_PASS_VIEW into the bound view image (as th_view_draw); *fragments (optional):
+ *                      the fragments blended.  The pass runs the stream-ordered pipeline - the ring goes to texel order as for
+ *                      a stream-ordered built-in pass, th_draw_query reports TH_DRAW_STREAM - from a context-owned vertex buffer
+ *                      of 64 bytes per particle that grows and stays.  Nothing of the pass is reused by the next one, nor of
+ *                      the one before by it.  The ring's content is untouched.
+ *                      On a row-band shard: TH_ERR_UNSUPPORTED, nothing launched.  TH_ERR_INVALID: another kind's program, more
+ *                      than 1024 uniform bytes, null uniforms with a size, a null program, an unknown pass. */
+th_status th_draw_program_compile(const char *source, const char *name, th_program **out);
+th_status th_draw_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
+                              int32_t pass /* TH_PASS_FLOW | TH_PASS_VIEW */, uint64_t *fragments);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */
 th_status th_frames_upload(th_context *ctx, const uint8_t *rgba8);     /* setPixels -> buffers[0] */
@@ -462,8 +499,9 @@ th_status th_state_device_ptr(th_context *ctx, int32_t buffer, void **dptr);
 th_status th_timer_start(th_context *ctx);
 th_status th_timer_stop(th_context *ctx, float *elapsed_ms);           /* synchronises */
 /* Per-launch timing of the integrator kernel alone: while enabled, every th_step records a HIP
- * event pair around its logic-kernel launch; _read synchronises, returns the mean duration and the
- * number of launches since the last read, and resets. */
+ * event pair around its logic-kernel launch - and every th_draw_program_run one around its vertex
+ * kernel -; _read synchronises, returns the mean duration and the number of launches since the last
+ * read, and resets. */
 th_status th_kernel_timing(th_context *ctx, int32_t enable);
 th_status th_kernel_timing_read(th_context *ctx, float *mean_ms, int32_t *launches);
 /* The context's current texture shapes, for bindings that must size host arrays: state (this context's band),

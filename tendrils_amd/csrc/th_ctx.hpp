@@ -10,6 +10,7 @@
 //   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run), and what both kinds of
 //                  program share: the hiprtc binding, the compile, the log, the per-context modules
 //   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
+//   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,10 +74,10 @@ struct th_options {
     bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
 };
 
-// A compiled program of either kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
+// A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
 // anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
 namespace thi {
-enum ProgramKind { kStateProgram = 0, kScreenProgram = 1 };      // th_program_compile / th_screen_program_compile
+enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile
 }
 struct th_program {
     thi::ProgramKind kind = thi::kStateProgram;
@@ -93,7 +94,7 @@ namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel
+    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -253,7 +254,7 @@ struct th_context {
     Texture textures[TH_MAX_TEXTURES];
     DevBuf<unsigned long long> d_respawned;      // [0]: particles replaced by respawn passes, [1]: scratch (passes into `targets`)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool kernel_timing = false;          // th_kernel_timing: event pair around every logic launch
+    bool kernel_timing = false;          // th_kernel_timing: event pair around every logic launch (and a draw program's vertex kernel)
     std::vector<hipEvent_t> kt_events;   // pairs (start, stop); kt_used of them recorded
     size_t kt_used = 0;
     std::vector<GraphEntry> graphs;      // th_step_n cache
@@ -307,8 +308,12 @@ struct th_context {
 
     thi::FlowLineScratch *flow_lines = nullptr;   // th_flow_lines: staging and scratch (grow-only)
 
-    std::vector<thi::ProgramModule> programs;     // th_program_run / th_screen_run: the programs this context has loaded
+    std::vector<thi::ProgramModule> programs;     // th_program_run / th_screen_run / th_draw_program_run: the programs this context has loaded
     DevBuf<unsigned> prog_flag;                   // ... and the word a pass on a row band raises (th_particles outside the band)
+
+    // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
+    // (grows and stays, like the flow lines' scratch)
+    DevBuf<float4> draw_vertices;
 
     size_t texels() const { return (size_t)cfg.width * cfg.height; }
     size_t state_bytes() const { return texels() * (packed ? sizeof(uint2) : sizeof(float4)); }
@@ -345,8 +350,11 @@ inline void state_moved(th_context *c, const float4 *from, const float4 *to)
     if (c->seen.cur == from || c->seen.prev == from) c->seen.cur = c->seen.prev = nullptr;
 }
 
+// ---- th_step.hip -----------------------------------------------------------------------------------------------------
+th_status timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1);      // th_kernel_timing: the next pair of events to record around a launch
+
 // ---- th_program.hip --------------------------------------------------------------------------------------------------
-constexpr uint32_t kUniformBytes = 1024;        // a program's uniform block (th_program_uniform_block in both preludes)
+constexpr uint32_t kUniformBytes = 1024;        // a program's uniform block (th_program_uniform_block in the preludes)
 const char *program_kind_name(ProgramKind kind);
 // `prelude` + `#line 1 "<name>"` + `source` through hiprtc into a program of `kind`; th_program_log() holds the compiler's output
 th_status program_compile(ProgramKind kind, const std::string &prelude, const char *source, const char *name, th_program **out);
@@ -387,6 +395,8 @@ th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t
 th_status deposit_count(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
 th_status deposit_temp(th_context *c, size_t need);
+// the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, sort by texel, blend
+th_status deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments);
 th_status view_storage(th_context *c);
 void view_fields(th_context *c, const th_render_uniforms *u, th::DepositParams &p);
 th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr);

@@ -35,6 +35,9 @@ namespace {
 // the particle texture row-major in pieces of 256 columns of a row (coalesced state reads, no division per line); the
 // line's place in the fragment array is its position in the vertex stream (column-major): the scan below is over
 // that order.  Only the common case is done here, with everything in registers; the rest goes to the slow list.
+// (PROGRAM, here and in the three kernels below that set a line up: a caller's vertex stage has run - th_drawprog.hip - and the
+// vertices are read from p.vertices, th_raster.hpp: dep_vertex_read; <false> is the library's own stage)
+template <bool PROGRAM>
 __global__ __launch_bounds__(256) void deposit_raster_kernel(const DepositParams p)
 {
     const uint32_t pieces = (p.W + 255u) >> 8, groups = pieces * p.rows;
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(256) void deposit_raster_kernel(const DepositParams
         bool slow = false;
         if (have) {
             DepositLine L;
-            dep_setup(p, col, p.row0 + row, L, (size_t)row * p.W + col);
+            dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, (size_t)row * p.W + col);
             if (L.draws) {
                 float cx[6], cy[6];
                 const int where = dep_hexagon(p, L, cx, cy);
@@ -66,6 +69,7 @@ __global__ __launch_bounds__(256) void deposit_raster_kernel(const DepositParams
     }
 }
 
+template <bool PROGRAM>
 __global__ __launch_bounds__(256) void deposit_raster_slow_kernel(const DepositParams p)
 {
     __shared__ float polygons[48 * 256];                  // (the clipped polygon, indexed at run time: LDS, not scratch memory)
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void deposit_raster_slow_kernel(const DepositP
         if (have) {
             const uint32_t row = t / p.W, col = t - row * p.W;
             DepositLine L;
-            dep_setup(p, col, p.row0 + row, L, (size_t)row * p.W + col);
+            dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, (size_t)row * p.W + col);
             dep_raster_line(p, L, [&](int x, int y) { rec_add(r, x, y); }, words);
             p.count[t] = r.n;
             if (r.n) rec_store(p, t, r);
@@ -107,6 +111,7 @@ TH_D void dep_put(const DepositParams &p, const DepositLine &L, uint32_t id, uin
 // somewhere else: 1.2 ms for this pass at C3 against 0.3); a patch reads whole 128-byte lines of the state rows.
 constexpr uint32_t kPatchCols = 8, kPatchRows = 64;
 
+template <bool PROGRAM>
 __global__ __launch_bounds__(kPatchCols * 64) void deposit_emit_kernel(const DepositParams p)
 {
     const uint32_t patches_x = (p.W + kPatchCols - 1) / kPatchCols, patches_y = (p.rows + kPatchRows - 1) / kPatchRows;
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(kPatchCols * 64) void deposit_emit_kernel(const Dep
         const uint32_t id = col * p.H + p.row0 + row;
         const uint32_t at = p.offset[t];
         DepositLine L;
-        dep_setup(p, col, p.row0 + row, L, (size_t)row * p.W + col);           // vertices and snapped endpoints
+        dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, (size_t)row * p.W + col);           // vertices and snapped endpoints
         const uint4 ra = p.record[2u * t];
         uint4 rb = make_uint4(0u, 0u, 0u, 0u);
         if (n > 4u) rb = p.record[2u * t + 1u];
@@ -134,6 +139,7 @@ __global__ __launch_bounds__(kPatchCols * 64) void deposit_emit_kernel(const Dep
 }
 
 // ... and the lines of more fragments than a record holds, rasterised again
+template <bool PROGRAM>
 __global__ __launch_bounds__(256) void deposit_emit_long_kernel(const DepositParams p)
 {
     __shared__ float polygons[48 * 256];
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void deposit_emit_long_kernel(const DepositPar
         const uint32_t id = col * p.H + p.row0 + row;
         uint32_t at = p.offset[t];
         DepositLine L;
-        dep_setup(p, col, p.row0 + row, L, (size_t)row * p.W + col);
+        dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, (size_t)row * p.W + col);
         dep_raster_line(p, L, [&](int x, int y) { dep_put(p, L, id, at, x, y); ++at; }, words);
     });
 }
@@ -507,8 +513,14 @@ void launch_deposit_count(const DepositParams &p, hipStream_t s)
 {
     const uint32_t groups = ((p.W + 255u) >> 8) * p.rows;
     (void)hipMemsetAsync(p.list_n, 0, deposit_list_counter_bytes(), s);
-    hipLaunchKernelGGL(deposit_raster_kernel, dim3(groups < 65536u * 16u ? (groups ? groups : 1u) : 65536u * 16u), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(deposit_raster_slow_kernel, dim3(kDepLists * 8u), dim3(256), 0, s, p);
+    const dim3 grid(groups < 65536u * 16u ? (groups ? groups : 1u) : 65536u * 16u);
+    if (p.vertices) {           // (a caller's vertex stage has left the vertices there)
+        hipLaunchKernelGGL(deposit_raster_kernel<true>, grid, dim3(256), 0, s, p);
+        hipLaunchKernelGGL(deposit_raster_slow_kernel<true>, dim3(kDepLists * 8u), dim3(256), 0, s, p);
+        return;
+    }
+    hipLaunchKernelGGL(deposit_raster_kernel<false>, grid, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(deposit_raster_slow_kernel<false>, dim3(kDepLists * 8u), dim3(256), 0, s, p);
 }
 
 // scratch: deposit_scan_words(W, rows) words (row-block partial sums, then the column bases)
@@ -526,8 +538,14 @@ void launch_deposit_scan(const DepositParams &p, uint32_t *scratch, uint32_t *to
 void launch_deposit_scatter(const DepositParams &p, hipStream_t s)
 {
     const uint32_t patches = ((p.W + kPatchCols - 1) / kPatchCols) * ((p.rows + kPatchRows - 1) / kPatchRows);
-    hipLaunchKernelGGL(deposit_emit_kernel, dim3(patches < 65536u * 16u ? (patches ? patches : 1u) : 65536u * 16u), dim3(kPatchCols * 64u), 0, s, p);
-    hipLaunchKernelGGL(deposit_emit_long_kernel, dim3(kDepLists * 8u), dim3(256), 0, s, p);
+    const dim3 grid(patches < 65536u * 16u ? (patches ? patches : 1u) : 65536u * 16u);
+    if (p.vertices) {
+        hipLaunchKernelGGL(deposit_emit_kernel<true>, grid, dim3(kPatchCols * 64u), 0, s, p);
+        hipLaunchKernelGGL(deposit_emit_long_kernel<true>, dim3(kDepLists * 8u), dim3(256), 0, s, p);
+        return;
+    }
+    hipLaunchKernelGGL(deposit_emit_kernel<false>, grid, dim3(kPatchCols * 64u), 0, s, p);
+    hipLaunchKernelGGL(deposit_emit_long_kernel<false>, dim3(kDepLists * 8u), dim3(256), 0, s, p);
 }
 
 int deposit_key_bits(const DepositParams &p)

@@ -318,7 +318,7 @@ static th_status export_run(th_context *c, th::DepositParams &p, float *lines, u
 }
 
 // the fragments of the (prepared) pass `p`: count, emit, sort by texel, blend
-static th_status deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments)
+th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments)
 {
     // Same state, same view, same resolution as the pass before (the view pass after the flow pass of one draw()): the
     // lines cover the same texels in the same order - counts, offsets, records and the sorted order of the fragments are

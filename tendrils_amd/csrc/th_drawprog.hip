@@ -1,0 +1,111 @@
+// th_drawprog.hip - draw programs: a caller's vertex stage in one pass of draw().  The reference's third seam (th_program.hip and
+// th_screen.hip have the other two): new Tendrils(gl, { renderShader, flowShader }) (src/index.js:70-71, 114-120) - the shader
+// pair particles.draw(..., gl.LINES) runs in the two passes of draw(); the vertex stage itself is a template over an `apply`
+// function there (src/flow/vert/main.vert).  Here the caller's vertex shader is HIP source for one device function,
+// th_vertex_main (th_draw_prelude.inc), compiled for gfx950 at run time like the other two kinds (th_program.hip:
+// program_compile).  It runs once per vertex of the stream into a context-owned vertex buffer; the stream-ordered pipeline
+// (th_deposit.hip) then draws the lines from that buffer instead of from the library's own vertex stage - everything behind
+// the vertex stage is the same code (th_raster.hpp: dep_vertex_read).
+#include "th_ctx.hpp"
+
+using namespace thi;
+
+namespace {
+
+// the tap rules and the stream lookup as text (th_taps.inc, th_stream.inc: the library's kernels compile the same lines), then
+// the prelude
+#define TH_TAPS(...) #__VA_ARGS__
+const char kTaps[] =
+#include "th_taps.inc"
+    ;
+#undef TH_TAPS
+#define TH_STREAM(...) #__VA_ARGS__
+const char kStream[] =
+#include "th_stream.inc"
+    ;
+#undef TH_STREAM
+const char kPrelude[] =
+#include "th_draw_prelude.inc"
+    ;
+
+// the launch record (th_draw_prelude.inc: th_draw_args, th_program_uniform_block - the same layout)
+struct DrawArgs {
+    const float4 *cur, *prev;
+    void *vertices;
+    const float4 *flow, *colormap;
+    double inv_x, inv_y;
+    uint32_t W, H, count;
+    int32_t fw, fh, cw, ch;
+    uint32_t reserved[3];
+};
+struct KernArgs {
+    DrawArgs a;
+    alignas(16) unsigned char u[kUniformBytes];
+};
+static_assert(sizeof(DrawArgs) == 96 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
+              "launch record: layout shared with th_draw_prelude.inc");
+
+}  // namespace
+
+extern "C" {
+
+th_status th_draw_program_compile(const char *source, const char *name, th_program **out)
+{
+    return program_compile(kDrawProgram, std::string(kTaps) + "\n" + kStream + "\n" + kPrelude, source, name, out);
+}
+
+// One pass of draw() with the program as its vertex stage: the ring goes to texel order as for a stream-ordered built-in pass,
+// the vertex kernel fills the vertex buffer, the stream-ordered pipeline draws from it.  The counts and the sorted order a
+// built-in pass left (c->drawn) are not this pass's, nor this pass's a built-in's: invalid before and after.
+th_status th_draw_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t pass, uint64_t *fragments)
+{
+    if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;      // (the view pass writes no state and no flow: th_view_draw)
+    if (th_status s = program_run_args(prog, kDrawProgram, "th_draw_program_run", uniforms, uniform_bytes)) return s;
+    TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
+    if (c->cfg.height != c->cfg.global_height)
+        return fail(TH_ERR_UNSUPPORTED, "draw program on a row-band shard (%d of %d rows): a band's pass goes through the owners' exchange, which carries the built-in stages alone",
+                    c->cfg.height, c->cfg.global_height);
+    const size_t lines = c->texels();
+    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a %dx%d particle texture is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
+    c->drawn.valid = false;
+    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;      // (a local draw moves nothing between ranks)
+    ProgramModule *m = nullptr;
+    if (th_status s = program_loaded(c, prog, &m)) return s;
+    if (pass == TH_PASS_VIEW) if (th_status s = view_storage(c)) return s;
+    // the pass as a stream-ordered built-in pass prepares it (texel order, held for a while; the per-line buffers); what the
+    // built-in vertex stage takes from its uniforms - viewSize, time, speedLimit - is the program's own business here
+    th::DepositParams p;
+    const th_deposit_uniforms none{};
+    if (th_status s = deposit_prepare(c, &none, p)) return s;
+    if (pass == TH_PASS_VIEW) { p.mode = 1; p.view = c->view; }
+    p.line_half = 0.5f * drawn_line_width(c, pass);
+    if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
+    p.vertices = c->draw_vertices;
+    float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
+    if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
+    if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
+    KernArgs k{};
+    DrawArgs &a = k.a;
+    a.cur = cur; a.prev = prev; a.vertices = c->draw_vertices.get();
+    a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
+    a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
+    a.inv_x = p.inv_x; a.inv_y = p.inv_y;
+    a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
+    if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
+    if (a.count) {
+        // the record and the uniform block travel in the kernel's argument segment (th_program_run).  A memory-bound pass: at
+        // most 256 CUs x 8 workgroups, the rest of the vertices by the grid's stride
+        size_t bytes = sizeof k;
+        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+        const uint32_t blocks = (a.count + 255u) / 256u, cap = 256u * 8u;
+        hipEvent_t k0 = nullptr, k1 = nullptr;          // (th_kernel_timing: the vertex kernel alone)
+        if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
+        TH_HIP(hipModuleLaunchKernel(m->fn, blocks < cap ? blocks : cap, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
+        if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+    }
+    const th_status s = deposit_run(c, p, fragments);
+    c->drawn.valid = false;
+    return s;
+}
+
+}  // extern "C"

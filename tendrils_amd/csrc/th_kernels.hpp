@@ -192,7 +192,15 @@ struct DepositParams {
     // id (nullptr = texel order); fragments go straight from the rasteriser into the 16 x 16-texel bin of the target they
     // fall into.  A bin is kBinReplicas lists of pages of kBinPage places: page 0 of list r of bin b is page
     // b * kBinReplicas + r, further pages come from a pool.
-    const uint32_t *perm;
+    // ... or, in a pass of the stream-ordered pipeline (where `perm` has no meaning and is null): a caller's draw program has run
+    // as this pass's vertex stage (th_drawprog.hip) and left 32 bytes per stream vertex - { float px, py; uint32 live, pad;
+    // float c[4] } at 2 * (local row * W + column) + (j & 1) - which are read instead of computed (th_raster.hpp:
+    // dep_vertex_read); nullptr: the library's own stage.  (One word for both: a field more, anywhere, moves the hidden
+    // arguments behind the block, and hipcc then schedules kernels of th_bins.hip and th_deposit.hip otherwise - as the note on `packed` below found.)
+    union {
+        const uint32_t *perm;
+        const float4 *vertices;
+    };
     const uint32_t *draw_blocks;                   // the blocks of 256 slots that hold a line that can draw at all, in rising order (launch_bins_block_list)
     const uint32_t *block_seen;                    // per block of 256 slots: the four bytes the step left (LogicParams::seen); nullptr: every listed block is walked
     uint32_t draw_nblocks;
@@ -220,6 +228,8 @@ struct DepositParams {
     uint32_t packed;             // cur / prev hold the packed 8-byte form (TH_STATE_F16): read through dep_state (th_raster.hpp)
     LineSources src;
 };
+
+static_assert(sizeof(DepositParams) == 552, "DepositParams: the kernels' argument block keeps its size (see the note on `vertices`)");
 
 // row-band shards drawing with the binned pipeline (th_bins.hip "the bins travel to the ranks that own them")
 struct OwnerParams {

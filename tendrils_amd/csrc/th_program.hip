@@ -9,7 +9,7 @@
 // else by soname; TH_HIPRTC_LIB names another.  Nothing here is linked against it: a host that never compiles a program never
 // loads it, and compiling needs no device.
 //
-// What the two kinds of program share (th_screen.hip: screen programs) is here too: the hiprtc binding, the compile, the log,
+// What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs) is here too: the hiprtc binding, the compile, the log,
 // what is read out of the code object, the per-context modules (thi::program_*).
 #include <dlfcn.h>
 #include <elf.h>
@@ -24,7 +24,8 @@ namespace {
 const char kPrelude[] =
 #include "th_program_prelude.inc"
     ;
-const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel"};      // by ProgramKind
+const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel"};      // by ProgramKind
+const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude"};
 
 // the launch record (th_program_prelude.inc: th_program_args, th_program_uniform_block - the same layout)
 struct ProgramArgs {
@@ -133,7 +134,11 @@ void ProgramModule::reset()
     module = nullptr; fn = nullptr; prog = nullptr;
 }
 
-const char *program_kind_name(ProgramKind kind) { return kind == kScreenProgram ? "screen program (th_screen_program_compile)" : "state program (th_program_compile)"; }
+const char *program_kind_name(ProgramKind kind)
+{
+    return kind == kScreenProgram ? "screen program (th_screen_program_compile)"
+         : kind == kDrawProgram   ? "draw program (th_draw_program_compile)" : "state program (th_program_compile)";
+}
 
 th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes)
 {
@@ -170,7 +175,7 @@ th_status program_compile(ProgramKind kind, const std::string &prelude, const ch
     // the user's text begins at line 1 of a file called `label`: a diagnostic names the line the user wrote
     const std::string text = prelude + "\n#line 1 \"" + label + "\"\n" + source + "\n";
     hiprtcProgram hp = nullptr;
-    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), kind == kScreenProgram ? "th_screen_prelude" : "th_program_prelude", 0, nullptr, nullptr);
+    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), kPreludeNames[kind], 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) return fail(TH_ERR_INVALID, "hiprtcCreateProgram: %s", R.GetErrorString(r));
     // the product's arithmetic flags (csrc/Makefile: HIPFLAGS)
     const char *opts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950"};

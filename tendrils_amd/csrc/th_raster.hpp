@@ -12,6 +12,12 @@
 
 namespace th {
 
+// which texel of which buffer vertex j of column i of the stream reads (th_stream.inc: the one copy - the text put in front of a
+// caller's draw program looks its texel up through the same lines)
+#define TH_STREAM(...) __VA_ARGS__
+#include "th_stream.inc"
+#undef TH_STREAM
+
 // texel `at` of a state buffer of the pass: f32 texels, or what a packed ring's 8-byte texel decodes to (the lines are made of that)
 TH_D float4 dep_state(const DepositParams &p, const float4 *buf, size_t at)
 {
@@ -103,18 +109,31 @@ TH_D void dep_vertex_colors(const DepositParams &p, float4 t, DepositVertex &v)
 struct OwnTexels { bool have = false; float4 cur{}, prev{}; };
 // PLAIN: f32 texels, and a texel's place in cur / prev is its index or the line's own slot - no packed ring, no table of where
 // other lines' particles lie (the binned pass's kernel for the shapes of the frame loop it was tuned on: nothing it does not need)
-template <bool PLAIN = false>
+// PROGRAM: the vertex stage has run already - a caller's draw program (th_drawprog.hip) - and left its vertices in p.vertices:
+// position, varying and whether it is live are read (dep_vertex_read), nothing is looked up or computed
+TH_D DepositVertex dep_vertex_read(const DepositParams &p, uint32_t i, uint32_t j, uint32_t own_row, bool colors)
+{
+    const float4 *rec = p.vertices + 2u * (2u * ((size_t)own_row * p.W + i) + (j & 1u));      // { px, py, live, pad | c[4] }
+    const float4 head = rec[0];
+    DepositVertex v;
+    v.live = __float_as_uint(head.z) != 0u;
+    v.px = head.x; v.py = head.y;
+    v.from_cur = false; v.uvx = 0.0f; v.uvy = 0.0f;
+    if (colors) { const float4 c = rec[1]; v.c[0] = c.x; v.c[1] = c.y; v.c[2] = c.z; v.c[3] = c.w; }
+    return v;
+}
+template <bool PLAIN = false, bool PROGRAM = false>
 TH_D DepositVertex dep_fetch(const DepositParams &p, uint32_t i, uint32_t j, uint32_t own_row, size_t own_at, const OwnTexels own = OwnTexels{}, bool colors = true)
 {
+    if constexpr (PROGRAM) return dep_vertex_read(p, i, j, own_row, colors);
     const int W = (int)p.W, H = (int)p.H;
-    const float uvx = (float)((double)i * p.inv_x), uvy = (float)((double)j * p.inv_y);   // Float32Array of JS doubles
-    const float near_index = uvy * (float)H;
-    const float fl = th_floor(near_index);
-    const float offset = near_index - fl;
-    const float ly = fl / (float)H;
-    const float4 *tex = offset > 0.25f ? p.cur : p.prev;
-    int row = dep_nearest(ly, H) - (int)p.row0;              // row-band shard: the band (or its halo rows) must hold the row
-    const int col = dep_nearest(uvx, W);
+    // (th_stream.inc; row: local to a row-band shard, whose band - or its halo rows - must hold it)
+    const th_stream_at<float4> at_stream = th_stream_lookup(i, j, p.inv_x, p.inv_y, W, H, p.row0, p.cur, p.prev);
+    const float uvx = at_stream.uvx, uvy = at_stream.uvy;
+    const bool from_cur = at_stream.from_cur;
+    const float4 *tex = at_stream.tex;
+    int row = at_stream.row;
+    const int col = at_stream.col;
     // (one unconditional load from a selected address: a load under a branch is awaited at the join, and the second
     // vertex's load would only go out after the first had come back)
     const bool self = row == (int)own_row && col == (int)i;
@@ -126,12 +145,12 @@ TH_D DepositVertex dep_fetch(const DepositParams &p, uint32_t i, uint32_t j, uin
         if (self) at = own_at;
         const float4 *from = tex + at;
         if (!(row >= 0 && row < (int)p.rows)) {
-            if (row == -1 && p.halo_lo) from = p.halo_lo + (offset > 0.25f ? 0 : W) + col;
-            else if (row == (int)p.rows && p.halo_hi) from = p.halo_hi + (offset > 0.25f ? 0 : W) + col;
+            if (row == -1 && p.halo_lo) from = p.halo_lo + (from_cur ? 0 : W) + col;
+            else if (row == (int)p.rows && p.halo_hi) from = p.halo_hi + (from_cur ? 0 : W) + col;
             else *p.oob = 1u;
         }
         if (own.have && self) {
-            const bool c = offset > 0.25f;
+            const bool c = from_cur;
             t = make_float4(c ? own.cur.x : own.prev.x, c ? own.cur.y : own.prev.y, c ? own.cur.z : own.prev.z, c ? own.cur.w : own.prev.w);
         } else t = *from;
     } else {
@@ -140,12 +159,12 @@ TH_D DepositVertex dep_fetch(const DepositParams &p, uint32_t i, uint32_t j, uin
         if (at == ~(size_t)0) { at = own_at; if (inside) *p.oob = 1u; }        // (a texel the tables should hold and do not: the pass is refused)
         const float4 *halo = nullptr;                            // (the neighbouring bands' edge rows: always f32, in texel order)
         if (!inside) {
-            if (row == -1 && p.halo_lo) halo = p.halo_lo + (offset > 0.25f ? 0 : W) + col;
-            else if (row == (int)p.rows && p.halo_hi) halo = p.halo_hi + (offset > 0.25f ? 0 : W) + col;
+            if (row == -1 && p.halo_lo) halo = p.halo_lo + (from_cur ? 0 : W) + col;
+            else if (row == (int)p.rows && p.halo_hi) halo = p.halo_hi + (from_cur ? 0 : W) + col;
             else *p.oob = 1u;
         }
         if (own.have && self) {
-            const bool c = offset > 0.25f;
+            const bool c = from_cur;
             t = make_float4(c ? own.cur.x : own.prev.x, c ? own.cur.y : own.prev.y, c ? own.cur.z : own.prev.z, c ? own.cur.w : own.prev.w);
         } else t = halo ? *halo : dep_state(p, tex, at);
     }
@@ -153,7 +172,7 @@ TH_D DepositVertex dep_fetch(const DepositParams &p, uint32_t i, uint32_t j, uin
     v.live = (t.x != kInert) || (t.y != kInert);
     v.px = t.x * p.view_x;
     v.py = t.y * p.view_y;
-    v.from_cur = offset > 0.25f; v.uvx = uvx; v.uvy = uvy;
+    v.from_cur = from_cur; v.uvx = uvx; v.uvy = uvy;
     if (colors) dep_vertex_colors(p, t, v);
     return v;
 }
@@ -262,14 +281,14 @@ template <typename Words>
 struct PolygonY { Words &w; TH_D int operator[](int k) const { return w.i(36 + k); } };
 
 // everything about line `id` (stream index = i*H + m) that does not depend on the texel, except the polygon
-template <bool PLAIN = false>
+template <bool PLAIN = false, bool PROGRAM = false>
 TH_D void dep_setup(const DepositParams &p, uint32_t i, uint32_t m, DepositLine &L, size_t own_at, const OwnTexels own = OwnTexels{}, bool colors = true)
 {
     L.draws = false;
     L.short32 = false;
     L.n = 0;
-    L.a = dep_fetch<PLAIN>(p, i, 2u * m, m - p.row0, own_at, own, colors);
-    L.b = dep_fetch<PLAIN>(p, i, 2u * m + 1u, m - p.row0, own_at, own, colors);
+    L.a = dep_fetch<PLAIN, PROGRAM>(p, i, 2u * m, m - p.row0, own_at, own, colors);
+    L.b = dep_fetch<PLAIN, PROGRAM>(p, i, 2u * m + 1u, m - p.row0, own_at, own, colors);
     if (!L.a.live || !L.b.live) return;                                  // see the header: inert vertex = no line
     const float fw = (float)p.fw, fh = (float)p.fh;
     const float dx = (0.5f * fw) * (L.b.px - L.a.px), dy = (0.5f * fh) * (L.b.py - L.a.py);

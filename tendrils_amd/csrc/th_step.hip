@@ -166,7 +166,7 @@ static bool same_key(const th::LogicParams &a, const th::LogicParams &b)
            memcmp(&ua, &ub, sizeof ua) == 0 && a.s2_cap == b.s2_cap && a.pos_bound == b.pos_bound;
 }
 
-static th_status timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1)
+th_status thi::timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1)
 {
     if (c->kt_used + 2 > c->kt_events.size()) {
         hipEvent_t a = nullptr, b = nullptr;

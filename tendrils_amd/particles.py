@@ -98,6 +98,14 @@ class ScreenProgram(Program):
     COMPILE, SOURCE_KIND = "th_screen_program_compile", "screen"
 
 
+class DrawProgram(Program):
+    """A draw program (include/tendrils_hip.h "draw programs"): from_source() takes HIP source defining
+    `__device__ th_vertex th_vertex_main(const th_vertex_pass &v)` - the vertex shader of one pass of draw() - and is otherwise
+    Program.from_source: compiled once, for gfx950, no GPU needed; TendrilsHipError with the compiler's output; pack(),
+    query() and dispose() as there.  Tendrils runs it as its flowShader / renderShader."""
+    COMPILE, SOURCE_KIND = "th_draw_program_compile", "draw"
+
+
 LOGIC = "logic"
 
 

@@ -3,7 +3,8 @@ particle-update path: state uniforms, timer, flow/targets textures, step(), spaw
 spawnShader(), resize(), and draw() = the flow pass + the view pass (the particles' lines with the
 render shader's colours into an RGBA8 image of the drawing buffer: `view`, read with read_view()).
 The demo's last pass - a shader of its own over the finished view (src/screen) - is screenShader() with a caller's
-ScreenProgram; the reference's own blur shader is outside this build.
+ScreenProgram; the reference's own blur shader is outside this build.  The constructor's flowShader / renderShader options
+take a caller's DrawProgram: the vertex stage of the flow pass / the view pass of draw().
 """
 import ctypes as C
 import math
@@ -12,7 +13,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import LOGIC, Particles, Program, ScreenProgram, run_pass
+from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, run_pass
 from .timer import Timer
 
 
@@ -222,6 +223,10 @@ class Tendrils:
         self.screen = ScreenImage(self)
         self.logicShader = None
         self._logic_option = params.get("logicShader")         # new Tendrils(gl, { logicShader }): the caller's integrator
+        # new Tendrils(gl, { flowShader, renderShader }) (src/index.js:70-71, 114-120): a caller's DrawProgram as the vertex stage
+        # of the flow pass / the view pass of draw(); None = the library's own stage.  Assignable, as there.
+        self.flowShader = params.get("flowShader")
+        self.renderShader = params.get("renderShader")
         self.uniforms = dict(render={}, update={})
         self.viewRes = [0, 0]
         self.viewSize = [0, 0]
@@ -474,6 +479,8 @@ class Tendrils:
         asks for).  Both passes draw the same lines: one call rasterises and sorts them once (th_draw) when they draw them
         with the same width."""
         self.line_widths()
+        if self.flowShader is not None or self.renderShader is not None:
+            return self._draw_programs()
         if self.dist is not None:          # row-band shard of a torch.distributed job: emit / exchange / merge, pass by pass
             from .sharding import draw_sharded
             if self.renderView:            # (every rank holds the whole view buffer: the clear / fade are the same everywhere)
@@ -515,6 +522,43 @@ class Tendrils:
         u, n = self.render_uniforms(), C.c_uint64(0)
         call("th_draw", self.particles._ctx, C.byref(d), C.byref(u), C.byref(n))
         self.fragments = self.view_fragments = int(n.value)
+        return self
+
+    def _draw_program(self, program, which, uniforms):
+        if not isinstance(program, DrawProgram) or not program.handle:
+            raise TypeError("draw: %r is no compiled DrawProgram" % (program,))
+        block, n = program.pack(uniforms), C.c_uint64(0)
+        call("th_draw_program_run", self.particles._ctx, program.handle, None if block is None else C.byref(block),
+             0 if block is None else C.sizeof(block), which, C.byref(n))
+        return int(n.value)
+
+    def _draw_programs(self):
+        """draw() with a caller's vertex stage in one pass or both (src/index.js:278-340): the flow pass, then - with
+        renderView - the clear, the fade and the view pass; each pass runs its program or, where there is none, the library's
+        own stage.  Both programs get what the reference hands both shaders (src/index.js:284-293): the state, time, viewSize,
+        viewRes, colorMapRes - and dataRes, geomRes (src/particles.js:149-155) - with self.uniforms["render"] on top, packed
+        into each program's uniform block by field name."""
+        p = self.particles
+        uniforms = dict(self.state, time=float(self.timer.time), viewSize=self.viewSize, viewRes=self.viewRes,
+                        dataRes=p.shape, geomRes=p.geomShape, colorMapRes=self.colorMap.shape)
+        uniforms.update(self.uniforms["render"])
+        if self.flowShader is not None:
+            self.fragments = self._draw_program(self.flowShader, _capi.TH_PASS_FLOW, uniforms)
+        else:
+            self.fragments = p.deposit_flow(self.viewSize, self.timer.time, self.state["speedLimit"])
+        if not self.renderView:
+            return self
+        self._bind_view(self.buffers[0] if self.buffers else None)
+        if self.state["autoClearView"]:
+            self.clearView()
+        if self.state["autoFade"]:
+            self.drawFade()
+        if self.renderShader is not None:
+            self.view_fragments = self._draw_program(self.renderShader, _capi.TH_PASS_VIEW, uniforms)
+        else:
+            u, n = self.render_uniforms(), C.c_uint64(0)
+            call("th_view_draw", p._ctx, C.byref(u), C.byref(n))
+            self.view_fragments = int(n.value)
         return self
 
     def export_lines(self, view=False):
