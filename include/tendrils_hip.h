@@ -351,10 +351,19 @@ th_status th_screen_run(th_context *ctx, th_program *program, const void *unifor
  *                      and th_draw_program_run refuse each other's programs (TH_ERR_INVALID, both kinds named, nothing launched).
  *  th_draw_program_run one pass of draw() with the program as its vertex stage: pass = TH_PASS_FLOW blends into the flow field
  *                      (as th_flow_deposit), TH_PASS_VIEW into the bound view image (as th_view_draw); *fragments (optional):
- *                      the fragments blended.  The pass runs the stream-ordered pipeline - the ring goes to texel order as for
- *                      a stream-ordered built-in pass, th_draw_query reports TH_DRAW_STREAM - from a context-owned vertex buffer
- *                      of 64 bytes per particle that grows and stays.  Nothing of the pass is reused by the next one, nor of
- *                      the one before by it.  The ring's content is untouched.
+ *                      the fragments blended.  The pass draws from a context-owned vertex buffer of 64 bytes per particle
+ *                      that grows and stays, through the pipeline the built-in pass of this context would take (th_draw_pipeline /
+ *                      TH_DRAW; th_draw_query reports which, and the pass's fragments):
+ *                        binned          wherever a built-in pass takes the bins AND every vertex of the texture's shape reads its
+ *                                        line's own texel AND the ring holds f32 texels.  The ring stays in whatever order it is
+ *                                        held in: a tile-sorted ring stays sorted, so a frame loop of th_step and program passes
+ *                                        keeps the order the integrator steps over (the passes of one frame take one pipeline, as
+ *                                        built-in passes do)
+ *                        stream-ordered  otherwise (shapes whose lookup lands beside the line's texel, packed rings, the policy
+ *                                        `stream`, lines wider than 2 under `auto`): the ring goes to texel order as for a
+ *                                        stream-ordered built-in pass
+ *                      The results are the same bits either way.  Nothing of the pass is reused by the next one, nor of the one
+ *                      before by it.  The ring's content is untouched.
  *                      On a row-band shard: TH_ERR_UNSUPPORTED, nothing launched.  TH_ERR_INVALID: another kind's program, more
  *                      than 1024 uniform bytes, null uniforms with a size, a null program, an unknown pass. */
 th_status th_draw_program_compile(const char *source, const char *name, th_program **out);

@@ -126,9 +126,15 @@ TH_D void bins_put(const DepositParams &p, const DepositLine &L, uint32_t id, ui
 }
 
 // slot s: its particle's texel (col, row) and whether draw() can make a line of it at all (th_api.hip: line_rows)
+// (PROGRAM, here and in the three kernels below that set a line up: a caller's vertex stage has run - th_drawprog.hip - and left
+// its vertices in p.vertices, texel-indexed.  Nothing of such a line is read from the ring, so the pass walks the records in
+// TEXEL order whatever order the ring is held in - s is the particle's id - and the word `perm` shares with `vertices` is never
+// read as a table; <false> is the library's own stage, the text it was)
+template <bool PROGRAM = false>
 TH_D bool slot_particle(const DepositParams &p, uint32_t s, uint32_t &col, uint32_t &row)
 {
-    const uint32_t pid = p.perm ? p.perm[s] : s;
+    uint32_t pid = s;
+    if constexpr (!PROGRAM) pid = p.perm ? p.perm[s] : s;
     if ((p.W & (p.W - 1u)) == 0u) { row = pid >> (31 - __builtin_clz(p.W)); col = pid & (p.W - 1u); }       // (uniform branch)
     else { row = pid / p.W; col = pid - row * p.W; }
     const uint32_t g = p.row0 + row;
@@ -244,9 +250,11 @@ struct LineStage {
 // PLAIN: f32 texels and every vertex of every line its own particle (the shapes of the frame loop this kernel was tuned on: the
 // own texels go through the kernel by value); otherwise - a packed ring, or a shape whose vertex lookup drifts off the line's own
 // texel (LineSources) - the vertices are fetched by dep_fetch, again when the varyings are made.
-template <uint32_t BS, bool DEAL, bool PLAIN>
+// PROGRAM (never PLAIN): the vertices are read from the records the caller's vertex stage left (dep_vertex_read), the ring is not.
+template <uint32_t BS, bool DEAL, bool PLAIN, bool PROGRAM = false>
 __global__ __launch_bounds__(BS, 6) void bins_fused_kernel(const DepositParams p)
 {
+    static_assert(!(PLAIN && PROGRAM), "a program pass reads records, not texels");
     static_assert(DEAL, "the last phase reads every line's record from the stage (every lane walking its own line's rows was measured and dropped: 0.65 against 0.58 ms)");
     constexpr uint32_t kTab = BS * 2u;          // table entries: <= 2 bins per line reserve here (a third bin goes to its cursor directly): never more bins than entries
     __shared__ Reservations<kTab> t;
@@ -267,12 +275,13 @@ __global__ __launch_bounds__(BS, 6) void bins_fused_kernel(const DepositParams p
     if (p.block_seen && p.block_seen[block] == 0u) return;
     const uint32_t s = block * BS + threadIdx.x;
     uint32_t col = 0, row = 0;
-    const bool can = s < slots && slot_particle(p, s, col, row);
+    const bool can = s < slots && slot_particle<PROGRAM>(p, s, col, row);
     for (uint32_t e = threadIdx.x; e < kTab; e += BS) { t.tag[e] = 0u; t.sum[e] = 0u; }
     __syncthreads();
 
     OwnTexels own;                                      // (both ends of the line, before anything else)
     if constexpr (PLAIN) { if (can) { own.have = true; own.cur = p.cur[s]; own.prev = p.prev[s]; } }
+    else if constexpr (PROGRAM) { }                     // (the records are the line: no texel of the ring is read)
     else if (can) { own.have = true; own.cur = dep_state(p, p.cur, s); own.prev = dep_state(p, p.prev, s); }
     DepositLine L;
     L.draws = false;
@@ -280,7 +289,7 @@ __global__ __launch_bounds__(BS, 6) void bins_fused_kernel(const DepositParams p
     bool slow = false;
     uint32_t dealt = 0;                                 // rows of this line handed to the wave's lanes
     if (can) {
-        dep_setup<PLAIN>(p, col, p.row0 + row, L, s, own, false);          // (the varyings: once the line is known to cover a texel)
+        dep_setup<PLAIN, PROGRAM>(p, col, p.row0 + row, L, s, own, false);          // (the varyings: once the line is known to cover a texel)
         if (L.draws) {
             float cx[6], cy[6];
             const int where = dep_hexagon(p, L, cx, cy);
@@ -394,8 +403,8 @@ __global__ __launch_bounds__(BS, 6) void bins_fused_kernel(const DepositParams p
             dep_vertex_colors(p, texel(L.a.from_cur), L.a);
             dep_vertex_colors(p, texel(L.b.from_cur), L.b);
         } else {            // (whichever particles the vertices are: fetched as the set-up fetched them, with their varyings this time)
-            L.a = dep_fetch(p, col, 2u * (p.row0 + row), row, s);
-            L.b = dep_fetch(p, col, 2u * (p.row0 + row) + 1u, row, s);
+            L.a = dep_fetch<false, PROGRAM>(p, col, 2u * (p.row0 + row), row, s);
+            L.b = dep_fetch<false, PROGRAM>(p, col, 2u * (p.row0 + row) + 1u, row, s);
         }
         // (one fragment at a time, the record read back from the line's own words of the stage: eight fragments' varyings side
         // by side were the kernel's register peak)
@@ -417,6 +426,7 @@ __global__ __launch_bounds__(BS, 6) void bins_fused_kernel(const DepositParams p
 // run-time indexed edges): one place at a time from the lists' cursors.  (Counting a line's fragments per bin first and
 // reserving them together - two rasterisations, one round trip - was slower with the polygon in scratch memory, 115 against
 // 92 us, and is no faster with it in LDS, 58 against 54: the pass is bound by the general rasteriser, not by its atomics.)
+template <bool PROGRAM>
 TH_D void bins_slow_lines(const DepositParams &p, uint32_t block, uint32_t blocks, float *polygons)
 {
     LdsWords<256> words{polygons + threadIdx.x};          // (the clipped polygon: indexed at run time - in LDS, not in scratch memory)
@@ -429,8 +439,8 @@ TH_D void bins_slow_lines(const DepositParams &p, uint32_t block, uint32_t block
         uint32_t id = 0;
         if (have) {
             uint32_t col, row;
-            slot_particle(p, s, col, row);
-            dep_setup(p, col, p.row0 + row, L, s);
+            slot_particle<PROGRAM>(p, s, col, row);
+            dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, s);
             id = col * p.H + p.row0 + row;
             if (L.draws) { float cx[6], cy[6]; dep_hexagon(p, L, cx, cy); spans = dep_hexagon_spans(p, cx, cy); }
         }
@@ -444,15 +454,16 @@ TH_D void bins_slow_lines(const DepositParams &p, uint32_t block, uint32_t block
 
 // ... and the lines of the long list: small hexagons inside the view like the rest, only with more fragments than a record
 // holds - the same register-resident rasteriser, every fragment straight to a place of its own
+template <bool PROGRAM>
 TH_D void bins_long_lines(const DepositParams &p, uint32_t block, uint32_t blocks)
 {
     dep_list_work(p, kListLong, [&](bool have, uint32_t s, uint32_t seg) {
         const uint32_t rep = seg & (kBinReplicas - 1u);
         if (have) {
             uint32_t col, row;
-            slot_particle(p, s, col, row);
+            slot_particle<PROGRAM>(p, s, col, row);
             DepositLine L;
-            dep_setup(p, col, p.row0 + row, L, s);
+            dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, s);
             const uint32_t id = col * p.H + p.row0 + row;
             float cx[6], cy[6];
             int PX[6], PY[6], ymin, ymax;
@@ -514,6 +525,7 @@ TH_D void bins_long_lines(const DepositParams &p, uint32_t block, uint32_t block
 // Here the wave's lanes take the polygon's ROWS (64 at a time: the span of each, the same edge arithmetic in the same vertex
 // order as dep_raster_poly), the spans' texels are dealt evenly to the lanes (a prefix sum over the rows, a search per lane),
 // and the places of the lanes that meet in one bin are reserved with ONE atomic on that bin's cursor.
+template <bool PROGRAM>
 TH_D void bins_span_lines(const DepositParams &p, uint32_t block, uint32_t blocks, float *scratch)
 {
     const uint32_t wave = threadIdx.x >> 6, lane = __lane_id();
@@ -536,9 +548,9 @@ TH_D void bins_span_lines(const DepositParams &p, uint32_t block, uint32_t block
         if (e >= n) break;
         const uint32_t s = list[e];
         uint32_t col, row;
-        slot_particle(p, s, col, row);
+        slot_particle<PROGRAM>(p, s, col, row);
         DepositLine L;
-        dep_setup(p, col, p.row0 + row, L, s);
+        dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, s);
         const uint32_t id = col * p.H + p.row0 + row;
         if (!L.draws) continue;                          // (wave-uniform: every lane set the same line up)
         float cx[6], cy[6];
@@ -633,19 +645,21 @@ TH_D void bins_span_lines(const DepositParams &p, uint32_t block, uint32_t block
 }
 
 // both lists in one launch, half of the grid each: two small grids that wait on their loads and atomics, side by side
+template <bool PROGRAM>
 __global__ __launch_bounds__(256) void bins_listed_kernel(const DepositParams p)
 {
     __shared__ float polygons[48 * 256];                  // (48 KB: three workgroups per CU - the grid is that large)
     const uint32_t half = gridDim.x >> 1;
-    if (blockIdx.x < half) bins_long_lines(p, blockIdx.x, half);
-    else bins_slow_lines(p, blockIdx.x - half, half, polygons);
+    if (blockIdx.x < half) bins_long_lines<PROGRAM>(p, blockIdx.x, half);
+    else bins_slow_lines<PROGRAM>(p, blockIdx.x - half, half, polygons);
 }
 // ... and behind it the spanning lines the slow list's pass found (none on an ordinary frame: the workgroups read a zero and
 // leave - a launch of ~3 us in the draw's chain, where classifying every line in the emit cost that kernel 3 %: 473 -> 487 us)
+template <bool PROGRAM>
 __global__ __launch_bounds__(256) void bins_span_kernel(const DepositParams p)
 {
     __shared__ float scratch[4 * 128];
-    bins_span_lines(p, blockIdx.x, gridDim.x, scratch);
+    bins_span_lines<PROGRAM>(p, blockIdx.x, gridDim.x, scratch);
 }
 
 // the places handed out in bin b (all its lists; saturated)
@@ -2008,7 +2022,7 @@ void launch_bins_block_list(const DepositParams &p, uint8_t *flags, uint32_t *li
     hipLaunchKernelGGL(bins_block_list_kernel, dim3(1), dim3(1024), 0, s, (const uint8_t *)flags, blocks, list, count);
 }
 
-void launch_bins_fused(const DepositParams &p, hipStream_t s)
+void launch_bins_fused(const DepositParams &p, hipStream_t s, bool program)
 {
     const uint32_t blocks = p.draw_nblocks;
     // the pass's totals, the two lists' counters and the bins' cursors start from zero: one launch (three memsets are three
@@ -2019,10 +2033,16 @@ void launch_bins_fused(const DepositParams &p, hipStream_t s)
     // the blocks; workgroups of 64 or 128 slots; register CAPS for 5, 6 or 8 waves per SIMD instead of 4 - spills; what got it to
     // six in round 5 was fewer registers needed, not fewer allowed: profiles/r5_h_emit_taken_apart.txt)
     // (DEAL: the rows of a wave's lines dealt evenly to its lanes; every lane walking its own line's rows was 0.65 against 0.58 ms)
-    if (!p.packed && !p.src.row_index) hipLaunchKernelGGL((bins_fused_kernel<256u, true, true>), dim3(blocks ? blocks : 1u), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((bins_fused_kernel<256u, true, false>), dim3(blocks ? blocks : 1u), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(bins_listed_kernel, dim3(2u * kDepLists * 6u), dim3(256), 0, s, p);
-    hipLaunchKernelGGL(bins_span_kernel, dim3(kDepLists * (p.src.row_index ? 32u : 4u)), dim3(256), 0, s, p);      // (drifting lookups: tens of thousands of them; the lines are taken from a queue)
+    if (program && p.vertices) {          // (a caller's vertex stage has left the vertices there: the word is not `perm`, the walk is in texel order)
+        hipLaunchKernelGGL((bins_fused_kernel<256u, true, false, true>), dim3(blocks ? blocks : 1u), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(bins_listed_kernel<true>, dim3(2u * kDepLists * 6u), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(bins_span_kernel<true>, dim3(kDepLists * 4u), dim3(256), 0, s, p);
+    } else {
+        if (!p.packed && !p.src.row_index) hipLaunchKernelGGL((bins_fused_kernel<256u, true, true>), dim3(blocks ? blocks : 1u), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((bins_fused_kernel<256u, true, false>), dim3(blocks ? blocks : 1u), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(bins_listed_kernel<false>, dim3(2u * kDepLists * 6u), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(bins_span_kernel<false>, dim3(kDepLists * (p.src.row_index ? 32u : 4u)), dim3(256), 0, s, p);      // (drifting lookups: tens of thousands of them; the lines are taken from a queue)
+    }
     hipLaunchKernelGGL(bins_plan_kernel, dim3((p.nbins + 255u) / 256u), dim3(256), 0, s, p);
     hipLaunchKernelGGL(crowd_plan_kernel, dim3(1), dim3(1024), 0, s, p);
 }

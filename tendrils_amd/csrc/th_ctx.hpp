@@ -95,13 +95,14 @@ struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel
+    hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;
     ProgramModule &operator=(const ProgramModule &) = delete;
-    ProgramModule(ProgramModule &&o) noexcept : prog(o.prog), module(o.module), fn(o.fn) { o.prog = nullptr; o.module = nullptr; o.fn = nullptr; }
+    ProgramModule(ProgramModule &&o) noexcept : prog(o.prog), module(o.module), fn(o.fn), fn_slots(o.fn_slots) { o.prog = nullptr; o.module = nullptr; o.fn = nullptr; o.fn_slots = nullptr; }
     ProgramModule &operator=(ProgramModule &&o) noexcept
     {
-        if (this != &o) { reset(); prog = o.prog; module = o.module; fn = o.fn; o.prog = nullptr; o.module = nullptr; o.fn = nullptr; }
+        if (this != &o) { reset(); prog = o.prog; module = o.module; fn = o.fn; fn_slots = o.fn_slots; o.prog = nullptr; o.module = nullptr; o.fn = nullptr; o.fn_slots = nullptr; }
         return *this;
     }
     ~ProgramModule() { reset(); }
@@ -189,6 +190,12 @@ struct th_context {
     DevBuf<uint8_t> draw_block_flags;
     int draw_blocks_order = -2;
     unsigned long long draw_blocks_stamp = 0;
+    // ... and the same list for TEXEL order, an entry of its own: a draw program's binned pass walks its vertex records in texel
+    // order whatever order the ring is held in, and a frame that mixes it with a built-in pass over sorted slots would otherwise
+    // rebuild a list (a read-back each) twice per frame.  A property of the texture's shape alone: listed once per context.
+    DevBuf<uint32_t> texel_blocks;
+    uint32_t texel_nblocks = 0;
+    bool texel_blocks_listed = false;
     uint32_t bin_max_pages = 0;          // (widened when a bin outgrows its lists: bins_table_widen)
     bool bins_dirty = false;             // an emitting pass filled the store and no blend has emptied it since (a sharded draw that ended
                                          // between the two): the next emitting pass wipes it first
@@ -390,13 +397,17 @@ th_status align_slot_orders(th_context *c);
 // ---- th_draw.hip -----------------------------------------------------------------------------------------------------
 int deposit_texel_bits(const th_context *c);
 float drawn_line_width(const th_context *c, int pass);
-th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr);
+// program: the pass of a caller's draw program (th_drawprog.hip) - its binned form walks the vertex records in texel order over
+// a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list)
+th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
 th_status deposit_count(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
 th_status deposit_temp(th_context *c, size_t need);
 // the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, sort by texel, blend
 th_status deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments);
+// ... and the binned one (program: p.vertices holds a draw program's records).  kRetryInStreamOrder: see below
+th_status deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program = false);
 th_status view_storage(th_context *c);
 void view_fields(th_context *c, const th_render_uniforms *u, th::DepositParams &p);
 th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr);
@@ -405,7 +416,7 @@ constexpr th_status kRetryInStreamOrder = -1;        // (internal) the binned pa
 th_status bins_store_for(th_context *c, th::DepositParams &p, uint32_t at_least);
 th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t pool);
 th_status bins_table_widen(th_context *c, th::DepositParams &p, bool keep);       // kRetryInStreamOrder: as wide as it goes (or no memory)
-th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early);
+th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program = false);
 void bins_pass_expect(th_context *c, th::DepositParams &p);          // before the plan's kernels are launched with p ...
 th_status bins_pass_totals(th_context *c, const th::DepositParams &p);  // ... their totals in c->bins_totals_host
 th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragments, bool blended_early);

@@ -47,8 +47,17 @@ static bool draw_uses_bins(th_context *c)
     return sorting_possible(c);
 }
 
-// per-line buffers + parameters.  want_bins: the caller can run the binned pipeline (*bins tells whether it will)
-static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool use_bins);
+// How a prepared pass walks the lines: the stream-ordered pipeline in texel order; the bins by SLOT, in the order the ring is
+// held in; or the bins in TEXEL order whatever that order is - the pass of a draw program, whose lines are the records its vertex
+// stage left (texel-indexed) and read nothing of the ring.
+enum class Walk { stream, slots, texels };
+// per-line buffers + parameters
+static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, Walk walk);
+
+// Draw programs and the auto policy: a program pass goes through the bins wherever the built-in pass of the same context would
+// (and the gate in deposit_prepare holds) - the frame loop then keeps its sorted slots (DESIGN.md 3.10 has the measurement the
+// default rests on).  false: only a forced policy (th_draw_pipeline / TH_DRAW = bins) sends a program pass there.
+constexpr bool kAutoBinsPrograms = true;
 
 // Does a sharded job draw through the bins?  Only what every rank sees alike may enter: the job's shapes, the lines' widths,
 // the switches (set alike on all ranks) - not this band's size, not how crowded its last draw was.
@@ -72,13 +81,14 @@ th_status deposit_prepare_bins(th_context *c, const th_deposit_uniforms *u, th::
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
     if (any_sorted(c)) if (th_status s = align_slot_orders(c)) return s;
     c->last_binned_draw = c->total_steps;
-    return prepare_pass(c, u, p, true);
+    return prepare_pass(c, u, p, Walk::slots);
 }
 
-th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins)
+th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins, bool program)
 {
     TH_REQUIRE(u, "null uniforms");
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
+    if (program && !kAutoBinsPrograms && (c->draw_pipeline != TH_DRAW_AUTO ? c->draw_pipeline : c->opt.draw) != 1) want_bins = false;
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -88,7 +98,9 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
         // another particle, through the table of where those particles lie in the slot order (line_rows, th::LineSources); the
         // few shapes with more such rows / columns than the table holds keep to the stream-ordered pipeline in texel order
         if (th_status s = line_rows(c)) return s;
-        if (c->lines_local != 1 && c->lines_local != 0) use_bins = false;
+        // (a draw program's vertex stage over a slot order reads the slot's own f32 texels: shapes whose lookup drifts off the
+        // line's texel, and packed rings - seen through an unpacked copy in texel order - keep to the stream-ordered path)
+        if (program ? (c->lines_local != 1 || c->packed) : (c->lines_local != 1 && c->lines_local != 0)) use_bins = false;
         else if (any_sorted(c)) { if (th_status s = align_slot_orders(c)) return s; }
     }
     if (bins) *bins = use_bins;
@@ -98,12 +110,13 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
         if (th_status s = ensure_identity(c)) return s;      // the vertex stream addresses particles in texel order
         c->hold_texel_order_until = c->total_steps + c->opt.rebucket_steps;   // a frame loop of step + draw stays in texel order
     }
-    return prepare_pass(c, u, p, use_bins);
+    return prepare_pass(c, u, p, !use_bins ? Walk::stream : (program ? Walk::texels : Walk::slots));
 }
 
 // per-line buffers + parameters of a pass whose pipeline is decided
-static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool use_bins)
+static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, Walk walk)
 {
+    const bool use_bins = walk != Walk::stream, by_texel = walk == Walk::texels;
     const size_t lines = c->texels();
     TH_REQUIRE((size_t)c->fw * c->fh > 0 && (uint64_t)c->cfg.width * c->cfg.global_height < (1ull << 32), "bad shapes");
     if (c->dep_lines != lines) {
@@ -147,7 +160,9 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
         p.src.row_index = c->src_row_index; p.src.col_index = c->src_col_index; p.src.nrows = c->src_nrows; p.src.ncols = c->src_ncols;
     }
     if (use_bins) {
-        const int o = order_of(c, c->ring[0]);
+        // (by_texel: the walk is over texel indices - no perm, and nothing that describes the ring's slots below: what the step
+        // saw of its lines is where the BUILT-IN stage puts them, not where a program does)
+        const int o = by_texel ? -1 : order_of(c, c->ring[0]);
         p.perm = o >= 0 ? c->orders[(size_t)o].perm : nullptr;
         p.bins_x = ((uint32_t)c->fw + (1u << th::kBinShift) - 1u) >> th::kBinShift;
         p.nbins = p.bins_x * (((uint32_t)c->fh + (1u << th::kBinShift) - 1u) >> th::kBinShift);
@@ -172,14 +187,27 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
         const unsigned long long stamp = o >= 0 ? c->orders[(size_t)o].stamp : 0ull;
         // what the step that wrote these two buffers saw of their lines (th_step.hip): only for exactly this pair, order and view
         // (... and only where a line's two ends ARE the slot's own particle, now and a step ago: lines_local)
-        if (c->opt.skip_unseen && c->lines_local == 1 && c->seen.bytes && c->seen.cur == c->ring[0] && c->seen.prev == c->ring[1] && p.cur == c->ring[0] && p.prev == c->ring[1] &&
+        if (!by_texel && c->opt.skip_unseen && c->lines_local == 1 && c->seen.bytes && c->seen.cur == c->ring[0] && c->seen.prev == c->ring[1] && p.cur == c->ring[0] && p.prev == c->ring[1] &&
             c->seen.order == o && c->seen.stamp == stamp && c->seen.view_x == p.view_x && c->seen.view_y == p.view_y && c->seen.fw == c->fw && c->seen.fh == c->fh &&
             drawn_line_width(c, TH_PASS_FLOW) <= 2.0f && drawn_line_width(c, TH_PASS_VIEW) <= 2.0f)
             p.block_seen = reinterpret_cast<const uint32_t *>(c->seen.bytes.get());
+        if (by_texel) {
+            if (!c->texel_blocks_listed) {
+                const size_t blocks = (c->texels() + 255) / 256;
+                if (!c->draw_block_flags) if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
+                if (!c->texel_blocks) if (th_status s = c->texel_blocks.alloc(blocks + 1)) return s;
+                th::launch_bins_block_list(p, c->draw_block_flags, c->texel_blocks + 1, c->texel_blocks, nullptr, c->stream);
+                TH_HIP(hipGetLastError());
+                if (th_status s = read_back(c, &c->texel_nblocks, c->texel_blocks, sizeof(uint32_t))) return s;
+                c->texel_blocks_listed = true;
+            }
+            p.draw_blocks = c->texel_blocks + 1; p.draw_nblocks = c->texel_nblocks;
+            return TH_OK;
+        }
         if (!c->draw_blocks || c->draw_blocks_order != o || c->draw_blocks_stamp != stamp) {
             const size_t blocks = (c->texels() + 255) / 256;
             if (!c->draw_blocks) {
-                if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
+                if (!c->draw_block_flags) if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
                 if (c->lines_local == 0)
                     if (th_status s = c->src_slots.alloc((size_t)c->src_nrows * c->cfg.width + (size_t)c->src_ncols * c->cfg.height + 1)) return s;
                 if (th_status s = c->draw_blocks.alloc(blocks + 1)) return s;          // (last: the three are there when this one is)
@@ -482,7 +510,7 @@ th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t poo
 // Part 1: rasterise + emit into the bins, the plan; repeated with a larger pool when the pool ran dry (nothing has been
 // blended).  blend_early: the ordinary bins' blend goes out right behind the pass and covers the totals' read-back.
 // Leaves the totals in c->bins_totals_host.  kRetryInStreamOrder: a bin outgrew its lists (or the store cannot be had).
-th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early)
+th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program)
 {
     c->drawn.valid = false;
     if (th_status s = bins_streams(c)) return s;
@@ -498,7 +526,7 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early)
     for (int attempt = 0;; ++attempt) {
         if (th_status s = bins_store_for(c, p, 0)) return s;
         bins_expect(c, p);
-        th::launch_bins_fused(p, c->stream);
+        th::launch_bins_fused(p, c->stream, program);
         // the totals come back over the side stream while the ordinary bins are already being blended (the kernel looks at the
         // pass's flags itself): the host's round trip - it sizes the crowded bins' launches - costs the GPU nothing
         TH_HIP(hipEventRecord(c->forked, c->stream));
@@ -621,14 +649,14 @@ th_status bins_pass_totals(th_context *c, const th::DepositParams &p)
 
 }  // namespace thi
 
-static th_status deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments)
+th_status thi::deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program)
 {
     if (th_status s = bins_streams(c)) return s;
     // Which comes first behind the emitting pass: the ordinary bins' blend - it needs nothing from the host and covers the
     // read-back - or, on a crowded target, the crowded bins' kernels: their long runs (walked by one thread each, on the
     // side stream) are then the longest chain of the draw and must start as early as they can.  Decided by the last draw.
     const bool early = !(c->last_draw.pipeline == TH_DRAW_BINS && (double)c->last_draw.crowded_fragments > kEarlyBlendShare * (double)c->last_draw.fragments);
-    if (th_status s = bins_pass_emit(c, p, early)) return s;
+    if (th_status s = bins_pass_emit(c, p, early, program)) return s;
     return bins_pass_finish(c, p, fragments, early);
 }
 

@@ -19,7 +19,8 @@ struct th_draw_args {
     double inv_x, inv_y;         // 1/(max(W,2)-1), 1/(max(2H,2)-1): Particles.generateLUT
     unsigned W, H, count;        // the particle texture; count = 2 W H stream vertices
     int fw, fh, cw, ch;
-    unsigned reserved[3];
+    unsigned reserved0;
+    const unsigned *perm;        // th_draw_vertex_slots_kernel alone: cur / prev are held in a slot order, perm[slot] = particle id
 };
 static_assert(sizeof(th_draw_args) == 96, "th_draw_args: layout shared with th_drawprog.hip");
 struct __attribute__((aligned(16))) th_program_uniform_block { unsigned char bytes[1024]; };
@@ -108,6 +109,45 @@ extern "C" __global__ __launch_bounds__(256) void th_draw_vertex_kernel(const th
         const th_vertex o = th_vertex_main(v);
         records[2u * (size_t)idx] = make_float4(o.position.x, o.position.y, __uint_as_float(o.live ? 1u : 0u), 0.0f);
         records[2u * (size_t)idx + 1u] = o.color;
+    }
+}
+
+// The same stage over a ring held in a SLOT order (the tile-sorted order the integrator steps over): one lane per slot s,
+// a.perm[s] its particle - texel (column, row) - and a.cur[s] / a.prev[s] that particle's texels: coalesced 16-byte loads whatever
+// the order.  Both stream vertices of the particle's line go through th_vertex_main and their records are written where the
+// other kernel writes them - 64 adjacent bytes per lane at the line's texel index, scattered between lanes - so that whatever
+// reads the buffer finds it the same.  th_stream_lookup still chooses texel and buffer; only for shapes whose lookup lands on
+// the line's own texel is this kernel launched (th_draw.hip: deposit_prepare), and the texel is then the slot's.
+// th_vertex_pass is field for field what the kernel above hands the program.
+extern "C" __global__ __launch_bounds__(256) void th_draw_vertex_slots_kernel(const th_draw_args a, const th_program_uniform_block u)
+{
+    th_vertex_pass v;
+    v.dataRes = make_float2((float)a.W, (float)a.H);
+    v.geomRes = make_float2((float)a.W, (float)(2u * a.H));
+    v.uniforms = u.bytes;
+    v.args = &a;
+    float4 *records = static_cast<float4 *>(a.vertices);
+    const unsigned slots = a.count >> 1;
+    for (unsigned s = blockIdx.x * 256u + threadIdx.x; s < slots; s += gridDim.x * 256u) {
+        const unsigned t = a.perm[s], row = t / a.W, col = t - row * a.W;
+        const th_float4_load own_cur = *reinterpret_cast<const th_float4_load *>(a.cur + s);
+        const th_float4_load own_prev = *reinterpret_cast<const th_float4_load *>(a.prev + s);
+        v.column = col;
+        v.line = col * a.H + row;
+#pragma unroll
+        for (unsigned e = 0; e < 2u; ++e) {
+            const unsigned j = 2u * row + e;
+            const th_stream_at<float4> at = th_stream_lookup(col, j, a.inv_x, a.inv_y, (int)a.W, (int)a.H, 0u, a.cur, a.prev);
+            v.uv = make_float2(at.uvx, at.uvy);
+            v.from_current = at.from_cur;
+            const th_float4_load t4 = at.from_cur ? own_cur : own_prev;
+            v.state = make_float4(t4.x, t4.y, t4.z, t4.w);
+            v.vertex = j;
+            const th_vertex o = th_vertex_main(v);
+            const size_t idx = 2u * (size_t)t + e;
+            records[2u * idx] = make_float4(o.position.x, o.position.y, __uint_as_float(o.live ? 1u : 0u), 0.0f);
+            records[2u * idx + 1u] = o.color;
+        }
     }
 }
 )TH_PRELUDE"

@@ -3,9 +3,12 @@
 // pair particles.draw(..., gl.LINES) runs in the two passes of draw(); the vertex stage itself is a template over an `apply`
 // function there (src/flow/vert/main.vert).  Here the caller's vertex shader is HIP source for one device function,
 // th_vertex_main (th_draw_prelude.inc), compiled for gfx950 at run time like the other two kinds (th_program.hip:
-// program_compile).  It runs once per vertex of the stream into a context-owned vertex buffer; the stream-ordered pipeline
-// (th_deposit.hip) then draws the lines from that buffer instead of from the library's own vertex stage - everything behind
-// the vertex stage is the same code (th_raster.hpp: dep_vertex_read).
+// program_compile).  It runs once per vertex of the stream into a context-owned vertex buffer; the pipeline the built-in pass of
+// the same context would take - binned (th_bins.hip) or stream-ordered (th_deposit.hip) - then draws the lines from that buffer
+// instead of from the library's own vertex stage: everything behind the vertex stage is the same code (th_raster.hpp:
+// dep_vertex_read).  The buffer is texel-indexed and the raster stage of such a pass reads nothing else, so the binned pass
+// walks it in texel order and a tile-sorted ring stays as it is: only the vertex kernel follows the slots
+// (th_draw_vertex_slots_kernel).
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -36,13 +39,14 @@ struct DrawArgs {
     double inv_x, inv_y;
     uint32_t W, H, count;
     int32_t fw, fh, cw, ch;
-    uint32_t reserved[3];
+    uint32_t reserved0;
+    const uint32_t *perm;        // th_draw_vertex_slots_kernel: slot -> particle id of the order cur / prev are held in
 };
 struct KernArgs {
     DrawArgs a;
     alignas(16) unsigned char u[kUniformBytes];
 };
-static_assert(sizeof(DrawArgs) == 96 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
+static_assert(sizeof(DrawArgs) == 96 && offsetof(DrawArgs, perm) == 88 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
               "launch record: layout shared with th_draw_prelude.inc");
 
 }  // namespace
@@ -54,9 +58,15 @@ th_status th_draw_program_compile(const char *source, const char *name, th_progr
     return program_compile(kDrawProgram, std::string(kTaps) + "\n" + kStream + "\n" + kPrelude, source, name, out);
 }
 
-// One pass of draw() with the program as its vertex stage: the ring goes to texel order as for a stream-ordered built-in pass,
-// the vertex kernel fills the vertex buffer, the stream-ordered pipeline draws from it.  The counts and the sorted order a
-// built-in pass left (c->drawn) are not this pass's, nor this pass's a built-in's: invalid before and after.
+// One pass of draw() with the program as its vertex stage, through the pipeline the built-in pass of this context would take
+// (deposit_prepare: the policy, the frame's one-pipeline rule, the gate), as th_flow_deposit / th_view_draw go about it.
+//   binned: the ring stays in the order it is held in.  The vertex kernel fills the texel-indexed vertex buffer - over a sorted
+//           ring one lane per SLOT, the state read where it lies (th_draw_vertex_slots_kernel) - and the bins walk the records
+//           in texel order.  A pass that gives up before blending is repeated in stream order, from its start.
+//   stream: the ring goes to texel order as for a stream-ordered built-in pass (held for a while), the vertex kernel runs one
+//           lane per vertex, the stream-ordered pipeline draws from the buffer.
+// The counts and the sorted order a built-in pass left (c->drawn) are not this pass's, nor this pass's a built-in's: invalid
+// before and after.
 th_status th_draw_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t pass, uint64_t *fragments)
 {
     if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;      // (the view pass writes no state and no flow: th_view_draw)
@@ -72,40 +82,53 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (pass == TH_PASS_VIEW) if (th_status s = view_storage(c)) return s;
-    // the pass as a stream-ordered built-in pass prepares it (texel order, held for a while; the per-line buffers); what the
-    // built-in vertex stage takes from its uniforms - viewSize, time, speedLimit - is the program's own business here
-    th::DepositParams p;
-    const th_deposit_uniforms none{};
-    if (th_status s = deposit_prepare(c, &none, p)) return s;
-    if (pass == TH_PASS_VIEW) { p.mode = 1; p.view = c->view; }
-    p.line_half = 0.5f * drawn_line_width(c, pass);
-    if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
-    p.vertices = c->draw_vertices;
-    float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
-    if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
-    if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
-    KernArgs k{};
-    DrawArgs &a = k.a;
-    a.cur = cur; a.prev = prev; a.vertices = c->draw_vertices.get();
-    a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
-    a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
-    a.inv_x = p.inv_x; a.inv_y = p.inv_y;
-    a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
-    if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
-    if (a.count) {
-        // the record and the uniform block travel in the kernel's argument segment (th_program_run).  A memory-bound pass: at
-        // most 256 CUs x 8 workgroups, the rest of the vertices by the grid's stride
-        size_t bytes = sizeof k;
-        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-        const uint32_t blocks = (a.count + 255u) / 256u, cap = 256u * 8u;
-        hipEvent_t k0 = nullptr, k1 = nullptr;          // (th_kernel_timing: the vertex kernel alone)
-        if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
-        TH_HIP(hipModuleLaunchKernel(m->fn, blocks < cap ? blocks : cap, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
-        if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+    for (int attempt = 0;; ++attempt) {          // (a binned pass that gives up before blending is repeated in stream order)
+        // what the built-in vertex stage takes from its uniforms - viewSize, time, speedLimit - is the program's own business here
+        th::DepositParams p;
+        const th_deposit_uniforms none{};
+        bool bins = false;
+        if (th_status s = deposit_prepare(c, &none, p, attempt == 0, &bins, true)) return s;
+        if (pass == TH_PASS_VIEW) { p.mode = 1; p.view = c->view; }
+        p.line_half = 0.5f * drawn_line_width(c, pass);
+        if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
+        p.vertices = c->draw_vertices;
+        KernArgs k{};
+        DrawArgs &a = k.a;
+        hipFunction_t fn = m->fn;
+        uint32_t lanes = (uint32_t)(2 * lines);         // (one per stream vertex)
+        const int order = bins ? order_of(c, c->ring[0]) : -1;
+        if (order >= 0) {
+            // over sorted slots (f32 texels, both buffers in ONE order: the gate, align_slot_orders): one lane per slot
+            a.cur = c->ring[0]; a.prev = c->ring[1]; a.perm = c->orders[(size_t)order].perm;
+            fn = m->fn_slots; lanes = (uint32_t)lines;
+        } else {
+            float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
+            if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
+            if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
+            a.cur = cur; a.prev = prev;
+        }
+        a.vertices = c->draw_vertices.get();
+        a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
+        a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
+        a.inv_x = p.inv_x; a.inv_y = p.inv_y;
+        a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
+        if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
+        if (lanes) {
+            // the record and the uniform block travel in the kernel's argument segment (th_program_run).  A memory-bound pass: at
+            // most 256 CUs x 8 workgroups, the rest of the vertices (slots) by the grid's stride
+            size_t bytes = sizeof k;
+            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+            const uint32_t blocks = (lanes + 255u) / 256u, cap = 256u * 8u;
+            hipEvent_t k0 = nullptr, k1 = nullptr;          // (th_kernel_timing: the vertex kernel alone)
+            if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
+            TH_HIP(hipModuleLaunchKernel(fn, blocks < cap ? blocks : cap, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
+            if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+        }
+        const th_status s = bins ? deposit_run_bins(c, p, fragments, true) : deposit_run(c, p, fragments);
+        c->drawn.valid = false;
+        if (!bins || s != kRetryInStreamOrder) return s;
+        c->frame_bins = 0;                  // (the other passes of this frame as well)
     }
-    const th_status s = deposit_run(c, p, fragments);
-    c->drawn.valid = false;
-    return s;
 }
 
 }  // extern "C"

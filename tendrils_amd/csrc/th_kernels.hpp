@@ -195,7 +195,9 @@ struct DepositParams {
     // ... or, in a pass of the stream-ordered pipeline (where `perm` has no meaning and is null): a caller's draw program has run
     // as this pass's vertex stage (th_drawprog.hip) and left 32 bytes per stream vertex - { float px, py; uint32 live, pad;
     // float c[4] } at 2 * (local row * W + column) + (j & 1) - which are read instead of computed (th_raster.hpp:
-    // dep_vertex_read); nullptr: the library's own stage.  (One word for both: a field more, anywhere, moves the hidden
+    // dep_vertex_read); nullptr: the library's own stage.  A program pass through the BINS holds `vertices` here too: its
+    // emit walks the records in texel order and reads nothing of the ring, so it needs no `perm` (th_bins.hip: the PROGRAM
+    // instantiations, chosen by launch_bins_fused's flag - the word alone cannot tell).  (One word for both: a field more, anywhere, moves the hidden
     // arguments behind the block, and hipcc then schedules kernels of th_bins.hip and th_deposit.hip otherwise - as the note on `packed` below found.)
     union {
         const uint32_t *perm;
@@ -345,7 +347,9 @@ enum { kTotFragments = 0, kTotOob = 1, kTotFlags = 2, kTotLarge = 3, kTotGiant =
 enum { kBinsPoolExhausted = 1u, kBinsBoundBroken = 2u, kBinsBinFull = 4u, kBinsWaitBroken = 8u };      // (8: a page nobody published - page_of)
 void launch_bins_block_list(const DepositParams &p, uint8_t *flags, uint32_t *list, uint32_t *count, uint32_t *src_slots, hipStream_t stream);   // list: a word per block of 256 slots; src_slots: LineSources::slot to fill (or nullptr)
 void launch_bins_edge_rows(const DepositParams &p, float4 *rows, hipStream_t stream);   // a band's first and last row of cur and of prev, f32, in texel order: [first cur | first prev | last cur | last prev]
-void launch_bins_fused(const DepositParams &p, hipStream_t stream);                   // rasterise + emit every line's fragments into its bins; then the large-bin plan
+// rasterise + emit every line's fragments into its bins; then the large-bin plan.  program: p.vertices holds a caller's vertex stage's
+// records (th_drawprog.hip) - walked in texel order, the PROGRAM instantiations; otherwise the word is `perm`
+void launch_bins_fused(const DepositParams &p, hipStream_t stream, bool program = false);
 void launch_bins_owner_counts(const DepositParams &p, const OwnerParams &o, hipStream_t stream);
 void launch_bins_owner_extract(const DepositParams &p, const OwnerParams &o, hipStream_t stream);
 void launch_bins_owner_insert(const DepositParams &p, const OwnerParams &o, hipStream_t stream);

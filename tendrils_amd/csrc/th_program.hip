@@ -131,7 +131,7 @@ void ProgramModule::reset()
 {
     if (module) (void)hipModuleUnload(module);
     program_release(prog);
-    module = nullptr; fn = nullptr; prog = nullptr;
+    module = nullptr; fn = nullptr; fn_slots = nullptr; prog = nullptr;
 }
 
 const char *program_kind_name(ProgramKind kind)
@@ -157,6 +157,7 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     ProgramModule m;
     TH_HIP(hipModuleLoadData(&m.module, prog->code.data()));
     TH_HIP(hipModuleGetFunction(&m.fn, m.module, kKernelNames[prog->kind]));
+    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m.fn_slots, m.module, "th_draw_vertex_slots_kernel"));
     m.prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));

@@ -102,7 +102,8 @@ class DrawProgram(Program):
     """A draw program (include/tendrils_hip.h "draw programs"): from_source() takes HIP source defining
     `__device__ th_vertex th_vertex_main(const th_vertex_pass &v)` - the vertex shader of one pass of draw() - and is otherwise
     Program.from_source: compiled once, for gfx950, no GPU needed; TendrilsHipError with the compiler's output; pack(),
-    query() and dispose() as there.  Tendrils runs it as its flowShader / renderShader."""
+    query() and dispose() as there.  Tendrils runs it as its flowShader / renderShader, through the draw() pipeline the
+    library's own pass would take (Particles.draw_pipeline): the binned one leaves a tile-sorted ring in its slot order."""
     COMPILE, SOURCE_KIND = "th_draw_program_compile", "draw"
 
 

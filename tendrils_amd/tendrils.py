@@ -537,7 +537,9 @@ class Tendrils:
         renderView - the clear, the fade and the view pass; each pass runs its program or, where there is none, the library's
         own stage.  Both programs get what the reference hands both shaders (src/index.js:284-293): the state, time, viewSize,
         viewRes, colorMapRes - and dataRes, geomRes (src/particles.js:149-155) - with self.uniforms["render"] on top, packed
-        into each program's uniform block by field name."""
+        into each program's uniform block by field name.  A program pass takes the pipeline the library's own pass of this
+        context would (Particles.draw_pipeline / TH_DRAW: binned where the shape and the ring allow it, else stream-ordered -
+        include/tendrils_hip.h "draw programs"); through the bins a tile-sorted ring stays sorted, so step(); draw() keeps it."""
         p = self.particles
         uniforms = dict(self.state, time=float(self.timer.time), viewSize=self.viewSize, viewRes=self.viewRes,
                         dataRes=p.shape, geomRes=p.geomShape, colorMapRes=self.colorMap.shape)

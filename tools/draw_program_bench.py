@@ -15,6 +15,19 @@ Each pass figure is the GPU time per call between two events on the context's st
 The programs' registers / scratch / code size (th_program_query) go out with the figures.
 
 Usage: python tools/draw_program_bench.py [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out profiles/draw_program.txt]
+
+--bins: program passes through the binned pipeline (th_bins.hip: the PROGRAM instantiations; th_draw_vertex_slots_kernel) against
+the stream-ordered one, and - with --parent-lib, a libtendrils_hip.so built from the parent commit - against that build.  One fresh
+process per library and round (TH_LIB chooses the library), the libraries alternating; the median round is reported with the spread.
+Every process measures, on one context (4096^2 particles, the C3 state of benchlib, 1920 x 1080):
+  (a) pass_*     a flow / a view program pass with the policy forced to stream / bins, ring in texel order, reuse off
+  (b) loop_*     the frame loop tick(); step(); draw() over the shapes whose step runs over sorted slots - GPU ms per frame, step
+                 and draw apart - with both stages as programs under `auto` and under `bins`, and the library's own stages beside
+                 them (th_draw: both passes in one rasterisation; and th_flow_deposit + th_view_draw: two, as a program frame has)
+                 --frames frames per arm, one arm after the other at the same frames of the wake in every process
+  (c) vertex_*   the vertex kernel alone (th_kernel_timing) over sorted slots and in texel order, and the unpermute of one state
+                 buffer (ensure_identity: what a stream-ordered program pass costs a sorted ring, twice)
+Usage: python tools/draw_program_bench.py --bins [--parent-lib PATH] [--rounds 5] [--frames 20] [--out profiles/...]
 """
 import argparse
 import ctypes as C
@@ -28,6 +41,167 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))          # the restated stages are the tests' (one copy)
 
 
+def bins_child(args):
+    """one process, one library (TH_LIB): a JSON line of GPU ms per arm"""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("draw_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import DrawProgram
+    from tendrils_amd.tendrils import View
+    from test_draw_program_build import FLOW
+    from test_gpu_draw_program import VIEW, FlowUniforms, ViewUniforms
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    flow, view = DrawProgram.from_source(FLOW, FlowUniforms, "flow_stage"), DrawProgram.from_source(VIEW, ViewUniforms, "view_stage")
+    t = ta.Tendrils(View(w, h))
+    t.resize()
+    t.setup(n)
+    p, ctx = t.particles, t.particles._ctx
+    p.upload_texels(workload.synth_state(0))
+    t.timer.time = 1000.0
+    t.line_widths()
+    out, ms = {}, C.c_float(0)
+    info, order = _capi.DrawInfo(), _capi.SlotOrderInfo()
+
+    def timed(fn, reps=1):
+        call("th_timer_start", ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", ctx, C.byref(ms))
+        return ms.value / reps
+
+    def kernel_timed(fn, reps):
+        """(GPU ms per call, mean ms of the vertex kernel alone)"""
+        mean, launches = C.c_float(0), C.c_int32(0)
+        call("th_kernel_timing", ctx, 1)
+        per_call = timed(fn, reps)
+        call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+        call("th_kernel_timing", ctx, 0)
+        assert launches.value == reps, (launches.value, reps)
+        return per_call, mean.value
+
+    def uniforms():
+        return dict(t.state, time=float(t.timer.time), viewSize=t.viewSize, sinTerm=t.render_uniforms().sinTerm)
+
+    # (b) the frame loops.  One arm after the other, the library's own stages first: a stream-ordered pass holds the ring in texel
+    # order for rebucket_steps (256) frames afterwards, so an arm that takes that path comes after the arms that must not inherit
+    # it.  Every library runs the arms at the same frames of the same wake; the rounds alternate the libraries.
+    def both_passes():
+        t.particles.deposit_flow(t.viewSize, t.timer.time, t.state["speedLimit"])
+        u, count = t.render_uniforms(), C.c_uint64(0)
+        call("th_view_draw", ctx, C.byref(u), C.byref(count))
+
+    def loop(name, policy, fs, rs, draw=None):
+        q = dict(step=[], draw=[], sorted=[], pipeline=[])
+        p.draw_pipeline(policy)
+        t.flowShader, t.renderShader = fs, rs
+        for k in range(3 + args.frames):              # (three frames for the pipeline to settle after the arm before)
+            t.timer.tick()
+            t.uniforms["render"]["sinTerm"] = t.render_uniforms().sinTerm
+            step = timed(t.step)
+            ms_draw = timed(draw or t.draw)
+            if k >= 3:
+                call("th_draw_query", ctx, C.byref(info))
+                call("th_slot_order", ctx, C.byref(order))
+                q["step"].append(step); q["draw"].append(ms_draw)
+                q["sorted"].append(order.sorted_buffers); q["pipeline"].append(info.pipeline)
+        out[name + "_step"], out[name + "_draw"] = float(np.mean(q["step"])), float(np.mean(q["draw"]))
+        out[name] = out[name + "_step"] + out[name + "_draw"]
+        out["sorted_" + name] = float(np.mean(q["sorted"]))
+        out["pipeline_" + name] = float(np.mean(q["pipeline"]))
+
+    t.renderView = True
+    loop("loop_builtin_th_draw", "auto", None, None)
+    loop("loop_builtin_two_passes", "auto", None, None, both_passes)
+    loop("loop_programs_bins", "bins", flow, view)
+
+    # (c) the vertex kernel over sorted slots; the unpermute it spares
+    p.draw_pipeline("bins")
+    t.flowShader = t.renderShader = None
+    t.timer.tick(); t.step(); t.draw()
+    call("th_slot_order", ctx, C.byref(order))
+    out["sorted_before_vertex_slots"] = order.sorted_buffers
+    for name, prog, which in (("flow", flow, _capi.TH_PASS_FLOW), ("view", view, _capi.TH_PASS_VIEW)):
+        run = lambda: t._draw_program(prog, which, uniforms())
+        timed(run, args.warmup)
+        _, out["vertex_slots_%s" % name] = kernel_timed(run, args.reps)
+    call("th_slot_order", ctx, C.byref(order))
+    out["sorted_after_vertex_slots"] = order.sorted_buffers
+    unpermute, ptr = [], C.c_void_p()
+    for _ in range(args.reps):
+        t.timer.tick(); t.step(); t.draw()
+        call("th_slot_order", ctx, C.byref(order))
+        if order.sorted_buffers:
+            unpermute.append(timed(lambda: call("th_state_device_ptr", ctx, 0, C.byref(ptr))) / order.sorted_buffers)
+    out["unpermute_one_buffer"] = float(np.mean(unpermute)) if unpermute else None
+    loop("loop_programs_auto", "auto", flow, view)
+    t.flowShader = t.renderShader = None
+
+    # (a) single passes, ring in texel order (one tick + step first: the C3 state a step apart, as the loop draws it)
+    p.option("bucket", 0)
+    t.timer.tick()
+    t.step()
+    p.option("draw_reuse", 0)
+    for policy in ("stream", "bins"):
+        p.draw_pipeline(policy)
+        for name, prog, which in (("flow", flow, _capi.TH_PASS_FLOW), ("view", view, _capi.TH_PASS_VIEW)):
+            run = lambda: t._draw_program(prog, which, uniforms())
+            timed(run, args.warmup)
+            out["pass_%s_%s" % (name, policy)], kernel = kernel_timed(run, args.reps)
+            call("th_draw_query", ctx, C.byref(info))
+            out["pipeline_pass_%s_%s" % (name, policy)] = info.pipeline
+            if policy == "stream":
+                out["vertex_texels_%s" % name] = kernel
+
+    out["query"] = dict(flow=flow.query(p), view=view.query(p))
+    out["device"] = torch.cuda.get_device_name(0)
+    print("BINS_CHILD " + json.dumps(out))
+    t.dispose()
+    flow.dispose(), view.dispose()
+
+
+def bins_main(args):
+    """the driver: no GPU in this process; one child per library and round"""
+    import subprocess
+    libs = [("this", None)] + ([("parent", os.path.abspath(args.parent_lib))] if args.parent_lib else [])
+    rounds = {name: [] for name, _ in libs}
+    for r in range(args.rounds):
+        for name, lib in (libs if r % 2 == 0 else libs[::-1]):
+            env = dict(os.environ)
+            if lib:
+                env["TH_LIB"] = lib
+            cmd = [sys.executable, os.path.abspath(__file__), "--bins-child"] + [a for a in sys.argv[1:] if a != "--bins"]
+            done = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.child_timeout)
+            line = [ln for ln in done.stdout.splitlines() if ln.startswith("BINS_CHILD ")]
+            if done.returncode != 0 or not line:          # (a child that failed: nothing more is started on the GPU)
+                sys.exit("draw_program_bench: the %s child of round %d failed (%d)\n%s\n%s" % (name, r, done.returncode, done.stdout[-2000:], done.stderr[-4000:]))
+            rounds[name].append(json.loads(line[0][len("BINS_CHILD "):]))
+            print("round %d %s: %s" % (r, name, line[0][len("BINS_CHILD "):]), flush=True)
+    lines = ["draw programs through the bins: %d^2 particles into %d x %d; %d rounds (one process per library and round, alternating), GPU ms (events on the context's stream)"
+             % (args.root, args.width, args.height, args.rounds),
+             "device: %s" % rounds["this"][0]["device"],
+             "loops: %d frames per arm after 3, one arm after the other; passes and kernels: %d calls after %d" % (args.frames, args.reps, args.warmup),
+             "%-34s %-7s %10s %10s %10s" % ("figure", "library", "median", "min", "max")]
+    keys = [k for k in rounds["this"][0] if k not in ("query", "device")]
+    for k in keys:
+        for name, _ in libs:
+            v = [q[k] for q in rounds[name] if q.get(k) is not None]
+            if v:
+                lines.append("%-34s %-7s %10.4f %10.4f %10.4f" % (k, name, statistics.median(v), min(v), max(v)))
+    lines.append("th_program_query: %s" % json.dumps(rounds["this"][0]["query"]))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", type=int, default=4096)
@@ -37,7 +211,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bins", action="store_true")
+    ap.add_argument("--bins-child", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--child-timeout", type=int, default=240)
     args = ap.parse_args()
+    if args.bins_child:
+        return bins_child(args)
+    if args.bins:
+        return bins_main(args)
 
     import torch
     if not torch.cuda.is_available():
