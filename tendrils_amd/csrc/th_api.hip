@@ -160,6 +160,14 @@ th_status read_back(th_context *c, void *host, const void *dev, size_t bytes)
     return TH_OK;
 }
 
+// (pageable host memory: the runtime stages the copy)
+th_status image_copy(th_context *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+{
+    TH_HIP(hipMemcpyAsync(dst, src, bytes, kind, c->stream));
+    TH_HIP(hipStreamSynchronize(c->stream));
+    return TH_OK;
+}
+
 }  // namespace thi
 
 extern "C" {
@@ -364,18 +372,14 @@ th_status th_flow_upload(th_context *c, const float *rgba)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(rgba, "null pixels");
-    TH_HIP(hipMemcpyAsync(c->flow, rgba, (size_t)c->fw * c->fh * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_upload(c, c->flow, rgba, (size_t)c->fw * c->fh * sizeof(float4));
 }
 
 th_status th_flow_download(th_context *c, float *rgba)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(rgba, "null pixels");
-    TH_HIP(hipMemcpyAsync(rgba, c->flow, (size_t)c->fw * c->fh * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_download(c, rgba, c->flow, (size_t)c->fw * c->fh * sizeof(float4));
 }
 
 th_status th_flow_clear(th_context *c)
@@ -389,8 +393,7 @@ th_status th_targets_upload(th_context *c, const float *rgba)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(rgba, "null pixels");
-    TH_HIP(hipMemcpyAsync(c->targets, rgba, c->texels() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
+    if (th_status s = image_upload(c, c->targets, rgba, c->texels() * sizeof(float4))) return s;
     c->targets_checked = false;
     return TH_OK;
 }
@@ -399,9 +402,7 @@ th_status th_targets_download(th_context *c, float *rgba)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(rgba, "null pixels");
-    TH_HIP(hipMemcpyAsync(rgba, c->targets, c->texels() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_download(c, rgba, c->targets, c->texels() * sizeof(float4));
 }
 
 th_status th_targets_clear(th_context *c)
@@ -447,9 +448,7 @@ th_status th_frames_upload(th_context *c, const uint8_t *rgba8)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(rgba8 && c->frames[0], "no frame buffers (call th_frames_resize) or null pixels");
-    TH_HIP(hipMemcpyAsync(c->frames[0], rgba8, (size_t)c->frw * c->frh * sizeof(uchar4), hipMemcpyHostToDevice, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_upload(c, c->frames[0], rgba8, (size_t)c->frw * c->frh * sizeof(uchar4));
 }
 
 th_status th_frames_rotate(th_context *c)

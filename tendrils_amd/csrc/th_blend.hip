@@ -71,13 +71,15 @@ __global__ __launch_bounds__(256) void colormap_blend_kernel(const BlendParams p
     }
 }
 
+constexpr uint32_t kBlendViews = view_bit(TH_VIEW_TEXTURE) | view_bit(TH_VIEW_FRAMES) | view_bit(TH_VIEW_SPAWN_IMAGE);      // what a blend sums
+
 size_t texel_bytes(int32_t format) { return format == TH_TEX_RGBA32F ? sizeof(float4) : 4; }
 
-// a float texture: a side below 2^24 (its taps are computed in fp32, as the flow's and the spawn image's); an 8-bit one: at most
-// 65536 a side, what the fixed-point tap (nearest_texel_fx16) holds in 32 bits
+// a float texture: a side below 2^24 (its taps are computed in fp32, as the flow's and the spawn image's); an 8-bit one: what
+// its fixed-point tap holds (tap_size_ok)
 bool shape_ok(int32_t format, int32_t w, int32_t h)
 {
-    const int32_t side = format == TH_TEX_RGBA8 ? 65536 : (1 << 24) - 1;
+    const int32_t side = format == TH_TEX_RGBA8 ? kRgba8MaxSide : (1 << 24) - 1;
     return w > 0 && h > 0 && w <= side && h <= side && (uint64_t)w * h < (1ull << 28);
 }
 
@@ -95,6 +97,42 @@ th_status colormap_storage(th_context *c)
     return TH_OK;
 }
 
+th_status view_image(th_context *c, int32_t source, int32_t index, uint32_t accepted, const char *noun, int32_t ordinal, Image *out)
+{
+    // "unit 3: ..." / "target: ..." (put together only when something is wrong)
+    auto refuse = [&](const char *fmt, auto... args) {
+        const std::string who = ordinal < 0 ? std::string(noun) : std::string(noun) + " " + std::to_string(ordinal);
+        return fail(TH_ERR_INVALID, (who + ": " + fmt).c_str(), args...);
+    };
+    if (source < 0 || source >= 32 || !(accepted & view_bit(source))) return refuse("unknown source %d", source);
+    if (source == TH_VIEW_BUFFER || source == TH_VIEW_SCREEN) if (th_status s = view_storage(c)) return s;
+    if (source == TH_VIEW_TEXTURE) {
+        if (index < 0 || index >= TH_MAX_TEXTURES) return refuse("texture slot %d outside 0..%d", index, TH_MAX_TEXTURES - 1);
+        const th_context::Texture &t = c->textures[index];
+        if (!t.texels) return refuse("texture slot %d is empty (call th_texture_upload)", index);
+        *out = Image{t.texels.get(), t.w, t.h, t.format};
+    } else if (source == TH_VIEW_FRAMES) {
+        if (index != 0 && index != 1) return refuse("frame buffer %d (OpticalFlow has buffers 0 and 1)", index);
+        if (!c->frames[index]) return refuse("no frame buffers (call th_frames_resize)");
+        *out = Image{c->frames[index].get(), c->frw, c->frh, TH_TEX_RGBA8};
+    } else if (source == TH_VIEW_SPAWN_IMAGE) {
+        if (!c->image) return refuse("no spawn image (call th_spawn_image_upload)");
+        *out = Image{c->image.get(), c->iw, c->ih, TH_TEX_RGBA32F};
+    } else if (source == TH_VIEW_BUFFER) {
+        if (index < 0 || index >= (int32_t)c->view_ring.size()) return refuse("no view buffer %d (there are %zu)", index, c->view_ring.size());
+        *out = Image{c->view_ring[(size_t)index], c->view_w, c->view_h, TH_TEX_RGBA8};
+    } else if (source == TH_VIEW_SCREEN) {
+        *out = Image{c->view_screen.get(), c->view_w, c->view_h, TH_TEX_RGBA8};
+    } else if (source == TH_VIEW_COLORMAP) {
+        if (th_status s = colormap_storage(c)) return s;
+        *out = Image{c->colormap.get(), c->cmap_w, c->cmap_h, TH_TEX_RGBA32F};
+    } else {                                    // TH_VIEW_FLOW
+        if (!c->flow) return refuse("no flow field");
+        *out = Image{c->flow.get(), c->fw, c->fh, TH_TEX_RGBA32F};
+    }
+    return TH_OK;
+}
+
 }  // namespace thi
 
 extern "C" {
@@ -107,17 +145,13 @@ th_status th_texture_upload(th_context *c, int32_t slot, int32_t format, const v
     TH_REQUIRE(texels && shape_ok(format, w, h), "bad texture %dx%d (an RGBA8 texture: at most 65536 a side) or null texels", w, h);
     th_context::Texture &t = c->textures[slot];
     const size_t bytes = (size_t)w * h * texel_bytes(format);
-    if (w != t.w || h != t.h || format != t.format) {
-        TH_HIP(hipStreamSynchronize(c->stream));          // (a blend under way may still read the old texels)
-        t.w = t.h = 0; t.format = -1;
-        if (th_status s = t.texels.alloc(bytes)) return s;
-        t.w = w; t.h = h; t.format = format;
+    if (w != t.w || h != t.h || format != t.format) {      // (a blend under way may still read the old texels)
+        if (th_status s = image_reshape(c, t.texels, t.w, t.h, w, h, texel_bytes(format))) return s;
+        t.format = format;
     }
     // (pageable host memory: the copy is staged by the runtime; the caller may reuse `texels` when the call returns, as after
     // th_frames_upload)
-    TH_HIP(hipMemcpyAsync(t.texels, texels, bytes, hipMemcpyHostToDevice, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_upload(c, t.texels, texels, bytes);
 }
 
 th_status th_texture_download(th_context *c, int32_t slot, void *texels)
@@ -126,9 +160,7 @@ th_status th_texture_download(th_context *c, int32_t slot, void *texels)
     TH_REQUIRE(slot >= 0 && slot < TH_MAX_TEXTURES, "texture slot %d outside 0..%d", slot, TH_MAX_TEXTURES - 1);
     const th_context::Texture &t = c->textures[slot];
     TH_REQUIRE(texels && t.texels, "texture slot %d is empty (call th_texture_upload) or null texels", slot);
-    TH_HIP(hipMemcpyAsync(texels, t.texels, (size_t)t.w * t.h * texel_bytes(t.format), hipMemcpyDeviceToHost, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_download(c, texels, t.texels, (size_t)t.w * t.h * texel_bytes(t.format));
 }
 
 th_status th_colormap_resize(th_context *c, int32_t w, int32_t h)
@@ -136,10 +168,7 @@ th_status th_colormap_resize(th_context *c, int32_t w, int32_t h)
     if (th_status s = use(c, true)) return s;
     TH_REQUIRE(w > 0 && h > 0 && w < (1 << 24) && h < (1 << 24) && (uint64_t)w * h < (1ull << 28), "bad colour map %dx%d", w, h);
     if (c->colormap && w == c->cmap_w && h == c->cmap_h) return TH_OK;      // gl-fbo: same shape is a no-op
-    TH_HIP(hipStreamSynchronize(c->stream));
-    c->cmap_w = c->cmap_h = 0;
-    if (th_status s = c->colormap.alloc((size_t)w * h)) return s;
-    c->cmap_w = w; c->cmap_h = h;
+    if (th_status s = image_reshape(c, c->colormap, c->cmap_w, c->cmap_h, w, h)) return s;
     TH_HIP(hipMemsetAsync(c->colormap, 0, (size_t)w * h * sizeof(float4), c->stream));
     return TH_OK;
 }
@@ -156,9 +185,7 @@ th_status th_colormap_download(th_context *c, float *rgba)
     if (th_status s = use(c, true)) return s;
     TH_REQUIRE(rgba, "null pixels");
     if (th_status s = colormap_storage(c)) return s;
-    TH_HIP(hipMemcpyAsync(rgba, c->colormap, (size_t)c->cmap_w * c->cmap_h * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_download(c, rgba, c->colormap, (size_t)c->cmap_w * c->cmap_h * sizeof(float4));
 }
 
 // Writes the colour map (and reads it with clear = 0) and nothing else: the ring, its slot orders, the statistics a fused
@@ -169,32 +196,19 @@ th_status th_colormap_blend(th_context *c, const th_blend_view *views, int32_t n
     TH_REQUIRE(views && n >= 1 && n <= TH_MAX_BLEND_VIEWS, "a blend takes 1..%d views (got %d)", TH_MAX_BLEND_VIEWS, n);
     BlendParams p{};
     for (int32_t i = 0; i < n; ++i) {
-        BlendView &v = p.v[i];
-        const th_blend_view &in = views[i];
-        if (in.source == TH_VIEW_TEXTURE) {
-            TH_REQUIRE(in.index >= 0 && in.index < TH_MAX_TEXTURES, "view %d: texture slot %d outside 0..%d", i, in.index, TH_MAX_TEXTURES - 1);
-            const th_context::Texture &t = c->textures[in.index];
-            TH_REQUIRE(t.texels, "view %d: texture slot %d is empty (call th_texture_upload)", i, in.index);
-            v.texels = t.texels.get(); v.w = t.w; v.h = t.h; v.format = t.format;
-        } else if (in.source == TH_VIEW_FRAMES) {
-            TH_REQUIRE(in.index == 0 || in.index == 1, "view %d: frame buffer %d (OpticalFlow has buffers 0 and 1)", i, in.index);
-            TH_REQUIRE(c->frames[in.index], "view %d: no frame buffers (call th_frames_resize)", i);
-            TH_REQUIRE(c->frw <= 65536 && c->frh <= 65536, "view %d: %dx%d frames are beyond what a blend samples (65536 a side)", i, c->frw, c->frh);
-            v.texels = c->frames[in.index].get(); v.w = c->frw; v.h = c->frh; v.format = TH_TEX_RGBA8;
-        } else if (in.source == TH_VIEW_SPAWN_IMAGE) {
-            TH_REQUIRE(c->image, "view %d: no spawn image (call th_spawn_image_upload)", i);
-            v.texels = c->image.get(); v.w = c->iw; v.h = c->ih; v.format = TH_TEX_RGBA32F;
-        } else return fail(TH_ERR_INVALID, "view %d: unknown source %d", i, in.source);
-        v.alpha = in.alpha;
+        Image img;
+        if (th_status s = view_image(c, views[i].source, views[i].index, kBlendViews, "view", i, &img)) return s;
+        // (the frames alone: an RGBA8 texture beyond the rule is refused where it is uploaded - shape_ok)
+        TH_REQUIRE(views[i].source != TH_VIEW_FRAMES || tap_size_ok(img), "view %d: %dx%d frames are beyond what a blend samples (65536 a side)", i, img.w, img.h);
+        p.v[i] = BlendView{img.texels, img.w, img.h, img.format, views[i].alpha};
     }
     if (th_status s = colormap_storage(c)) return s;
     p.dst = c->colormap;
     p.w = (uint32_t)c->cmap_w; p.count = (uint32_t)((size_t)c->cmap_w * c->cmap_h);
     p.wf = (float)c->cmap_w; p.hf = (float)c->cmap_h;
     p.n = n; p.gl_blend = gl_blend != 0; p.keep = clear == 0;
-    // a memory-bound pass: at most 256 CUs x 8 workgroups, the rest of the texels by the grid's stride
-    const uint32_t blocks = (p.count + 255u) / 256u, cap = 256u * 8u;
-    hipLaunchKernelGGL(colormap_blend_kernel, dim3(blocks < cap ? blocks : cap), dim3(256), 0, c->stream, p);
+    // a memory-bound pass: the grid of the streaming passes, the rest of the texels by its stride
+    hipLaunchKernelGGL(colormap_blend_kernel, dim3(th::grid_for(p.count, 8)), dim3(256), 0, c->stream, p);
     TH_HIP(hipGetLastError());
     return TH_OK;
 }

@@ -4,14 +4,15 @@
 //   th_api.hip    context life cycle, textures, read-backs, timers, options
 //   th_order.hip  tile-sorted slot orders of the ring buffers, captured th_step_n graphs
 //   th_step.hip   Particles.step: th_step / th_step_n
-//   th_spawn.hip  the spawners
+//   th_spawn.hip  the spawners, and what a pass over the ring starts from: its buffers (RingPass), its spawnData (spawn_data)
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
 //   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
 //   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run), and what both kinds of
 //                  program share: the hiprtc binding, the compile, the log, the per-context modules
 //   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
 //   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
-//   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload)
+//   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
+//                 names as images (view_image)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -97,14 +99,8 @@ struct ProgramModule {
     hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
     ProgramModule() = default;
-    ProgramModule(const ProgramModule &) = delete;
+    ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
-    ProgramModule(ProgramModule &&o) noexcept : prog(o.prog), module(o.module), fn(o.fn), fn_slots(o.fn_slots) { o.prog = nullptr; o.module = nullptr; o.fn = nullptr; o.fn_slots = nullptr; }
-    ProgramModule &operator=(ProgramModule &&o) noexcept
-    {
-        if (this != &o) { reset(); prog = o.prog; module = o.module; fn = o.fn; fn_slots = o.fn_slots; o.prog = nullptr; o.module = nullptr; o.fn = nullptr; o.fn_slots = nullptr; }
-        return *this;
-    }
     ~ProgramModule() { reset(); }
     void reset();                        // th_program.hip
 };
@@ -315,7 +311,7 @@ struct th_context {
 
     thi::FlowLineScratch *flow_lines = nullptr;   // th_flow_lines: staging and scratch (grow-only)
 
-    std::vector<thi::ProgramModule> programs;     // th_program_run / th_screen_run / th_draw_program_run: the programs this context has loaded
+    std::vector<std::unique_ptr<thi::ProgramModule>> programs;     // th_program_run / th_screen_run / th_draw_program_run: the programs this context has loaded
     DevBuf<unsigned> prog_flag;                   // ... and the word a pass on a row band raises (th_particles outside the band)
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
@@ -342,6 +338,20 @@ th_status render_target(th_context *c, float4 *buf, int k, float4 **out);
 th_status commit_target(th_context *c, float4 *buf, float4 *rendered);
 constexpr size_t kPinnedBytes = 1024;
 th_status read_back(th_context *c, void *host, const void *dev, size_t bytes);
+// a whole device image from / to the caller's memory, and the wait for it: `host` is the caller's again when the call returns
+th_status image_copy(th_context *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind);
+inline th_status image_upload(th_context *c, void *dev, const void *host, size_t bytes) { return image_copy(c, dev, host, bytes, hipMemcpyHostToDevice); }
+inline th_status image_download(th_context *c, void *host, const void *dev, size_t bytes) { return image_copy(c, host, dev, bytes, hipMemcpyDeviceToHost); }
+// A device image takes another shape: what the stream still does with the old texels ends first, the stored shape is 0 x 0 while
+// there is no storage, then `per_texel` elements of `buf` a texel (uninitialised).  The shape's limits are the entry point's own.
+template <class T> th_status image_reshape(th_context *c, DevBuf<T> &buf, int32_t &w, int32_t &h, int32_t new_w, int32_t new_h, size_t per_texel = 1)
+{
+    TH_HIP(hipStreamSynchronize(c->stream));
+    w = h = 0;
+    if (th_status s = buf.alloc((size_t)new_w * new_h * per_texel)) return s;
+    w = new_w; h = new_h;
+    return TH_OK;
+}
 // the gathered whole-texture copy (th_state_gather / _ptr) is a copy of one ring buffer's CONTENT: writing that buffer ends
 // its validity, moving the content to another allocation (slot-order moves through `spare`) takes the association along
 inline void state_written(th_context *c, const float4 *buf)
@@ -357,6 +367,23 @@ inline void state_moved(th_context *c, const float4 *from, const float4 *to)
     if (c->seen.cur == from || c->seen.prev == from) c->seen.cur = c->seen.prev = nullptr;
 }
 
+// ---- th_spawn.hip ----------------------------------------------------------------------------------------------------
+// one of the ring's buffers as a pass samples it: f32 texels - `particles` itself when k is 1 (the view of ring[1] the pass
+// already holds), else the buffer's f32 view in staging slot 2
+th_status ring_view(th_context *c, int32_t k, float4 *particles, float4 **out);
+// A pass's spawnData by name: TH_SOURCE_FLOW, TH_SOURCE_IMAGE, ring buffer k in the ring order the pass sees (after the
+// rotation) - on a row band the gathered copy of the whole texture, if it is of that buffer - or, where the pass can do
+// without (none_ok), TH_SOURCE_NONE: no texels, 1 x 1
+th_status spawn_data(th_context *c, int32_t source, float4 *particles, bool none_ok, const float4 **data, int32_t *dw, int32_t *dh);
+// What a pass over the ring (in texel order: ensure_identity; at least 2 buffers: the caller's check) works on: the target `out` -
+// the ring rotated for TH_TARGET_RING -, where the pass writes it (`rt`: staging when packed) and the f32 view of `particles` =
+// ring[1], which the pass reads like every Particles.step (src/particles.js:139); commit() packs `rt` into `out`
+struct RingPass {
+    float4 *out = nullptr, *rt = nullptr, *particles = nullptr;
+    th_status begin(th_context *c, int32_t target);
+    th_status commit(th_context *c) { return commit_target(c, out, rt); }
+};
+
 // ---- th_step.hip -----------------------------------------------------------------------------------------------------
 th_status timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1);      // th_kernel_timing: the next pair of events to record around a launch
 
@@ -369,8 +396,27 @@ th_status program_compile(ProgramKind kind, const std::string &prelude, const ch
 th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes);
 // the context's module of `prog`, loaded on first use
 th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out);
+// the launch record of a program's kernel: the kind's Args (th_*_args in its prelude), then the uniform block
+template <class Args> struct ProgramKernArgs {
+    Args a;
+    alignas(16) unsigned char u[kUniformBytes];
+    void set_uniforms(const void *uniforms, uint32_t bytes) { if (bytes) memcpy(u, uniforms, bytes); }
+};
+// `fn` over `lanes` lanes (not 0) on the grid of the streaming passes (th::grid_for(lanes, 8)) with the filled record as its
+// argument segment: the runtime copies it when it enqueues the launch - no copy of the library's own, nothing to wait for
+th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *record, size_t bytes);
+template <class Args> th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, ProgramKernArgs<Args> &k) { return program_launch(c, fn, lanes, &k, sizeof k); }
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
+// an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format
+struct Image { const void *texels; int32_t w, h, format; };
+constexpr uint32_t view_bit(int32_t source) { return 1u << source; }
+// (source, index) of the sources in `accepted` (view_bit of each) as an image - the view images and the colour map get their
+// storage on the way (view_storage, colormap_storage); what is wrong is said of "<noun> <ordinal>" ("<noun>": ordinal < 0)
+th_status view_image(th_context *c, int32_t source, int32_t index, uint32_t accepted, const char *noun, int32_t ordinal, Image *out);
+// an RGBA8 image is tapped through a 16-bit fixed-point coordinate (nearest_texel_fx16), which holds 65536 texels a side in 32 bits
+constexpr int32_t kRgba8MaxSide = 65536;
+inline bool tap_size_ok(const Image &i) { return i.format != TH_TEX_RGBA8 || (i.w <= kRgba8MaxSide && i.h <= kRgba8MaxSide); }
 
 // ---- th_order.hip ----------------------------------------------------------------------------------------------------
 void destroy_graph(GraphEntry &g);

@@ -805,24 +805,15 @@ th_status th_view_download(th_context *c, uint8_t *rgba8)
     if (th_status s = use(c, true)) return s;
     TH_REQUIRE(rgba8, "null pixels");
     if (th_status s = view_storage(c)) return s;
-    TH_HIP(hipMemcpyAsync(rgba8, c->view, (size_t)c->view_w * c->view_h * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    return image_download(c, rgba8, c->view, (size_t)c->view_w * c->view_h * sizeof(uchar4));
 }
 
 th_status th_colormap_upload(th_context *c, const float *rgba, int32_t w, int32_t h)
 {
     if (th_status s = use(c, true)) return s;
     TH_REQUIRE(rgba && w > 0 && h > 0 && (uint64_t)w * h < (1ull << 28), "bad colour map %dx%d", w, h);
-    if (w != c->cmap_w || h != c->cmap_h) {
-        TH_HIP(hipStreamSynchronize(c->stream));
-        c->cmap_w = c->cmap_h = 0;
-        if (th_status s = c->colormap.alloc((size_t)w * h)) return s;
-        c->cmap_w = w; c->cmap_h = h;
-    }
-    TH_HIP(hipMemcpyAsync(c->colormap, rgba, (size_t)w * h * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    TH_HIP(hipStreamSynchronize(c->stream));
-    return TH_OK;
+    if (w != c->cmap_w || h != c->cmap_h) if (th_status s = image_reshape(c, c->colormap, c->cmap_w, c->cmap_h, w, h)) return s;
+    return image_upload(c, c->colormap, rgba, (size_t)w * h * sizeof(float4));
 }
 
 th_status th_export_view_lines(th_context *c, const th_render_uniforms *u, float *lines, uint64_t capacity, uint64_t *count)

@@ -42,10 +42,7 @@ struct DrawArgs {
     uint32_t reserved0;
     const uint32_t *perm;        // th_draw_vertex_slots_kernel: slot -> particle id of the order cur / prev are held in
 };
-struct KernArgs {
-    DrawArgs a;
-    alignas(16) unsigned char u[kUniformBytes];
-};
+using KernArgs = ProgramKernArgs<DrawArgs>;
 static_assert(sizeof(DrawArgs) == 96 && offsetof(DrawArgs, perm) == 88 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
               "launch record: layout shared with th_draw_prelude.inc");
 
@@ -112,16 +109,12 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
         a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
         a.inv_x = p.inv_x; a.inv_y = p.inv_y;
         a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
-        if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
+        k.set_uniforms(uniforms, uniform_bytes);
         if (lanes) {
-            // the record and the uniform block travel in the kernel's argument segment (th_program_run).  A memory-bound pass: at
-            // most 256 CUs x 8 workgroups, the rest of the vertices (slots) by the grid's stride
-            size_t bytes = sizeof k;
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-            const uint32_t blocks = (lanes + 255u) / 256u, cap = 256u * 8u;
+            // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
             hipEvent_t k0 = nullptr, k1 = nullptr;          // (th_kernel_timing: the vertex kernel alone)
             if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
-            TH_HIP(hipModuleLaunchKernel(fn, blocks < cap ? blocks : cap, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
+            if (th_status s = program_launch(c, fn, lanes, k)) return s;
             if (k1) TH_HIP(hipEventRecord(k1, c->stream));
         }
         const th_status s = bins ? deposit_run_bins(c, p, fragments, true) : deposit_run(c, p, fragments);

@@ -20,15 +20,6 @@
 namespace th {
 
 
-static int grid_for(size_t n, int blocks_per_cu)
-{
-    size_t blocks = (n + 255) / 256;
-    size_t cap = (size_t)256 * blocks_per_cu;
-    return (int)(blocks < cap ? (blocks ? blocks : 1) : cap);
-}
-
-
-
 __global__ __launch_bounds__(256) void pack_state_kernel(uint2 *dst, const float4 *src, uint32_t n)
 {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) dst[i] = pack_state(src[i]);

@@ -10,6 +10,15 @@
 
 namespace th {
 
+// the grid of a streaming pass over n elements, one a lane: workgroups of 256, at most blocks_per_cu on each of the 256 CUs -
+// the rest of the elements by the grid's stride
+inline int grid_for(size_t n, int blocks_per_cu)
+{
+    size_t blocks = (n + 255) / 256;
+    size_t cap = (size_t)256 * blocks_per_cu;
+    return (int)(blocks < cap ? (blocks ? blocks : 1) : cap);
+}
+
 constexpr uint32_t kMaxFusedSteps = 32;
 // fused launches over a window of the noise lattice (th_logic.hpp "over a window"; th_step.hip: hash_window)
 constexpr int kWinSpan = 286;                // widest range hi - lo of lattice coordinates that a window takes

@@ -37,10 +37,7 @@ struct ProgramArgs {
     int32_t dw, dh, fw, fh;
     uint32_t reserved[3];
 };
-struct KernArgs {
-    ProgramArgs a;
-    alignas(16) unsigned char u[kUniformBytes];
-};
+using KernArgs = ProgramKernArgs<ProgramArgs>;
 static_assert(sizeof(ProgramArgs) == 96 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
               "launch record: layout shared with th_program_prelude.inc");
 
@@ -151,17 +148,24 @@ th_status program_run_args(const th_program *prog, ProgramKind kind, const char 
 
 th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
 {
-    for (ProgramModule &m : c->programs) if (m.prog == prog) { *out = &m; return TH_OK; }
+    for (const std::unique_ptr<ProgramModule> &m : c->programs) if (m->prog == prog) { *out = m.get(); return TH_OK; }
     std::lock_guard<std::mutex> hold(prog->lock);
     TH_REQUIRE(!prog->destroyed, "program '%s' was destroyed before this context had loaded it", prog->name.c_str());
-    ProgramModule m;
-    TH_HIP(hipModuleLoadData(&m.module, prog->code.data()));
-    TH_HIP(hipModuleGetFunction(&m.fn, m.module, kKernelNames[prog->kind]));
-    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m.fn_slots, m.module, "th_draw_vertex_slots_kernel"));
-    m.prog = prog;
+    std::unique_ptr<ProgramModule> m(new ProgramModule);
+    TH_HIP(hipModuleLoadData(&m->module, prog->code.data()));
+    TH_HIP(hipModuleGetFunction(&m->fn, m->module, kKernelNames[prog->kind]));
+    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_draw_vertex_slots_kernel"));
+    m->prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));
-    *out = &c->programs.back();
+    *out = c->programs.back().get();
+    return TH_OK;
+}
+
+th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *record, size_t bytes)
+{
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, record, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+    TH_HIP(hipModuleLaunchKernel(fn, (unsigned)th::grid_for(lanes, 8), 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
     return TH_OK;
 }
 
@@ -241,52 +245,26 @@ th_status th_program_run(th_context *c, th_program *prog, const void *uniforms, 
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (th_status s = ensure_identity(c)) return s;      // a pass operates in texel order, like every spawn pass
-    // the pass reads `particles` = buffers[1] like every Particles.step (src/particles.js:139)
     TH_REQUIRE(c->ring.size() >= 2, "a pass needs at least 2 state buffers (have %zu)", c->ring.size());
     const bool band = c->cfg.height != c->cfg.global_height;
     if (!c->prog_flag) {
         if (th_status s = c->prog_flag.alloc(1)) return s;
         TH_HIP(hipMemsetAsync(c->prog_flag, 0, sizeof(unsigned), c->stream));
     }
-    float4 *out = nullptr;
-    if (th_status s = resolve_target(c, target, true, &out)) return s;
-    float4 *rt = nullptr, *particles = nullptr;
-    if (th_status s = render_target(c, out, 0, &rt)) return s;
-    if (th_status s = unpacked_view(c, c->ring[1], 1, &particles)) return s;
+    RingPass pass;
+    if (th_status s = pass.begin(c, target)) return s;
     KernArgs k{};
-    k.a.particles = particles;
-    k.a.out = rt;
-    // `source` names the spawnData texture in the ring order the pass sees (after the rotation)
-    if (source == TH_SOURCE_NONE) { k.a.data = nullptr; k.a.dw = k.a.dh = 1; }
-    else if (source == TH_SOURCE_FLOW) { k.a.data = c->flow; k.a.dw = c->fw; k.a.dh = c->fh; }
-    else if (source == TH_SOURCE_IMAGE) {
-        TH_REQUIRE(c->image, "no spawn image (call th_spawn_image_upload)");
-        k.a.data = c->image; k.a.dw = c->iw; k.a.dh = c->ih;
-    } else if (source >= 0 && source < (int32_t)c->ring.size()) {
-        float4 *data = nullptr;
-        if (band) {
-            // as th_spawn_sample on a row band: the WHOLE texture, from the copy the ranks gathered beforehand
-            TH_REQUIRE(c->gathered && c->gathered_of == (const void *)c->ring[(size_t)source],
-                       "sampling the particle texture on a row-band shard (%d of %d rows) reads every band: gather buffer %d first (th_state_gather / th_state_gather_ptr)",
-                       c->cfg.height, c->cfg.global_height, source);
-            data = c->gathered;
-        } else if (source == 1) data = particles;
-        else if (th_status s = unpacked_view(c, c->ring[source], 2, &data)) return s;
-        k.a.data = data; k.a.dw = c->cfg.width; k.a.dh = c->cfg.global_height;
-    } else return fail(TH_ERR_INVALID, "bad spawnData source %d", source);
+    k.a.particles = pass.particles;
+    k.a.out = pass.rt;
+    if (th_status s = spawn_data(c, source, pass.particles, true, &k.a.data, &k.a.dw, &k.a.dh)) return s;
     k.a.flow = c->flow; k.a.fw = c->fw; k.a.fh = c->fh;
     k.a.targets = c->targets;
     k.a.flag = c->prog_flag;
     k.a.count = (uint32_t)c->texels(); k.a.width = (uint32_t)c->cfg.width; k.a.rows = (uint32_t)c->cfg.height;
     k.a.row0 = (uint32_t)c->cfg.row0; k.a.global_height = (uint32_t)c->cfg.global_height;
-    if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
-    // The uniform block travels in the kernel's argument segment, which the runtime copies when it enqueues the launch: no
-    // copy of its own, nothing to wait for.  Grid as the other streaming passes (th_kernels.hip: grid_for(count, 8)).
-    size_t bytes = sizeof k;
-    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    const size_t blocks = (c->texels() + 255) / 256, cap = 256 * 8;
-    TH_HIP(hipModuleLaunchKernel(m->fn, (unsigned)std::min(blocks, cap), 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
-    if (th_status s = commit_target(c, out, rt)) return s;
+    k.set_uniforms(uniforms, uniform_bytes);
+    if (th_status s = program_launch(c, m->fn, c->texels(), k)) return s;
+    if (th_status s = pass.commit(c)) return s;
     if (band) {
         // only a row band can be asked for rows it does not hold: checked like the sharded spawn's out-of-band flag
         unsigned flag = 0;

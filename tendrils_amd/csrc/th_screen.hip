@@ -34,13 +34,11 @@ struct ScreenArgs {
     uint32_t reserved[4];
     ScreenUnit unit[TH_MAX_BLEND_VIEWS];
 };
-struct KernArgs {
-    ScreenArgs a;
-    alignas(16) unsigned char u[kUniformBytes];
-};
+using KernArgs = ProgramKernArgs<ScreenArgs>;
 static_assert(sizeof(ScreenUnit) == 24 && sizeof(ScreenArgs) == 240 && offsetof(KernArgs, u) == 240 && sizeof(KernArgs) == 240 + kUniformBytes,
               "launch record: layout shared with th_screen_prelude.inc");
 
+constexpr uint32_t kScreenViews = view_bit(TH_VIEW_FLOW + 1) - 1u;      // a unit is any of the sources, TH_VIEW_TEXTURE .. TH_VIEW_FLOW
 const char *const kSourceNames[] = {"TH_VIEW_TEXTURE", "TH_VIEW_FRAMES", "TH_VIEW_SPAWN_IMAGE", "TH_VIEW_BUFFER", "TH_VIEW_SCREEN", "TH_VIEW_COLORMAP", "TH_VIEW_FLOW"};
 
 }  // namespace
@@ -65,7 +63,7 @@ th_status th_screen_run(th_context *c, th_program *prog, const void *uniforms, u
     for (int32_t i = 0; i < n_units; ++i) views = views || units[i].source == TH_VIEW_BUFFER || units[i].source == TH_VIEW_SCREEN;
     if (target == TH_SCREEN_TARGET_VIEW && band)
         return fail(TH_ERR_UNSUPPORTED, "screen pass into the view on a row-band shard (%d of %d rows): a band's view image holds only what it owns", c->cfg.height, c->cfg.global_height);
-    if (views) if (th_status s = view_storage(c)) return s;
+    if (views) if (th_status s = view_storage(c)) return s;      // (here for the order of the refusals, and before a.dst is taken: view_image's own call then finds the storage there)
     KernArgs k{};
     ScreenArgs &a = k.a;
     if (target == TH_SCREEN_TARGET_VIEW) {
@@ -74,57 +72,28 @@ th_status th_screen_run(th_context *c, th_program *prog, const void *uniforms, u
         if (th_status s = colormap_storage(c)) return s;
         a.dst = c->colormap.get(); a.w = (uint32_t)c->cmap_w; a.h = (uint32_t)c->cmap_h; a.format = TH_TEX_RGBA32F;
     } else if (target == TH_SCREEN_TARGET_TEXTURE) {
-        TH_REQUIRE(target_index >= 0 && target_index < TH_MAX_TEXTURES, "target: texture slot %d outside 0..%d", target_index, TH_MAX_TEXTURES - 1);
-        const th_context::Texture &t = c->textures[target_index];
-        TH_REQUIRE(t.texels, "target: texture slot %d is empty (call th_texture_upload)", target_index);
+        Image t;
+        if (th_status s = view_image(c, TH_VIEW_TEXTURE, target_index, view_bit(TH_VIEW_TEXTURE), "target", -1, &t)) return s;
         TH_REQUIRE(t.format == TH_TEX_RGBA32F || t.format == TH_TEX_RGBA8, "target: texture slot %d holds a one-channel texture (a pass renders into RGBA32F or RGBA8)", target_index);
-        a.dst = t.texels.get(); a.w = (uint32_t)t.w; a.h = (uint32_t)t.h; a.format = t.format;
+        a.dst = const_cast<void *>(t.texels); a.w = (uint32_t)t.w; a.h = (uint32_t)t.h; a.format = t.format;
     } else return fail(TH_ERR_INVALID, "unknown screen target %d", target);
     TH_REQUIRE((uint64_t)a.w * a.h <= 0x7fffffffull, "a %ux%u target is beyond what a screen pass indexes", a.w, a.h);
     a.count = a.w * a.h;
     for (int32_t i = 0; i < n_units; ++i) {
-        ScreenUnit &v = a.unit[i];
-        const th_screen_unit &in = units[i];
-        if (in.source == TH_VIEW_TEXTURE) {
-            TH_REQUIRE(in.index >= 0 && in.index < TH_MAX_TEXTURES, "unit %d: texture slot %d outside 0..%d", i, in.index, TH_MAX_TEXTURES - 1);
-            const th_context::Texture &t = c->textures[in.index];
-            TH_REQUIRE(t.texels, "unit %d: texture slot %d is empty (call th_texture_upload)", i, in.index);
-            v.texels = t.texels.get(); v.w = t.w; v.h = t.h; v.format = t.format;
-        } else if (in.source == TH_VIEW_FRAMES) {
-            TH_REQUIRE(in.index == 0 || in.index == 1, "unit %d: frame buffer %d (OpticalFlow has buffers 0 and 1)", i, in.index);
-            TH_REQUIRE(c->frames[in.index], "unit %d: no frame buffers (call th_frames_resize)", i);
-            v.texels = c->frames[in.index].get(); v.w = c->frw; v.h = c->frh; v.format = TH_TEX_RGBA8;
-        } else if (in.source == TH_VIEW_SPAWN_IMAGE) {
-            TH_REQUIRE(c->image, "unit %d: no spawn image (call th_spawn_image_upload)", i);
-            v.texels = c->image.get(); v.w = c->iw; v.h = c->ih; v.format = TH_TEX_RGBA32F;
-        } else if (in.source == TH_VIEW_BUFFER) {
-            TH_REQUIRE(in.index >= 0 && in.index < (int32_t)c->view_ring.size(), "unit %d: no view buffer %d (there are %zu)", i, in.index, c->view_ring.size());
-            v.texels = c->view_ring[(size_t)in.index]; v.w = c->view_w; v.h = c->view_h; v.format = TH_TEX_RGBA8;
-        } else if (in.source == TH_VIEW_SCREEN) {
-            v.texels = c->view_screen.get(); v.w = c->view_w; v.h = c->view_h; v.format = TH_TEX_RGBA8;
-        } else if (in.source == TH_VIEW_COLORMAP) {
-            if (th_status s = colormap_storage(c)) return s;
-            v.texels = c->colormap.get(); v.w = c->cmap_w; v.h = c->cmap_h; v.format = TH_TEX_RGBA32F;
-        } else if (in.source == TH_VIEW_FLOW) {
-            TH_REQUIRE(c->flow, "unit %d: no flow field", i);
-            v.texels = c->flow.get(); v.w = c->fw; v.h = c->fh; v.format = TH_TEX_RGBA32F;
-        } else return fail(TH_ERR_INVALID, "unit %d: unknown source %d", i, in.source);
-        TH_REQUIRE(v.format != TH_TEX_RGBA8 || (v.w <= 65536 && v.h <= 65536), "unit %d: a %dx%d RGBA8 texture is beyond what a tap samples (65536 a side)", i, v.w, v.h);
+        Image v;
+        if (th_status s = view_image(c, units[i].source, units[i].index, kScreenViews, "unit", i, &v)) return s;
+        TH_REQUIRE(tap_size_ok(v), "unit %d: a %dx%d RGBA8 texture is beyond what a tap samples (65536 a side)", i, v.w, v.h);
         // GL's feedback loop - undefined there, a race here: the pass would read texels other lanes are writing
-        TH_REQUIRE(v.texels != a.dst, "unit %d (%s %d) is the memory this pass renders into: a pass cannot sample its own target", i, kSourceNames[in.source], in.index);
+        TH_REQUIRE(v.texels != a.dst, "unit %d (%s %d) is the memory this pass renders into: a pass cannot sample its own target", i, kSourceNames[units[i].source], units[i].index);
+        a.unit[i] = ScreenUnit{v.texels, v.w, v.h, v.format, 0};
     }
     a.n_units = n_units; a.gl_blend = gl_blend != 0;
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (!a.count) return TH_OK;
-    if (uniform_bytes) memcpy(k.u, uniforms, uniform_bytes);
-    // the record and the uniform block travel in the kernel's argument segment (th_program_run).  A memory-bound pass: at most
-    // 256 CUs x 8 workgroups, the rest of the texels by the grid's stride
-    size_t bytes = sizeof k;
-    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &k, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    const uint32_t blocks = (a.count + 255u) / 256u, cap = 256u * 8u;
-    TH_HIP(hipModuleLaunchKernel(m->fn, blocks < cap ? blocks : cap, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
-    return TH_OK;
+    // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
+    k.set_uniforms(uniforms, uniform_bytes);
+    return program_launch(c, m->fn, a.count, k);
 }
 
 }  // extern "C"

@@ -735,8 +735,7 @@ th_status th_spawn_sample_sharded(th_context *c, const th_spawn_sample_uniforms 
         staged = rt == out && out == c->ring[(size_t)source];
         if (staged) { if (th_status s = staging(c, 0, &rt)) return s; }
         if (th_status s = unpacked_view(c, c->ring[1], 1, &particles)) return s;
-        if (source == 1) data = particles;
-        else if (th_status s = unpacked_view(c, c->ring[(size_t)source], 2, &data)) return s;
+        if (th_status s = ring_view(c, source, particles, &data)) return s;
         const size_t taps = (size_t)std::min(chunk_rows, my_rows) * (size_t)W * (size_t)samples;
         if (c->sp_taps.size() < taps * kSpawnTapBytes) {
             TH_HIP(hipStreamSynchronize(c->stream));
