@@ -370,6 +370,44 @@ th_status th_draw_program_compile(const char *source, const char *name, th_progr
 th_status th_draw_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
                               int32_t pass /* TH_PASS_FLOW | TH_PASS_VIEW */, uint64_t *fragments);
 
+/* -- step programs: n steps of an integrator the CALLER wrote, fused in one launch -----------------------------------
+ * new Tendrils(gl, { logicShader }) takes a caller's integrator (src/index.js:70, 107-113).  As a state program (above) it
+ * runs, but one launch per step; a step program is the same pass under ONE restriction, which is what th_step_n's fusion rests
+ * on: of the ring it reads its own texel alone.  HIP source defining one device function,
+ *     __device__ float4 th_step_main(const th_step_pass &s);   - one step of one particle: returns its next state
+ * compiled exactly as a user program is (same hiprtc, same flags, same `#line 1 "<name>"`, same th_program_log()) behind a
+ * prelude of its own (tendrils_amd/csrc/th_step_prelude.inc) that declares:
+ *   th_step_pass       x, y, index, dataRes, geomRes, uv, self, uniforms - as th_pass has them, the same fp32 expressions -,
+ *                      time, dt (this step's: times[step] and dt of the call), step (this step's index within the CALL, 0 .. n - 1:
+ *                      it keeps counting across the launches a call is split into)
+ *   th_uniforms<T>(s), th_flow(s, u, v), th_flow_res(s), th_data(s, u, v), th_data_res(s), th_targets(s)   as for a state program;
+ *                      the taps land on the texels a state program's land on, for every coordinate (NaN: texel 0)
+ * There is NO th_particles(): a source that names it does not compile, and that is the whole enforcement of the restriction.
+ * Everything else a step may read - the flow field, the spawn image, `targets`, the uniform block - does not change inside a call.
+ *  th_step_program_compile    as th_program_compile (a source without th_step_main does not compile).  The handle is a th_program
+ *                      of a fourth kind: th_program_destroy / _query / _log serve all four; th_program_run, th_screen_run,
+ *                      th_draw_program_run and th_step_program_run refuse each other's programs (TH_ERR_INVALID, both kinds
+ *                      named, nothing launched).
+ *  th_step_program_run n consecutive passes with the ring semantics of TH_TARGET_RING: n rotations, buffers[0] is state n
+ *                      afterwards and buffers[1] state n - 1.  Step k sees time = times[k] (the caller's n values: no arithmetic
+ *                      is hidden here - Tendrils.step hands (float)timer.time, a run of fixed steps what th_step_n computes,
+ *                      t += dt_ms in double from time0, each value cast), dt and step = k.  The result and the ring order of a
+ *                      call with n steps are bit for bit those of n calls with one step each, on every ring:
+ *                        fused   the plain two-buffer f32 ring with TH_OPT_FUSE on: a particle's state stays in registers for up to
+ *                                32 steps per launch - 16 bytes read and 32 written per particle and launch
+ *                        single  every other ring (more than two buffers, TH_STATE_F16, fuse off): the same kernel, one step per
+ *                                launch, a packed ring quantised after every step as single passes would
+ *                      The ring goes to texel order first, as for every program pass.  source: TH_SOURCE_NONE, TH_SOURCE_FLOW or
+ *                      TH_SOURCE_IMAGE; a ring buffer is refused (TH_ERR_INVALID): the ring is what the call writes, a fused
+ *                      launch overwrites its input.  Row bands need nothing extra: x, y, index, uv are those of the whole texture,
+ *                      and there is no read outside the band to flag.  The `respawned` counter is not touched.  th_kernel_timing
+ *                      puts an event pair around every launch.  n = 0 does nothing.  TH_ERR_INVALID, before anything is launched:
+ *                      n < 0, null times with n > 0, fewer than 2 state buffers, another kind's program, more than 1024 uniform
+ *                      bytes, null uniforms with a size, a null program. */
+th_status th_step_program_compile(const char *source, const char *name, th_program **out);
+th_status th_step_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
+                              int32_t source /* TH_SOURCE_NONE | _FLOW | _IMAGE */, const float *times, float dt, int32_t n);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */
 th_status th_frames_upload(th_context *ctx, const uint8_t *rgba8);     /* setPixels -> buffers[0] */

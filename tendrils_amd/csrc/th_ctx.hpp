@@ -11,6 +11,7 @@
 //                  program share: the hiprtc binding, the compile, the log, the per-context modules
 //   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
 //   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
+//   th_stepprog.hip step programs: n steps of a caller's integrator in one launch (th_step_program_compile / th_step_program_run)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -79,7 +80,7 @@ struct th_options {
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
 // anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
 namespace thi {
-enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile
+enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile
 }
 struct th_program {
     thi::ProgramKind kind = thi::kStateProgram;
@@ -96,7 +97,7 @@ namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel
+    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)

@@ -9,7 +9,7 @@
 // else by soname; TH_HIPRTC_LIB names another.  Nothing here is linked against it: a host that never compiles a program never
 // loads it, and compiling needs no device.
 //
-// What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs) is here too: the hiprtc binding, the compile, the log,
+// What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs; th_stepprog.hip: step programs) is here too: the hiprtc binding, the compile, the log,
 // what is read out of the code object, the per-context modules (thi::program_*).
 #include <dlfcn.h>
 #include <elf.h>
@@ -24,8 +24,8 @@ namespace {
 const char kPrelude[] =
 #include "th_program_prelude.inc"
     ;
-const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel"};      // by ProgramKind
-const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude"};
+const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel", "th_step_kernel"};      // by ProgramKind
+const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude", "th_step_prelude"};
 
 // the launch record (th_program_prelude.inc: th_program_args, th_program_uniform_block - the same layout)
 struct ProgramArgs {
@@ -134,7 +134,8 @@ void ProgramModule::reset()
 const char *program_kind_name(ProgramKind kind)
 {
     return kind == kScreenProgram ? "screen program (th_screen_program_compile)"
-         : kind == kDrawProgram   ? "draw program (th_draw_program_compile)" : "state program (th_program_compile)";
+         : kind == kDrawProgram   ? "draw program (th_draw_program_compile)"
+         : kind == kStepProgram   ? "step program (th_step_program_compile)" : "state program (th_program_compile)";
 }
 
 th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes)

@@ -1,0 +1,128 @@
+// th_stepprog.hip - step programs: n steps of a caller's integrator in one launch.  new Tendrils(gl, { logicShader }) takes a
+// caller's integrator (src/index.js:70, 107-113); as a state program (th_program.hip) it runs one launch per step and moves the
+// ring through memory every time.  An integrator reads nothing of the ring but its own texel - the built-in one, src/logic.frag
+// and the reference's Euler and Verlet bodies alike - and a step program is a state program whose contract is that restriction
+// (th_step_prelude.inc: no th_particles).  Everything else a pass may read does not change inside a run of steps, so the steps
+// of one particle run back to back with its state in registers, as th_step_n's fused launch runs the built-in integrator
+// (th_step.hip): the ring is read once and written twice per launch of up to kMaxFusedSteps steps.
+#include "th_ctx.hpp"
+
+using namespace thi;
+
+namespace {
+
+// the tap rule as text (th_taps.inc: the library's kernels compile the same lines), then the prelude
+#define TH_TAPS(...) #__VA_ARGS__
+const char kTaps[] =
+#include "th_taps.inc"
+    ;
+#undef TH_TAPS
+const char kPrelude[] =
+#include "th_step_prelude.inc"
+    ;
+
+// the launch record (th_step_prelude.inc: th_step_args, th_program_uniform_block - the same layout)
+struct StepArgs {
+    const float4 *in;
+    float4 *out, *out_prev;
+    const float4 *data, *flow, *targets;
+    uint32_t count, width, rows, row0, global_height;
+    int32_t dw, dh, fw, fh;
+    uint32_t nsteps, step0;
+    float dt;
+    float times[th::kMaxFusedSteps];
+};
+using KernArgs = ProgramKernArgs<StepArgs>;
+static_assert(th::kMaxFusedSteps == 32 && sizeof(StepArgs) == 224 && offsetof(StepArgs, times) == 96 && offsetof(KernArgs, u) == 224 &&
+                  sizeof(KernArgs) == 224 + kUniformBytes,
+              "launch record: layout shared with th_step_prelude.inc");
+
+// one launch of th_step_kernel (th_kernel_timing: an event pair around it, as around every logic launch)
+th_status step_launch(th_context *c, hipFunction_t fn, KernArgs &k)
+{
+    hipEvent_t k0 = nullptr, k1 = nullptr;
+    if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
+    if (th_status s = program_launch(c, fn, c->texels(), k)) return s;
+    if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+    return TH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+th_status th_step_program_compile(const char *source, const char *name, th_program **out)
+{
+    return program_compile(kStepProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
+}
+
+// n passes with the ring semantics of TH_TARGET_RING: buffers[0] is state n afterwards, buffers[1] state n - 1.
+//   fused:  the plain two-buffer f32 ring with th_options::fuse on - at most kMaxFusedSteps steps per launch, both outputs
+//           routed as th_step_n routes them (a lane touches its own texel alone: one output may be the input buffer)
+//   single: every other ring (more buffers: all of them rotate; packed: quantised after every step; fuse off) - the same
+//           kernel with nsteps = 1 between RingPass::begin and commit, once per step
+// One kernel on both paths, fp32 state between the steps of a fused launch exactly what a single pass stores: a call with n
+// steps leaves the bits and the ring order of n calls with one.
+th_status th_step_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t source,
+                              const float *times, float dt, int32_t n)
+{
+    if (th_status s = use(c)) return s;
+    if (th_status s = program_run_args(prog, kStepProgram, "th_step_program_run", uniforms, uniform_bytes)) return s;
+    TH_REQUIRE(n >= 0, "%d steps", n);
+    TH_REQUIRE(times || n == 0, "null times");
+    TH_REQUIRE(!(source >= 0 && source < (int32_t)c->ring.size()),
+               "state buffer %d as a step program's spawnData: the ring is what the call writes (a fused launch overwrites its input)", source);
+    TH_REQUIRE(source == TH_SOURCE_NONE || source == TH_SOURCE_FLOW || source == TH_SOURCE_IMAGE, "bad spawnData source %d", source);
+    TH_REQUIRE(c->ring.size() >= 2, "a pass needs at least 2 state buffers (have %zu)", c->ring.size());
+    KernArgs k{};
+    StepArgs &a = k.a;
+    if (th_status s = spawn_data(c, source, nullptr, true, &a.data, &a.dw, &a.dh)) return s;
+    if (n == 0) return TH_OK;
+    ProgramModule *m = nullptr;
+    if (th_status s = program_loaded(c, prog, &m)) return s;
+    if (th_status s = asort_drop(c)) return s;
+    if (th_status s = ensure_identity(c)) return s;      // a pass operates in texel order, like every program pass
+    a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
+    a.targets = c->targets;
+    a.count = (uint32_t)c->texels(); a.width = (uint32_t)c->cfg.width; a.rows = (uint32_t)c->cfg.height;
+    a.row0 = (uint32_t)c->cfg.row0; a.global_height = (uint32_t)c->cfg.global_height;
+    a.dt = dt;
+    k.set_uniforms(uniforms, uniform_bytes);
+
+    if (c->opt.fuse && c->ring.size() == 2 && !c->packed) {
+        for (int32_t done = 0; done < n;) {
+            const int32_t steps = std::min<int32_t>(n - done, (int32_t)th::kMaxFusedSteps);
+            float4 *cur = c->ring[0], *other = c->ring[1];
+            state_written(c, cur); state_written(c, other);
+            // after `steps` rotations of [cur, other]: even -> [cur, other], odd -> [other, cur] (th_step_n)
+            a.in = cur;
+            a.out = (steps & 1) ? other : cur;                                   // state `steps`     (ends up in buffers[0])
+            a.out_prev = steps == 1 ? nullptr : (steps & 1) ? cur : other;       // state `steps` - 1 (ends up in buffers[1])
+            a.nsteps = (uint32_t)steps; a.step0 = (uint32_t)done;
+            for (int32_t j = 0; j < steps; ++j) a.times[j] = times[(size_t)(done + j)];
+            if (th_status s = step_launch(c, m->fn, k)) return s;
+            if (steps & 1) { c->ring[0] = other; c->ring[1] = cur; }
+            c->steps_since_sort += steps; c->total_steps += steps;
+            done += steps;
+        }
+    } else {
+        a.nsteps = 1; a.out_prev = nullptr;
+        for (int32_t done = 0; done < n; ++done) {
+            RingPass pass;
+            if (th_status s = pass.begin(c, TH_TARGET_RING)) return s;
+            a.in = pass.particles; a.out = pass.rt;
+            a.step0 = (uint32_t)done; a.times[0] = times[(size_t)done];
+            if (th_status s = step_launch(c, m->fn, k)) return s;
+            if (th_status s = pass.commit(c)) return s;
+            ++c->steps_since_sort; ++c->total_steps;
+        }
+    }
+    // what is remembered of the buffers' content ended with use() and state_written(); the ring stays in texel order, and no
+    // pass of this call has counted tiles or taken statistics of what it wrote
+    c->counted.buf = nullptr;
+    c->fused_stats.valid = false;
+    c->drawn.valid = false;
+    return TH_OK;
+}
+
+}  // extern "C"

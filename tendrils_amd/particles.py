@@ -107,6 +107,15 @@ class DrawProgram(Program):
     COMPILE, SOURCE_KIND = "th_draw_program_compile", "draw"
 
 
+class StepProgram(Program):
+    """A step program (include/tendrils_hip.h "step programs"): from_source() takes HIP source defining
+    `__device__ float4 th_step_main(const th_step_pass &s)` - one step of one particle's integrator, which reads nothing of the
+    ring but its own texel (there is no th_particles) - and is otherwise Program.from_source: compiled once, for gfx950, no GPU
+    needed; TendrilsHipError with the compiler's output; pack(), query() and dispose() as there.  Tendrils runs it as its
+    logicShader: step() one step of it, step_n() n steps fused in one launch, with the same bits and the same ring order."""
+    COMPILE, SOURCE_KIND = "th_step_program_compile", "step"
+
+
 LOGIC = "logic"
 
 
@@ -242,14 +251,23 @@ class Particles:
     def step_n(self, update, time0, dt_ms, n):
         """n consecutive logic passes with a fixed-step timer (time_k = time0 + (k+1)*dt_ms, accumulated in
         double like src/timer.js:28-31), replayed from a captured hipGraph.  Extension: the reference
-        issues these one draw call at a time."""
+        issues these one draw call at a time.  With a StepProgram as `logic`: the same n steps of the caller's
+        integrator in one th_step_program_run, fused where the ring allows (the same bits either way)."""
         uniforms = Particles.applyUpdate(
             dict(self.logic.uniforms, dataRes=self.shape, geomRes=self.geomShape), update)
         self.logic.uniforms = uniforms
-        if self.logic.kind != LOGIC:
+        if self.logic.kind == StepProgram.SOURCE_KIND:
+            # the times th_step_n computes (th_step.hip): t += dt_ms in double from time0, each value cast to fp32
+            times, t = np.empty(max(int(n), 0), np.float32), float(time0)
+            for k in range(times.size):
+                t += float(dt_ms)
+                times[k] = t
+            run_step_program(self, self.logic, uniforms, times, np.float32(dt_ms), int(n))
+        elif self.logic.kind != LOGIC:
             raise ValueError("step_n runs the logic program only")
-        s = logic_uniforms(uniforms)
-        call("th_step_n", self._ctx, C.byref(s), C.c_double(time0), C.c_double(dt_ms), int(n))
+        else:
+            s = logic_uniforms(uniforms)
+            call("th_step_n", self._ctx, C.byref(s), C.c_double(time0), C.c_double(dt_ms), int(n))
         for _ in range(int(n) % max(len(self.buffers), 1)):
             self.buffers.insert(0, self.buffers.pop())
 
@@ -392,19 +410,40 @@ def run_pass(particles, program, uniforms, target):
         if not program.handle:
             raise ValueError("user program %r was disposed" % (program.fixed.get("name"),))
         block = program.pack(uniforms)
-        src = uniforms.get("spawnData")
-        if src is None:
-            source = _capi.TH_SOURCE_NONE
-        else:
-            if hasattr(src, "bind_for"):                  # a spawner's own image buffer: uploaded on use
-                src.bind_for(particles)
-            source = src if isinstance(src, int) else src.source_index()
-            if source >= 0 and target == _capi.TH_TARGET_RING:
-                source = (source + 1) % len(particles.buffers)      # (as above: the order the pass sees)
+        source = _program_source(particles, uniforms, target)
         call("th_program_run", ctx, program.handle, C.byref(block) if block is not None else None,
              C.sizeof(block) if block is not None else 0, source, target)
+    elif kind == "step":
+        if target != _capi.TH_TARGET_RING:
+            raise ValueError("a step program steps the ring: it has no other target")
+        times = np.array([uniforms.get("time", 0.0)], np.float64).astype(np.float32)
+        run_step_program(particles, program, uniforms, times, np.float32(uniforms.get("dt", 0.0)), 1)
     else:
         raise ValueError("unknown program kind %r" % (kind,))
+
+
+def _program_source(particles, uniforms, target):
+    """the spawnData of a caller's pass as the library names it (TH_SOURCE_NONE without one)"""
+    src = uniforms.get("spawnData")
+    if src is None:
+        return _capi.TH_SOURCE_NONE
+    if hasattr(src, "bind_for"):                  # a spawner's own image buffer: uploaded on use
+        src.bind_for(particles)
+    source = src if isinstance(src, int) else src.source_index()
+    if source >= 0 and target == _capi.TH_TARGET_RING:
+        source = (source + 1) % len(particles.buffers)      # (as for the sample passes: the order the pass sees)
+    return source
+
+
+def run_step_program(particles, program, uniforms, times, dt, n):
+    """n steps of a step program over the ring in one call (th_step_program_run): step k sees times[k], dt and k."""
+    if not program.handle:
+        raise ValueError("step program %r was disposed" % (program.fixed.get("name"),))
+    block = program.pack(uniforms)
+    source = _program_source(particles, uniforms, _capi.TH_TARGET_RING)
+    times = np.ascontiguousarray(times, np.float32)
+    call("th_step_program_run", particles._ctx, program.handle, C.byref(block) if block is not None else None,
+         C.sizeof(block) if block is not None else 0, source, times.ctypes.data_as(_capi._fp), C.c_float(float(dt)), int(n))
 
 
 default = Particles

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, run_pass
+from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, StepProgram, run_pass
 from .timer import Timer
 
 
@@ -455,9 +455,10 @@ class Tendrils:
         return self
 
     def step_n(self, n):
-        """n x (timer.tick(); step()) for a fixed-step, unpaused timer, as one captured-graph replay."""
+        """n x (timer.tick(); step()) for a fixed-step, unpaused timer, as one captured-graph replay - of a StepProgram
+        logicShader: as one th_step_program_run, its steps fused."""
         tm = self.timer
-        if tm.paused or tm.step < 0 or tm.end >= 0 or self.logicShader.kind != LOGIC:
+        if tm.paused or tm.step < 0 or tm.end >= 0 or self.logicShader.kind not in (LOGIC, StepProgram.SOURCE_KIND):
             for _ in range(n):
                 tm.tick()
                 self.step()

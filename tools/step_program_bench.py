@@ -1,0 +1,229 @@
+"""GPU time of n fused steps of a step program (tendrils_amd/csrc/th_stepprog.hip) against the ways to run the same steps, on one
+MI355X.
+
+Workload: 4096 x 4096 particles (a 256 MiB RGBA32F ring buffer), flow 1920 x 1080, 20 steps per call, two programs - the drift
+program (pos += vel * dt) and this repository's flow-only integrator (a flow tap, decay, force, damping, speed clamp, Euler).
+Arms, all in this process (one library), each on a context of its own:
+  fused        one th_step_program_run(n = 20): 16 B read + 32 B written per particle and call
+  single       the same call with the option `fuse` off: 20 launches of the same kernel, 32 B per particle-step
+  state_prog   20 x th_program_run of the program's state-program form: what there was before step programs
+  builtin      th_step_n(20) of the built-in integrator with the noise off (the flow-only program's arithmetic, the library's
+               own fused launch, tile-sorted slots where its policy sorts)
+  memcpy_d2d   hipMemcpyAsync, device to device, of one 256 MiB buffer: 1.5 x this is 16 B in + 32 B out per particle
+Each figure is the GPU time per call between two events on the context's stream (th_timer_start / th_timer_stop around --reps
+calls, after --warmup calls); the arms alternate for --rounds rounds and the median round is reported, with the spread.  The
+programs' registers / scratch / code size (th_program_query) go out with the figures.
+
+Usage: python tools/step_program_bench.py [--size 4096] [--steps 20] [--reps 5] [--warmup 2] [--rounds 5] [--out FILE]
+       (--out appends the measurement to FILE, behind whatever it holds)
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STEP_DRIFT = """__device__ float4 th_step_main(const th_step_pass &s)
+{
+    float4 p = s.self;
+    p.x = p.x + p.z * s.dt;
+    p.y = p.y + p.w * s.dt;
+    return p;
+}
+"""
+STATE_DRIFT = """struct Drift { float dt; };
+__device__ float4 th_main(const th_pass &p)
+{
+    const Drift &u = th_uniforms<Drift>(p);
+    float4 s = p.self;
+    s.x = s.x + s.z * u.dt;
+    s.y = s.y + s.w * u.dt;
+    return s;
+}
+"""
+# the flow-only integrator (tendrils_amd/csrc/th_logic.hpp: logic_texel_ref without its noise and target terms); %(...)s: the
+# entry point, the pass type and where time / dt come from
+FLOW_ONLY = """struct Logic {
+    float viewSize[2];
+    float time, dt, speedLimit, damping, forceWeight, flowWeight, noiseWeight, flowDecay, noiseSpeed, noiseScale, target;
+    float varyForce, varyFlow, varyNoise, varyNoiseScale, varyNoiseSpeed, varyTarget;
+};
+__device__ float vary(float base, float offset, float variance) { return base + (offset * variance * base); }
+__device__ float4 %(entry)s(const %(pass)s &p)
+{
+    const Logic &u = th_uniforms<Logic>(p);
+    const float4 st = p.self;
+    if (!(st.x != -1000000.0f || st.y != -1000000.0f)) return st;
+    const float fcx = (float)p.x + 0.5f, fcy = (float)p.y + 0.5f;
+    const float i = (fcx + (fcy * p.dataRes.x)) / (p.dataRes.x * p.dataRes.y);
+    const float sx = st.x * u.viewSize[0], sy = st.y * u.viewSize[1];
+    const float4 ft = th_flow(p, 0.0f + (1.0f * (sx + 1.0f)) / 2.0f, 0.0f + (1.0f * (sy + 1.0f)) / 2.0f);
+    const float k = fmaxf(0.0f, 1.0f - ((%(clock)s.time - ft.z) * u.flowDecay));
+    const float ffx = (0.0f + ft.x * k * 1.0f) / 1.0f, ffy = (0.0f + ft.y * k * 1.0f) / 1.0f;
+    const float force = vary(u.forceWeight, i, u.varyForce), flow = vary(u.flowWeight, i, u.varyFlow);
+    float vx = (st.z * u.damping * %(clock)s.dt) + (force * (ffx * %(clock)s.dt * flow));
+    float vy = (st.w * u.damping * %(clock)s.dt) + (force * (ffy * %(clock)s.dt * flow));
+    const float speed = sqrtf(vx * vx + vy * vy);
+    const float r = fminf(speed, u.speedLimit) / speed;
+    vx *= r; vy *= r;
+    return make_float4(st.x + vx, st.y + vy, vx, vy);
+}
+"""
+HIP_MEMCPY_DEVICE_TO_DEVICE = 3
+
+
+class DriftU(C.Structure):
+    _fields_ = [("dt", C.c_float)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--flow", type=int, nargs=2, default=(1920, 1080))
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("step_program_bench: no GPU - nothing is measured without one")
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import LOGIC, Particles, Program, StepProgram, run_pass
+    from tendrils_amd.tendrils import defaults
+
+    n, steps = args.size, args.steps
+    fw, fh = args.flow
+    time0, dt = 1000.0, 1000.0 / 60.0
+    uniforms = {k: v for k, v in defaults()["state"].items() if isinstance(v, (int, float)) and not isinstance(v, bool)}
+    uniforms.update(noiseWeight=0, viewSize=(1.0, fh / fw), time=time0, dt=dt)
+    rng = np.random.default_rng(5)
+    flow = np.zeros((fh, fw, 4), np.float32)
+    flow[..., :2] = rng.uniform(-0.01, 0.01, (fh, fw, 2))
+    flow[..., 2] = time0 - 10.0
+    flow[..., 3] = 1.0
+
+    programs = dict(
+        drift=(StepProgram.from_source(STEP_DRIFT, name="drift"), Program.from_source(STATE_DRIFT, DriftU, name="state_drift")),
+        flow_only=(StepProgram.from_source(FLOW_ONLY % dict(entry="th_step_main", **{"pass": "th_step_pass"}, clock="p"), _capi.LogicUniforms, name="flow_only"),
+                   Program.from_source(FLOW_ONLY % dict(entry="th_main", **{"pass": "th_pass"}, clock="u"), _capi.LogicUniforms, name="state_flow_only")),
+    )
+
+    def context(fuse=None):
+        p = Particles(None, dict(shape=[n, n]))
+        p.setup(2)
+        if fuse is not None:
+            p.option("fuse", fuse)
+        ball = _capi.SpawnBallUniforms(radius=0.8, speed=0.004)
+        for k in (0, 1):
+            call("th_spawn_ball", p._ctx, C.byref(ball), k)
+        call("th_flow_resize", p._ctx, fw, fh)
+        call("th_flow_upload", p._ctx, flow.ctypes.data_as(_capi._fp))
+        return p
+
+    fused, single, state, builtin = context(), context(fuse=0), context(), context()
+    contexts = (fused, single, state, builtin)
+
+    # the process's one HIP runtime (the copy _capi.load() settled on), for the copy arm
+    runtime, = _capi._mapped("libamdhip64")
+    hip = C.CDLL(runtime)
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemcpyAsync.restype = C.c_int
+    stream, dst, src = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    call("th_stream", state._ctx, C.byref(stream))
+    call("th_state_device_ptr", state._ctx, 0, C.byref(dst))
+    call("th_state_device_ptr", state._ctx, 1, C.byref(src))
+    nbytes = n * n * 16
+
+    def step_program(p, prog):
+        def run():
+            p.logic = prog
+            p.step_n(dict(uniforms), time0, dt, steps)
+        return run
+
+    def state_program(p, prog):
+        def run():
+            t = time0
+            for _ in range(steps):
+                t += dt
+                run_pass(p, prog, dict(uniforms, time=t, dt=dt), _capi.TH_TARGET_RING)
+        return run
+
+    def builtin_steps():
+        builtin.logic = Program(LOGIC)
+        builtin.step_n(dict(uniforms), time0, dt, steps)
+
+    def copy():
+        e = hip.hipMemcpyAsync(dst, src, nbytes, HIP_MEMCPY_DEVICE_TO_DEVICE, stream)
+        if e:
+            raise RuntimeError("hipMemcpyAsync: error %d" % e)
+
+    # (bytes through HBM per call as the arm is built, context whose stream times it, the call)
+    arms = {}
+    for name, (step_form, state_form) in programs.items():
+        arms[name + " fused"] = (nbytes * (1 + 2 * ((steps + 31) // 32)), fused, step_program(fused, step_form))
+        arms[name + " single"] = (2 * nbytes * steps, single, step_program(single, step_form))
+        arms[name + " state_prog"] = (2 * nbytes * steps, state, state_program(state, state_form))
+    arms["builtin th_step_n"] = (3 * nbytes, builtin, builtin_steps)
+    arms["memcpy_d2d"] = (2 * nbytes, state, copy)
+
+    def timed(p, fn, reps):
+        ms = C.c_float(0)
+        call("th_timer_start", p._ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", p._ctx, C.byref(ms))
+        return ms.value / reps
+
+    for _, p, fn in arms.values():
+        timed(p, fn, args.warmup)
+    rounds = {name: [] for name in arms}
+    for _ in range(args.rounds):
+        for name, (_, p, fn) in arms.items():
+            rounds[name].append(timed(p, fn, args.reps))
+
+    lines = ["step programs, %d x %d particles, flow %d x %d, %d steps per call, %d rounds of %d calls, arms alternating; GPU ms per call (events on the context's stream)"
+             % (n, n, fw, fh, steps, args.rounds, args.reps),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "%-24s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)")]
+    result = dict(size=n, flow=[fw, fh], steps=steps, reps=args.reps, rounds=args.rounds, arms={}, query={})
+    for name, (moved, _, _) in arms.items():
+        ms = rounds[name]
+        med = statistics.median(ms)
+        result["arms"][name] = dict(median_ms=med, min_ms=min(ms), max_ms=max(ms), bytes=moved, gbps=moved / med / 1e6)
+        lines.append("%-24s %10.4f %10.4f %10.4f %14.1f" % (name, med, min(ms), max(ms), moved / med / 1e6))
+    med = {k: v["median_ms"] for k, v in result["arms"].items()}
+    for name in programs:
+        a, b, c = (result["arms"]["%s %s" % (name, arm)] for arm in ("fused", "single", "state_prog"))
+        lines.append("%s: fused / state_prog = %.3f (rounds apart: fused max %.4f < state_prog min %.4f: %s); fused / (1.5 x memcpy_d2d) = %.3f; "
+                     "single / state_prog = %.3f (single median %.4f against state_prog max %.4f)"
+                     % (name, a["median_ms"] / c["median_ms"], a["max_ms"], c["min_ms"], a["max_ms"] < c["min_ms"],
+                        a["median_ms"] / (1.5 * med["memcpy_d2d"]), b["median_ms"] / c["median_ms"], b["median_ms"], c["max_ms"]))
+    lines.append("flow_only fused / builtin th_step_n = %.3f" % (med["flow_only fused"] / med["builtin th_step_n"]))
+    for name, (step_form, state_form) in programs.items():
+        result["query"][name] = dict(step=step_form.query(fused), state=state_form.query(state))
+        lines.append("th_program_query(%s): th_step_kernel %s; th_program_kernel %s"
+                     % (name, json.dumps(result["query"][name]["step"]), json.dumps(result["query"][name]["state"])))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(result))
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    for p in contexts:
+        p.dispose()
+    for pair in programs.values():
+        for prog in pair:
+            prog.dispose()
+
+
+if __name__ == "__main__":
+    main()
