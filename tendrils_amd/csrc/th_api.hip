@@ -90,10 +90,7 @@ th_status resolve_target(th_context *c, int32_t target, bool rotate_ok, float4 *
 {
     if (target == TH_TARGET_RING) {
         if (!rotate_ok) return fail(TH_ERR_INVALID, "TH_TARGET_RING not valid here");
-        float4 *last = c->ring.back();               // utils.step: pop -> unshift
-        c->ring.pop_back();
-        c->ring.insert(c->ring.begin(), last);
-        *out = c->ring[0];
+        *out = ring_rotate(c);
         state_written(c, *out);
     } else if (target == TH_TARGET_TARGETS) {
         *out = c->targets;

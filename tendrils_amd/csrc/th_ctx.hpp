@@ -7,7 +7,7 @@
 //   th_spawn.hip  the spawners, and what a pass over the ring starts from: its buffers (RingPass), its spawnData (spawn_data)
 //   th_draw.hip   Tendrils.draw(): flow pass, view pass, trail export (binned and stream-ordered pipeline)
 //   th_shard.hip  row-band shards: emit / merge, th_draw_sharded, the job's communicator, gathers, counter all-reduce, the sampled spawn
-//   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run), and what both kinds of
+//   th_program.hip user programs: a caller's HIP pass compiled through hiprtc (th_program_compile / _run), and what the four kinds of
 //                  program share: the hiprtc binding, the compile, the log, the per-context modules
 //   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
 //   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
@@ -368,6 +368,9 @@ inline void state_moved(th_context *c, const float4 *from, const float4 *to)
     if (c->seen.cur == from || c->seen.prev == from) c->seen.cur = c->seen.prev = nullptr;
 }
 
+// Particles.step's rotation (utils.step: pop -> unshift): the last buffer becomes buffers[0]
+inline float4 *ring_rotate(th_context *c) { std::rotate(c->ring.begin(), c->ring.end() - 1, c->ring.end()); return c->ring[0]; }
+
 // ---- th_spawn.hip ----------------------------------------------------------------------------------------------------
 // one of the ring's buffers as a pass samples it: f32 texels - `particles` itself when k is 1 (the view of ring[1] the pass
 // already holds), else the buffer's f32 view in staging slot 2
@@ -386,7 +389,18 @@ struct RingPass {
 };
 
 // ---- th_step.hip -----------------------------------------------------------------------------------------------------
-th_status timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1);      // th_kernel_timing: the next pair of events to record around a launch
+// th_kernel_timing: begin() records the first event of the next pair in front of a launch if timing is on (and `on`: captured
+// launches are never bracketed), end() the second behind it
+struct LaunchTimer {
+    hipEvent_t k1 = nullptr;
+    th_status begin(th_context *c, bool on = true);
+    th_status end(th_context *c);
+};
+// One fused launch of m steps on a two-buffer ring: `in` = buffers[0]; state m goes to `out`, state m - 1 to `out_prev` (one is
+// `in`, one `other`) - buffers[0] and [1] once fused_routed() has flipped the ring (m odd) and advanced the step counters
+struct FusedRoute { float4 *in, *out, *out_prev, *other; };
+FusedRoute fused_route(th_context *c, int32_t m);
+void fused_routed(th_context *c, int32_t m);
 
 // ---- th_program.hip --------------------------------------------------------------------------------------------------
 constexpr uint32_t kUniformBytes = 1024;        // a program's uniform block (th_program_uniform_block in the preludes)
@@ -424,7 +438,6 @@ void destroy_graph(GraphEntry &g);
 void clear_graphs(th_context *c);
 constexpr int kTileShift = 5;            // 32 x 32 texel tiles (th_kernels.hip kTile)
 constexpr size_t kTileWords = 2 * (size_t)th::kSortReplicas * th::kMaxTileBins;   // histogram + cursors, all copies
-uint32_t tile_count(const th_context *c, uint32_t *tiles_x);
 bool sorting_possible(const th_context *c);
 th_status line_rows(th_context *c);
 th::TileGeom tile_geom(const th_context *c, const th_logic_uniforms &u);
@@ -432,9 +445,11 @@ bool same_geom(const th::TileGeom &a, const th::TileGeom &b);
 int order_of(const th_context *c, const float4 *buf);
 void set_order(th_context *c, float4 *buf, int order);
 bool any_sorted(const th_context *c);
+bool order_stale(const th_context *c, int order, const th::TileGeom &g);      // `order` no longer describes the field under `g` (-1: never stale)
+void ring_trade(th_context *c, float4 *&slot, float4 *&with, int order);
 th_status sort_storage(th_context *c);
-th_status free_order(th_context *c, int *out);
 th_status asort_drop(th_context *c);
+th_status asort_take(th_context *c);
 th_status asort_start(th_context *c, const th::TileGeom &g, float4 *src, int src_order);
 th_status ensure_identity(th_context *c, bool *launched = nullptr);
 th_status begin_sort(th_context *c, const th::TileGeom &g, const float4 *state, const uint32_t *perm_in, int *order,

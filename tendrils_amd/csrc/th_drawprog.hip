@@ -112,10 +112,10 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
         k.set_uniforms(uniforms, uniform_bytes);
         if (lanes) {
             // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
-            hipEvent_t k0 = nullptr, k1 = nullptr;          // (th_kernel_timing: the vertex kernel alone)
-            if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
+            LaunchTimer timer;                              // (th_kernel_timing: the vertex kernel alone)
+            if (th_status s = timer.begin(c)) return s;
             if (th_status s = program_launch(c, fn, lanes, k)) return s;
-            if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+            if (th_status s = timer.end(c)) return s;
         }
         const th_status s = bins ? deposit_run_bins(c, p, fragments, true) : deposit_run(c, p, fragments);
         c->drawn.valid = false;

@@ -26,7 +26,7 @@ void clear_graphs(th_context *c)
 // plane does not fit one XCD's 4 MiB L2 and there are enough particles to amortise the sort (measurements:
 // profiles/r1_c_bucketing.txt, r2_b_*).  th_options::bucket = 0 / 1 forces the layout off / on (the parity suite reruns
 // under 1); resort_steps / rebucket_steps set the re-sort period of single-step / fused launches.
-uint32_t tile_count(const th_context *c, uint32_t *tiles_x)
+static uint32_t tile_count(const th_context *c, uint32_t *tiles_x)
 {
     const uint32_t tx = ((uint32_t)c->fw + (1u << kTileShift) - 1u) >> kTileShift;
     const uint32_t ty = ((uint32_t)c->fh + (1u << kTileShift) - 1u) >> kTileShift;
@@ -130,6 +130,27 @@ void set_order(th_context *c, float4 *buf, int order)
     if (order >= 0) { c->buf_order.emplace_back(buf, order); ++c->orders[(size_t)order].refs; }
 }
 bool any_sorted(const th_context *c) { return !c->buf_order.empty(); }
+bool order_stale(const th_context *c, int order, const th::TileGeom &g)
+{
+    if (order < 0) return false;
+    const th_context::SlotOrder &o = c->orders[(size_t)order];
+    return !same_geom(o.geom, g) || o.fw != c->fw || o.fh != c->fh;
+}
+
+// Ring element `slot`'s content now lives in allocation `with` (c->spare or c->asort.dst), held in slot order `order` (-1: texel
+// order): the two allocations trade places.  The caller has launched what fills `with` and dropped the captured sequences, which
+// name ring buffers (clear_graphs waits for the stream while graphs exist: it stays where the caller has it among its launches).
+// Independent pairs - any order of them gives the same context: set_order (buf_order, orders[*].refs) against state_moved
+// (gathered_of, asort.valid, seen) against the swap (the two pointers); only the old order's reference goes before the new one's
+// comes.  A buffer in texel order has no entry: set_order(., -1) is free there.
+void ring_trade(th_context *c, float4 *&slot, float4 *&with, int order)
+{
+    float4 *old = slot;
+    set_order(c, old, -1);
+    state_moved(c, old, with);
+    slot = with; with = old;
+    set_order(c, slot, order);
+}
 
 th_status sort_storage(th_context *c)
 {
@@ -147,7 +168,7 @@ th_status sort_storage(th_context *c)
 }
 
 // an order no ring buffer is stored in (allocates the first few)
-th_status free_order(th_context *c, int *out)
+static th_status free_order(th_context *c, int *out)
 {
     for (size_t k = 0; k < c->orders.size(); ++k) if (c->orders[k].refs == 0) { *out = (int)k; return TH_OK; }
     th_context::SlotOrder o;
@@ -179,6 +200,35 @@ th_status asort_drop(th_context *c)
     return TH_OK;
 }
 
+// A new order `o` for `state` (held in the order of `perm_in`; null: texel order) under the key function `g`: the order takes
+// the key, the sort's passes their common parameters - the scratch and the order's arrays.  Where the moved state goes
+// (state_out), whether tile_hist tables the blocks (block_records) and the ring's format (packed) are the caller's.
+static th::TileSortParams sort_params(th_context *c, const th::TileGeom &g, const float4 *state, const uint32_t *perm_in, th_context::SlotOrder &o)
+{
+    o.geom = g; o.fw = c->fw; o.fh = c->fh;
+    th::TileSortParams b{};
+    b.state = state; b.perm_in = perm_in; b.count = (uint32_t)c->texels();
+    b.g = g;
+    b.hist = c->tile_mem; b.cursor = c->tile_mem + kTileWords / 2;
+    b.totals = c->tile_mem + kTileWords + 8; b.starts = b.totals + th::kMaxTileBins;
+    b.chunks = o.chunks; b.nchunks = o.nchunks;
+    b.perm_out = o.perm;
+    return b;
+}
+
+// the copy is of the next step's input (the caller's check): it takes the input's place in the ring, the input becomes the next
+// copy's destination
+th_status asort_take(th_context *c)
+{
+    TH_HIP(hipStreamWaitEvent(c->stream, c->asort.done, 0));
+    clear_graphs(c);                       // captured sequences name the ring buffers: one of them changes places with the copy
+    c->asort.pending = c->asort.valid = false;
+    c->asort.src = nullptr;
+    ring_trade(c, c->ring[1], c->asort.dst, c->asort.order);
+    c->steps_since_sort = 0;
+    return TH_OK;
+}
+
 th_status asort_start(th_context *c, const th::TileGeom &g, float4 *src, int src_order)
 {
     if (th_status s = sort_storage(c)) return s;
@@ -190,14 +240,7 @@ th_status asort_start(th_context *c, const th::TileGeom &g, float4 *src, int src
     int order = -1;
     if (th_status s = free_order(c, &order)) return s;
     th_context::SlotOrder &o = c->orders[(size_t)order];
-    o.geom = g; o.fw = c->fw; o.fh = c->fh;
-    th::TileSortParams b{};
-    b.state = src; b.perm_in = src_order >= 0 ? c->orders[(size_t)src_order].perm : nullptr; b.count = (uint32_t)c->texels();
-    b.g = g;
-    b.hist = c->tile_mem; b.cursor = c->tile_mem + kTileWords / 2;
-    b.totals = c->tile_mem + kTileWords + 8; b.starts = b.totals + th::kMaxTileBins;
-    b.chunks = o.chunks; b.nchunks = o.nchunks;
-    b.perm_out = o.perm;
+    th::TileSortParams b = sort_params(c, g, src, src_order >= 0 ? c->orders[(size_t)src_order].perm : nullptr, o);
     b.block_records = c->block_records;
     b.state_out = c->asort.dst;
     TH_HIP(hipEventRecord(c->asort.ready, c->stream));
@@ -227,9 +270,7 @@ th_status ensure_identity(th_context *c, bool *launched)
         const int o = order_of(c, b);
         if (o < 0) continue;
         th::launch_unpermute_state(c->spare, b, c->orders[(size_t)o].perm, (uint32_t)c->texels(), c->packed, c->stream);
-        set_order(c, b, -1);
-        state_moved(c, b, c->spare);
-        float4 *t = b; b = c->spare; c->spare = t;
+        ring_trade(c, b, c->spare, -1);
         if (launched) *launched = true;
     }
     TH_HIP(hipGetLastError());
@@ -245,14 +286,7 @@ th_status begin_sort(th_context *c, const th::TileGeom &g, const float4 *state, 
     if (th_status s = asort_drop(c)) return s;          // (one sort at a time: the scratch and the free orders are shared)
     if (th_status s = free_order(c, order)) return s;
     th_context::SlotOrder &o = c->orders[(size_t)*order];
-    o.geom = g; o.fw = c->fw; o.fh = c->fh;
-    th::TileSortParams b{};
-    b.state = state; b.perm_in = perm_in; b.count = (uint32_t)c->texels();
-    b.g = g;
-    b.hist = c->tile_mem; b.cursor = c->tile_mem + kTileWords / 2;
-    b.totals = c->tile_mem + kTileWords + 8; b.starts = b.totals + th::kMaxTileBins;
-    b.chunks = o.chunks; b.nchunks = o.nchunks;
-    b.perm_out = o.perm;
+    th::TileSortParams b = sort_params(c, g, state, perm_in, o);
     b.block_records = have_hist ? nullptr : c->block_records;      // (only a tile_hist pass over the same blocks fills them)
     b.packed = c->packed ? 1u : 0u;
     if (!have_hist) {          // (a COUNT pass whose histogram was never used may have left counts behind)
@@ -281,15 +315,11 @@ th_status align_slot_orders(th_context *c)
     float4 *&b = c->ring[1];
     if (o1 >= 0) {
         th::launch_unpermute_state(c->spare, b, c->orders[(size_t)o1].perm, (uint32_t)c->texels(), c->packed, c->stream);
-        set_order(c, b, -1);
-        state_moved(c, b, c->spare);
-        float4 *t = b; b = c->spare; c->spare = t;
+        ring_trade(c, b, c->spare, -1);
     }
     if (o0 >= 0) {
         th::launch_permute_state(c->spare, b, c->orders[(size_t)o0].perm, (uint32_t)c->texels(), c->packed, c->stream);
-        state_moved(c, b, c->spare);
-        float4 *t = b; b = c->spare; c->spare = t;
-        set_order(c, b, o0);
+        ring_trade(c, b, c->spare, o0);
     }
     TH_HIP(hipGetLastError());
     c->counted.buf = nullptr;

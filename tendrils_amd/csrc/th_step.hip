@@ -75,7 +75,6 @@ bool hash_window(const th_logic_uniforms &u, float pos_bound, const float *times
 
 }  // namespace
 
-// Build the launch parameters of one integrator pass and pick the kernel variant.
 // ---- one integrator pass = plan (host decisions, may synchronise) + enqueue (launches only) -------
 struct StepPlan {
     th::LogicParams p{};         // everything except in / out / perm / time_dev
@@ -166,15 +165,201 @@ static bool same_key(const th::LogicParams &a, const th::LogicParams &b)
            memcmp(&ua, &ub, sizeof ua) == 0 && a.s2_cap == b.s2_cap && a.pos_bound == b.pos_bound;
 }
 
-th_status thi::timing_events(th_context *c, hipEvent_t *k0, hipEvent_t *k1)
+th_status thi::LaunchTimer::begin(th_context *c, bool on)
 {
-    if (c->kt_used + 2 > c->kt_events.size()) {
+    if (!on || !c->kernel_timing) return TH_OK;
+    if (c->kt_used + 2 > c->kt_events.size()) {          // (timing_events: the next pair, made on first use)
         hipEvent_t a = nullptr, b = nullptr;
         TH_HIP(hipEventCreate(&a)); TH_HIP(hipEventCreate(&b));
         c->kt_events.push_back(a); c->kt_events.push_back(b);
     }
-    *k0 = c->kt_events[c->kt_used]; *k1 = c->kt_events[c->kt_used + 1];
+    hipEvent_t k0 = c->kt_events[c->kt_used]; k1 = c->kt_events[c->kt_used + 1];
     c->kt_used += 2;
+    TH_HIP(hipEventRecord(k0, c->stream));
+    return TH_OK;
+}
+th_status thi::LaunchTimer::end(th_context *c)
+{
+    if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+    return TH_OK;
+}
+
+// a lane only ever touches its own texel, so one of the two outputs may overwrite the input;
+// after m rotations of [cur, other]: m even -> [cur, other], m odd -> [other, cur]
+thi::FusedRoute thi::fused_route(th_context *c, int32_t m)
+{
+    float4 *cur = c->ring[0], *other = c->ring[1];
+    state_written(c, cur); state_written(c, other);
+    return {cur, (m & 1) ? other : cur, (m & 1) ? cur : other, other};
+}
+void thi::fused_routed(th_context *c, int32_t m)
+{
+    if (m & 1) std::swap(c->ring[0], c->ring[1]);
+    c->steps_since_sort += m; c->total_steps += m;
+}
+
+// ---- one pass, stage by stage (enqueue_step) ----------------------------------------------------
+struct StepSlots {               // what the stages hand on: the pass's buffers and what its slot plan decided
+    float4 *in = nullptr, *out = nullptr, *rt = nullptr;     // the input, the target, where the pass writes it (staging when packed)
+    int in_order = -1, out_order = -1;                       // the slot orders they are held in (-1: texel order)
+    // the sorted pass - first sort (in_order < 0), re-sort (scatter) or count in place - or the plain kernel over the slots (gather)
+    bool use_sorted = false, scatter = false, count = false, gather = false;
+    bool async = false, seeing = false;      // the re-sort runs beside the draws (asort_start); the pass notes what may touch the view
+};
+
+// Buffers and staging: the target (the ring rotated for TH_TARGET_RING) and the input - Particles.step binds buffers[1] as
+// `particles` (src/particles.js:139); a packed ring under an f32 kernel goes through f32 staging on both sides.
+static th_status step_buffers(th_context *c, bool packed_kernel, int32_t target, StepSlots &s)
+{
+    if (th_status st = resolve_target(c, target, true, &s.out)) return st;
+    s.in = c->ring[1]; s.rt = s.out;
+    if (c->packed && !packed_kernel) {
+        if (th_status st = unpacked_view(c, c->ring[1], 1, &s.in)) return st;
+        if (th_status st = render_target(c, s.out, 0, &s.rt)) return st;
+    }
+    return TH_OK;
+}
+
+// The slot plan of a packed ring: the plain grid-stride kernel over the sorted slots; a re-sort is a plain move of the input
+// (tile_hist, scan, tile_scatter into the spare buffer, which then takes the input's place in the ring).
+static th_status plan_packed_slots(th_context *c, th::LogicParams &p, StepSlots &s)
+{
+    const th::TileGeom g = tile_geom(c, p.u);
+    if (s.in_order < 0 || order_stale(c, s.in_order, g) || c->steps_since_sort >= c->opt.resort_steps) {
+        int fresh = -1;
+        th::TileSortParams b;
+        if (th_status st = begin_sort(c, g, s.in, s.in_order >= 0 ? c->orders[(size_t)s.in_order].perm : nullptr, &fresh, &b)) return st;
+        b.state_out = c->spare;
+        th::launch_tile_scatter(b, c->stream);
+        TH_HIP(hipGetLastError());
+        clear_graphs(c);               // captured sequences name the ring buffers: one of them changes places with the spare
+        // (a packed kernel's input is ring[1] itself, and no other ring element is that allocation)
+        ring_trade(c, c->ring[1], c->spare, fresh);
+        s.in = c->ring[1]; s.in_order = fresh;
+    }
+    p.perm = c->orders[(size_t)s.in_order].perm;
+    s.out_order = s.in_order;
+    return TH_OK;
+}
+
+// The slot plan of an f32 pass.  The input keeps its order; the output is written either at the same slots or - every
+// c->opt.resort_steps steps, and when the input is not sorted yet or was sorted for another view / field shape - at
+// the slots of a new sort keyed on the input positions (counted just before the launch).
+static th_status plan_f32_slots(th_context *c, const StepPlan &plan, int32_t target, th::LogicParams &p, StepSlots &s)
+{
+    const th::TileGeom g = tile_geom(c, p.u);
+    if (order_stale(c, s.in_order, g)) {   // the chunk table no longer describes the field: start over from texel order
+        if (th_status st = ensure_identity(c)) return st;
+        s.in = c->ring[1]; s.out = s.rt = c->ring[0];
+        s.in_order = -1;
+    }
+    // The re-sort of a frame loop (th_order.hip: asort_start): while draws over the slot order are going on, no step counts
+    // or scatters - the order laid out beside the last draw is taken up here, its copy of this step's input in the input's
+    // place - and the next one is started behind the step that is `resort_steps` launches on.
+    const bool drawing = c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps;
+    s.async = c->opt.async_sort && s.in_order >= 0 && plan.v.decoded && c->side && s.in == c->ring[1] && target == TH_TARGET_RING && drawing;
+    if (c->asort.pending) {
+        const bool take = s.async && c->asort.valid && c->asort.src == s.in && c->asort.src_order == s.in_order && c->asort.at_step == c->total_steps &&
+                          same_geom(c->orders[(size_t)c->asort.order].geom, g);
+        if (th_status st = take ? asort_take(c) : asort_drop(c)) return st;
+        if (take) { s.in = c->ring[1]; s.in_order = c->asort.order; }
+    }
+    s.scatter = !s.async && (s.in_order < 0 || c->steps_since_sort >= c->opt.resort_steps);
+    s.use_sorted = true;
+    // between two sorts the pass is the plain grid-stride kernel over the sorted slots (taps gathered from the
+    // decoded plane: a wave's taps fall into one neighbourhood); the chunk kernel counts and scatters around a re-sort
+    s.gather = !s.scatter && plan.v.decoded && (s.async || c->steps_since_sort + 1 < c->opt.resort_steps);
+    p.geom = g;
+    if (s.in_order >= 0) {
+        const th_context::SlotOrder &o = c->orders[(size_t)s.in_order];
+        p.perm = o.perm; p.chunks = o.chunks; p.nchunks = o.nchunks; p.records = o.records;
+    }
+    if (s.scatter) {
+        // counted by the pass that wrote `in`?  Then the histogram is complete and every chunk has its table.
+        const bool counted = s.in_order >= 0 && c->counted.buf == s.in && c->counted.order == s.in_order &&
+                             same_geom(c->counted.geom, g) && c->counted.at_step == c->total_steps;
+        set_order(c, s.out, -1);       // the output buffer's old content (and order) dies here
+        th::TileSortParams b;
+        if (th_status st = begin_sort(c, g, s.in, s.in_order >= 0 ? c->orders[(size_t)s.in_order].perm : nullptr, &s.out_order, &b, counted)) return st;
+        p.cursor = b.cursor; p.perm_out = b.perm_out;
+        p.use_records = counted ? 1u : 0u;
+        // draws over the slot order are going on (th_bins.hip): the pass moves its INPUT along to the new slots, so
+        // that buffers[0] and buffers[1] - the two ends of every line - stay in one order
+        if (s.in == c->ring[1] && drawing) p.in_moved = c->spare;
+    } else {
+        s.out_order = s.in_order;
+        s.count = !s.gather && c->steps_since_sort + 1 >= c->opt.resort_steps;      // the next pass will re-sort: count for it
+        if (s.count) {
+            if (th_status st = sort_storage(c)) return st;
+            p.hist = c->tile_mem;
+            TH_HIP(hipMemsetAsync(p.hist, 0, kTileWords / 2 * sizeof(uint32_t), c->stream));
+        }
+    }
+    return TH_OK;
+}
+
+// A frame loop: the plain kernel notes per 64 slots whether any of their lines - input position to output position - may
+// touch the view (LogicParams::seen); the draw that follows skips the blocks of 256 slots of which none may (44 % of the
+// bench's particles live outside the view, and the tile order keeps them together).  Hidden for sure = both ends beyond one
+// edge by more than 2 texels: more than a line of width <= 2 reaches (its diamonds: one texel) and its snapping moves.
+// Never inside a stream capture (th_step_n's graphs: time_dev set): the bytes would be allocated on a capturing thread, the
+// captured launch would keep writing them at every replay, and `seen` would describe a launch that has not run.
+static th_status step_sees(th_context *c, const StepPlan &plan, int32_t target, th::LogicParams &p, StepSlots &s)
+{
+    const float vx = p.u.viewSize[0], vy = p.u.viewSize[1];
+    if (!(c->opt.skip_unseen && !p.time_dev && target == TH_TARGET_RING && !c->packed && !plan.generic && (s.gather || !s.use_sorted) && s.rt == s.out &&
+          c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps && vx > 0.0f && vy > 0.0f && std::isfinite(vx) && std::isfinite(vy)))
+        return TH_OK;
+    if (!c->seen.bytes) {
+        const size_t bytes = ((c->texels() + 63) / 64 + 7) & ~(size_t)3;
+        if (th_status st = c->seen.bytes.alloc(bytes)) return st;
+        TH_HIP(hipMemsetAsync(c->seen.bytes, 0, bytes, c->stream));
+    }
+    const float mx = 4.0f / (float)c->fw, my = 4.0f / (float)c->fh;
+    p.seen = c->seen.bytes;
+    p.seen_xlo = (-1.0f - mx) / vx; p.seen_xhi = (1.0f + mx) / vx;
+    p.seen_ylo = (-1.0f - my) / vy; p.seen_yhi = (1.0f + my) / vy;
+    s.seeing = true;
+    return TH_OK;
+}
+
+// the kernel the plan asks for, between the th_kernel_timing events (`timing`: never inside a capture)
+static th_status launch_step(th_context *c, const StepPlan &plan, bool timing, const th::LogicParams &p, const StepSlots &s)
+{
+    LaunchTimer timer;
+    if (th_status st = timer.begin(c, timing)) return st;
+    if (s.use_sorted && !s.gather) {
+        const th::SortedPass pass = s.in_order < 0 ? th::SortedPass::first_sort : s.scatter ? th::SortedPass::resort : th::SortedPass::count_in_place;
+        th::launch_logic_sorted(p, plan.v, pass, c->max_chunks, c->stream);
+    } else if (plan.generic)
+        th::launch_logic_generic(p, c->stream);
+    else
+        th::launch_logic(p, plan.v, c->stream);
+    if (th_status st = timer.end(c)) return st;
+    TH_HIP(hipGetLastError());
+    return TH_OK;
+}
+
+// behind the launch: the output's order, the moved input, the packed commit, what the pass saw and counted, the next re-sort
+static th_status step_done(th_context *c, bool packed_kernel, int32_t target, const th::LogicParams &p, const StepSlots &s)
+{
+    if (target == TH_TARGET_RING || (target >= 0 && target < (int32_t)c->ring.size())) set_order(c, s.out, s.out_order);
+    if (p.in_moved) {                       // the moved copy takes the input's place in the ring
+        clear_graphs(c);
+        ring_trade(c, c->ring[1], c->spare, s.out_order);
+    }
+    if (c->packed && !packed_kernel)
+        if (th_status st = commit_target(c, s.out, s.rt)) return st;
+    if (s.seeing) {
+        c->seen.cur = s.out; c->seen.prev = s.in; c->seen.order = s.out_order;
+        c->seen.stamp = s.out_order >= 0 ? c->orders[(size_t)s.out_order].stamp : 0ull;
+        c->seen.view_x = p.u.viewSize[0]; c->seen.view_y = p.u.viewSize[1]; c->seen.fw = c->fw; c->seen.fh = c->fh;
+    }
+    ++c->steps_since_sort; ++c->total_steps;
+    if (s.count) { c->counted.buf = s.out; c->counted.order = s.out_order; c->counted.geom = p.geom; c->counted.at_step = c->total_steps; }
+    else c->counted.buf = nullptr;
+    if (s.async && !c->asort.pending && s.out_order >= 0 && c->steps_since_sort >= c->opt.resort_steps)
+        return asort_start(c, p.geom, s.out, s.out_order);
     return TH_OK;
 }
 
@@ -185,318 +370,119 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
                               bool timing, bool sorted = false)
 {
     th::LogicParams p = plan.p;
-    float4 *out = nullptr;
-    if (th_status s = resolve_target(c, target, true, &out)) return s;
     const bool packed_kernel = plan.v.format == th::StateFormat::packed;      // (else a packed ring goes through f32 staging)
-    float4 *in = c->ring[1], *rt = out;     // Particles.step binds buffers[1] as `particles` (src/particles.js:139)
-    if (c->packed && !packed_kernel) {
-        if (th_status s = unpacked_view(c, c->ring[1], 1, &in)) return s;
-        if (th_status s = render_target(c, out, 0, &rt)) return s;
-    }
-    p.in = in;
-    p.out = rt;
+    StepSlots s;
+    if (th_status st = step_buffers(c, packed_kernel, target, s)) return st;
     p.u.time = time;
     p.time_dev = time_dev;
-
-    // Sorted slots.  The input keeps its order; the output is written either at the same slots or - every
-    // c->opt.resort_steps steps, and when the input is not sorted yet or was sorted for another view / field shape - at
-    // the slots of a new sort keyed on the input positions (counted just before the launch).
-    int in_order = sorted ? order_of(c, in) : -1, out_order = -1;
-    bool use_sorted = false, scatter = false, count = false, gather = false;
-    if (c->asort.pending && (!sorted || packed_kernel)) if (th_status s = asort_drop(c)) return s;
-    bool async = false;
-    if (sorted && packed_kernel) {
-        // packed ring: the plain grid-stride kernel over the sorted slots; a re-sort is a plain move of the input
-        // (tile_hist, scan, tile_scatter into the spare buffer, which then takes the input's place in the ring)
-        const th::TileGeom g = tile_geom(c, p.u);
-        const bool stale = in_order >= 0 && (!same_geom(c->orders[(size_t)in_order].geom, g) ||
-                                             c->orders[(size_t)in_order].fw != c->fw || c->orders[(size_t)in_order].fh != c->fh);
-        if (in_order < 0 || stale || c->steps_since_sort >= c->opt.resort_steps) {
-            int fresh = -1;
-            th::TileSortParams b;
-            if (th_status s = begin_sort(c, g, in, in_order >= 0 ? c->orders[(size_t)in_order].perm : nullptr, &fresh, &b)) return s;
-            b.state_out = c->spare;
-            th::launch_tile_scatter(b, c->stream);
-            TH_HIP(hipGetLastError());
-            clear_graphs(c);               // captured sequences name the ring buffers: one of them changes places with the spare
-            float4 *old = in;
-            state_moved(c, old, c->spare);
-            for (float4 *&r : c->ring) if (r == old) r = c->spare;
-            c->spare = old;
-            set_order(c, old, -1);
-            in = c->ring[1];
-            set_order(c, in, fresh);
-            p.in = in;
-            in_order = fresh;
-        }
-        p.perm = c->orders[(size_t)in_order].perm;
-        out_order = in_order;
-    } else if (sorted) {
-        const th::TileGeom g = tile_geom(c, p.u);
-        const bool stale = in_order >= 0 && (!same_geom(c->orders[(size_t)in_order].geom, g) ||
-                                             c->orders[(size_t)in_order].fw != c->fw || c->orders[(size_t)in_order].fh != c->fh);
-        if (stale) {                       // the chunk table no longer describes the field: start over from texel order
-            if (th_status s = ensure_identity(c)) return s;
-            in = c->ring[1]; out = rt = c->ring[0];
-            p.in = in; p.out = rt;
-            in_order = -1;
-        }
-        // The re-sort of a frame loop (th_order.hip: asort_start): while draws over the slot order are going on, no step counts
-        // or scatters - the order laid out beside the last draw is taken up here, its copy of this step's input in the input's
-        // place - and the next one is started behind the step that is `resort_steps` launches on.
-        async = c->opt.async_sort && in_order >= 0 && plan.v.decoded && c->side && in == c->ring[1] && target == TH_TARGET_RING &&
-                c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps;
-        if (c->asort.pending) {
-            const bool take = async && c->asort.valid && c->asort.src == in && c->asort.src_order == in_order && c->asort.at_step == c->total_steps &&
-                              same_geom(c->orders[(size_t)c->asort.order].geom, g);
-            if (!take) { if (th_status s = asort_drop(c)) return s; }
-            else {
-                TH_HIP(hipStreamWaitEvent(c->stream, c->asort.done, 0));
-                clear_graphs(c);               // captured sequences name the ring buffers: one of them changes places with the copy
-                float4 *old = in, *copy = c->asort.dst;
-                const int fresh = c->asort.order;
-                c->asort.pending = c->asort.valid = false;
-                c->asort.src = nullptr;
-                set_order(c, old, -1);
-                state_moved(c, old, copy);
-                c->ring[1] = copy; c->asort.dst = old;
-                set_order(c, copy, fresh);
-                in = copy; p.in = in; in_order = fresh;
-                c->steps_since_sort = 0;
-            }
-        }
-        scatter = !async && (in_order < 0 || c->steps_since_sort >= c->opt.resort_steps);
-        use_sorted = true;
-        // between two sorts the pass is the plain grid-stride kernel over the sorted slots (taps gathered from the
-        // decoded plane: a wave's taps fall into one neighbourhood); the chunk kernel counts and scatters around a re-sort
-        gather = !scatter && plan.v.decoded && (async || c->steps_since_sort + 1 < c->opt.resort_steps);
-        p.geom = g;
-        if (in_order >= 0) {
-            const th_context::SlotOrder &o = c->orders[(size_t)in_order];
-            p.perm = o.perm; p.chunks = o.chunks; p.nchunks = o.nchunks; p.records = o.records;
-        }
-        if (scatter) {
-            // counted by the pass that wrote `in`?  Then the histogram is complete and every chunk has its table.
-            const bool counted = in_order >= 0 && c->counted.buf == in && c->counted.order == in_order &&
-                                 same_geom(c->counted.geom, g) && c->counted.at_step == c->total_steps;
-            set_order(c, out, -1);         // the output buffer's old content (and order) dies here
-            th::TileSortParams b;
-            if (th_status s = begin_sort(c, g, in, in_order >= 0 ? c->orders[(size_t)in_order].perm : nullptr, &out_order, &b, counted)) return s;
-            p.cursor = b.cursor; p.perm_out = b.perm_out;
-            p.use_records = counted ? 1u : 0u;
-            // draws over the slot order are going on (th_bins.hip): the pass moves its INPUT along to the new slots, so
-            // that buffers[0] and buffers[1] - the two ends of every line - stay in one order
-            if (in == c->ring[1] && c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps) p.in_moved = c->spare;
-        } else {
-            out_order = in_order;
-            count = !gather && c->steps_since_sort + 1 >= c->opt.resort_steps;      // the next pass will re-sort: count for it
-            if (count) {
-                if (th_status s = sort_storage(c)) return s;
-                p.hist = c->tile_mem;
-                TH_HIP(hipMemsetAsync(p.hist, 0, kTileWords / 2 * sizeof(uint32_t), c->stream));
-            }
-        }
-    }
-
+    s.in_order = sorted ? order_of(c, s.in) : -1;
+    if (c->asort.pending && (!sorted || packed_kernel)) if (th_status st = asort_drop(c)) return st;
+    if (sorted)
+        if (th_status st = packed_kernel ? plan_packed_slots(c, p, s) : plan_f32_slots(c, plan, target, p, s)) return st;
+    p.in = s.in;
+    p.out = s.rt;
     if (plan.v.decoded)
         th::launch_flow_decode(c->flow, c->flow_dec, (size_t)c->fw * c->fh, time, time_dev, p.u.flowDecay, c->stream);
+    if (th_status st = step_sees(c, plan, target, p, s)) return st;
+    if (th_status st = launch_step(c, plan, timing, p, s)) return st;
+    return step_done(c, packed_kernel, target, p, s);
+}
 
-    // A frame loop: the plain kernel notes per 64 slots whether any of their lines - input position to output position - may
-    // touch the view (LogicParams::seen); the draw that follows skips the blocks of 256 slots of which none may (44 % of the
-    // bench's particles live outside the view, and the tile order keeps them together).  Hidden for sure = both ends beyond one
-    // edge by more than 2 texels: more than a line of width <= 2 reaches (its diamonds: one texel) and its snapping moves.
-    // Never inside a stream capture (th_step_n's graphs: time_dev set): the bytes would be allocated on a capturing thread, the
-    // captured launch would keep writing them at every replay, and `seen` would describe a launch that has not run.
-    bool seeing = false;
-    const float vx = p.u.viewSize[0], vy = p.u.viewSize[1];
-    if (c->opt.skip_unseen && !time_dev && target == TH_TARGET_RING && !c->packed && !plan.generic && (gather || !use_sorted) && rt == out &&
-        c->total_steps - c->last_binned_draw <= 2ll * c->opt.resort_steps && vx > 0.0f && vy > 0.0f && std::isfinite(vx) && std::isfinite(vy)) {
-        if (!c->seen.bytes) {
-            const size_t bytes = ((c->texels() + 63) / 64 + 7) & ~(size_t)3;
-            if (th_status s = c->seen.bytes.alloc(bytes)) return s;
-            TH_HIP(hipMemsetAsync(c->seen.bytes, 0, bytes, c->stream));
-        }
-        const float mx = 4.0f / (float)c->fw, my = 4.0f / (float)c->fh;
-        p.seen = c->seen.bytes;
-        p.seen_xlo = (-1.0f - mx) / vx; p.seen_xhi = (1.0f + mx) / vx;
-        p.seen_ylo = (-1.0f - my) / vy; p.seen_yhi = (1.0f + my) / vy;
-        seeing = true;
-    }
-
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    if (timing && c->kernel_timing) {
-        if (th_status s = timing_events(c, &k0, &k1)) return s;
-        TH_HIP(hipEventRecord(k0, c->stream));
-    }
-    if (use_sorted && !gather) {
-        const th::SortedPass pass = in_order < 0 ? th::SortedPass::first_sort : scatter ? th::SortedPass::resort : th::SortedPass::count_in_place;
-        th::launch_logic_sorted(p, plan.v, pass, c->max_chunks, c->stream);
-    } else if (plan.generic)
-        th::launch_logic_generic(p, c->stream);
-    else
-        th::launch_logic(p, plan.v, c->stream);
-    if (k1) TH_HIP(hipEventRecord(k1, c->stream));
+// ---- th_step_n's three paths --------------------------------------------------------------------
+// Slot layout of the fused passes: the newest state (ring[0]) may be in a tile-sorted order; both outputs of a
+// pass keep the slots of its input.  (Re)sorted every c->opt.rebucket_steps steps by a plain move into the other
+// buffer, whose content (state n-1 of the previous call) the pass overwrites anyway.
+static th_status fused_slots(th_context *c, const StepPlan &plan)
+{
+    if (!plan.may_sort) return ensure_identity(c);
+    const th::TileGeom g = tile_geom(c, plan.p.u);
+    const int o = order_of(c, c->ring[0]);
+    if (o >= 0 && !order_stale(c, o, g) && c->steps_since_sort < c->opt.rebucket_steps) return TH_OK;
+    float4 *cur = c->ring[0], *other = c->ring[1];
+    set_order(c, other, -1);
+    int fresh = -1;
+    th::TileSortParams b;
+    if (th_status s = begin_sort(c, g, cur, o >= 0 ? c->orders[(size_t)o].perm : nullptr, &fresh, &b)) return s;
+    b.state_out = other;
+    th::launch_tile_scatter(b, c->stream);
     TH_HIP(hipGetLastError());
-    if (target == TH_TARGET_RING || (target >= 0 && target < (int32_t)c->ring.size())) set_order(c, out, out_order);
-    if (p.in_moved) {                       // the moved copy takes the input's place in the ring
-        clear_graphs(c);
-        float4 *old = c->ring[1];
-        set_order(c, old, -1);
-        state_moved(c, old, c->spare);
-        c->ring[1] = c->spare; c->spare = old;
-        set_order(c, c->ring[1], out_order);
-    }
-    if (c->packed && !packed_kernel)
-        if (th_status s = commit_target(c, out, rt)) return s;
-    if (seeing) {
-        c->seen.cur = out; c->seen.prev = in; c->seen.order = out_order;
-        c->seen.stamp = out_order >= 0 ? c->orders[(size_t)out_order].stamp : 0ull;
-        c->seen.view_x = vx; c->seen.view_y = vy; c->seen.fw = c->fw; c->seen.fh = c->fh;
-    }
-    ++c->steps_since_sort; ++c->total_steps;
-    if (count) { c->counted.buf = out; c->counted.order = out_order; c->counted.geom = p.geom; c->counted.at_step = c->total_steps; }
-    else c->counted.buf = nullptr;
-    if (async && !c->asort.pending && out_order >= 0 && c->steps_since_sort >= c->opt.resort_steps)
-        if (th_status s = asort_start(c, p.geom, out, out_order)) return s;
+    set_order(c, other, fresh);
+    set_order(c, cur, -1);                 // (its content is dead: the sorted copy is the newest state now)
+    state_written(c, other); state_moved(c, cur, other);
+    c->ring[0] = other; c->ring[1] = cur;
     return TH_OK;
 }
 
-extern "C" {
-
-th_status th_step(th_context *c, const th_logic_uniforms *u, int32_t target)
+// Temporal fusion (logic_fused_kernel): all n steps of a particle in one pass, <= kMaxFusedSteps per launch.
+static th_status step_n_fused(th_context *c, const StepPlan &plan, const std::vector<float> &times, int32_t n)
 {
-    if (th_status s = use(c)) return s;
-    TH_REQUIRE(u, "null uniforms");
-    // Particles.step reads this.buffers[1] (src/particles.js:139): needs >= 2 buffers
-    TH_REQUIRE(c->ring.size() >= 2, "step needs at least 2 state buffers (have %zu)", c->ring.size());
-    StepPlan plan;
-    if (th_status s = plan_step(c, *u, target, plan)) return s;
-    const bool sorted = plan.may_sort && !plan.generic;
-    if (!sorted) { if (th_status s = asort_drop(c)) return s; if (th_status s = ensure_identity(c)) return s; }
-    return enqueue_step(c, plan, target, u->time, nullptr, true, sorted);
+    if (th_status s = fused_slots(c, plan)) return s;
+    // The field does not change inside the call.  Without the noise the pass waits for its taps (a dependent gather per
+    // step): the field's x, y, z packed 12 B apart once per call - three quarters of the footprint, and the band one
+    // XCD taps fits its L2 (0.574 -> 0.546 ms per 20-step launch at C3; with the noise on the pass is bound by its
+    // arithmetic and the packing pass only costs: 1.829 against 1.818 + 0.01)
+    const bool pack3 = th::fused_taps_flow3(plan.v);
+    if (pack3) {
+        if (!c->flow3) if (th_status s = c->flow3.alloc((size_t)c->fw * c->fh * 3)) return s;
+        th::launch_flow_pack3(c->flow, c->flow3, (size_t)c->fw * c->fh, c->stream);
+    }
+    for (int32_t done = 0; done < n;) {
+        const int32_t m = std::min<int32_t>(n - done, (int32_t)th::kMaxFusedSteps);
+        th::LogicParams p = plan.p;
+        p.flow3 = pack3 ? c->flow3 : nullptr;
+        const int order = order_of(c, c->ring[0]);
+        const FusedRoute r = fused_route(c, m);
+        p.in = r.in;
+        p.out = r.out;                             // state m     (ends up in buffers[0])
+        p.out_prev = r.out_prev;                   // state m - 1 (ends up in buffers[1]; m == 1: state 0 back into its own buffer)
+        p.perm = order >= 0 ? c->orders[(size_t)order].perm : nullptr;
+        p.nsteps = (uint32_t)m;
+        for (int32_t k = 0; k < m; ++k) p.times[k] = times[(size_t)(done + k)];
+        const bool window = plan.v.noise && plan.v.mode != TH_MODE_FAST && c->opt.hash_window && hash_window(p.u, p.pos_bound, p.times, m, &p.win_bound, p.win_k);
+        if (window) p.win = c->win_block;
+        // the last launch of the call takes the statistics of the state it leaves in buffers[0] (a packed ring's: of
+        // what the stored texels decode to)
+        const bool takes_stats = done + m == n;
+        if (takes_stats) {
+            const uint32_t parts = th::fused_stats_parts(p.count, p.perm != nullptr), need = parts + (parts + 255u) / 256u + 16u;
+            if (c->fused_parts.size() < need) {
+                TH_HIP(hipStreamSynchronize(c->stream));
+                // (no memset, here or in front of a launch: every wave writes its partial - an empty one where it met no particle)
+                if (th_status s = c->fused_parts.alloc(need)) return s;
+            }
+            p.stats_part = c->fused_parts;
+            c->fused_stats.nparts = parts; c->fused_stats.limit = p.u.speedLimit;
+        }
+        LaunchTimer timer;
+        if (th_status s = timer.begin(c)) return s;
+        th::launch_logic_fused(p, plan.v, c->stream);
+        if (th_status s = timer.end(c)) return s;
+        TH_HIP(hipGetLastError());
+        if (window) ++c->hash_window_launches;
+        set_order(c, r.other, order);              // both outputs sit at the input's slots
+        c->counted.buf = nullptr;
+        fused_routed(c, m);
+        done += m;
+        if (takes_stats) { c->fused_stats.valid = true; c->fused_stats.buf = c->ring[0]; }
+    }
+    return TH_OK;
 }
 
-// n fixed-step Tendrils.step() calls.  The launch sequence (2 kernels per step) is captured once into
-// a hipGraph per (n, uniforms, ring order, layout) and replayed; the per-step `time` values live in a
-// small device array refreshed before every replay, so replays need no node updates.
-th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, double dt_ms, int32_t n)
+// step by step, in texel order: one plan per step (the domain checks see every step's time)
+static th_status step_n_single(th_context *c, th_logic_uniforms v, StepPlan &plan, const std::vector<float> &times, int32_t n)
 {
-    if (th_status s = use(c)) return s;
-    TH_REQUIRE(u && n >= 0, "bad arguments");
-    TH_REQUIRE(c->ring.size() >= 2, "step needs at least 2 state buffers (have %zu)", c->ring.size());
-    if (n == 0) return TH_OK;
-    if (th_status s = asort_drop(c)) return s;          // (a frame loop's re-sort under way: these launches lay their own orders out)
-    th_logic_uniforms v = *u;
-    v.dt = (float)dt_ms;
-    std::vector<float> times((size_t)n);
-    double t = time0, tmax = 0.0;
     for (int32_t k = 0; k < n; ++k) {
-        t += dt_ms;                                   // src/timer.js:28-31: time accumulates in double
-        times[(size_t)k] = (float)t;
-        if (std::fabs(t) > std::fabs(tmax)) tmax = t;
+        if (k) { v.time = times[(size_t)k]; if (th_status s = plan_step(c, v, TH_TARGET_RING, plan)) return s; }
+        if (th_status s = enqueue_step(c, plan, TH_TARGET_RING, times[(size_t)k], nullptr, true)) return s;
     }
-    v.time = (float)tmax;
-    StepPlan plan;
-    if (th_status s = plan_step(c, v, TH_TARGET_RING, plan)) return s;
+    return TH_OK;
+}
 
-    // Temporal fusion (logic_fused_kernel): all n steps of a particle in one pass, <= kMaxFusedSteps per launch.
-    // Needs the plain 2-buffer ring (only the last two states survive n rotations) and the specialised kernel;
-    // both ring formats.  th_options::fuse = 0 turns it off (the tests compare both paths).
-    if (c->opt.fuse && n >= 2 && c->ring.size() == 2 && !plan.generic) {
-        // Slot layout of the fused passes: the newest state (ring[0]) may be in a tile-sorted order; both outputs of a
-        // pass keep the slots of its input.  (Re)sorted every c->opt.rebucket_steps steps by a plain move into the other
-        // buffer, whose content (state n-1 of the previous call) the pass overwrites anyway.
-        if (plan.may_sort) {
-            const th::TileGeom g = tile_geom(c, plan.p.u);
-            int o = order_of(c, c->ring[0]);
-            const bool stale = o >= 0 && (!same_geom(c->orders[(size_t)o].geom, g) || c->orders[(size_t)o].fw != c->fw ||
-                                          c->orders[(size_t)o].fh != c->fh);
-            if (o < 0 || stale || c->steps_since_sort >= c->opt.rebucket_steps) {
-                float4 *cur = c->ring[0], *other = c->ring[1];
-                set_order(c, other, -1);
-                int fresh = -1;
-                th::TileSortParams b;
-                if (th_status s = begin_sort(c, g, cur, o >= 0 ? c->orders[(size_t)o].perm : nullptr, &fresh, &b)) return s;
-                b.state_out = other;
-                th::launch_tile_scatter(b, c->stream);
-                TH_HIP(hipGetLastError());
-                set_order(c, other, fresh);
-                set_order(c, cur, -1);                 // (its content is dead: the sorted copy is the newest state now)
-                state_written(c, other); state_moved(c, cur, other);
-                c->ring[0] = other; c->ring[1] = cur;
-            }
-        } else if (th_status s = ensure_identity(c)) return s;
-        // The field does not change inside the call.  Without the noise the pass waits for its taps (a dependent gather per
-        // step): the field's x, y, z packed 12 B apart once per call - three quarters of the footprint, and the band one
-        // XCD taps fits its L2 (0.574 -> 0.546 ms per 20-step launch at C3; with the noise on the pass is bound by its
-        // arithmetic and the packing pass only costs: 1.829 against 1.818 + 0.01)
-        const bool pack3 = th::fused_taps_flow3(plan.v);
-        if (pack3) {
-            if (!c->flow3) if (th_status s = c->flow3.alloc((size_t)c->fw * c->fh * 3)) return s;
-            th::launch_flow_pack3(c->flow, c->flow3, (size_t)c->fw * c->fh, c->stream);
-        }
-        {
-            int32_t done = 0;
-            while (done < n) {
-                const int32_t m = std::min<int32_t>(n - done, (int32_t)th::kMaxFusedSteps);
-                th::LogicParams p = plan.p;
-                p.flow3 = pack3 ? c->flow3 : nullptr;
-                float4 *cur = c->ring[0], *other = c->ring[1];
-                const int order = order_of(c, cur);
-                state_written(c, cur); state_written(c, other);
-                p.in = cur;
-                // a lane only ever touches its own texel, so one of the two outputs may overwrite the input;
-                // after m rotations of [cur, other]: m even -> [cur, other], m odd -> [other, cur]
-                p.out = (m & 1) ? other : cur;             // state m     (ends up in buffers[0])
-                p.out_prev = (m & 1) ? cur : other;        // state m - 1 (ends up in buffers[1])
-                p.perm = order >= 0 ? c->orders[(size_t)order].perm : nullptr;
-                p.nsteps = (uint32_t)m;
-                for (int32_t k = 0; k < m; ++k) p.times[k] = times[(size_t)(done + k)];
-                const bool window = plan.v.noise && plan.v.mode != TH_MODE_FAST && c->opt.hash_window && hash_window(p.u, p.pos_bound, p.times, m, &p.win_bound, p.win_k);
-                if (window) p.win = c->win_block;
-                // the last launch of the call takes the statistics of the state it leaves in buffers[0] (a packed ring's: of
-                // what the stored texels decode to)
-                const bool takes_stats = done + m == n;
-                if (takes_stats) {
-                    const uint32_t parts = th::fused_stats_parts(p.count, p.perm != nullptr), need = parts + (parts + 255u) / 256u + 16u;
-                    if (c->fused_parts.size() < need) {
-                        TH_HIP(hipStreamSynchronize(c->stream));
-                        // (no memset, here or in front of a launch: every wave writes its partial - an empty one where it met no particle)
-                        if (th_status s = c->fused_parts.alloc(need)) return s;
-                    }
-                    p.stats_part = c->fused_parts;
-                    c->fused_stats.nparts = parts; c->fused_stats.limit = p.u.speedLimit;
-                }
-                hipEvent_t k0 = nullptr, k1 = nullptr;
-                if (c->kernel_timing) {
-                    if (th_status s = timing_events(c, &k0, &k1)) return s;
-                    TH_HIP(hipEventRecord(k0, c->stream));
-                }
-                th::launch_logic_fused(p, plan.v, c->stream);
-                if (k1) TH_HIP(hipEventRecord(k1, c->stream));
-                TH_HIP(hipGetLastError());
-                if (window) ++c->hash_window_launches;
-                set_order(c, other, order);                // both outputs sit at the input's slots
-                c->counted.buf = nullptr;
-                if (m & 1) { c->ring[0] = other; c->ring[1] = cur; }
-                c->steps_since_sort += m; c->total_steps += m;
-                done += m;
-                if (takes_stats) { c->fused_stats.valid = true; c->fused_stats.buf = c->ring[0]; }
-            }
-            return TH_OK;
-        }
-    }
-
-    // everything below runs in texel order
-    if (th_status s = ensure_identity(c)) return s;
-    if (!c->opt.graph || n < 2 || (c->packed && plan.generic)) {
-        for (int32_t k = 0; k < n; ++k) {
-            if (k) { v.time = times[(size_t)k]; if (th_status s = plan_step(c, v, TH_TARGET_RING, plan)) return s; }
-            if (th_status s = enqueue_step(c, plan, TH_TARGET_RING, times[(size_t)k], nullptr, true)) return s;
-        }
-        return TH_OK;
-    }
-
+// The launch sequence (2 kernels per step) is captured once into a hipGraph per (n, uniforms, ring order, layout) and
+// replayed; the per-step `time` values live in a small device array refreshed before every replay, so replays need no
+// node updates.
+static th_status step_n_graph(th_context *c, const StepPlan &plan, const std::vector<float> &times, int32_t n)
+{
     // cache lookup: same n, same parameters (time excluded), same ring order and layout
     th::LogicParams key = plan.p;
     key.u.time = 0.0f;
@@ -528,8 +514,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
         c->total_steps = total_before;
         if (e != hipSuccess || st != TH_OK) {
             destroy_graph(g);
-            if (st != TH_OK) return st;
-            return fail(TH_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e));
+            return st != TH_OK ? st : fail(TH_ERR_HIP, "graph capture failed: %s", hipGetErrorString(e));
         }
         c->graphs.push_back(std::move(g));
         hit = &c->graphs.back();
@@ -538,11 +523,7 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
     memcpy(hit->times_host, times.data(), (size_t)n * sizeof(float));
     TH_HIP(hipMemcpyAsync(hit->times_dev, hit->times_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     TH_HIP(hipGraphLaunch(hit->exec, c->stream));
-    for (int32_t k = 0; k < n; ++k) {                  // host-side ring bookkeeping of the n rotations
-        float4 *last = c->ring.back();
-        c->ring.pop_back();
-        c->ring.insert(c->ring.begin(), last);
-    }
+    for (int32_t k = 0; k < n; ++k) (void)ring_rotate(c);      // host-side ring bookkeeping of the n rotations
     // the replay wrote the buffers the capture's resolve_target() calls named - at capture time only: what is remembered of
     // their content (a step's `seen` bytes, a gathered copy, a re-sort's copy) ends here, as it does behind a plain step
     for (float4 *r : c->ring) state_written(c, r);
@@ -550,6 +531,49 @@ th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, dou
     // times_host must stay untouched until the copy has run; a later replay of this entry waits here
     TH_HIP(hipEventRecord(hit->copied, c->stream));
     return TH_OK;
+}
+
+extern "C" {
+
+th_status th_step(th_context *c, const th_logic_uniforms *u, int32_t target)
+{
+    if (th_status s = use(c)) return s;
+    TH_REQUIRE(u, "null uniforms");
+    // Particles.step reads this.buffers[1] (src/particles.js:139): needs >= 2 buffers
+    TH_REQUIRE(c->ring.size() >= 2, "step needs at least 2 state buffers (have %zu)", c->ring.size());
+    StepPlan plan;
+    if (th_status s = plan_step(c, *u, target, plan)) return s;
+    const bool sorted = plan.may_sort && !plan.generic;
+    if (!sorted) { if (th_status s = asort_drop(c)) return s; if (th_status s = ensure_identity(c)) return s; }
+    return enqueue_step(c, plan, target, u->time, nullptr, true, sorted);
+}
+
+// n fixed-step Tendrils.step() calls: fused launches, or single steps - replayed from a captured graph where that is on.
+th_status th_step_n(th_context *c, const th_logic_uniforms *u, double time0, double dt_ms, int32_t n)
+{
+    if (th_status s = use(c)) return s;
+    TH_REQUIRE(u && n >= 0, "bad arguments");
+    TH_REQUIRE(c->ring.size() >= 2, "step needs at least 2 state buffers (have %zu)", c->ring.size());
+    if (n == 0) return TH_OK;
+    if (th_status s = asort_drop(c)) return s;          // (a frame loop's re-sort under way: these launches lay their own orders out)
+    th_logic_uniforms v = *u;
+    v.dt = (float)dt_ms;
+    std::vector<float> times((size_t)n);
+    double t = time0, tmax = 0.0;
+    for (int32_t k = 0; k < n; ++k) {
+        t += dt_ms;                                   // src/timer.js:28-31: time accumulates in double
+        times[(size_t)k] = (float)t;
+        if (std::fabs(t) > std::fabs(tmax)) tmax = t;
+    }
+    v.time = (float)tmax;
+    StepPlan plan;
+    if (th_status s = plan_step(c, v, TH_TARGET_RING, plan)) return s;
+    // Fusion needs the plain 2-buffer ring (only the last two states survive n rotations) and the specialised kernel;
+    // both ring formats.  th_options::fuse = 0 turns it off (the tests compare both paths).
+    if (c->opt.fuse && n >= 2 && c->ring.size() == 2 && !plan.generic) return step_n_fused(c, plan, times, n);
+    if (th_status s = ensure_identity(c)) return s;     // everything else runs in texel order
+    if (!c->opt.graph || n < 2 || (c->packed && plan.generic)) return step_n_single(c, v, plan, times, n);
+    return step_n_graph(c, plan, times, n);
 }
 
 }  // extern "C"

@@ -40,11 +40,10 @@ static_assert(th::kMaxFusedSteps == 32 && sizeof(StepArgs) == 224 && offsetof(St
 // one launch of th_step_kernel (th_kernel_timing: an event pair around it, as around every logic launch)
 th_status step_launch(th_context *c, hipFunction_t fn, KernArgs &k)
 {
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    if (c->kernel_timing) { if (th_status s = timing_events(c, &k0, &k1)) return s; TH_HIP(hipEventRecord(k0, c->stream)); }
+    LaunchTimer timer;
+    if (th_status s = timer.begin(c)) return s;
     if (th_status s = program_launch(c, fn, c->texels(), k)) return s;
-    if (k1) TH_HIP(hipEventRecord(k1, c->stream));
-    return TH_OK;
+    return timer.end(c);
 }
 
 }  // namespace
@@ -92,17 +91,16 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
     if (c->opt.fuse && c->ring.size() == 2 && !c->packed) {
         for (int32_t done = 0; done < n;) {
             const int32_t steps = std::min<int32_t>(n - done, (int32_t)th::kMaxFusedSteps);
-            float4 *cur = c->ring[0], *other = c->ring[1];
-            state_written(c, cur); state_written(c, other);
-            // after `steps` rotations of [cur, other]: even -> [cur, other], odd -> [other, cur] (th_step_n)
-            a.in = cur;
-            a.out = (steps & 1) ? other : cur;                                   // state `steps`     (ends up in buffers[0])
-            a.out_prev = steps == 1 ? nullptr : (steps & 1) ? cur : other;       // state `steps` - 1 (ends up in buffers[1])
+            const FusedRoute r = fused_route(c, steps);
+            a.in = r.in;
+            a.out = r.out;                                           // state `steps`     (ends up in buffers[0])
+            // state `steps` - 1 (ends up in buffers[1]) - of a single step it is the input, where it lies: a step program
+            // stores none (the built-in kernel always does)
+            a.out_prev = steps == 1 ? nullptr : r.out_prev;
             a.nsteps = (uint32_t)steps; a.step0 = (uint32_t)done;
             for (int32_t j = 0; j < steps; ++j) a.times[j] = times[(size_t)(done + j)];
             if (th_status s = step_launch(c, m->fn, k)) return s;
-            if (steps & 1) { c->ring[0] = other; c->ring[1] = cur; }
-            c->steps_since_sort += steps; c->total_steps += steps;
+            fused_routed(c, steps);
             done += steps;
         }
     } else {
