@@ -2144,6 +2144,14 @@ void launch_bins_blend(const DepositParams &p, hipStream_t s)
     else hipLaunchKernelGGL(bins_blend_kernel<2>, dim3(p.nbins), dim3(256), 0, s, p);
 }
 size_t crowd_words_per_bin() { return 7u * kBinTexels + 1u; }       // counts, cursors, starts (+ 1), the long list, the giants' list, the giants' windows (2)
+size_t crowd_count_words(size_t bins) { return bins * kBinTexels; }    // (the first of them: the words that start from zero)
+// ... and where those arrays lie in `mem`, room for `bins` large bins
+void crowd_carve(DepositParams &p, uint32_t *mem, size_t bins)
+{
+    p.crowd_count = mem; p.crowd_cursor = p.crowd_count + bins * kBinTexels; p.crowd_start = p.crowd_cursor + bins * kBinTexels;
+    p.crowd_long = p.crowd_start + bins * (kBinTexels + 1u); p.crowd_giant = p.crowd_long + bins * kBinTexels;
+    p.crowd_giant_win = p.crowd_giant + bins * kBinTexels;
+}
 
 }  // namespace th
 

@@ -463,7 +463,6 @@ float drawn_line_width(const th_context *c, int pass);
 // a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list)
 th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
-th_status deposit_count(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
 th_status deposit_temp(th_context *c, size_t need);
 // the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, sort by texel, blend
@@ -482,7 +481,31 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
 void bins_pass_expect(th_context *c, th::DepositParams &p);          // before the plan's kernels are launched with p ...
 th_status bins_pass_totals(th_context *c, const th::DepositParams &p);  // ... their totals in c->bins_totals_host
 th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragments, bool blended_early);
+// the flags of an emitting / laying-out attempt that is not worth another one: anything but a dry pool or a full bin, or six attempts
+inline bool bins_flags_final(uint32_t flags, int attempt) { return (flags & ~(th::kBinsPoolExhausted | th::kBinsBinFull)) || attempt >= 6; }
 bool binned_shards(const th_context *c);              // a sharded draw() of this job goes through the bins (the same answer on every rank)
 th_status deposit_prepare_bins(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p);
+// what the entry points of a draw say alike
+void draw_moves_nothing(th_context *c);               // a local draw: nothing travels between ranks (th_draw_query)
+th_status refuse_band(const th_context *c, const char *what, const char *instead);       // TH_OK on a whole texture
+th_status shared_uniforms(const th_deposit_uniforms *du, const th_render_uniforms *ru);  // the passes of one draw agree on what they draw
+th_deposit_uniforms deposit_uniforms_of(const th_render_uniforms &u);
+th_status missing_halo(const th_context *c);          // the error of a band's line that reads a row nobody supplied
+
+// One pass of a local draw: prepare(p, first, &bins) readies `p` for an attempt - the first may take the bins - and says which
+// pipeline it takes; a binned pass that gives up before blending is repeated in stream order, and so are the other passes of its frame.
+template <class Prepare>
+th_status draw_pass(th_context *c, uint64_t *fragments, bool program, Prepare prepare)
+{
+    for (int attempt = 0;; ++attempt) {
+        th::DepositParams p;
+        bool bins = false;
+        if (th_status s = prepare(p, attempt == 0, &bins)) return s;
+        if (!bins) return deposit_run(c, p, fragments);
+        const th_status s = deposit_run_bins(c, p, fragments, program);
+        if (s != kRetryInStreamOrder) return s;
+        c->frame_bins = 0;                  // (the other passes of this frame as well)
+    }
+}
 
 }  // namespace thi

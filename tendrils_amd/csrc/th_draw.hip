@@ -35,16 +35,18 @@ float drawn_line_width(const th_context *c, int pass)
     return w < c->line_range[0] ? c->line_range[0] : (w > c->line_range[1] ? c->line_range[1] : w);
 }
 
+static int draw_policy(const th_context *c) { return c->draw_pipeline != TH_DRAW_AUTO ? c->draw_pipeline : c->opt.draw; }
+// Both passes draw lines at most 2 wide.  (Wider lines cover more texels than a line's record holds: nearly all of them would
+// leave the fused pass for the long list, one atomic per fragment - the stream-ordered pipeline counts and scans instead)
+static bool lines_fit_records(const th_context *c) { return drawn_line_width(c, TH_PASS_FLOW) <= 2.0f && drawn_line_width(c, TH_PASS_VIEW) <= 2.0f; }
+
 static bool draw_uses_bins(th_context *c)
 {
-    const int policy = c->draw_pipeline != TH_DRAW_AUTO ? c->draw_pipeline : c->opt.draw;
+    const int policy = draw_policy(c);
     if (policy == 0) return false;
     if (c->cfg.height != c->cfg.global_height || c->fw > th::kBinsMaxExtent || c->fh > th::kBinsMaxExtent) return false;
     if (policy == 1) return true;
-    // (lines wider than 2 cover more texels than a line's record holds: nearly all of them would leave the fused pass
-    // for the long list, one atomic per fragment - the stream-ordered pipeline counts and scans instead)
-    if (drawn_line_width(c, TH_PASS_FLOW) > 2.0f || drawn_line_width(c, TH_PASS_VIEW) > 2.0f) return false;
-    return sorting_possible(c);
+    return lines_fit_records(c) && sorting_possible(c);
 }
 
 // How a prepared pass walks the lines: the stream-ordered pipeline in texel order; the bins by SLOT, in the order the ring is
@@ -60,13 +62,14 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
 constexpr bool kAutoBinsPrograms = true;
 
 // Does a sharded job draw through the bins?  Only what every rank sees alike may enter: the job's shapes, the lines' widths,
-// the switches (set alike on all ranks) - not this band's size, not how crowded its last draw was.
+// the switches (set alike on all ranks) - not this band's size, not how crowded its last draw was.  (lines_local below
+// IS rank-local - kept as it is here)
 bool binned_shards(const th_context *c)
 {
-    const int policy = c->draw_pipeline != TH_DRAW_AUTO ? c->draw_pipeline : c->opt.draw;
+    const int policy = draw_policy(c);
     if (policy == 0 || (c->lines_local != 1 && c->lines_local != 0)) return false;      // (2: lookups off the line's own texel that no table holds)
     if (c->fw > th::kBinsMaxExtent || c->fh > th::kBinsMaxExtent) return false;
-    if (drawn_line_width(c, TH_PASS_FLOW) > 2.0f || drawn_line_width(c, TH_PASS_VIEW) > 2.0f) return false;
+    if (!lines_fit_records(c)) return false;
     if (policy == 1 || c->opt.bucket == 1) return true;
     if (c->opt.bucket == 0) return false;
     // (sorting_possible's rule on the job's average band: the integrator steps over sorted slots there)
@@ -88,7 +91,7 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
 {
     TH_REQUIRE(u, "null uniforms");
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
-    if (program && !kAutoBinsPrograms && (c->draw_pipeline != TH_DRAW_AUTO ? c->draw_pipeline : c->opt.draw) != 1) want_bins = false;
+    if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -113,24 +116,27 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
     return prepare_pass(c, u, p, !use_bins ? Walk::stream : (program ? Walk::texels : Walk::slots));
 }
 
-// per-line buffers + parameters of a pass whose pipeline is decided
-static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, Walk walk)
+// the five per-line buffers and the totals, all or nothing
+static th_status line_buffers(th_context *c)
 {
-    const bool use_bins = walk != Walk::stream, by_texel = walk == Walk::texels;
     const size_t lines = c->texels();
-    TH_REQUIRE((size_t)c->fw * c->fh > 0 && (uint64_t)c->cfg.width * c->cfg.global_height < (1ull << 32), "bad shapes");
-    if (c->dep_lines != lines) {
-        TH_HIP(hipStreamSynchronize(c->stream));
-        c->dep_lines = 0;                   // (all five per-line buffers and `lines`, or nothing: a failure below leaves the next call to start over)
-        c->dep_count.reset(); c->dep_offset.reset(); c->dep_blocks.reset(); c->dep_record.reset(); c->dep_lists.reset();
-        if (th_status s = c->dep_count.alloc(lines)) return s;
-        if (th_status s = c->dep_offset.alloc(lines)) return s;
-        if (th_status s = c->dep_record.alloc(2 * lines)) return s;
-        if (th_status s = c->dep_lists.alloc(th::deposit_list_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, &c->dep_list_cap))) return s;
-        if (th_status s = c->dep_blocks.alloc(th::deposit_scan_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height))) return s;
-        if (th_status s = c->dep_total.reserve(th::kTotWords, th::kTotWords)) return s;      // [0] total, [1] out-of-band flag, [2] largest bin, [3] large bins, [4] their blocks
-        c->dep_lines = lines;
-    }
+    if (c->dep_lines == lines) return TH_OK;
+    TH_HIP(hipStreamSynchronize(c->stream));
+    c->dep_lines = 0;                   // (all five per-line buffers and `lines`, or nothing: a failure below leaves the next call to start over)
+    c->dep_count.reset(); c->dep_offset.reset(); c->dep_blocks.reset(); c->dep_record.reset(); c->dep_lists.reset();
+    if (th_status s = c->dep_count.alloc(lines)) return s;
+    if (th_status s = c->dep_offset.alloc(lines)) return s;
+    if (th_status s = c->dep_record.alloc(2 * lines)) return s;
+    if (th_status s = c->dep_lists.alloc(th::deposit_list_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, &c->dep_list_cap))) return s;
+    if (th_status s = c->dep_blocks.alloc(th::deposit_scan_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height))) return s;
+    if (th_status s = c->dep_total.reserve(th::kTotWords, th::kTotWords)) return s;      // [0] total, [1] out-of-band flag, [2] largest bin, [3] large bins, [4] their blocks
+    c->dep_lines = lines;
+    return TH_OK;
+}
+
+// what every pass fills: the ring, the shapes, the uniforms, the per-line buffers
+static void pass_fields(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p)
+{
     p = th::DepositParams{};
     // a packed ring is read in place, texel by texel, as what the stored texels decode to (dep_state: no f32 copy of the ring
     // per draw - two passes over 10.7 GB at config 5's size)
@@ -153,74 +159,98 @@ static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::D
         p.lists = c->dep_lists + (th::deposit_list_words((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, &cap) - (size_t)3 * 64 * cap);      // (three kinds of list, 64 segments each: th_raster.hpp)
     }
     p.halo_lo = c->halo_lo; p.halo_hi = c->halo_hi;
-    if (!use_bins) TH_HIP(hipMemsetAsync(c->dep_total, 0, th::kTotWords * sizeof(uint32_t), c->stream));      // (bins: launch_bins_fused)
+}
+
+// the bins' tables (grown when the target has more bins than ever before) and where they lie
+static th_status bins_tables(th_context *c, th::DepositParams &p)
+{
+    p.bins_x = ((uint32_t)c->fw + (1u << th::kBinShift) - 1u) >> th::kBinShift;
+    p.nbins = p.bins_x * (((uint32_t)c->fh + (1u << th::kBinShift) - 1u) >> th::kBinShift);
+    if (c->bin_capacity < p.nbins) {
+        TH_HIP(hipStreamSynchronize(c->stream));
+        c->bin_capacity = 0; c->bin_mem.reset(); c->chunk_table.reset();
+        const size_t stride = ((size_t)p.nbins + 255) / 256 * 256 + 64;      // (the lists' cursors of one bin on different memory channels)
+        if (th_status s = c->bin_mem.alloc(th::kBinReplicas * stride + 2 * (size_t)p.nbins + 2)) return s;
+        // (TH_OPT_BINS_PAGES: how far a list can grow at first - tests make it small to run the widening path)
+        const int first = c->opt.bins_pages;
+        c->bin_max_pages = first > 0 ? (uint32_t)first : (first < 0 ? (uint32_t)-first : th::kBinFirstPages);
+        if (th_status s = c->chunk_table.alloc((size_t)p.nbins * th::kBinReplicas * c->bin_max_pages)) return s;
+        TH_HIP(hipMemsetAsync(c->chunk_table, 0, c->chunk_table.bytes(), c->stream));        // (every reader of a list leaves its entries empty)
+        c->bin_capacity = p.nbins;
+    }
+    p.bin_stride = (uint32_t)(((size_t)c->bin_capacity + 255) / 256 * 256 + 64);
+    p.bin_cursor = c->bin_mem; p.large_bins = c->bin_mem + (size_t)th::kBinReplicas * p.bin_stride;
+    p.large_key0 = p.large_bins + c->bin_capacity;
+    p.page_table = c->chunk_table; p.max_pages = c->bin_max_pages;
+    p.totals = c->dep_total; p.totals_host = nullptr; p.totals_seq = 0;       // (bins_expect, before the plan's kernels go out)
+    return TH_OK;
+}
+
+// the blocks of 256 lines with something to draw into `list` (its count in front, read back into `n`): both caches below
+static th_status list_blocks(th_context *c, const th::DepositParams &p, DevBuf<uint32_t> &list, uint32_t &n, uint32_t *src_slots)
+{
+    const size_t blocks = (c->texels() + 255) / 256;
+    if (!c->draw_block_flags) if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
+    if (!list) if (th_status s = list.alloc(blocks + 1)) return s;          // (last: what goes with a list is there when the list is)
+    th::launch_bins_block_list(p, c->draw_block_flags, list + 1, list, src_slots, c->stream);
+    TH_HIP(hipGetLastError());
+    return read_back(c, &n, list, sizeof(uint32_t));
+}
+
+// the walk of a binned pass: the slot order's perm, what the step saw of the lines, the block list - cached per slot order (one
+// read-back per re-sort), or, by_texel, once per context
+static th_status bins_walk(th_context *c, th::DepositParams &p, bool by_texel)
+{
+    // (by_texel: the walk is over texel indices - no perm, and nothing that describes the ring's slots below: what the step
+    // saw of its lines is where the BUILT-IN stage puts them, not where a program does)
+    const int o = by_texel ? -1 : order_of(c, c->ring[0]);
+    p.perm = o >= 0 ? c->orders[(size_t)o].perm : nullptr;
+    const unsigned long long stamp = o >= 0 ? c->orders[(size_t)o].stamp : 0ull;
+    // what the step that wrote these two buffers saw of their lines (th_step.hip): only for exactly this pair, order and view
+    // (... and only where a line's two ends ARE the slot's own particle, now and a step ago: lines_local)
+    if (!by_texel && c->opt.skip_unseen && c->lines_local == 1 && c->seen.bytes && c->seen.cur == c->ring[0] && c->seen.prev == c->ring[1] && p.cur == c->ring[0] && p.prev == c->ring[1] &&
+        c->seen.order == o && c->seen.stamp == stamp && c->seen.view_x == p.view_x && c->seen.view_y == p.view_y && c->seen.fw == c->fw && c->seen.fh == c->fh &&
+        lines_fit_records(c))
+        p.block_seen = reinterpret_cast<const uint32_t *>(c->seen.bytes.get());
+    if (by_texel) {
+        if (!c->texel_blocks_listed) {
+            if (th_status s = list_blocks(c, p, c->texel_blocks, c->texel_nblocks, nullptr)) return s;
+            c->texel_blocks_listed = true;
+        }
+        p.draw_blocks = c->texel_blocks + 1; p.draw_nblocks = c->texel_nblocks;
+        return TH_OK;
+    }
+    if (!c->draw_blocks || c->draw_blocks_order != o || c->draw_blocks_stamp != stamp) {
+        if (!c->draw_blocks && c->lines_local == 0)
+            if (th_status s = c->src_slots.alloc((size_t)c->src_nrows * c->cfg.width + (size_t)c->src_ncols * c->cfg.height + 1)) return s;
+        if (th_status s = list_blocks(c, p, c->draw_blocks, c->draw_nblocks, o >= 0 ? c->src_slots.get() : nullptr)) return s;
+        c->draw_blocks_order = o; c->draw_blocks_stamp = stamp;
+    }
+    p.draw_blocks = c->draw_blocks + 1; p.draw_nblocks = c->draw_nblocks;
+    if (c->lines_local == 0 && o >= 0) p.src.slot = c->src_slots;
+    return TH_OK;
+}
+
+// per-line buffers + parameters of a pass whose pipeline is decided
+static th_status prepare_pass(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, Walk walk)
+{
+    TH_REQUIRE((size_t)c->fw * c->fh > 0 && (uint64_t)c->cfg.width * c->cfg.global_height < (1ull << 32), "bad shapes");
+    if (th_status s = line_buffers(c)) return s;
+    pass_fields(c, u, p);
+    if (walk == Walk::stream) TH_HIP(hipMemsetAsync(c->dep_total, 0, th::kTotWords * sizeof(uint32_t), c->stream));      // (bins: launch_bins_fused)
     if (th_status s = line_rows(c)) return s;
     p.row_draws = c->d_row_draws;
     if (c->lines_local == 0) {          // (the tables; `slot` stays null in texel order: a texel's slot is its index)
         p.src.row_index = c->src_row_index; p.src.col_index = c->src_col_index; p.src.nrows = c->src_nrows; p.src.ncols = c->src_ncols;
     }
-    if (use_bins) {
-        // (by_texel: the walk is over texel indices - no perm, and nothing that describes the ring's slots below: what the step
-        // saw of its lines is where the BUILT-IN stage puts them, not where a program does)
-        const int o = by_texel ? -1 : order_of(c, c->ring[0]);
-        p.perm = o >= 0 ? c->orders[(size_t)o].perm : nullptr;
-        p.bins_x = ((uint32_t)c->fw + (1u << th::kBinShift) - 1u) >> th::kBinShift;
-        p.nbins = p.bins_x * (((uint32_t)c->fh + (1u << th::kBinShift) - 1u) >> th::kBinShift);
-        if (c->bin_capacity < p.nbins) {
-            TH_HIP(hipStreamSynchronize(c->stream));
-            c->bin_capacity = 0; c->bin_mem.reset(); c->chunk_table.reset();
-            const size_t stride = ((size_t)p.nbins + 255) / 256 * 256 + 64;      // (the lists' cursors of one bin on different memory channels)
-            if (th_status s = c->bin_mem.alloc(th::kBinReplicas * stride + 2 * (size_t)p.nbins + 2)) return s;
-            // (TH_OPT_BINS_PAGES: how far a list can grow at first - tests make it small to run the widening path)
-            const int first = c->opt.bins_pages;
-            c->bin_max_pages = first > 0 ? (uint32_t)first : (first < 0 ? (uint32_t)-first : th::kBinFirstPages);
-            if (th_status s = c->chunk_table.alloc((size_t)p.nbins * th::kBinReplicas * c->bin_max_pages)) return s;
-            TH_HIP(hipMemsetAsync(c->chunk_table, 0, c->chunk_table.bytes(), c->stream));        // (every reader of a list leaves its entries empty)
-            c->bin_capacity = p.nbins;
-        }
-        p.bin_stride = (uint32_t)(((size_t)c->bin_capacity + 255) / 256 * 256 + 64);
-        p.bin_cursor = c->bin_mem; p.large_bins = c->bin_mem + (size_t)th::kBinReplicas * p.bin_stride;
-        p.large_key0 = p.large_bins + c->bin_capacity;
-        p.page_table = c->chunk_table; p.max_pages = c->bin_max_pages;
-        p.totals = c->dep_total; p.totals_host = nullptr; p.totals_seq = 0;       // (bins_expect, before the plan's kernels go out)
-        // the blocks of slots with something to draw: listed once per slot order (one read-back per re-sort)
-        const unsigned long long stamp = o >= 0 ? c->orders[(size_t)o].stamp : 0ull;
-        // what the step that wrote these two buffers saw of their lines (th_step.hip): only for exactly this pair, order and view
-        // (... and only where a line's two ends ARE the slot's own particle, now and a step ago: lines_local)
-        if (!by_texel && c->opt.skip_unseen && c->lines_local == 1 && c->seen.bytes && c->seen.cur == c->ring[0] && c->seen.prev == c->ring[1] && p.cur == c->ring[0] && p.prev == c->ring[1] &&
-            c->seen.order == o && c->seen.stamp == stamp && c->seen.view_x == p.view_x && c->seen.view_y == p.view_y && c->seen.fw == c->fw && c->seen.fh == c->fh &&
-            drawn_line_width(c, TH_PASS_FLOW) <= 2.0f && drawn_line_width(c, TH_PASS_VIEW) <= 2.0f)
-            p.block_seen = reinterpret_cast<const uint32_t *>(c->seen.bytes.get());
-        if (by_texel) {
-            if (!c->texel_blocks_listed) {
-                const size_t blocks = (c->texels() + 255) / 256;
-                if (!c->draw_block_flags) if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
-                if (!c->texel_blocks) if (th_status s = c->texel_blocks.alloc(blocks + 1)) return s;
-                th::launch_bins_block_list(p, c->draw_block_flags, c->texel_blocks + 1, c->texel_blocks, nullptr, c->stream);
-                TH_HIP(hipGetLastError());
-                if (th_status s = read_back(c, &c->texel_nblocks, c->texel_blocks, sizeof(uint32_t))) return s;
-                c->texel_blocks_listed = true;
-            }
-            p.draw_blocks = c->texel_blocks + 1; p.draw_nblocks = c->texel_nblocks;
-            return TH_OK;
-        }
-        if (!c->draw_blocks || c->draw_blocks_order != o || c->draw_blocks_stamp != stamp) {
-            const size_t blocks = (c->texels() + 255) / 256;
-            if (!c->draw_blocks) {
-                if (!c->draw_block_flags) if (th_status s = c->draw_block_flags.alloc(blocks)) return s;
-                if (c->lines_local == 0)
-                    if (th_status s = c->src_slots.alloc((size_t)c->src_nrows * c->cfg.width + (size_t)c->src_ncols * c->cfg.height + 1)) return s;
-                if (th_status s = c->draw_blocks.alloc(blocks + 1)) return s;          // (last: the three are there when this one is)
-            }
-            th::launch_bins_block_list(p, c->draw_block_flags, c->draw_blocks + 1, c->draw_blocks, o >= 0 ? c->src_slots : nullptr, c->stream);
-            TH_HIP(hipGetLastError());
-            if (th_status s = read_back(c, &c->draw_nblocks, c->draw_blocks, sizeof(uint32_t))) return s;
-            c->draw_blocks_order = o; c->draw_blocks_stamp = stamp;
-        }
-        p.draw_blocks = c->draw_blocks + 1; p.draw_nblocks = c->draw_nblocks;
-        if (c->lines_local == 0 && o >= 0) p.src.slot = c->src_slots;
-    }
-    return TH_OK;
+    if (walk == Walk::stream) return TH_OK;
+    if (th_status s = bins_tables(c, p)) return s;
+    return bins_walk(c, p, walk == Walk::texels);
+}
+
+th_status missing_halo(const th_context *c)
+{
+    return fail(TH_ERR_UNSUPPORTED, "a line of this row band looks up a particle row outside the band (rows %d..%d of %d) and no halo row was supplied (th_deposit_set_halo)", c->cfg.row0, c->cfg.row0 + c->cfg.height, c->cfg.global_height);
 }
 
 // scan of p.count (filled by the caller's marking pass) -> p.offset, total (one sync); reports band violations
@@ -229,18 +259,10 @@ th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t
     th::launch_deposit_scan(p, c->dep_blocks, c->dep_total, c->stream);
     uint32_t host[2] = {0, 0};
     if (th_status s = read_back(c, host, c->dep_total, sizeof host)) return s;
-    if (host[1]) return fail(TH_ERR_UNSUPPORTED, "a line of this row band looks up a particle row outside the band (rows %d..%d of %d) and no halo row was supplied (th_deposit_set_halo)", c->cfg.row0, c->cfg.row0 + c->cfg.height, c->cfg.global_height);
+    if (host[1]) return missing_halo(c);
     if (host[0] >= (1u << 31)) return fail(TH_ERR_UNSUPPORTED, "too many fragments for one draw (2^31 or more)");
     *total = host[0];
     return TH_OK;
-}
-
-// counts this context's fragments
-th_status deposit_count(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, uint32_t *total)
-{
-    if (th_status s = deposit_prepare(c, u, p)) return s;
-    th::launch_deposit_count(p, c->stream);
-    return deposit_scan_total(c, p, total);
 }
 
 // per-fragment buffers for `total` fragments (grow-only)
@@ -313,15 +335,40 @@ void view_fields(th_context *c, const th_render_uniforms *u, th::DepositParams &
     p.colormap = c->colormap; p.cw = c->cmap_w; p.ch = c->cmap_h;
 }
 
+// what the vertex stage takes of a view pass's uniforms
+th_deposit_uniforms deposit_uniforms_of(const th_render_uniforms &u)
+{
+    th_deposit_uniforms d{};
+    d.viewSize[0] = u.viewSize[0]; d.viewSize[1] = u.viewSize[1]; d.time = u.time; d.speedLimit = u.speedLimit;
+    return d;
+}
+
 th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins)
 {
     TH_REQUIRE(u, "null uniforms");
-    th_deposit_uniforms d{};
-    d.viewSize[0] = u->viewSize[0]; d.viewSize[1] = u->viewSize[1]; d.time = u->time; d.speedLimit = u->speedLimit;
+    const th_deposit_uniforms d = deposit_uniforms_of(*u);
     if (th_status s = deposit_prepare(c, &d, p, want_bins, bins)) return s;
     p.mode = 1;
     p.line_half = 0.5f * drawn_line_width(c, TH_PASS_VIEW);
     view_fields(c, u, p);
+    return TH_OK;
+}
+
+// ---- what the entry points of a draw say alike --------------------------------------------------------------------------------
+void draw_moves_nothing(th_context *c) { c->last_draw.sent_bytes = c->last_draw.received_bytes = 0; }
+
+// a local entry point on a row band: `what` it is and where a band's pass goes `instead`, in the entry point's own words
+th_status refuse_band(const th_context *c, const char *what, const char *instead)
+{
+    if (c->cfg.height == c->cfg.global_height) return TH_OK;
+    return fail(TH_ERR_UNSUPPORTED, "%s on a row-band shard (%d of %d rows): %s", what, c->cfg.height, c->cfg.global_height, instead);
+}
+
+th_status shared_uniforms(const th_deposit_uniforms *du, const th_render_uniforms *ru)
+{
+    TH_REQUIRE(memcmp(du->viewSize, ru->viewSize, sizeof du->viewSize) == 0 && memcmp(&du->time, &ru->time, sizeof du->time) == 0 &&
+               memcmp(&du->speedLimit, &ru->speedLimit, sizeof du->speedLimit) == 0,
+               "the two passes of one draw share viewSize, time and speedLimit");
     return TH_OK;
 }
 
@@ -388,6 +435,16 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragme
 // at a quarter of the bins' first pages: the growth path is there (deposit_run_bins repeats a pass whose pool ran dry), and
 // at 1920 x 1080 the store is 0.9 GB for a flow-only host, 1.4 GB with both passes - not 2.7 GB up front.  A store that
 // cannot be allocated (a small device, many contexts) leaves the draw to the stream-ordered pipeline.
+static size_t bins_places(uint32_t bins, uint32_t pool) { return ((size_t)bins * th::kBinReplicas + pool) * th::kBinPage; }
+
+// the store as every blend leaves it: keys to "empty", the lists' page tables to "no page"
+static th_status bins_wipe(th_context *c)
+{
+    if (c->bins_keys) TH_HIP(hipMemsetAsync(c->bins_keys, 0xff, bins_places(c->bins_store_bins, c->bins_pool) * sizeof(unsigned long long), c->stream));
+    if (c->chunk_table) TH_HIP(hipMemsetAsync(c->chunk_table, 0, (size_t)c->bin_capacity * th::kBinReplicas * c->bin_max_pages * sizeof(uint32_t), c->stream));
+    return TH_OK;
+}
+
 static th_status bins_store(th_context *c, uint32_t nbins, uint32_t pool, bool pairs)
 {
     if (c->bins_keys && c->bins_store_bins == nbins && c->bins_pool >= pool && (c->bins_pairs || !pairs)) return TH_OK;
@@ -396,7 +453,7 @@ static th_status bins_store(th_context *c, uint32_t nbins, uint32_t pool, bool p
     pool = pool > c->bins_pool ? pool : c->bins_pool;
     pairs = pairs || c->bins_pairs;
     c->bins_pool = 0; c->bins_store_bins = 0;
-    const size_t places = ((size_t)nbins * th::kBinReplicas + pool) * th::kBinPage;
+    const size_t places = bins_places(nbins, pool);
     TH_REQUIRE(places < ((size_t)1 << 32), "the binned draw's chunk store would hold 2^32 places or more");
     const std::string said = last_error();          // (a store that cannot be had is no error: th_last_error() keeps what it said)
     if (c->bins_colors.alloc(places * (pairs ? 2 : 1)) != TH_OK || c->bins_keys.alloc(places) != TH_OK) {      // (the keys last: the store is there when they are)
@@ -492,8 +549,7 @@ th_status bins_table_widen(th_context *c, th::DepositParams &p, bool keep)
 th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t pool)
 {
     if (pool <= c->bins_pool) return TH_OK;
-    const size_t had = ((size_t)c->bins_store_bins * th::kBinReplicas + c->bins_pool) * th::kBinPage;
-    const size_t places = ((size_t)c->bins_store_bins * th::kBinReplicas + pool) * th::kBinPage, per = c->bins_pairs ? 2 : 1;
+    const size_t had = bins_places(c->bins_store_bins, c->bins_pool), places = bins_places(c->bins_store_bins, pool), per = c->bins_pairs ? 2 : 1;
     TH_REQUIRE(places < ((size_t)1 << 32), "the binned draw's chunk store would hold 2^32 places or more");
     DevBuf<unsigned long long> keys;
     DevBuf<float4> colors;
@@ -519,8 +575,7 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
     // succeeded) left keys in its places and page ids in its lists' tables: a page id found there before this pass publishes
     // its own would send fragments to pages another list owns now, and stale keys would blend as fragments nobody drew.
     if (c->bins_dirty) {
-        if (c->bins_keys) TH_HIP(hipMemsetAsync(c->bins_keys, 0xff, ((size_t)c->bins_store_bins * th::kBinReplicas + c->bins_pool) * th::kBinPage * sizeof(unsigned long long), c->stream));
-        if (c->chunk_table) TH_HIP(hipMemsetAsync(c->chunk_table, 0, (size_t)c->bin_capacity * th::kBinReplicas * c->bin_max_pages * sizeof(uint32_t), c->stream));
+        if (th_status s = bins_wipe(c)) return s;
         c->bins_dirty = false;
     }
     for (int attempt = 0;; ++attempt) {
@@ -535,14 +590,13 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
         const uint32_t flags = host[th::kTotFlags];
         if (host[th::kTotOob]) {          // (a store nobody will blend: wiped by the next pass)
             c->bins_dirty = true;
-            return fail(TH_ERR_UNSUPPORTED, "a line of this row band looks up a particle row outside the band (rows %d..%d of %d) and no halo row was supplied (th_deposit_set_halo)", c->cfg.row0, c->cfg.row0 + c->cfg.height, c->cfg.global_height);
+            return missing_halo(c);
         }
         if (flags == 0) { c->bins_dirty = true; return TH_OK; }        // (until bins_pass_finish has sent the blends after it)
         // nothing has been blended yet: the store is wiped, and the pass is repeated with a larger pool - or, when a bin
         // outgrew its chunk table or a line its reservation, left to the stream-ordered pipeline
-        TH_HIP(hipMemsetAsync(c->bins_keys, 0xff, ((size_t)c->bins_store_bins * th::kBinReplicas + c->bins_pool) * th::kBinPage * sizeof(unsigned long long), c->stream));
-        TH_HIP(hipMemsetAsync(c->chunk_table, 0, (size_t)c->bin_capacity * th::kBinReplicas * c->bin_max_pages * sizeof(uint32_t), c->stream));
-        if ((flags & ~(th::kBinsPoolExhausted | th::kBinsBinFull)) || attempt >= 6) return kRetryInStreamOrder;
+        if (th_status s = bins_wipe(c)) return s;
+        if (bins_flags_final(flags, attempt)) return kRetryInStreamOrder;
         // (a bin that outgrew its lists - the wake of a long-running loop draws half a million fragments into 16 x 16 texels -
         // gets a wider page table: a list's pages x 4, up to kBinPagesLimit)
         if (flags & th::kBinsBinFull) { if (th_status s = bins_table_widen(c, p, false)) return s; }
@@ -553,30 +607,25 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
     }
 }
 
-// Part 2: with the totals in c->bins_totals_host - the crowded bins regrouped and blended on the side streams, the ordinary
-// bins' blend unless it went out early.
-th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragments, bool blended_early)
+// Part 2: with the totals in c->bins_totals_host.  First, room for the crowded bins: `nlarge` of them holding `crowd_keys` of the
+// pass's `total` fragments (both buffers grow-only), and where their arrays lie.
+static th_status crowd_room(th_context *c, th::DepositParams &p, uint32_t nlarge, uint32_t crowd_keys, uint32_t total)
 {
-    uint32_t *host = c->bins_totals_host;
-    const uint32_t total = host[th::kTotFragments], nlarge = host[th::kTotLarge];
-    if (fragments) *fragments = total;
-    c->last_draw.pipeline = TH_DRAW_BINS; c->last_draw.fragments = total; c->last_draw.crowded_fragments = host[th::kTotCrowdKeys];
-    if (host[th::kTotCrowdKeys] == 0xffffffffu) return fail(TH_ERR_UNSUPPORTED, "too many fragments in crowded bins for one draw (2^32 or more places)");
     if (c->crowd_capacity < nlarge) {
         c->crowd_capacity = 0;
         const uint32_t cap = std::min(p.nbins, std::max(2u * nlarge + 256u, p.nbins / 4u));      // (a quarter of the bins at once: no growth step by step)
         if (th_status s = c->crowd_mem.alloc((size_t)cap * th::crowd_words_per_bin())) return s;
-        // (the fragment counts per texel - the first cap * 256 words - start from zero; crowd_scan_kernel leaves them so)
-        TH_HIP(hipMemsetAsync(c->crowd_mem, 0, (size_t)cap * 256 * sizeof(uint32_t), c->stream));
+        // (the fragment counts per texel - the first of the arrays - start from zero; crowd_scan_kernel leaves them so)
+        TH_HIP(hipMemsetAsync(c->crowd_mem, 0, th::crowd_count_words(cap) * sizeof(uint32_t), c->stream));
         TH_HIP(hipStreamSynchronize(c->stream));         // (whichever stream the regroup runs on: a new buffer is rare)
         c->crowd_capacity = cap;
     }
-    if (c->crowd_keys_cap < host[th::kTotCrowdKeys]) {
+    if (c->crowd_keys_cap < crowd_keys) {
         c->crowd_keys.reset(); c->crowd_sorted.reset(); c->crowd_parted.reset(); c->crowd_windows.reset(); c->crowd_keys_cap = 0;
         // (room for every fragment of a pass like this one and a quarter more: the share of the crowded bins grows from a third
         // to three quarters over the first hundred frames of a loop - sized by what it is now, the four buffers were freed and
         // allocated again every few frames on the way, milliseconds each time)
-        const size_t cap = std::max(2 * (size_t)host[th::kTotCrowdKeys], (size_t)total + total / 4) + ((size_t)1 << 20);
+        const size_t cap = std::max(2 * (size_t)crowd_keys, (size_t)total + total / 4) + ((size_t)1 << 20);
         if (th_status s = c->crowd_keys.alloc(cap)) return s;
         if (th_status s = c->crowd_sorted.alloc(cap)) return s;
         if (th_status s = c->crowd_parted.alloc(cap)) return s;
@@ -584,11 +633,17 @@ th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragme
         c->crowd_keys_cap = cap;
     }
     p.nlarge = nlarge;
-    p.crowd_count = c->crowd_mem; p.crowd_cursor = c->crowd_mem + (size_t)c->crowd_capacity * 256; p.crowd_start = p.crowd_cursor + (size_t)c->crowd_capacity * 256;
-    p.crowd_long = p.crowd_start + (size_t)c->crowd_capacity * 257; p.crowd_giant = p.crowd_long + (size_t)c->crowd_capacity * 256;
-    p.crowd_giant_win = p.crowd_giant + (size_t)c->crowd_capacity * 256;
+    th::crowd_carve(p, c->crowd_mem, c->crowd_capacity);
     p.crowd_keys = c->crowd_keys; p.crowd_sorted = c->crowd_sorted; p.crowd_parted = c->crowd_parted;
     p.crowd_windows = c->crowd_windows; p.crowd_windows_cap = (uint32_t)(c->crowd_keys_cap / 512 + 2);
+    return TH_OK;
+}
+
+// ... then the launches: the crowded bins regrouped and blended on the side streams, the ordinary bins' blend unless it went
+// out early.  The two topologies are written out in full: they are what was measured.
+static th_status bins_pass_blend(th_context *c, th::DepositParams &p, bool blended_early)
+{
+    const uint32_t nlarge = p.nlarge;
     if (nlarge && !blended_early) {
         // A crowded target: the crowded bins' short runs - regroup, sort, walk: the longest chain of the draw - stay on the MAIN
         // stream, right behind the plan (no event to wait for) and right in front of whatever the host sends next (a frame
@@ -638,6 +693,17 @@ th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragme
     return TH_OK;
 }
 
+th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragments, bool blended_early)
+{
+    const uint32_t *host = c->bins_totals_host;
+    const uint32_t total = host[th::kTotFragments], nlarge = host[th::kTotLarge];
+    if (fragments) *fragments = total;
+    c->last_draw.pipeline = TH_DRAW_BINS; c->last_draw.fragments = total; c->last_draw.crowded_fragments = host[th::kTotCrowdKeys];
+    if (host[th::kTotCrowdKeys] == 0xffffffffu) return fail(TH_ERR_UNSUPPORTED, "too many fragments in crowded bins for one draw (2^32 or more places)");
+    if (th_status s = crowd_room(c, p, nlarge, host[th::kTotCrowdKeys], total)) return s;
+    return bins_pass_blend(c, p, blended_early);
+}
+
 // (row-band shards, th_shard.hip) the received bins are in the store, laid out by launch_bins_owner_insert: the totals of its
 // plan to the host
 void bins_pass_expect(th_context *c, th::DepositParams &p) { bins_expect(c, p); }
@@ -674,18 +740,9 @@ th_status th_export_lines(th_context *c, const th_deposit_uniforms *u, float *li
 th_status th_flow_deposit(th_context *c, const th_deposit_uniforms *u, uint64_t *fragments)
 {
     if (th_status s = use(c)) return s;
-    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;      // (a local draw moves nothing between ranks)
-    if (c->cfg.height != c->cfg.global_height)
-        return fail(TH_ERR_UNSUPPORTED, "flow deposit on a row-band shard (%d of %d rows): use th_deposit_emit / th_deposit_merge with the exchange of tendrils_amd/sharding.py", c->cfg.height, c->cfg.global_height);
-    for (int pass = 0;; ++pass) {            // (a binned pass that gives up before blending is repeated in stream order)
-        th::DepositParams p;
-        bool bins = false;
-        if (th_status s = deposit_prepare(c, u, p, pass == 0, &bins)) return s;
-        if (!bins) return deposit_run(c, p, fragments);
-        const th_status s = deposit_run_bins(c, p, fragments);
-        if (s != kRetryInStreamOrder) return s;
-        c->frame_bins = 0;                  // (the other passes of this frame as well)
-    }
+    draw_moves_nothing(c);
+    if (th_status s = refuse_band(c, "flow deposit", "use th_deposit_emit / th_deposit_merge with the exchange of tendrils_amd/sharding.py")) return s;
+    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) { return deposit_prepare(c, u, p, first, bins); });
 }
 
 // Both passes of Tendrils.draw() (src/index.js:278-337) in one: the lines are rasterised, scanned, emitted and sorted once,
@@ -696,49 +753,35 @@ th_status th_flow_deposit(th_context *c, const th_deposit_uniforms *u, uint64_t 
 th_status th_draw(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
 {
     if (th_status s = use(c)) return s;
-    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;      // (a local draw moves nothing between ranks)
+    draw_moves_nothing(c);
     TH_REQUIRE(du && ru, "null uniforms");
-    if (c->cfg.height != c->cfg.global_height)
-        return fail(TH_ERR_UNSUPPORTED, "draw on a row-band shard (%d of %d rows): the passes go through th_deposit_emit / th_deposit_merge and th_view_emit / th_view_merge with the owners' exchange in between", c->cfg.height, c->cfg.global_height);
-    TH_REQUIRE(memcmp(du->viewSize, ru->viewSize, sizeof du->viewSize) == 0 && memcmp(&du->time, &ru->time, sizeof du->time) == 0 &&
-               memcmp(&du->speedLimit, &ru->speedLimit, sizeof du->speedLimit) == 0,
-               "the two passes of one draw share viewSize, time and speedLimit");
+    if (th_status s = refuse_band(c, "draw", "the passes go through th_deposit_emit / th_deposit_merge and th_view_emit / th_view_merge with the owners' exchange in between")) return s;
+    if (th_status s = shared_uniforms(du, ru)) return s;
     if (drawn_line_width(c, TH_PASS_FLOW) != drawn_line_width(c, TH_PASS_VIEW)) {       // two widths: two rasterisations
         if (th_status s = th_flow_deposit(c, du, fragments)) return s;
         return th_view_draw(c, ru, nullptr);
     }
     if (th_status s = view_storage(c)) return s;
-    for (int pass = 0;; ++pass) {
-        th::DepositParams p;
-        bool bins = false;
-        if (th_status s = deposit_prepare(c, du, p, pass == 0, &bins)) return s;
+    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
+        if (th_status s = deposit_prepare(c, du, p, first, bins)) return s;
         p.mode = 2;
         view_fields(c, ru, p);
         p.view = c->view;
-        if (!bins) return deposit_run(c, p, fragments);
-        const th_status s = deposit_run_bins(c, p, fragments);
-        if (s != kRetryInStreamOrder) return s;
-        c->frame_bins = 0;                  // (the other passes of this frame as well)
-    }
+        return TH_OK;
+    });
 }
 
 th_status th_view_draw(th_context *c, const th_render_uniforms *u, uint64_t *fragments)
 {
     if (th_status s = use(c, true)) return s;
-    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;      // (a local draw moves nothing between ranks)
-    if (c->cfg.height != c->cfg.global_height)
-        return fail(TH_ERR_UNSUPPORTED, "view pass on a row-band shard (%d of %d rows): use th_view_emit / th_view_merge with the owners' exchange in between", c->cfg.height, c->cfg.global_height);
+    draw_moves_nothing(c);
+    if (th_status s = refuse_band(c, "view pass", "use th_view_emit / th_view_merge with the owners' exchange in between")) return s;
     if (th_status s = view_storage(c)) return s;
-    for (int pass = 0;; ++pass) {
-        th::DepositParams p;
-        bool bins = false;
-        if (th_status s = view_params(c, u, p, pass == 0, &bins)) return s;
+    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
+        if (th_status s = view_params(c, u, p, first, bins)) return s;
         p.view = c->view;
-        if (!bins) return deposit_run(c, p, fragments);
-        const th_status s = deposit_run_bins(c, p, fragments);
-        if (s != kRetryInStreamOrder) return s;
-        c->frame_bins = 0;                  // (the other passes of this frame as well)
-    }
+        return TH_OK;
+    });
 }
 
 th_status th_view_fill(th_context *c, const float rgba[4])

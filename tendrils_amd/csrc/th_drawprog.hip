@@ -69,22 +69,21 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
     if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;      // (the view pass writes no state and no flow: th_view_draw)
     if (th_status s = program_run_args(prog, kDrawProgram, "th_draw_program_run", uniforms, uniform_bytes)) return s;
     TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
-    if (c->cfg.height != c->cfg.global_height)
-        return fail(TH_ERR_UNSUPPORTED, "draw program on a row-band shard (%d of %d rows): a band's pass goes through the owners' exchange, which carries the built-in stages alone",
-                    c->cfg.height, c->cfg.global_height);
+    if (th_status s = refuse_band(c, "draw program", "a band's pass goes through the owners' exchange, which carries the built-in stages alone")) return s;
     const size_t lines = c->texels();
     TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a %dx%d particle texture is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
     c->drawn.valid = false;
-    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;      // (a local draw moves nothing between ranks)
+    draw_moves_nothing(c);
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (pass == TH_PASS_VIEW) if (th_status s = view_storage(c)) return s;
-    for (int attempt = 0;; ++attempt) {          // (a binned pass that gives up before blending is repeated in stream order)
+    // every attempt of the pass (draw_pass: a binned one that gives up before blending is repeated in stream order, from its start)
+    // runs the vertex kernel over the order its pipeline walks
+    const th_status ran = draw_pass(c, fragments, true, [&](th::DepositParams &p, bool first, bool *use_bins) -> th_status {
         // what the built-in vertex stage takes from its uniforms - viewSize, time, speedLimit - is the program's own business here
-        th::DepositParams p;
         const th_deposit_uniforms none{};
-        bool bins = false;
-        if (th_status s = deposit_prepare(c, &none, p, attempt == 0, &bins, true)) return s;
+        if (th_status s = deposit_prepare(c, &none, p, first, use_bins, true)) return s;
+        const bool bins = *use_bins;
         if (pass == TH_PASS_VIEW) { p.mode = 1; p.view = c->view; }
         p.line_half = 0.5f * drawn_line_width(c, pass);
         if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
@@ -117,11 +116,10 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
             if (th_status s = program_launch(c, fn, lanes, k)) return s;
             if (th_status s = timer.end(c)) return s;
         }
-        const th_status s = bins ? deposit_run_bins(c, p, fragments, true) : deposit_run(c, p, fragments);
-        c->drawn.valid = false;
-        if (!bins || s != kRetryInStreamOrder) return s;
-        c->frame_bins = 0;                  // (the other passes of this frame as well)
-    }
+        return TH_OK;
+    });
+    c->drawn.valid = false;
+    return ran;
 }
 
 }  // extern "C"

@@ -369,7 +369,9 @@ void launch_bins_sort_long(const DepositParams &p, hipStream_t stream);         
 void launch_bins_walk_long(const DepositParams &p, hipStream_t stream);               // ... walked
 void launch_bins_blend_crowd(const DepositParams &p, hipStream_t stream);             // their other runs, a wave each: order by stream index, blend
 void launch_bins_blend(const DepositParams &p, hipStream_t stream);                   // the bins one workgroup orders: by (texel, stream index), blend (needs no host value)
-size_t crowd_words_per_bin();
+size_t crowd_words_per_bin();                                                        // the crowded bins' arrays: words per large bin ...
+size_t crowd_count_words(size_t bins);                                               // ... the fragment counts per texel among them, which lie first ...
+void crowd_carve(DepositParams &p, uint32_t *mem, size_t bins);                      // ... and p.crowd_count .. p.crowd_giant_win inside a buffer of `bins` times that
 // How a context's ranks exchange bytes.  th_shard.hip does the path's arithmetic - which fragments go to which owner, where
 // the bands and the owned texel ranges lie - and hands plain (pointer, count, offset) lists to one of two transports:
 //   rccl      one process per GPU, RCCL over xGMI (th_comm.hip; librccl bound at run time) - the product's;

@@ -16,9 +16,19 @@ th_status th_deposit_set_owners(th_context *c, int32_t world)
     return TH_OK;
 }
 
-// the (counted) fragments of this band's lines, keyed (owner, texel, global stream index) and parted by owner
-static th_status emit_parted(th_context *c, th::DepositParams &p, uint32_t total, uint64_t *count, void **keys_dev, void **colors_dev)
+static th_status texels_fit_keys(const th_context *c, const char *target)
 {
+    TH_REQUIRE((uint64_t)c->fw * c->fh <= (uint64_t)th::kTexelMask + 1u, "the sharded deposit keys hold 24 texel bits: %s %dx%d is too large", target, c->fw, c->fh);
+    return TH_OK;
+}
+
+// the tail of the three emits: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed (owner,
+// texel, global stream index) and parted by owner
+static th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev)
+{
+    th::launch_deposit_count(p, c->stream);
+    uint32_t total = 0;
+    if (th_status s = deposit_scan_total(c, p, &total)) return s;
     *count = total; *keys_dev = nullptr; *colors_dev = nullptr;
     if (total == 0) return TH_OK;
     const bool pairs = p.mode == 2;                  // th_draw_emit: two varyings per fragment, side by side
@@ -49,11 +59,10 @@ th_status th_deposit_emit(th_context *c, const th_deposit_uniforms *u, uint64_t 
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    TH_REQUIRE((uint64_t)c->fw * c->fh <= (uint64_t)th::kTexelMask + 1u, "the sharded deposit keys hold 24 texel bits: flow %dx%d is too large", c->fw, c->fh);
+    if (th_status s = texels_fit_keys(c, "flow")) return s;
     th::DepositParams p;
-    uint32_t total = 0;
-    if (th_status s = deposit_count(c, u, p, &total)) return s;
-    return emit_parted(c, p, total, count, keys_dev, colors_dev);
+    if (th_status s = deposit_prepare(c, u, p)) return s;
+    return emit_parted(c, p, count, keys_dev, colors_dev);
 }
 
 // the view pass of a row-band shard: the same lines with the render shader's colours
@@ -61,13 +70,10 @@ th_status th_view_emit(th_context *c, const th_render_uniforms *u, uint64_t *cou
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    TH_REQUIRE((uint64_t)c->fw * c->fh <= (uint64_t)th::kTexelMask + 1u, "the sharded deposit keys hold 24 texel bits: view %dx%d is too large", c->fw, c->fh);
+    if (th_status s = texels_fit_keys(c, "view")) return s;
     th::DepositParams p;
     if (th_status s = view_params(c, u, p)) return s;
-    th::launch_deposit_count(p, c->stream);
-    uint32_t total = 0;
-    if (th_status s = deposit_scan_total(c, p, &total)) return s;
-    return emit_parted(c, p, total, count, keys_dev, colors_dev);
+    return emit_parted(c, p, count, keys_dev, colors_dev);
 }
 
 // both passes of a row-band shard's draw() in one: every fragment with the flow pass's varying and the view pass's colour
@@ -76,10 +82,8 @@ th_status th_draw_emit(th_context *c, const th_deposit_uniforms *du, const th_re
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(du && ru && count && keys_dev && colors_dev, "null argument");
-    TH_REQUIRE((uint64_t)c->fw * c->fh <= (uint64_t)th::kTexelMask + 1u, "the sharded deposit keys hold 24 texel bits: target %dx%d is too large", c->fw, c->fh);
-    TH_REQUIRE(memcmp(du->viewSize, ru->viewSize, sizeof du->viewSize) == 0 && memcmp(&du->time, &ru->time, sizeof du->time) == 0 &&
-               memcmp(&du->speedLimit, &ru->speedLimit, sizeof du->speedLimit) == 0,
-               "the two passes of one draw share viewSize, time and speedLimit");
+    if (th_status s = texels_fit_keys(c, "target")) return s;
+    if (th_status s = shared_uniforms(du, ru)) return s;
     TH_REQUIRE(drawn_line_width(c, TH_PASS_FLOW) == drawn_line_width(c, TH_PASS_VIEW),
                "the two passes draw their lines %g and %g wide: th_deposit_emit and th_view_emit rasterise them apart",
                (double)drawn_line_width(c, TH_PASS_FLOW), (double)drawn_line_width(c, TH_PASS_VIEW));
@@ -87,10 +91,7 @@ th_status th_draw_emit(th_context *c, const th_deposit_uniforms *du, const th_re
     if (th_status s = deposit_prepare(c, du, p)) return s;
     p.mode = 2;
     view_fields(c, ru, p);
-    th::launch_deposit_count(p, c->stream);
-    uint32_t total = 0;
-    if (th_status s = deposit_scan_total(c, p, &total)) return s;
-    return emit_parted(c, p, total, count, keys_dev, colors_dev);
+    return emit_parted(c, p, count, keys_dev, colors_dev);
 }
 
 th_status th_deposit_set_halo(th_context *c, const void *lo_dev, const void *hi_dev)
@@ -109,7 +110,6 @@ static th_status merge_parted(th_context *c, const void *keys_dev, const void *c
     if (count == 0) return TH_OK;
     TH_REQUIRE(keys_dev && colors_dev && count < (1ull << 31), "bad fragment buffers");
     const uint32_t total = (uint32_t)count;
-    const bool into_view = target == 1;
     if (th_status s = merge_reserve(c, total, target)) return s;
     // what arrives is one part per source band, every part in that band's stream order: a stable sort by texel (the
     // owner bits above and the stream index below are left alone), then the blend merges the bands inside each texel
@@ -118,15 +118,12 @@ static th_status merge_parted(th_context *c, const void *keys_dev, const void *c
     // (the sort ping-pongs between its two buffer pairs: the caller's keys are copied, not sorted in place)
     TH_HIP(hipMemcpyAsync(c->mrg_keys, keys_dev, (size_t)total * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
     const int in_b = th::launch_radix_sort_u64(c->mrg_keys, c->mrg_vals[0], c->mrg_keys2, c->mrg_vals[1], total, 32, bits, c->dep_temp, true, c->stream);
-    if (target == 2)
-        th::launch_draw_blend64(c->flow, c->view, in_b ? c->mrg_keys2 : c->mrg_keys, in_b ? c->mrg_vals[1] : c->mrg_vals[0],
-                                static_cast<const float4 *>(colors_dev), c->mrg_colors, total, c->dep_total, c->stream);
-    else if (into_view)
-        th::launch_view_blend64(c->view, in_b ? c->mrg_keys2 : c->mrg_keys, in_b ? c->mrg_vals[1] : c->mrg_vals[0],
-                                static_cast<const float4 *>(colors_dev), c->mrg_colors, total, c->dep_total, c->stream);
-    else
-        th::launch_deposit_blend64(c->flow, in_b ? c->mrg_keys2 : c->mrg_keys, in_b ? c->mrg_vals[1] : c->mrg_vals[0],
-                                   static_cast<const float4 *>(colors_dev), c->mrg_colors, total, c->dep_total, c->stream);
+    const unsigned long long *keys = in_b ? c->mrg_keys2 : c->mrg_keys;          // (the pair the sort ended in)
+    const uint32_t *vals = in_b ? c->mrg_vals[1] : c->mrg_vals[0];
+    const float4 *colors = static_cast<const float4 *>(colors_dev);
+    if (target == 2) th::launch_draw_blend64(c->flow, c->view, keys, vals, colors, c->mrg_colors, total, c->dep_total, c->stream);
+    else if (target == 1) th::launch_view_blend64(c->view, keys, vals, colors, c->mrg_colors, total, c->dep_total, c->stream);
+    else th::launch_deposit_blend64(c->flow, keys, vals, colors, c->mrg_colors, total, c->dep_total, c->stream);
     TH_HIP(hipGetLastError());
     uint32_t too_many = 0;
     if (th_status s = read_back(c, &too_many, c->dep_total, sizeof too_many)) return s;        // (a sync: the input buffers may be reused by the caller now)
@@ -256,6 +253,55 @@ static th_status gather_owned(th_context *c, bool view, bool both, const std::ve
     return TH_OK;
 }
 
+// ---- the count exchange -----------------------------------------------------------------------------------------------------
+// x_counts, on the device: the owners' bounds of what this rank holds (world + 1 words, world <= 32), what it holds for every
+// owner, what every rank holds for it.  (The bounds stay on the device: what this rank holds for every owner is their
+// differences, computed there, and comes back to the host together with what the others hold for it - one trip where there
+// were two.  A rank with something to report, or nothing to send, uploads its words itself.)
+constexpr size_t kXBounds = 0, kXSend = 33, kXRecv = 65, kXWords = 97;
+struct CountExchange {
+    std::vector<size_t> scount, soff, rcount, roff;      // fragments for / from every rank, and where each rank's part begins
+    size_t total = 0;                                    // ... received in all
+};
+
+// One word per rank each way.  `mine`: how this rank's stage 1 went - whether it worked travels with the counts, so every rank
+// learns of every failure (kPeerFailed) and of a binned pass that gave up (kPeerRetries: nobody sends it in the stream-ordered
+// pass, and no count reaches bit 32 there); on_device: this rank's counts are at kXSend already.  A rank that failed returns its
+// own error; kRetryInStreamOrder on every rank together.
+static th_status exchange_counts(th_context *c, th_status mine, bool on_device, CountExchange &x)
+{
+    const size_t world = (size_t)c->comm_world;
+    unsigned long long *sendc = c->x_counts + kXSend, *recvc = c->x_counts + kXRecv;
+    const std::string why = mine != TH_OK ? last_error() : std::string();
+    std::vector<size_t> one(world, 1), idx(world);
+    for (size_t r = 0; r < world; ++r) idx[r] = r;
+    const std::vector<unsigned long long> hs(world, mine == TH_OK ? 0ull : (mine == kRetryInStreamOrder ? kPeerRetries : kPeerFailed));
+    if (!on_device) TH_HIP(hipMemcpyAsync(sendc, hs.data(), world * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+    if (c->transport->alltoallv(c->comm, sendc, one.data(), idx.data(), recvc, one.data(), idx.data(), sizeof(unsigned long long), (int)world, c->stream))
+        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+    std::vector<unsigned long long> words(kXWords);
+    if (th_status s = read_back(c, words.data(), c->x_counts, words.size() * sizeof(unsigned long long))) return s;
+    const unsigned long long *hb = words.data() + kXBounds, *hr = words.data() + kXRecv;
+    x.scount.assign(world, 0); x.soff.assign(world, 0); x.rcount.assign(world, 0); x.roff.assign(world, 0);
+    if (on_device) for (size_t r = 0; r < world; ++r) { x.scount[r] = (size_t)(hb[r + 1] - hb[r]); x.soff[r] = (size_t)hb[r]; }
+    if (mine != TH_OK && mine != kRetryInStreamOrder) { last_error() = why; return mine; }
+    for (size_t r = 0; r < world; ++r) if (hr[r] & kPeerFailed) return peer_failure(c, (int)r, "rasterising its band's lines");
+    for (size_t r = 0; r < world; ++r) if (hr[r] & kPeerRetries) return kRetryInStreamOrder;
+    x.total = 0;
+    for (size_t r = 0; r < world; ++r) { x.rcount[r] = (size_t)(hr[r] & 0xffffffffull); x.roff[r] = x.total; x.total += x.rcount[r]; }
+    return TH_OK;
+}
+
+// the fragments change hands: the keys, then the varyings, as the counts said
+static th_status exchange_fragments(th_context *c, const void *keys, const void *colors, size_t color_bytes, const CountExchange &x)
+{
+    const int world = c->comm_world;
+    if (c->transport->alltoallv(c->comm, keys, x.scount.data(), x.soff.data(), c->x_keys, x.rcount.data(), x.roff.data(), sizeof(unsigned long long), world, c->stream) ||
+        c->transport->alltoallv(c->comm, colors, x.scount.data(), x.soff.data(), c->x_colors, x.rcount.data(), x.roff.data(), color_bytes, world, c->stream))
+        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+    return TH_OK;
+}
+
 // One pass: this band's fragments parted by owner -> all-to-all -> the owner's merge -> all-gather of the owned ranges.
 // du alone: the flow pass; ru alone: the view pass; both: both passes over one rasterisation and one exchange (two all-gathers)
 static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
@@ -265,46 +311,29 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
     const size_t color_bytes = both ? 2 * sizeof(float4) : sizeof(float4);
     uint64_t count = 0;
     void *keys = nullptr, *colors = nullptr;
-    // stage 1 - rasterise and part by owner.  Whether it worked travels with the counts: every rank learns of every failure
-    std::vector<unsigned long long> hb((size_t)world + 1, 0ull);
+    // stage 1 - rasterise and part by owner
     th_status mine = injected(c, 2);
     if (mine == TH_OK)
         mine = both ? th_draw_emit(c, du, ru, &count, &keys, &colors)
                     : (view ? th_view_emit(c, ru, &count, &keys, &colors) : th_deposit_emit(c, du, &count, &keys, &colors));
-    // (the owners' bounds stay on the device: what this rank holds for every owner is their differences, computed there, and
-    // comes back to the host together with what the others hold for it - one trip where there were two.  A rank with
-    // something to report, or nothing to send, uploads its words itself.)
-    unsigned long long *bounds = c->x_counts, *sendc = c->x_counts + 33, *recvc = c->x_counts + 65;
-    const std::string why = mine != TH_OK ? last_error() : std::string();
+    // (exchange_counts would pass kRetryInStreamOrder on as a wish for this very pass: no emit returns it, and if one ever did it is a failure here)
+    if (mine == kRetryInStreamOrder) mine = fail(TH_ERR_HIP, "the stream-ordered emit asked for the stream-ordered pass");
     if (fragments) *fragments = mine == TH_OK ? count : 0;
     c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = mine == TH_OK ? count : 0; c->last_draw.crowded_fragments = 0;
-    std::vector<size_t> scount((size_t)world), soff((size_t)world), rcount((size_t)world), roff((size_t)world), one((size_t)world, 1), idx((size_t)world);
-    std::vector<unsigned long long> hs((size_t)world, mine != TH_OK ? kPeerFailed : 0ull), hr((size_t)world);
-    for (int r = 0; r < world; ++r) idx[(size_t)r] = (size_t)r;
     const bool on_device = mine == TH_OK && count;
     if (on_device) {
-        th::launch_owner_bounds(static_cast<const unsigned long long *>(keys), (uint32_t)count, (uint32_t)world, bounds, c->stream);
-        th::launch_exchange_send_counts(bounds, (uint32_t)world, sendc, c->stream);
+        th::launch_owner_bounds(static_cast<const unsigned long long *>(keys), (uint32_t)count, (uint32_t)world, c->x_counts + kXBounds, c->stream);
+        th::launch_exchange_send_counts(c->x_counts + kXBounds, (uint32_t)world, c->x_counts + kXSend, c->stream);
         TH_HIP(hipGetLastError());
-    } else TH_HIP(hipMemcpyAsync(sendc, hs.data(), (size_t)world * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    if (c->transport->alltoallv(c->comm, sendc, one.data(), idx.data(), recvc, one.data(), idx.data(), sizeof(unsigned long long), world, c->stream))
-        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-    {
-        std::vector<unsigned long long> words(97);
-        if (th_status s = read_back(c, words.data(), c->x_counts, words.size() * sizeof(unsigned long long))) return s;
-        if (on_device) std::copy(words.begin(), words.begin() + world + 1, hb.begin());
-        std::copy(words.begin() + 65, words.begin() + 65 + world, hr.begin());
     }
-    for (int r = 0; r < world; ++r) { scount[(size_t)r] = (size_t)(hb[(size_t)r + 1] - hb[(size_t)r]); soff[(size_t)r] = (size_t)hb[(size_t)r]; }
-    if (mine != TH_OK) { last_error() = why; return mine; }
-    for (int r = 0; r < world; ++r) if (hr[(size_t)r] & kPeerFailed) return peer_failure(c, r, "rasterising its band's lines");
-    size_t total = 0;
-    for (int r = 0; r < world; ++r) { rcount[(size_t)r] = (size_t)hr[(size_t)r]; roff[(size_t)r] = total; total += rcount[(size_t)r]; }
+    CountExchange x;
+    if (th_status s = exchange_counts(c, mine, on_device, x)) return s;
     for (int r = 0; r < world; ++r) if (r != rank) {
-        c->last_draw.sent_bytes += 8 + scount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
-        c->last_draw.received_bytes += 8 + rcount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
+        c->last_draw.sent_bytes += 8 + x.scount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
+        c->last_draw.received_bytes += 8 + x.rcount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
     }
     // stage 2 - room for what arrives and for its merge: the last thing that can fail on one rank alone
+    const size_t total = x.total;
     mine = total < ((size_t)1 << 31) ? TH_OK : fail(TH_ERR_UNSUPPORTED, "too many fragments for one owner");
     auto room = [&]() -> th_status {
         if (th_status s = exchange_room(c, total, both)) return s;
@@ -314,9 +343,7 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
     if (mine == TH_OK) mine = room();
     if (th_status s = agree_status(c, mine, "making room for the fragments it owns")) return s;
     // stage 3 - the exchange, the merge, the owned ranges back to everybody
-    if (c->transport->alltoallv(c->comm, keys, scount.data(), soff.data(), c->x_keys, rcount.data(), roff.data(), sizeof(unsigned long long), world, c->stream) ||
-        c->transport->alltoallv(c->comm, colors, scount.data(), soff.data(), c->x_colors, rcount.data(), roff.data(), color_bytes, world, c->stream))
-        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+    if (th_status s = exchange_fragments(c, keys, colors, color_bytes, x)) return s;
     if (th_status s = both ? th_draw_merge(c, c->x_keys, c->x_colors, total)
                            : (view ? th_view_merge(c, c->x_keys, c->x_colors, total) : th_deposit_merge(c, c->x_keys, c->x_colors, total))) return s;
     // the owners' texel ranges of the target(s) to every rank, in place
@@ -326,95 +353,110 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
     return gather_owned(c, view, both, lo, hi);
 }
 
+// ---- the same pass through the BINS, in its parts ------------------------------------------------------------------------------
+// the owner's tables inside own_mem (grow-only): the 8-byte arrays first
+static th_status owner_tables(th_context *c, const th::DepositParams &p, th::OwnerParams &o)
+{
+    const size_t words = (size_t)p.nbins * (1 + 2 + 1 + 1 + 32 * 1 + 32 * 2) + 2 * (2 + 33 + 32) + 64;
+    if (c->own_mem.size() < words) {
+        TH_HIP(hipStreamSynchronize(c->stream));
+        if (th_status s = c->own_mem.alloc(words)) return s;
+    }
+    unsigned long long *q = reinterpret_cast<unsigned long long *>(c->own_mem.get());
+    o.offsets = q; q += (size_t)p.nbins + 1;
+    q += 33;                                               // (the owners' bounds lived here: they lie beside the counts now)
+    o.owner_bounds = c->x_counts + kXBounds;
+    o.recv_base = q; q += 32;
+    o.src_prefix = q; q += (size_t)32 * p.nbins;
+    uint32_t *w = reinterpret_cast<uint32_t *>(q);
+    o.counts = w; w += p.nbins;
+    o.bin_total = w; w += p.nbins;
+    o.bin_page = w; w += p.nbins;
+    o.table = w;
+    return TH_OK;
+}
+
+// stage 1: my band's lines into my store, then compacted owner by owner; the counts for every owner are left on the device
+// (the owners' bounds come back with the counts the others send: one trip, exchange_counts)
+static th_status bins_emit_by_owner(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, th::DepositParams &p, th::OwnerParams &o, uint32_t *emitted)
+{
+    const int world = c->comm_world, rank = c->comm_rank;
+    const bool view = ru != nullptr, both = ru != nullptr && du != nullptr;
+    const th_deposit_uniforms d = du ? *du : deposit_uniforms_of(*ru);
+    if (th_status s = injected(c, 2)) return s;
+    if (injected_give_up(c)) return kRetryInStreamOrder;
+    if (th_status s = deposit_prepare_bins(c, &d, p)) return s;
+    p.mode = both ? 2 : (view ? 1 : 0);
+    if (view) { view_fields(c, ru, p); p.view = c->view; if (!both) p.line_half = 0.5f * drawn_line_width(c, TH_PASS_VIEW); }
+    if (th_status s = bins_pass_emit(c, p, false)) return s;
+    const uint32_t *host = c->bins_totals_host;
+    o.pool_used = host[th::kTotPool];                     // (my own bins stay in the store: what arrives goes behind them)
+    *emitted = host[th::kTotFragments];
+    const uint32_t bins_y = p.nbins / p.bins_x;
+    o.world = (uint32_t)world; o.rank = (uint32_t)rank;
+    for (int r = 0; r <= world; ++r) o.bin_lo[r] = (uint32_t)((unsigned long long)bins_y * (unsigned)r / (unsigned)world) * p.bins_x;
+    o.nb = o.bin_lo[rank + 1] - o.bin_lo[rank];
+    if (th_status s = owner_tables(c, p, o)) return s;
+    const uint32_t total = *emitted;                       // (an upper bound of what leaves)
+    if (total) {
+        if (th_status s = deposit_reserve(c, total, true, both)) return s;
+        o.out_keys = c->dep_u64[0]; o.out_colors = c->dep_colors;
+    }
+    th::launch_bins_owner_counts(p, o, c->stream);
+    if (total) th::launch_bins_owner_extract(p, o, c->stream);
+    th::launch_exchange_send_counts(o.owner_bounds, (uint32_t)world, c->x_counts + kXSend, c->stream);
+    TH_HIP(hipGetLastError());
+    return TH_OK;
+}
+
+// stage 3, the layout: the received bins into the owner's store as if it had emitted them, repeated with a wider table / a
+// larger pool that KEEP what the store holds.  `laid`: how it went - the ranks agree on it; what is returned otherwise ends the
+// call at once, as a failing launch or read-back does anywhere
+static th_status owner_lay_out(th_context *c, th::DepositParams &p, const th::OwnerParams &o, th_status *laid)
+{
+    const uint32_t *host = c->bins_totals_host;
+    for (int attempt = 0;; ++attempt) {
+        TH_HIP(hipMemsetAsync(c->dep_total, 0, th::kTotWords * sizeof(uint32_t), c->stream));
+        bins_pass_expect(c, p);
+        th::launch_bins_owner_insert(p, o, c->stream);
+        TH_HIP(hipGetLastError());
+        if (th_status s = bins_pass_totals(c, p)) return s;
+        const uint32_t flags = host[th::kTotFlags];
+        if (flags == 0) return TH_OK;
+        // (nothing has been blended; a bin beyond its lists' reach cannot be drawn through the bins at all)
+        if (bins_flags_final(flags, attempt)) { *laid = fail(TH_ERR_UNSUPPORTED, "the bins this rank owns could not be laid out (flags %u)", flags); return TH_OK; }
+        if (flags & th::kBinsBinFull) {         // (a wider page table, with the entries of what this rank emitted itself)
+            if ((*laid = bins_table_widen(c, p, true)) == kRetryInStreamOrder)
+                *laid = fail(TH_ERR_UNSUPPORTED, "a bin of the target received more fragments than its lists hold (%u places)", c->bin_max_pages * th::kBinPage * th::kBinReplicas);
+            if (*laid != TH_OK) return TH_OK;
+        }
+        if ((flags & th::kBinsPoolExhausted) && (*laid = bins_store_grow_keep(c, p, host[th::kTotPool] + host[th::kTotPool] / 2u + 64u)) != TH_OK) return TH_OK;
+    }
+}
+
 // The same pass through the BINS (th_bins.hip "the bins travel to the ranks that own them"): every rank rasterises its band's
 // lines into its own page store over whatever slot order its ring is held in (the integrator's tile-sorted one: no return to
 // texel order, no 64-bit keys, no sort anywhere); an owner owns whole bin rows; the bins change hands bin by bin with their
 // counts beside them and are laid out in the owner's store as if it had emitted them; plan and blend kernels as in a single
 // context.  kRetryInStreamOrder (on every rank together): a store could not be had or a bin outgrew its lists - the caller
-// runs the stream-ordered pass.
+// runs the stream-ordered pass.  (last_draw.pipeline is bins_pass_finish's to set: a pass that ends before it reports nothing.)
 static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
 {
     const int world = c->comm_world, rank = c->comm_rank;
     const bool view = ru != nullptr, both = ru != nullptr && du != nullptr;
-    th_deposit_uniforms d{};
-    if (du) d = *du; else { d.viewSize[0] = ru->viewSize[0]; d.viewSize[1] = ru->viewSize[1]; d.time = ru->time; d.speedLimit = ru->speedLimit; }
+    const size_t color_bytes = both ? 2 * sizeof(float4) : sizeof(float4);
     // ---- stage 1: my band's lines into my store, then compacted owner by owner
     th::DepositParams p;
     th::OwnerParams o{};
-    uint32_t *host = nullptr, emitted = 0;
-    std::vector<unsigned long long> hb((size_t)world + 1, 0ull);
-    auto stage1 = [&]() -> th_status {
-        if (th_status s = injected(c, 2)) return s;
-        if (injected_give_up(c)) return kRetryInStreamOrder;
-        if (th_status s = deposit_prepare_bins(c, &d, p)) return s;
-        p.mode = both ? 2 : (view ? 1 : 0);
-        if (view) { view_fields(c, ru, p); p.view = c->view; if (!both) p.line_half = 0.5f * drawn_line_width(c, TH_PASS_VIEW); }
-        if (th_status s = bins_pass_emit(c, p, false)) return s;
-        host = c->bins_totals_host;
-        o.pool_used = host[th::kTotPool];                     // (my own bins stay in the store: what arrives goes behind them)
-        emitted = host[th::kTotFragments];
-        const uint32_t bins_y = p.nbins / p.bins_x;
-        o.world = (uint32_t)world; o.rank = (uint32_t)rank;
-        for (int r = 0; r <= world; ++r) o.bin_lo[r] = (uint32_t)((unsigned long long)bins_y * (unsigned)r / (unsigned)world) * p.bins_x;
-        o.nb = o.bin_lo[rank + 1] - o.bin_lo[rank];
-        const size_t words = (size_t)p.nbins * (1 + 2 + 1 + 1 + 32 * 1 + 32 * 2) + 2 * (2 + 33 + 32) + 64;
-        if (c->own_mem.size() < words) {
-            TH_HIP(hipStreamSynchronize(c->stream));
-            if (th_status s = c->own_mem.alloc(words)) return s;
-        }
-        unsigned long long *q = reinterpret_cast<unsigned long long *>(c->own_mem.get());           // (the 8-byte arrays first)
-        o.offsets = q; q += (size_t)p.nbins + 1;
-        q += 33;                                               // (the owners' bounds lived here: they lie beside the counts now)
-        o.owner_bounds = c->x_counts;
-        unsigned long long *recv_base = q; q += 32;
-        o.recv_base = recv_base;
-        o.src_prefix = q; q += (size_t)32 * p.nbins;
-        uint32_t *w = reinterpret_cast<uint32_t *>(q);
-        o.counts = w; w += p.nbins;
-        o.bin_total = w; w += p.nbins;
-        o.bin_page = w; w += p.nbins;
-        o.table = w;
-        const uint32_t total = emitted;                        // (an upper bound of what leaves)
-        if (total) {
-            if (th_status s = deposit_reserve(c, total, true, both)) return s;
-            o.out_keys = c->dep_u64[0]; o.out_colors = c->dep_colors;
-        }
-        th::launch_bins_owner_counts(p, o, c->stream);
-        if (total) th::launch_bins_owner_extract(p, o, c->stream);
-        th::launch_exchange_send_counts(o.owner_bounds, (uint32_t)world, c->x_counts + 33, c->stream);
-        TH_HIP(hipGetLastError());
-        return TH_OK;                   // (the owners' bounds come back with the counts the others send: one trip, below)
-    };
-    th_status mine = stage1();
-    const std::string why = mine != TH_OK ? last_error() : std::string();
+    uint32_t emitted = 0;
+    th_status mine = bins_emit_by_owner(c, du, ru, p, o, &emitted);
     if (fragments) *fragments = mine == TH_OK ? emitted : 0;          // (what leaves + what stays)
-    unsigned long long *sendc = c->x_counts + 33, *recvc = c->x_counts + 65;
-    std::vector<size_t> scount((size_t)world), soff((size_t)world), rcount((size_t)world), roff((size_t)world), one((size_t)world, 1), idx((size_t)world);
-    std::vector<unsigned long long> hs((size_t)world, mine == kRetryInStreamOrder ? kPeerRetries : kPeerFailed), hr((size_t)world);
-    for (int r = 0; r < world; ++r) idx[(size_t)r] = (size_t)r;
-    // (a rank whose stage 1 went through left its counts on the device - launch_exchange_send_counts; one that has something to
-    // report uploads its words)
-    if (mine != TH_OK) TH_HIP(hipMemcpyAsync(sendc, hs.data(), (size_t)world * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    if (c->transport->alltoallv(c->comm, sendc, one.data(), idx.data(), recvc, one.data(), idx.data(), sizeof(unsigned long long), world, c->stream))
-        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-    {
-        std::vector<unsigned long long> words(97);
-        if (th_status s = read_back(c, words.data(), c->x_counts, words.size() * sizeof(unsigned long long))) return s;
-        if (mine == TH_OK) std::copy(words.begin(), words.begin() + world + 1, hb.begin());
-        std::copy(words.begin() + 65, words.begin() + 65 + world, hr.begin());
-    }
-    for (int r = 0; r < world; ++r) { scount[(size_t)r] = (size_t)(hb[(size_t)r + 1] - hb[(size_t)r]); soff[(size_t)r] = (size_t)hb[(size_t)r]; }
-    if (mine != TH_OK && mine != kRetryInStreamOrder) { last_error() = why; return mine; }
-    for (int r = 0; r < world; ++r) if (hr[(size_t)r] & kPeerFailed) return peer_failure(c, r, "rasterising its band's lines");
-    for (int r = 0; r < world; ++r) if (hr[(size_t)r] & kPeerRetries) return kRetryInStreamOrder;
-    size_t total = 0;
-    for (int r = 0; r < world; ++r) { rcount[(size_t)r] = (size_t)(hr[(size_t)r] & 0xffffffffull); roff[(size_t)r] = total; total += rcount[(size_t)r]; }
-    {   // (counts word, the per-bin counts of the owner's bins, keys + varyings of what changes hands)
-        const size_t frag_bytes = sizeof(unsigned long long) + (both ? 2 : 1) * sizeof(float4);
-        for (int r = 0; r < world; ++r) if (r != rank) {
-            c->last_draw.sent_bytes += 8 + (size_t)(o.bin_lo[r + 1] - o.bin_lo[r]) * sizeof(uint32_t) + scount[(size_t)r] * frag_bytes;
-            c->last_draw.received_bytes += 8 + (size_t)o.nb * sizeof(uint32_t) + rcount[(size_t)r] * frag_bytes;
-        }
+    CountExchange x;
+    if (th_status s = exchange_counts(c, mine, mine == TH_OK, x)) return s;
+    // (counts word, the per-bin counts of the owner's bins, keys + varyings of what changes hands)
+    for (int r = 0; r < world; ++r) if (r != rank) {
+        c->last_draw.sent_bytes += 8 + (size_t)(o.bin_lo[r + 1] - o.bin_lo[r]) * sizeof(uint32_t) + x.scount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
+        c->last_draw.received_bytes += 8 + (size_t)o.nb * sizeof(uint32_t) + x.rcount[(size_t)r] * (sizeof(unsigned long long) + color_bytes);
     }
     // ---- stage 2: every source's counts for my bins; room for what arrives; my store laid out for it (the last things that can
     // fail on one rank alone: agreed on before the fragments travel)
@@ -426,10 +468,10 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
     }
     auto stage2 = [&]() -> th_status {
         if (th_status s = injected(c, 3)) return s;
-        if (total >= ((size_t)1 << 31)) return fail(TH_ERR_UNSUPPORTED, "too many fragments for one owner");
-        if (world > 1) if (th_status s = exchange_room(c, total, both)) return s;
+        if (x.total >= ((size_t)1 << 31)) return fail(TH_ERR_UNSUPPORTED, "too many fragments for one owner");
+        if (world > 1) if (th_status s = exchange_room(c, x.total, both)) return s;
         // (where every source's part starts in what arrives: the running sum of the received counts, made on the device)
-        th::launch_exchange_recv_base(recvc, (uint32_t)world, const_cast<unsigned long long *>(o.recv_base), c->stream);
+        th::launch_exchange_recv_base(c->x_counts + kXRecv, (uint32_t)world, const_cast<unsigned long long *>(o.recv_base), c->stream);
         TH_HIP(hipGetLastError());
         return TH_OK;
     };
@@ -438,29 +480,11 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
     // ---- stage 3: the bins travel; laid out and blended where they are owned; the owned rows back to everybody
     if (world == 1) { o.in_keys = o.out_keys; o.in_colors = o.out_colors; }        // (nobody to send to: the compacted parts are the received ones)
     else {
-        if (c->transport->alltoallv(c->comm, o.out_keys, scount.data(), soff.data(), c->x_keys, rcount.data(), roff.data(), sizeof(unsigned long long), world, c->stream) ||
-            c->transport->alltoallv(c->comm, o.out_colors, scount.data(), soff.data(), c->x_colors, rcount.data(), roff.data(), both ? 2 * sizeof(float4) : sizeof(float4), world, c->stream))
-            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+        if (th_status s = exchange_fragments(c, o.out_keys, o.out_colors, color_bytes, x)) return s;
         o.in_keys = c->x_keys; o.in_colors = c->x_colors;
     }
     th_status laid = TH_OK;
-    for (int attempt = 0;; ++attempt) {
-        TH_HIP(hipMemsetAsync(c->dep_total, 0, th::kTotWords * sizeof(uint32_t), c->stream));
-        bins_pass_expect(c, p);
-        th::launch_bins_owner_insert(p, o, c->stream);
-        TH_HIP(hipGetLastError());
-        if (th_status s = bins_pass_totals(c, p)) return s;
-        const uint32_t flags = host[th::kTotFlags];
-        if (flags == 0) break;
-        // (nothing has been blended; a bin beyond its lists' reach cannot be drawn through the bins at all)
-        if ((flags & ~(th::kBinsPoolExhausted | th::kBinsBinFull)) || attempt >= 6) { laid = fail(TH_ERR_UNSUPPORTED, "the bins this rank owns could not be laid out (flags %u)", flags); break; }
-        if (flags & th::kBinsBinFull) {         // (a wider page table, with the entries of what this rank emitted itself)
-            if ((laid = bins_table_widen(c, p, true)) == kRetryInStreamOrder)
-                laid = fail(TH_ERR_UNSUPPORTED, "a bin of the target received more fragments than its lists hold (%u places)", c->bin_max_pages * th::kBinPage * th::kBinReplicas);
-            if (laid != TH_OK) break;
-        }
-        if ((flags & th::kBinsPoolExhausted) && (laid = bins_store_grow_keep(c, p, host[th::kTotPool] + host[th::kTotPool] / 2u + 64u)) != TH_OK) break;
-    }
+    if (th_status s = owner_lay_out(c, p, o, &laid)) return s;
     if (laid == TH_OK) laid = bins_pass_finish(c, p, nullptr, false);
     // (an owner that could not lay its bins out has blended nothing; the others have: the draw is lost, and everybody says so)
     if (th_status s = agree_status(c, laid == kRetryInStreamOrder ? fail(TH_ERR_HIP, "the owner's store could not be had") : laid, "laying out the bins it owns")) return s;
@@ -473,83 +497,103 @@ static th_status sharded_pass_bins(th_context *c, const th_deposit_uniforms *du,
     return gather_owned(c, view, both, lo, hi);
 }
 
+// ---- th_draw_sharded, in its parts -----------------------------------------------------------------------------------------------
+// the fixed buffers of the exchange, once - and the ranks make sure that every one of them has them
+static th_status sharded_draw_fixed(th_context *c, bool view)
+{
+    const int world = c->comm_world, W = c->cfg.width;
+    if (c->sharded_draw_ready) return view ? view_storage(c) : TH_OK;       // (a resized target: the same on every rank)
+    auto fixed = [&]() -> th_status {
+        if (th_status s = c->x_counts.reserve(kXWords, kXWords)) return s;
+        if (world > 1) if (th_status s = c->x_halo.reserve((size_t)4 * W, (size_t)4 * W)) return s;
+        if (th_status s = line_rows(c)) return s;
+        if (world > 1 && c->rows_cross_bands) if (th_status s = c->edge_rows.reserve((size_t)4 * W, (size_t)4 * W)) return s;
+        return view ? view_storage(c) : TH_OK;
+    };
+    if (th_status s = agree_status(c, fixed(), "allocating the exchange's buffers")) return s;
+    c->sharded_draw_ready = true;
+    return TH_OK;
+}
+
+// the tail of both halo exchanges: two rows of cur and prev each way are in x_halo - `lo` from the rank below, `hi` from the rank above
+static void halo_received(th_context *c)
+{
+    const int world = c->comm_world, rank = c->comm_rank, W = c->cfg.width;
+    const uint64_t rows_moved = 2ull * ((rank > 0 ? 1u : 0u) + (rank + 1 < world ? 1u : 0u)) * (uint64_t)W * sizeof(float4);
+    c->last_draw.sent_bytes += rows_moved; c->last_draw.received_bytes += rows_moved;
+    c->halo_lo = rank > 0 ? c->x_halo : nullptr;
+    c->halo_hi = rank + 1 < world ? c->x_halo + (size_t)2 * W : nullptr;
+}
+
+// a job that draws through the bins keeps its slot order: a band's two edge rows are picked out of the slot order
+// (th::LineSources) into texel order, f32, and sent from there.  (the gather's out-of-band word is cleared by the
+// draw that follows before anyone reads it - kept as it is here)
+static th_status halo_exchange_bins(th_context *c, const th_deposit_uniforms *du)
+{
+    const int world = c->comm_world, rank = c->comm_rank, W = c->cfg.width;
+    th::DepositParams p;
+    th_status mine = injected(c, 1);
+    if (mine == TH_OK) mine = deposit_prepare_bins(c, du, p);
+    if (mine == TH_OK) { th::launch_bins_edge_rows(p, c->edge_rows, c->stream); if (hipGetLastError() != hipSuccess) mine = fail(TH_ERR_HIP, "the edge rows' gather could not be launched"); }
+    if (th_status s = agree_status(c, mine, "gathering its edge rows")) return s;
+    std::vector<size_t> sc((size_t)world, 0), so((size_t)world, 0), rc((size_t)world, 0), ro((size_t)world, 0);
+    // to rank - 1: my first row of cur and of prev (its `hi`); to rank + 1: my last rows (its `lo`); two rows of W texels each
+    if (rank > 0) { sc[(size_t)rank - 1] = 2; so[(size_t)rank - 1] = 0; rc[(size_t)rank - 1] = 2; ro[(size_t)rank - 1] = 0; }
+    if (rank + 1 < world) { sc[(size_t)rank + 1] = 2; so[(size_t)rank + 1] = 2; rc[(size_t)rank + 1] = 2; ro[(size_t)rank + 1] = 2; }
+    if (c->transport->alltoallv(c->comm, c->edge_rows, sc.data(), so.data(), c->x_halo, rc.data(), ro.data(), (size_t)W * sizeof(float4), world, c->stream))
+        return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+    halo_received(c);
+    return TH_OK;
+}
+
+// ... and in texel order the rows are sent from the ring itself (a packed ring: from its f32 views - what the stored texels
+// decode to, what the lines are made of)
+static th_status halo_exchange_stream(th_context *c)
+{
+    const int world = c->comm_world, rank = c->comm_rank, W = c->cfg.width;
+    th_status mine = c->packed ? injected(c, 1) : TH_OK;
+    if (mine == TH_OK) mine = ensure_identity(c);
+    const float4 *state[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2 && mine == TH_OK; ++b) {
+        float4 *v = nullptr;
+        mine = unpacked_view(c, c->ring[(size_t)b], b, &v);
+        state[b] = v;
+    }
+    // (an f32 ring: nothing here fails on one rank alone - no agreement, no extra round trip)
+    if (c->packed) { if (th_status s = agree_status(c, mine, "decoding its packed edge rows")) return s; }
+    else if (mine != TH_OK) return mine;
+    std::vector<size_t> sc((size_t)world, 0), so((size_t)world, 0), rc((size_t)world, 0), ro((size_t)world, 0);
+    for (int b = 0; b < 2; ++b) {           // ring buffer b: one exchange each (the rows lie in different allocations)
+        std::fill(sc.begin(), sc.end(), 0); std::fill(rc.begin(), rc.end(), 0);
+        // to rank - 1: my first row (its `hi`); to rank + 1: my last row (its `lo`).  Offsets are in rows of W texels from `state`.
+        if (rank > 0) { sc[(size_t)rank - 1] = 1; so[(size_t)rank - 1] = 0; rc[(size_t)rank - 1] = 1; ro[(size_t)rank - 1] = (size_t)b; }
+        if (rank + 1 < world) { sc[(size_t)rank + 1] = 1; so[(size_t)rank + 1] = (size_t)c->cfg.height - 1; rc[(size_t)rank + 1] = 1; ro[(size_t)rank + 1] = 2 + (size_t)b; }
+        if (c->transport->alltoallv(c->comm, state[b], sc.data(), so.data(), c->x_halo, rc.data(), ro.data(), (size_t)W * sizeof(float4), world, c->stream))
+            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
+    }
+    halo_received(c);
+    return TH_OK;
+}
+
 th_status th_draw_sharded(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(du, "null uniforms");
     TH_REQUIRE(c->comm, "th_draw_sharded needs the job's communicator (th_comm_init)");
     TH_REQUIRE(c->comm_world <= 32, "the owners' merge handles up to 32 ranks");
-    if (ru) TH_REQUIRE(memcmp(du->viewSize, ru->viewSize, sizeof du->viewSize) == 0 && memcmp(&du->time, &ru->time, sizeof du->time) == 0 &&
-                       memcmp(&du->speedLimit, &ru->speedLimit, sizeof du->speedLimit) == 0,
-                       "the two passes of one draw share viewSize, time and speedLimit");      // (the same on every rank: a host error, not a rank-local one)
-    const int world = c->comm_world, rank = c->comm_rank, W = c->cfg.width;
+    if (ru) if (th_status s = shared_uniforms(du, ru)) return s;      // (the same on every rank: a host error, not a rank-local one)
+    const int world = c->comm_world;
     c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;
-    if (!c->sharded_draw_ready) {
-        // the fixed buffers of the exchange, once - and the ranks make sure that every one of them has them
-        auto fixed = [&]() -> th_status {
-            if (th_status s = c->x_counts.reserve(97, 97)) return s;
-            if (world > 1) if (th_status s = c->x_halo.reserve((size_t)4 * W, (size_t)4 * W)) return s;
-            if (th_status s = line_rows(c)) return s;
-            if (world > 1 && c->rows_cross_bands) if (th_status s = c->edge_rows.reserve((size_t)4 * W, (size_t)4 * W)) return s;
-            return ru ? view_storage(c) : TH_OK;
-        };
-        if (th_status s = agree_status(c, fixed(), "allocating the exchange's buffers")) return s;
-        c->sharded_draw_ready = true;
-    } else if (ru) if (th_status s = view_storage(c)) return s;       // (a resized target: the same on every rank)
+    if (th_status s = sharded_draw_fixed(c, ru != nullptr)) return s;
     // the neighbouring bands' edge rows of both state buffers (the fp32 row lookup of the vertex stream can land one row
     // beside a line's own row for some texture heights): my first row to the rank below, my last row to the rank above.
-    // A packed ring sends the rows of its f32 views - what the stored texels decode to, what the lines are made of.
-    // A job that draws through the bins keeps its slot order: where every vertex of every line is the line's own particle it
-    // needs none of this; where the row lookup drifts (rows_cross_bands: a property of the texture's shape, the same on every
-    // rank) a band's two edge rows are picked out of the slot order (th::LineSources) into texel order, f32, and sent from there.
+    // Through the bins, where every vertex of every line is the line's own particle, a job needs none of this; where the row
+    // lookup drifts (rows_cross_bands: a property of the texture's shape, the same on every rank) it does.
     if (th_status s = line_rows(c)) return s;
     const bool bins = binned_shards(c);
     c->halo_lo = c->halo_hi = nullptr;
-    if (world > 1 && bins && c->rows_cross_bands) {
-        th::DepositParams p;
-        th_status mine = injected(c, 1);
-        if (mine == TH_OK) mine = deposit_prepare_bins(c, du, p);
-        if (mine == TH_OK) { th::launch_bins_edge_rows(p, c->edge_rows, c->stream); if (hipGetLastError() != hipSuccess) mine = fail(TH_ERR_HIP, "the edge rows' gather could not be launched"); }
-        if (th_status s = agree_status(c, mine, "gathering its edge rows")) return s;
-        std::vector<size_t> sc((size_t)world, 0), so((size_t)world, 0), rc((size_t)world, 0), ro((size_t)world, 0);
-        // to rank - 1: my first row of cur and of prev (its `hi`); to rank + 1: my last rows (its `lo`); two rows of W texels each
-        if (rank > 0) { sc[(size_t)rank - 1] = 2; so[(size_t)rank - 1] = 0; rc[(size_t)rank - 1] = 2; ro[(size_t)rank - 1] = 0; }
-        if (rank + 1 < world) { sc[(size_t)rank + 1] = 2; so[(size_t)rank + 1] = 2; rc[(size_t)rank + 1] = 2; ro[(size_t)rank + 1] = 2; }
-        if (c->transport->alltoallv(c->comm, c->edge_rows, sc.data(), so.data(), c->x_halo, rc.data(), ro.data(), (size_t)W * sizeof(float4), world, c->stream))
-            return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-        const uint64_t rows_moved = 2ull * ((rank > 0 ? 1u : 0u) + (rank + 1 < world ? 1u : 0u)) * (uint64_t)W * sizeof(float4);
-        c->last_draw.sent_bytes += rows_moved; c->last_draw.received_bytes += rows_moved;
-        c->halo_lo = rank > 0 ? c->x_halo : nullptr;
-        c->halo_hi = rank + 1 < world ? c->x_halo + (size_t)2 * W : nullptr;
-    }
-    if (world > 1 && !bins) {
-        th_status mine = c->packed ? injected(c, 1) : TH_OK;
-        if (mine == TH_OK) mine = ensure_identity(c);
-        const float4 *state[2] = {nullptr, nullptr};
-        for (int b = 0; b < 2 && mine == TH_OK; ++b) {
-            float4 *v = nullptr;
-            mine = unpacked_view(c, c->ring[(size_t)b], b, &v);
-            state[b] = v;
-        }
-        // (an f32 ring: nothing here fails on one rank alone - no agreement, no extra round trip)
-        if (c->packed) { if (th_status s = agree_status(c, mine, "decoding its packed edge rows")) return s; }
-        else if (mine != TH_OK) return mine;
-        std::vector<size_t> sc((size_t)world, 0), so((size_t)world, 0), rc((size_t)world, 0), ro((size_t)world, 0);
-        for (int b = 0; b < 2; ++b) {           // ring buffer b: one exchange each (the rows lie in different allocations)
-            std::fill(sc.begin(), sc.end(), 0); std::fill(rc.begin(), rc.end(), 0);
-            // to rank - 1: my first row (its `hi`); to rank + 1: my last row (its `lo`).  Offsets are in rows of W texels from `state`.
-            if (rank > 0) { sc[(size_t)rank - 1] = 1; so[(size_t)rank - 1] = 0; rc[(size_t)rank - 1] = 1; ro[(size_t)rank - 1] = (size_t)b; }
-            if (rank + 1 < world) { sc[(size_t)rank + 1] = 1; so[(size_t)rank + 1] = (size_t)c->cfg.height - 1; rc[(size_t)rank + 1] = 1; ro[(size_t)rank + 1] = 2 + (size_t)b; }
-            if (c->transport->alltoallv(c->comm, state[b], sc.data(), so.data(), c->x_halo, rc.data(), ro.data(), (size_t)W * sizeof(float4), world, c->stream))
-                return fail(TH_ERR_UNSUPPORTED, "%s", th::comm_error());
-        }
-        {
-            const uint64_t rows_moved = 2ull * ((rank > 0 ? 1u : 0u) + (rank + 1 < world ? 1u : 0u)) * (uint64_t)W * sizeof(float4);
-            c->last_draw.sent_bytes += rows_moved; c->last_draw.received_bytes += rows_moved;
-        }
-        c->halo_lo = rank > 0 ? c->x_halo : nullptr;
-        c->halo_hi = rank + 1 < world ? c->x_halo + (size_t)2 * W : nullptr;
-    }
+    if (world > 1 && bins && c->rows_cross_bands) if (th_status s = halo_exchange_bins(c, du)) return s;
+    if (world > 1 && !bins) if (th_status s = halo_exchange_stream(c)) return s;
     c->dep_owners = (uint32_t)world;
     auto pass = [&](const th_deposit_uniforms *d, const th_render_uniforms *r, uint64_t *n) -> th_status {
         if (bins) {
