@@ -397,7 +397,11 @@ th_status th_draw_program_run(th_context *ctx, th_program *program, const void *
  *                                32 steps per launch - 16 bytes read and 32 written per particle and launch
  *                        single  every other ring (more than two buffers, TH_STATE_F16, fuse off): the same kernel, one step per
  *                                launch, a packed ring quantised after every step as single passes would
- *                      The ring goes to texel order first, as for every program pass.  source: TH_SOURCE_NONE, TH_SOURCE_FLOW or
+ *                      The fused path steps over the slot order buffers[0] is held in and leaves both buffers in it: a ring that
+ *                      built-in steps or a binned draw() left tile-sorted stays sorted (x, y, index, uv and the targets texel are
+ *                      the particle's, whatever slot holds it), a ring in texel order stays in texel order; with a key
+ *                      (th_step_program_view_size) the call also lays the order out and refreshes it.  The single path moves
+ *                      the ring to texel order first, as every other program pass does.  source: TH_SOURCE_NONE, TH_SOURCE_FLOW or
  *                      TH_SOURCE_IMAGE; a ring buffer is refused (TH_ERR_INVALID): the ring is what the call writes, a fused
  *                      launch overwrites its input.  Row bands need nothing extra: x, y, index, uv are those of the whole texture,
  *                      and there is no read outside the band to flag.  The `respawned` counter is not touched.  th_kernel_timing
@@ -407,6 +411,14 @@ th_status th_draw_program_run(th_context *ctx, th_program *program, const void *
 th_status th_step_program_compile(const char *source, const char *name, th_program **out);
 th_status th_step_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
                               int32_t source /* TH_SOURCE_NONE | _FLOW | _IMAGE */, const float *times, float dt, int32_t n);
+/* The key a step program's calls sort the slots under: the built-in integrator's tap - the flow tile of
+ * pos * viewSize (th::TileGeom).  NULL: none (the default) - a call then lays out no order of its own.
+ * With a key, a fused th_step_program_run does before its launches what th_step_n does: where the slots may be sorted at all
+ * (TH_OPT_BUCKET and its auto rule; no texel-order consumer holding the layout off) it sorts buffers[0] when it is unsorted,
+ * when its order is stale for this view size and flow shape, or after TH_OPT_REBUCKET_STEPS steps - a plain move into the other
+ * buffer -, and elsewhere it steps in texel order.  The key changes no result, only where the state lies.  A non-finite or
+ * non-positive component is refused (TH_ERR_INVALID, the value named) and the key in force stays. */
+th_status th_step_program_view_size(th_context *ctx, const float viewSize[2]);
 
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */

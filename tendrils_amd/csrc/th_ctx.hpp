@@ -285,6 +285,8 @@ struct th_context {
     int steps_since_sort = 0;
     unsigned long long sorts = 0;
     long long total_steps = 0, hold_texel_order_until = 0;   // texel-order consumers (draw) keep the layout off for a period
+    bool step_keyed = false;             // th_step_program_view_size: a step program's calls sort the slots themselves, under the
+    float step_view[2] = {1.0f, 1.0f};   // ... key of this view size
     HostBuf<uint32_t> miss_host;         // window misses since the last sort, as of some recent launch
     // A re-sort under way beside a draw() (th_step.hip "the re-sort of a frame loop"): the step's output `src` (held in order
     // `src_order`) is being copied into `dst` in the new order `order` on the side stream; the next step takes the copy for
@@ -421,6 +423,8 @@ template <class Args> struct ProgramKernArgs {
 // argument segment: the runtime copies it when it enqueues the launch - no copy of the library's own, nothing to wait for
 th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *record, size_t bytes);
 template <class Args> th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, ProgramKernArgs<Args> &k) { return program_launch(c, fn, lanes, &k, sizeof k); }
+// ... on a grid of the caller's (256-lane workgroups): a step program over tile-sorted slots takes the built-in fused launch's
+th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
 // an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format
@@ -440,7 +444,8 @@ constexpr int kTileShift = 5;            // 32 x 32 texel tiles (th_kernels.hip 
 constexpr size_t kTileWords = 2 * (size_t)th::kSortReplicas * th::kMaxTileBins;   // histogram + cursors, all copies
 bool sorting_possible(const th_context *c);
 th_status line_rows(th_context *c);
-th::TileGeom tile_geom(const th_context *c, const th_logic_uniforms &u);
+th::TileGeom tile_geom(const th_context *c, const float viewSize[2]);       // the sort key: the flow tile of pos * viewSize
+inline th::TileGeom tile_geom(const th_context *c, const th_logic_uniforms &u) { return tile_geom(c, u.viewSize); }
 bool same_geom(const th::TileGeom &a, const th::TileGeom &b);
 int order_of(const th_context *c, const float4 *buf);
 void set_order(th_context *c, float4 *buf, int order);
@@ -455,6 +460,8 @@ th_status ensure_identity(th_context *c, bool *launched = nullptr);
 th_status begin_sort(th_context *c, const th::TileGeom &g, const float4 *state, const uint32_t *perm_in, int *order,
                      th::TileSortParams *params, bool have_hist = false);
 th_status align_slot_orders(th_context *c);
+// Slot layout of fused passes (th_step_n, th_step_program_run): see th_order.hip
+th_status fused_slots(th_context *c, bool may_sort, const th::TileGeom &g);
 
 // ---- th_draw.hip -----------------------------------------------------------------------------------------------------
 int deposit_texel_bits(const th_context *c);

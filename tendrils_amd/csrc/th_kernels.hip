@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256, 5) void logic_fused_packed_kernel(const LogicP
 // unevenly loaded at the end of the pass (1280 resident + a 768-workgroup second round); with one short
 // workgroup per 256 slots the dispatcher keeps every CU full until the last few (C3, exact: 0.098 -> 0.086 ms per
 // step, profiles/r2_a_grid_sweep.txt).
-static int fused_grid(uint32_t count, bool bucketed)
+int fused_grid(uint32_t count, bool bucketed)
 {
     const uint32_t blocks = (count + 255u) / 256u;
     // bucketed: 8 XCD groups, group g = blockIdx % 8 sweeps its eighth of the slots

@@ -326,6 +326,9 @@ void launch_finite_check(const float4 *src, size_t n, unsigned int *flag, hipStr
 void launch_stats_fold(const StatsPartial *parts, uint32_t nparts, StatsPartial *scratch, size_t n, const unsigned long long *respawned,
                        th_counters *out, hipStream_t stream);
 uint32_t fused_stats_parts(uint32_t count, bool sorted);
+// workgroups of a fused pass over `count` slots (th_kernels.hip "Launch shape of the fused passes"); bucketed: a multiple of 8,
+// workgroup b sweeps the (b & 7)-th eighth of the slots - the shape a step program over tile-sorted slots takes too
+int fused_grid(uint32_t count, bool bucketed);
 void launch_stats(const float4 *state, size_t n, float speed_limit, StatsPartial *partials, const unsigned long long *respawned,
                   th_counters *out, hipStream_t stream);
 void launch_counter_add(unsigned long long *counter, unsigned long long n, hipStream_t s);

@@ -101,12 +101,12 @@ th_status line_rows(th_context *c)
     return TH_OK;
 }
 
-th::TileGeom tile_geom(const th_context *c, const th_logic_uniforms &u)
+th::TileGeom tile_geom(const th_context *c, const float viewSize[2])
 {
     th::TileGeom g{};
     g.width = (uint32_t)c->cfg.width; g.pow2w = is_pow2(g.width) ? 1u : 0u; g.log2w = g.pow2w ? ilog2(g.width) : 0u;
     g.row0 = (uint32_t)c->cfg.row0; g.row_draws = c->d_row_draws;
-    g.view_x = u.viewSize[0]; g.view_y = u.viewSize[1];
+    g.view_x = viewSize[0]; g.view_y = viewSize[1];
     g.half_fw = 0.5f * (float)c->fw; g.half_fh = 0.5f * (float)c->fh;
     g.fwm1 = (float)(c->fw - 1); g.fhm1 = (float)(c->fh - 1);
     g.ntiles = tile_count(c, &g.tiles_x);
@@ -301,6 +301,30 @@ th_status begin_sort(th_context *c, const th::TileGeom &g, const float4 *state, 
     o.stamp = c->sorts;
     c->counted.buf = nullptr;
     if (params) *params = b;
+    return TH_OK;
+}
+
+// Slot layout of the fused passes (th_step_n's and a keyed step program's): the newest state (ring[0]) may be in a tile-sorted
+// order; both outputs of a pass keep the slots of its input.  (Re)sorted every c->opt.rebucket_steps steps by a plain move into
+// the other buffer, whose content (state n-1 of the previous call) the pass overwrites anyway.  `may_sort`: the caller's
+// predicate (sorting_possible, the hold for texel-order consumers, what its kernel can do); without it: texel order.
+th_status fused_slots(th_context *c, bool may_sort, const th::TileGeom &g)
+{
+    if (!may_sort) return ensure_identity(c);
+    const int o = order_of(c, c->ring[0]);
+    if (o >= 0 && !order_stale(c, o, g) && c->steps_since_sort < c->opt.rebucket_steps) return TH_OK;
+    float4 *cur = c->ring[0], *other = c->ring[1];
+    set_order(c, other, -1);
+    int fresh = -1;
+    th::TileSortParams b;
+    if (th_status s = begin_sort(c, g, cur, o >= 0 ? c->orders[(size_t)o].perm : nullptr, &fresh, &b)) return s;
+    b.state_out = other;
+    th::launch_tile_scatter(b, c->stream);
+    TH_HIP(hipGetLastError());
+    set_order(c, other, fresh);
+    set_order(c, cur, -1);                 // (its content is dead: the sorted copy is the newest state now)
+    state_written(c, other); state_moved(c, cur, other);
+    c->ring[0] = other; c->ring[1] = cur;
     return TH_OK;
 }
 

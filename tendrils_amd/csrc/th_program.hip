@@ -165,8 +165,13 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
 
 th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *record, size_t bytes)
 {
+    return program_launch_grid(c, fn, th::grid_for(lanes, 8), record, bytes);
+}
+
+th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes)
+{
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, record, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    TH_HIP(hipModuleLaunchKernel(fn, (unsigned)th::grid_for(lanes, 8), 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
+    TH_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
     return TH_OK;
 }
 

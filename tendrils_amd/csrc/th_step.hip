@@ -389,34 +389,10 @@ static th_status enqueue_step(th_context *c, const StepPlan &plan, int32_t targe
 }
 
 // ---- th_step_n's three paths --------------------------------------------------------------------
-// Slot layout of the fused passes: the newest state (ring[0]) may be in a tile-sorted order; both outputs of a
-// pass keep the slots of its input.  (Re)sorted every c->opt.rebucket_steps steps by a plain move into the other
-// buffer, whose content (state n-1 of the previous call) the pass overwrites anyway.
-static th_status fused_slots(th_context *c, const StepPlan &plan)
-{
-    if (!plan.may_sort) return ensure_identity(c);
-    const th::TileGeom g = tile_geom(c, plan.p.u);
-    const int o = order_of(c, c->ring[0]);
-    if (o >= 0 && !order_stale(c, o, g) && c->steps_since_sort < c->opt.rebucket_steps) return TH_OK;
-    float4 *cur = c->ring[0], *other = c->ring[1];
-    set_order(c, other, -1);
-    int fresh = -1;
-    th::TileSortParams b;
-    if (th_status s = begin_sort(c, g, cur, o >= 0 ? c->orders[(size_t)o].perm : nullptr, &fresh, &b)) return s;
-    b.state_out = other;
-    th::launch_tile_scatter(b, c->stream);
-    TH_HIP(hipGetLastError());
-    set_order(c, other, fresh);
-    set_order(c, cur, -1);                 // (its content is dead: the sorted copy is the newest state now)
-    state_written(c, other); state_moved(c, cur, other);
-    c->ring[0] = other; c->ring[1] = cur;
-    return TH_OK;
-}
-
 // Temporal fusion (logic_fused_kernel): all n steps of a particle in one pass, <= kMaxFusedSteps per launch.
 static th_status step_n_fused(th_context *c, const StepPlan &plan, const std::vector<float> &times, int32_t n)
 {
-    if (th_status s = fused_slots(c, plan)) return s;
+    if (th_status s = fused_slots(c, plan.may_sort, tile_geom(c, plan.p.u))) return s;
     // The field does not change inside the call.  Without the noise the pass waits for its taps (a dependent gather per
     // step): the field's x, y, z packed 12 B apart once per call - three quarters of the footprint, and the band one
     // XCD taps fits its L2 (0.574 -> 0.546 ms per 20-step launch at C3; with the noise on the pass is bound by its

@@ -19,6 +19,7 @@ struct th_step_args {
     const float4 *data;          // spawnData (0: none)
     const float4 *flow;
     const float4 *targets;
+    const unsigned *perm;        // 0: texel order; else slot i of in / out / out_prev holds texel perm[i] of this context's rows
     unsigned count, width, rows, row0, global_height;
     int dw, dh, fw, fh;
     unsigned nsteps;             // steps of this launch (1 .. 32)
@@ -26,7 +27,7 @@ struct th_step_args {
     float dt;
     float times[32];             // this launch's steps' `time`
 };
-static_assert(sizeof(th_step_args) == 224, "th_step_args: layout shared with th_stepprog.hip");
+static_assert(sizeof(th_step_args) == 232, "th_step_args: layout shared with th_stepprog.hip");
 struct __attribute__((aligned(16))) th_program_uniform_block { unsigned char bytes[1024]; };
 
 struct th_step_pass {
@@ -73,41 +74,58 @@ __device__ __forceinline__ float4 th_targets(const th_step_pass &s)
     return a.targets[(unsigned)(s.y - (int)a.row0) * a.width + (unsigned)s.x];
 }
 
-// The harness: one thread per texel, 256-thread workgroups, grid-stride.  The own texel comes in as one 16-byte non-temporal
-// load, the steps of the launch run with the state in registers (the step count and so times[k] are wave-uniform: scalar loads
-// from the argument segment), states nsteps and nsteps - 1 leave as one 16-byte non-temporal store each.  A lane touches its own
-// texel alone, so `out` or `out_prev` may be `in`.  The step loop is not unrolled: its body is the caller's.
-extern "C" __global__ __launch_bounds__(256) void th_step_kernel(const th_step_args a, const th_program_uniform_block u)
+// The harness: one thread per slot, 256-thread workgroups.  The slot's state comes in as one 16-byte non-temporal load, the
+// steps of the launch run with the state in registers (the step count and so times[k] are wave-uniform: scalar loads from the
+// argument segment), states nsteps and nsteps - 1 leave as one 16-byte non-temporal store each.  A lane touches its own slot
+// alone, so `out` or `out_prev` may be `in`.  The step loop is not unrolled: its body is the caller's.
+// Everything a program sees of WHO it is - x, y, index, uv, its targets texel - derives from the particle id `pid` (its texel
+// within this context's rows); the loads and stores are at the slot.
+__device__ __forceinline__ void th_step_slot(const th_step_args &a, th_step_pass &s, unsigned idx, unsigned pid)
 {
     typedef float th_v4f __attribute__((ext_vector_type(4)));
+    const unsigned row = pid / a.width;
+    s.x = (int)(pid - row * a.width);
+    s.y = (int)(row + a.row0);
+    s.index = pid + a.row0 * a.width;
+    s.uv = make_float2(((float)s.x + 0.5f) / s.dataRes.x, ((float)s.y + 0.5f) / s.dataRes.y);
+    const th_v4f v0 = __builtin_nontemporal_load(reinterpret_cast<const th_v4f *>(a.in + idx));
+    float4 prev = make_float4(v0.x, v0.y, v0.z, v0.w), cur = prev;
+#pragma clang loop unroll(disable)
+    for (unsigned k = 0; k < a.nsteps; ++k) {
+        prev = cur;
+        s.self = cur;
+        s.time = a.times[k];
+        s.step = a.step0 + k;
+        cur = th_step_main(s);
+    }
+    const th_v4f v = {cur.x, cur.y, cur.z, cur.w};
+    __builtin_nontemporal_store(v, reinterpret_cast<th_v4f *>(a.out + idx));
+    if (a.out_prev) {
+        const th_v4f w = {prev.x, prev.y, prev.z, prev.w};
+        __builtin_nontemporal_store(w, reinterpret_cast<th_v4f *>(a.out_prev + idx));
+    }
+}
+
+// Texel order (perm null): grid-stride over the texels, slot = texel.  Tile-sorted slots (th_stepprog.hip launches a grid that is
+// a multiple of 8): workgroup b sweeps the (b & 7)-th eighth of the slots, as the built-in fused integrator does - workgroups b
+// and b + 8 have been seen to share an XCD, whose L2 then serves the band of the field that eighth taps (a speed matter only).
+// perm[slot] is read once, non-temporal.  The test on a.perm is wave-uniform (the argument segment).
+extern "C" __global__ __launch_bounds__(256) void th_step_kernel(const th_step_args a, const th_program_uniform_block u)
+{
     th_step_pass s;
     s.dataRes = make_float2((float)a.width, (float)a.global_height);
     s.geomRes = make_float2(s.dataRes.x, 2.0f * s.dataRes.y);
     s.dt = a.dt;
     s.uniforms = u.bytes;
     s.args = &a;
-    for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < a.count; idx += gridDim.x * 256u) {
-        const unsigned row = idx / a.width;
-        s.x = (int)(idx - row * a.width);
-        s.y = (int)(row + a.row0);
-        s.index = idx + a.row0 * a.width;
-        s.uv = make_float2(((float)s.x + 0.5f) / s.dataRes.x, ((float)s.y + 0.5f) / s.dataRes.y);
-        const th_v4f v0 = __builtin_nontemporal_load(reinterpret_cast<const th_v4f *>(a.in + idx));
-        float4 prev = make_float4(v0.x, v0.y, v0.z, v0.w), cur = prev;
-#pragma clang loop unroll(disable)
-        for (unsigned k = 0; k < a.nsteps; ++k) {
-            prev = cur;
-            s.self = cur;
-            s.time = a.times[k];
-            s.step = a.step0 + k;
-            cur = th_step_main(s);
-        }
-        const th_v4f v = {cur.x, cur.y, cur.z, cur.w};
-        __builtin_nontemporal_store(v, reinterpret_cast<th_v4f *>(a.out + idx));
-        if (a.out_prev) {
-            const th_v4f w = {prev.x, prev.y, prev.z, prev.w};
-            __builtin_nontemporal_store(w, reinterpret_cast<th_v4f *>(a.out_prev + idx));
-        }
+    if (!a.perm) {
+        for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < a.count; idx += gridDim.x * 256u) th_step_slot(a, s, idx, idx);
+    } else {
+        const unsigned group = blockIdx.x & 7u, rank = blockIdx.x >> 3, per = (a.count + 7u) >> 3;
+        const unsigned lo = group * per, stride = (gridDim.x >> 3) * 256u;
+        const unsigned end = lo + per < a.count ? lo + per : a.count;
+        for (unsigned idx = lo + rank * 256u + threadIdx.x; idx < end; idx += stride)
+            th_step_slot(a, s, idx, __builtin_nontemporal_load(a.perm + idx));
     }
 }
 )TH_PRELUDE"

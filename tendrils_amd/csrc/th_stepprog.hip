@@ -26,6 +26,7 @@ struct StepArgs {
     const float4 *in;
     float4 *out, *out_prev;
     const float4 *data, *flow, *targets;
+    const uint32_t *perm;
     uint32_t count, width, rows, row0, global_height;
     int32_t dw, dh, fw, fh;
     uint32_t nsteps, step0;
@@ -33,16 +34,19 @@ struct StepArgs {
     float times[th::kMaxFusedSteps];
 };
 using KernArgs = ProgramKernArgs<StepArgs>;
-static_assert(th::kMaxFusedSteps == 32 && sizeof(StepArgs) == 224 && offsetof(StepArgs, times) == 96 && offsetof(KernArgs, u) == 224 &&
-                  sizeof(KernArgs) == 224 + kUniformBytes,
+static_assert(th::kMaxFusedSteps == 32 && sizeof(StepArgs) == 232 && offsetof(StepArgs, times) == 104 && offsetof(KernArgs, u) == 240 &&
+                  sizeof(KernArgs) == 240 + kUniformBytes,
               "launch record: layout shared with th_step_prelude.inc");
 
-// one launch of th_step_kernel (th_kernel_timing: an event pair around it, as around every logic launch)
+// one launch of th_step_kernel (th_kernel_timing: an event pair around it, as around every logic launch): in texel order on the
+// grid of the streaming passes, over tile-sorted slots (k.a.perm) on the built-in fused launch's - 8 groups of workgroups, one
+// per eighth of the slots (th::fused_grid)
 th_status step_launch(th_context *c, hipFunction_t fn, KernArgs &k)
 {
     LaunchTimer timer;
     if (th_status s = timer.begin(c)) return s;
-    if (th_status s = program_launch(c, fn, c->texels(), k)) return s;
+    const int grid = k.a.perm ? th::fused_grid(k.a.count, true) : th::grid_for(c->texels(), 8);
+    if (th_status s = program_launch_grid(c, fn, grid, &k, sizeof k)) return s;
     return timer.end(c);
 }
 
@@ -55,11 +59,25 @@ th_status th_step_program_compile(const char *source, const char *name, th_progr
     return program_compile(kStepProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
 }
 
+th_status th_step_program_view_size(th_context *c, const float viewSize[2])
+{
+    if (th_status s = use(c, true)) return s;
+    if (viewSize)
+        for (int k = 0; k < 2; ++k)
+            TH_REQUIRE(std::isfinite(viewSize[k]) && viewSize[k] > 0.0f, "viewSize[%d] = %g: a step program's sort key needs a finite, positive view size", k, (double)viewSize[k]);
+    c->step_keyed = viewSize != nullptr;
+    if (viewSize) { c->step_view[0] = viewSize[0]; c->step_view[1] = viewSize[1]; }
+    return TH_OK;
+}
+
 // n passes with the ring semantics of TH_TARGET_RING: buffers[0] is state n afterwards, buffers[1] state n - 1.
 //   fused:  the plain two-buffer f32 ring with th_options::fuse on - at most kMaxFusedSteps steps per launch, both outputs
-//           routed as th_step_n routes them (a lane touches its own texel alone: one output may be the input buffer)
-//   single: every other ring (more buffers: all of them rotate; packed: quantised after every step; fuse off) - the same
-//           kernel with nsteps = 1 between RingPass::begin and commit, once per step
+//           routed as th_step_n routes them (a lane touches its own slot alone: one output may be the input buffer).  The
+//           launches run over the slot order buffers[0] is held in (perm) and leave both buffers in it: a tile-sorted ring stays
+//           sorted, stale or not (a stale order is still a permutation).  With a key (th_step_program_view_size) the call
+//           first lays an order out or refreshes it, as th_step_n does (fused_slots); without one it never creates an order.
+//   single: every other ring (more buffers: all of them rotate; packed: quantised after every step; fuse off) - texel order
+//           first (ensure_identity), then the same kernel with nsteps = 1 between RingPass::begin and commit, once per step
 // One kernel on both paths, fp32 state between the steps of a fused launch exactly what a single pass stores: a call with n
 // steps leaves the bits and the ring order of n calls with one.
 th_status th_step_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t source,
@@ -80,7 +98,13 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (th_status s = asort_drop(c)) return s;
-    if (th_status s = ensure_identity(c)) return s;      // a pass operates in texel order, like every program pass
+    const bool fused = c->opt.fuse && c->ring.size() == 2 && !c->packed;
+    if (fused && c->step_keyed) {
+        const bool may_sort = sorting_possible(c) && c->total_steps >= c->hold_texel_order_until;
+        if (th_status s = fused_slots(c, may_sort, tile_geom(c, c->step_view))) return s;
+    } else if (!fused) {
+        if (th_status s = ensure_identity(c)) return s;  // these rings step in texel order, like every other program pass
+    }
     a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
     a.targets = c->targets;
     a.count = (uint32_t)c->texels(); a.width = (uint32_t)c->cfg.width; a.rows = (uint32_t)c->cfg.height;
@@ -88,10 +112,12 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
     a.dt = dt;
     k.set_uniforms(uniforms, uniform_bytes);
 
-    if (c->opt.fuse && c->ring.size() == 2 && !c->packed) {
+    if (fused) {
         for (int32_t done = 0; done < n;) {
             const int32_t steps = std::min<int32_t>(n - done, (int32_t)th::kMaxFusedSteps);
+            const int order = order_of(c, c->ring[0]);
             const FusedRoute r = fused_route(c, steps);
+            a.perm = order >= 0 ? c->orders[(size_t)order].perm : nullptr;
             a.in = r.in;
             a.out = r.out;                                           // state `steps`     (ends up in buffers[0])
             // state `steps` - 1 (ends up in buffers[1]) - of a single step it is the input, where it lies: a step program
@@ -100,11 +126,12 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
             a.nsteps = (uint32_t)steps; a.step0 = (uint32_t)done;
             for (int32_t j = 0; j < steps; ++j) a.times[j] = times[(size_t)(done + j)];
             if (th_status s = step_launch(c, m->fn, k)) return s;
+            set_order(c, r.other, order);                            // both outputs sit at the input's slots (a single step's input stays)
             fused_routed(c, steps);
             done += steps;
         }
     } else {
-        a.nsteps = 1; a.out_prev = nullptr;
+        a.nsteps = 1; a.out_prev = nullptr; a.perm = nullptr;
         for (int32_t done = 0; done < n; ++done) {
             RingPass pass;
             if (th_status s = pass.begin(c, TH_TARGET_RING)) return s;
@@ -115,8 +142,8 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
             ++c->steps_since_sort; ++c->total_steps;
         }
     }
-    // what is remembered of the buffers' content ended with use() and state_written(); the ring stays in texel order, and no
-    // pass of this call has counted tiles or taken statistics of what it wrote
+    // what is remembered of the buffers' content ended with use() and state_written(); the ring stays in the order it was stepped in, and
+    // no pass of this call has counted tiles or taken statistics of what it wrote
     c->counted.buf = nullptr;
     c->fused_stats.valid = false;
     c->drawn.valid = false;

@@ -271,6 +271,15 @@ class Particles:
         for _ in range(int(n) % max(len(self.buffers), 1)):
             self.buffers.insert(0, self.buffers.pop())
 
+    def step_view_size(self, view_size):
+        """The key a StepProgram's calls sort the slots under (th_step_program_view_size): the view size the program's
+        particles tap the flow field through, as the built-in integrator does - pos * viewSize.  None: no key (the default);
+        a call then steps over whatever slot order it finds and lays out none of its own.  No key changes a result."""
+        if view_size is None:
+            call("th_step_program_view_size", self._ctx, None)
+        else:
+            call("th_step_program_view_size", self._ctx, (C.c_float * 2)(float(view_size[0]), float(view_size[1])))
+
     def draw(self, update=None, mode=None):          # src/particles.js:147-158 - no display here
         return None
 

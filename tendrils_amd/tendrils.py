@@ -450,9 +450,17 @@ class Tendrils:
                 dt=self.timer.dt, time=self.timer.time, start=self.timer.since,
                 flow=self.flow, targets=self.targets,
                 viewSize=self.viewSize, viewRes=self.viewRes)
+            self._key_step_program()
             self.particles.step(self.uniforms["update"])
             self.blending = True                                # src/index.js:267-268
         return self
+
+    def _key_step_program(self):
+        """a StepProgram logicShader taps the flow field through this viewSize, like the built-in integrator: its calls may
+        keep the slots sorted by it (Particles.step_view_size)"""
+        if self.logicShader.kind == StepProgram.SOURCE_KIND:
+            sized = all(math.isfinite(v) and v > 0 for v in self.viewSize)          # ([0, 0] until the first resize(): no key)
+            self.particles.step_view_size(self.viewSize if sized else None)
 
     def step_n(self, n):
         """n x (timer.tick(); step()) for a fixed-step, unpaused timer, as one captured-graph replay - of a StepProgram
@@ -468,6 +476,7 @@ class Tendrils:
         self.uniforms["update"].update(self.state)
         self.uniforms["update"].update(dt=dt, time=tm.time, start=tm.since, flow=self.flow, targets=self.targets,
                                        viewSize=self.viewSize, viewRes=self.viewRes)
+        self._key_step_program()
         self.particles.step_n(self.uniforms["update"], tm.time, dt, n)
         self.blending = self.blending or n > 0
         for _ in range(n):

@@ -5,6 +5,8 @@ Workload: 4096 x 4096 particles (a 256 MiB RGBA32F ring buffer), flow 1920 x 108
 program (pos += vel * dt) and this repository's flow-only integrator (a flow tap, decay, force, damping, speed clamp, Euler).
 Arms, all in this process (one library), each on a context of its own:
   fused        one th_step_program_run(n = 20): 16 B read + 32 B written per particle and call
+  fused sorted (flow_only) the fused call on a context with the sort key set (Particles.step_view_size) and `bucket` at its
+               default: the call keeps the slots tile-sorted where the auto policy sorts, as th_step_n does - same bits
   single       the same call with the option `fuse` off: 20 launches of the same kernel, 32 B per particle-step
   state_prog   20 x th_program_run of the program's state-program form: what there was before step programs
   builtin      th_step_n(20) of the built-in integrator with the noise off (the flow-only program's arithmetic, the library's
@@ -129,8 +131,9 @@ def main():
         call("th_flow_upload", p._ctx, flow.ctypes.data_as(_capi._fp))
         return p
 
-    fused, single, state, builtin = context(), context(fuse=0), context(), context()
-    contexts = (fused, single, state, builtin)
+    fused, single, state, builtin, keyed = context(), context(fuse=0), context(), context(), context()
+    keyed.step_view_size(uniforms["viewSize"])
+    contexts = (fused, single, state, builtin, keyed)
 
     # the process's one HIP runtime (the copy _capi.load() settled on), for the copy arm
     runtime, = _capi._mapped("libamdhip64")
@@ -170,6 +173,8 @@ def main():
     arms = {}
     for name, (step_form, state_form) in programs.items():
         arms[name + " fused"] = (nbytes * (1 + 2 * ((steps + 31) // 32)), fused, step_program(fused, step_form))
+        if name == "flow_only":         # (+ 4 B of perm per slot and launch; the periodic re-sort's move is inside the figure)
+            arms[name + " fused sorted"] = ((3 * nbytes + nbytes // 4) * ((steps + 31) // 32), keyed, step_program(keyed, step_form))
         arms[name + " single"] = (2 * nbytes * steps, single, step_program(single, step_form))
         arms[name + " state_prog"] = (2 * nbytes * steps, state, state_program(state, state_form))
     arms["builtin th_step_n"] = (3 * nbytes, builtin, builtin_steps)
@@ -208,6 +213,13 @@ def main():
                      % (name, a["median_ms"] / c["median_ms"], a["max_ms"], c["min_ms"], a["max_ms"] < c["min_ms"],
                         a["median_ms"] / (1.5 * med["memcpy_d2d"]), b["median_ms"] / c["median_ms"], b["median_ms"], c["max_ms"]))
     lines.append("flow_only fused / builtin th_step_n = %.3f" % (med["flow_only fused"] / med["builtin th_step_n"]))
+    a, b = result["arms"]["flow_only fused sorted"], result["arms"]["flow_only fused"]
+    info = _capi.SlotOrderInfo()
+    call("th_slot_order", keyed._ctx, C.byref(info))
+    lines.append("flow_only fused sorted / builtin th_step_n = %.3f; fused sorted / fused = %.3f (rounds apart: sorted max %.4f < texel-order min %.4f: %s); "
+                 "the keyed context: %d sorted buffers, %d sorts"
+                 % (a["median_ms"] / med["builtin th_step_n"], a["median_ms"] / b["median_ms"], a["max_ms"], b["min_ms"], a["max_ms"] < b["min_ms"],
+                    info.sorted_buffers, info.sorts))
     for name, (step_form, state_form) in programs.items():
         result["query"][name] = dict(step=step_form.query(fused), state=state_form.query(state))
         lines.append("th_program_query(%s): th_step_kernel %s; th_program_kernel %s"
