@@ -393,15 +393,19 @@ th_status th_draw_program_run(th_context *ctx, th_program *program, const void *
  *                      is hidden here - Tendrils.step hands (float)timer.time, a run of fixed steps what th_step_n computes,
  *                      t += dt_ms in double from time0, each value cast), dt and step = k.  The result and the ring order of a
  *                      call with n steps are bit for bit those of n calls with one step each, on every ring:
- *                        fused   the plain two-buffer f32 ring with TH_OPT_FUSE on: a particle's state stays in registers for up to
- *                                32 steps per launch - 16 bytes read and 32 written per particle and launch
- *                        single  every other ring (more than two buffers, TH_STATE_F16, fuse off): the same kernel, one step per
- *                                launch, a packed ring quantised after every step as single passes would
- *                      The fused path steps over the slot order buffers[0] is held in and leaves both buffers in it: a ring that
- *                      built-in steps or a binned draw() left tile-sorted stays sorted (x, y, index, uv and the targets texel are
- *                      the particle's, whatever slot holds it), a ring in texel order stays in texel order; with a key
- *                      (th_step_program_view_size) the call also lays the order out and refreshes it.  The single path moves
- *                      the ring to texel order first, as every other program pass does.  source: TH_SOURCE_NONE, TH_SOURCE_FLOW or
+ *                        fused   the two-buffer ring with TH_OPT_FUSE on, f32 or TH_STATE_F16: a particle's state stays in
+ *                                registers for up to 32 steps per launch - 16 bytes read and 32 written per particle and launch
+ *                                on an f32 ring; on a packed ring 8 read and 16 written, in place on the packed texels (the
+ *                                prelude's second kernel, th_step_packed_kernel: no f32 staging is allocated or touched), the
+ *                                state quantised after every step inside the launch exactly as the ring would hold it
+ *                        single  every other ring (more than two buffers, fuse off): th_step_kernel, one step per launch; a
+ *                                packed ring through f32 staging, unpacked before and packed after every step
+ *                      The fused path on an f32 ring steps over the slot order buffers[0] is held in and leaves both buffers in
+ *                      it: a ring that built-in steps or a binned draw() left tile-sorted stays sorted (x, y, index, uv and the
+ *                      targets texel are the particle's, whatever slot holds it), a ring in texel order stays in texel order;
+ *                      with a key (th_step_program_view_size) the call also lays the order out and refreshes it.  A packed ring
+ *                      and the single path move the ring to texel order first, key or no key, as every other program pass
+ *                      does.  source: TH_SOURCE_NONE, TH_SOURCE_FLOW or
  *                      TH_SOURCE_IMAGE; a ring buffer is refused (TH_ERR_INVALID): the ring is what the call writes, a fused
  *                      launch overwrites its input.  Row bands need nothing extra: x, y, index, uv are those of the whole texture,
  *                      and there is no read outside the band to flag.  The `respawned` counter is not touched.  th_kernel_timing

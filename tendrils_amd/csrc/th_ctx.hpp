@@ -99,6 +99,7 @@ struct ProgramModule {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
+    hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;

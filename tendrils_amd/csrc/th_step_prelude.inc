@@ -1,4 +1,5 @@
 R"TH_PRELUDE(// th_step_prelude.inc - what th_step_program_compile puts in front of a step program, behind the text of th_taps.inc
+// and of th_packed.inc (the packed-state codec, as namespace th)
 // (th_stepprog.hip embeds this file as text: the first and the last line make it one raw string literal).  Self-contained: no
 // project header, only what hiprtc's built-in headers give.  Compiled with the product's arithmetic flags (-ffp-contract=off:
 // a*b+c stays two rounded fp32 operations, as in the reference's shaders).
@@ -126,6 +127,61 @@ extern "C" __global__ __launch_bounds__(256) void th_step_kernel(const th_step_a
         const unsigned end = lo + per < a.count ? lo + per : a.count;
         for (unsigned idx = lo + rank * 256u + threadIdx.x; idx < end; idx += stride)
             th_step_slot(a, s, idx, __builtin_nontemporal_load(a.perm + idx));
+    }
+}
+
+// The same harness on a packed ring (TH_STATE_F16, 8 bytes a texel: th_packed.inc, whose text stands in front of this prelude
+// as namespace th): `in`, `out` and `out_prev` point at uint2 texels behind the record's float4 * fields, the record itself is
+// th_step_kernel's.  The slot's state comes in as one 8-byte non-temporal load and is decoded as every kernel of the library
+// decodes it; after EVERY step the result is replaced by what a packed ring would hold of it (quantize_state =
+// unpack_state(pack_state(.)) bit for bit), so a launch of n steps leaves the bits of n single passes; states nsteps and
+// nsteps - 1 leave as one 8-byte non-temporal store each (the codec is idempotent on quantised values: packing the carried
+// `prev` is exact).  A lane touches its own slot alone, so `out` or `out_prev` may be `in`.
+__device__ __forceinline__ void th_step_packed_slot(const th_step_args &a, th_step_pass &s, unsigned idx, unsigned pid)
+{
+    typedef unsigned th_v2u __attribute__((ext_vector_type(2)));
+    const unsigned row = pid / a.width;
+    s.x = (int)(pid - row * a.width);
+    s.y = (int)(row + a.row0);
+    s.index = pid + a.row0 * a.width;
+    s.uv = make_float2(((float)s.x + 0.5f) / s.dataRes.x, ((float)s.y + 0.5f) / s.dataRes.y);
+    const th_v2u v0 = __builtin_nontemporal_load(reinterpret_cast<const th_v2u *>(a.in) + idx);
+    float4 prev = th::unpack_state(make_uint2(v0.x, v0.y)), cur = prev;
+#pragma clang loop unroll(disable)
+    for (unsigned k = 0; k < a.nsteps; ++k) {
+        prev = cur;
+        s.self = cur;
+        s.time = a.times[k];
+        s.step = a.step0 + k;
+        cur = th::quantize_state(th_step_main(s));
+    }
+    const uint2 q = th::pack_state(cur);
+    const th_v2u v = {q.x, q.y};
+    __builtin_nontemporal_store(v, reinterpret_cast<th_v2u *>(a.out) + idx);
+    if (a.out_prev) {
+        const uint2 r = th::pack_state(prev);
+        const th_v2u w = {r.x, r.y};
+        __builtin_nontemporal_store(w, reinterpret_cast<th_v2u *>(a.out_prev) + idx);
+    }
+}
+
+// th_step_kernel's two loops (th_stepprog.hip launches the first alone on a packed ring: it goes to texel order first)
+extern "C" __global__ __launch_bounds__(256) void th_step_packed_kernel(const th_step_args a, const th_program_uniform_block u)
+{
+    th_step_pass s;
+    s.dataRes = make_float2((float)a.width, (float)a.global_height);
+    s.geomRes = make_float2(s.dataRes.x, 2.0f * s.dataRes.y);
+    s.dt = a.dt;
+    s.uniforms = u.bytes;
+    s.args = &a;
+    if (!a.perm) {
+        for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < a.count; idx += gridDim.x * 256u) th_step_packed_slot(a, s, idx, idx);
+    } else {
+        const unsigned group = blockIdx.x & 7u, rank = blockIdx.x >> 3, per = (a.count + 7u) >> 3;
+        const unsigned lo = group * per, stride = (gridDim.x >> 3) * 256u;
+        const unsigned end = lo + per < a.count ? lo + per : a.count;
+        for (unsigned idx = lo + rank * 256u + threadIdx.x; idx < end; idx += stride)
+            th_step_packed_slot(a, s, idx, __builtin_nontemporal_load(a.perm + idx));
     }
 }
 )TH_PRELUDE"

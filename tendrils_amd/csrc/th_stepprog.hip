@@ -11,12 +11,18 @@ using namespace thi;
 
 namespace {
 
-// the tap rule as text (th_taps.inc: the library's kernels compile the same lines), then the prelude
+// the tap rule and the packed-state codec as text (th_taps.inc, th_packed.inc: the library's kernels compile the same lines),
+// then the prelude
 #define TH_TAPS(...) #__VA_ARGS__
 const char kTaps[] =
 #include "th_taps.inc"
     ;
 #undef TH_TAPS
+#define TH_PACKED(...) #__VA_ARGS__
+const char kPacked[] =
+#include "th_packed.inc"
+    ;
+#undef TH_PACKED
 const char kPrelude[] =
 #include "th_step_prelude.inc"
     ;
@@ -38,7 +44,7 @@ static_assert(th::kMaxFusedSteps == 32 && sizeof(StepArgs) == 232 && offsetof(St
                   sizeof(KernArgs) == 240 + kUniformBytes,
               "launch record: layout shared with th_step_prelude.inc");
 
-// one launch of th_step_kernel (th_kernel_timing: an event pair around it, as around every logic launch): in texel order on the
+// one launch of th_step_kernel or, on a packed ring, th_step_packed_kernel (th_kernel_timing: an event pair around it, as around every logic launch): in texel order on the
 // grid of the streaming passes, over tile-sorted slots (k.a.perm) on the built-in fused launch's - 8 groups of workgroups, one
 // per eighth of the slots (th::fused_grid)
 th_status step_launch(th_context *c, hipFunction_t fn, KernArgs &k)
@@ -56,7 +62,7 @@ extern "C" {
 
 th_status th_step_program_compile(const char *source, const char *name, th_program **out)
 {
-    return program_compile(kStepProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
+    return program_compile(kStepProgram, std::string(kTaps) + "\nnamespace th {\n" + kPacked + "\n}\n" + kPrelude, source, name, out);
 }
 
 th_status th_step_program_view_size(th_context *c, const float viewSize[2])
@@ -71,15 +77,18 @@ th_status th_step_program_view_size(th_context *c, const float viewSize[2])
 }
 
 // n passes with the ring semantics of TH_TARGET_RING: buffers[0] is state n afterwards, buffers[1] state n - 1.
-//   fused:  the plain two-buffer f32 ring with th_options::fuse on - at most kMaxFusedSteps steps per launch, both outputs
-//           routed as th_step_n routes them (a lane touches its own slot alone: one output may be the input buffer).  The
-//           launches run over the slot order buffers[0] is held in (perm) and leave both buffers in it: a tile-sorted ring stays
-//           sorted, stale or not (a stale order is still a permutation).  With a key (th_step_program_view_size) the call
-//           first lays an order out or refreshes it, as th_step_n does (fused_slots); without one it never creates an order.
-//   single: every other ring (more buffers: all of them rotate; packed: quantised after every step; fuse off) - texel order
-//           first (ensure_identity), then the same kernel with nsteps = 1 between RingPass::begin and commit, once per step
-// One kernel on both paths, fp32 state between the steps of a fused launch exactly what a single pass stores: a call with n
-// steps leaves the bits and the ring order of n calls with one.
+//   fused:  the two-buffer ring with th_options::fuse on, f32 or packed - at most kMaxFusedSteps steps per launch, both outputs
+//           routed as th_step_n routes them (a lane touches its own slot alone: one output may be the input buffer).
+//           f32: the launches run over the slot order buffers[0] is held in (perm) and leave both buffers in it: a tile-sorted
+//           ring stays sorted, stale or not (a stale order is still a permutation).  With a key (th_step_program_view_size) the
+//           call first lays an order out or refreshes it, as th_step_n does (fused_slots); without one it never creates an order.
+//           packed: texel order first (ensure_identity), key or no key, then th_step_packed_kernel in place on the 8-byte
+//           texels - no f32 staging; the state is quantised after every step inside the launch, as the ring would hold it.
+//   single: every other ring (more buffers: all of them rotate; fuse off) - texel order first (ensure_identity), then
+//           th_step_kernel with nsteps = 1 between RingPass::begin and commit, once per step (a packed ring: through f32
+//           staging, unpacked before and packed after every step)
+// The state between the steps of a fused launch is exactly what a single pass stores: a call with n steps leaves the bits and
+// the ring order of n calls with one.
 th_status th_step_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t source,
                               const float *times, float dt, int32_t n)
 {
@@ -98,12 +107,12 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (th_status s = asort_drop(c)) return s;
-    const bool fused = c->opt.fuse && c->ring.size() == 2 && !c->packed;
-    if (fused && c->step_keyed) {
+    const bool fused = c->opt.fuse && c->ring.size() == 2;
+    if (!fused || c->packed) {
+        if (th_status s = ensure_identity(c)) return s;  // these rings step in texel order, like every other program pass
+    } else if (c->step_keyed) {
         const bool may_sort = sorting_possible(c) && c->total_steps >= c->hold_texel_order_until;
         if (th_status s = fused_slots(c, may_sort, tile_geom(c, c->step_view))) return s;
-    } else if (!fused) {
-        if (th_status s = ensure_identity(c)) return s;  // these rings step in texel order, like every other program pass
     }
     a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
     a.targets = c->targets;
@@ -125,7 +134,7 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
             a.out_prev = steps == 1 ? nullptr : r.out_prev;
             a.nsteps = (uint32_t)steps; a.step0 = (uint32_t)done;
             for (int32_t j = 0; j < steps; ++j) a.times[j] = times[(size_t)(done + j)];
-            if (th_status s = step_launch(c, m->fn, k)) return s;
+            if (th_status s = step_launch(c, c->packed ? m->fn_packed : m->fn, k)) return s;
             set_order(c, r.other, order);                            // both outputs sit at the input's slots (a single step's input stays)
             fused_routed(c, steps);
             done += steps;

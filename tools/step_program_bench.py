@@ -16,7 +16,21 @@ Each figure is the GPU time per call between two events on the context's stream 
 calls, after --warmup calls); the arms alternate for --rounds rounds and the median round is reported, with the spread.  The
 programs' registers / scratch / code size (th_program_query) go out with the figures.
 
+
+The packed arm (--packed): the same two programs, 20 steps a call, on a packed ring (TH_STATE_F16, 8 B per particle) at every
+--sizes entry the card's free memory allows (4096 and 16384: config 5's 268 M particles).  Arms per size and program:
+  fused        one th_step_program_run(n = 20) with `fuse` on: where the library has th_step_packed_kernel, one launch in place
+               on the packed texels - 8 B read + 16 B written per particle; before it, the staged path below
+  single       the same call with `fuse` off: per step unpack into f32 staging, the f32 kernel, pack - 80 B per particle-step
+  copy24       hipMemcpyAsync, device to device, of 12 B per particle: 24 B per particle through HBM, the fused call's traffic
+With --against LIB the whole measurement runs in child processes, one library each (TH_LIB), alternating LIB - the parent
+commit's build - and this tree's for --runs runs each in ONE session, and the fused arms are compared across the builds.  Each
+child also reports the device memory the process took (torch.cuda.mem_get_info before the contexts and after the calls; the ring
+is filled through th_state_device_ptr, so no staging exists but what the calls allocate) and the wall time of
+StepProgram.from_source for both programs.
+
 Usage: python tools/step_program_bench.py [--size 4096] [--steps 20] [--reps 5] [--warmup 2] [--rounds 5] [--out FILE]
+       python tools/step_program_bench.py --packed [--sizes 4096 16384] [--against LIB] [--runs 2] [--steps 20] ... [--out FILE]
        (--out appends the measurement to FILE, behind whatever it holds)
 """
 import argparse
@@ -24,7 +38,9 @@ import ctypes as C
 import json
 import os
 import statistics
+import subprocess
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -91,7 +107,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--packed", action="store_true", help="the packed-ring arm")
+    ap.add_argument("--sizes", type=int, nargs="+", default=(4096, 16384))
+    ap.add_argument("--against", default=None, help="the parent commit's libtendrils_hip.so: alternate it with this tree's")
+    ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--child-timeout", type=float, default=300.0, help="seconds one child process may take")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.packed:
+        return packed_compare(args) if args.against and not args.child else packed_arm(args)
 
     import numpy as np
     import torch
@@ -235,6 +259,213 @@ def main():
     for pair in programs.values():
         for prog in pair:
             prog.dispose()
+
+
+class _Raw:
+    """device memory as torch takes it (torch.as_tensor): n int16 values at ptr"""
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = dict(shape=(n,), typestr="<i2", data=(ptr, False), version=2)
+
+
+def packed_arm(args):
+    """the packed arm on the library this process loads (TH_LIB, else this tree's): prints the lines, then one JSON line"""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("step_program_bench: no GPU - nothing is measured without one")
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import Particles, StepProgram
+    from tendrils_amd.tendrils import defaults
+
+    steps = args.steps
+    fw, fh = args.flow
+    time0, dt = 1000.0, 1000.0 / 60.0
+    uniforms = {k: v for k, v in defaults()["state"].items() if isinstance(v, (int, float)) and not isinstance(v, bool)}
+    uniforms.update(noiseWeight=0, viewSize=(1.0, fh / fw), time=time0, dt=dt)
+    rng = np.random.default_rng(5)
+    flow = np.zeros((fh, fw, 4), np.float32)
+    flow[..., :2] = rng.uniform(-0.01, 0.01, (fh, fw, 2))
+    flow[..., 2] = time0 - 10.0
+    flow[..., 3] = 1.0
+
+    sources = dict(drift=(STEP_DRIFT, None),
+                   flow_only=(FLOW_ONLY % dict(entry="th_step_main", **{"pass": "th_step_pass"}, clock="p"), _capi.LogicUniforms))
+    programs, compile_s = {}, {}
+    for name, (source, block) in sources.items():
+        t0 = time.perf_counter()
+        programs[name] = StepProgram.from_source(source, block, name=name) if block else StepProgram.from_source(source, name=name)
+        compile_s[name] = time.perf_counter() - t0
+
+    runtime, = _capi._mapped("libamdhip64")
+    hip = C.CDLL(runtime)
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemcpyAsync.restype = C.c_int
+
+    lib = os.path.realpath(_capi.load()._name)
+    if lib.startswith(os.path.realpath(ROOT) + os.sep):
+        lib = os.path.relpath(lib, os.path.realpath(ROOT))
+    result = dict(lib=lib, steps=steps, reps=args.reps, rounds=args.rounds, compile_s=compile_s, sizes={})
+    lines = ["step programs on a packed ring (TH_STATE_F16), flow %d x %d, %d steps per call, %d rounds of %d calls, arms alternating; GPU ms per call"
+             % (fw, fh, steps, args.rounds, args.reps),
+             "library: %s   device: %s" % (result["lib"], torch.cuda.get_device_name(0)),
+             "StepProgram.from_source wall time: " + ", ".join("%s %.3f s" % kv for kv in compile_s.items())]
+    torch.cuda.init()
+    for n in args.sizes:
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        # two contexts (ring + spare, targets, flow: 8 B x 3 + 16 B per particle each), the staged path's two f32 staging
+        # buffers (32 B per particle, on whichever contexts take it), the copy's 24 B per particle
+        need = n * n * (2 * 40 + 2 * 32 + 24)
+        if need > free0:
+            lines.append("%d x %d: skipped - %.1f GB free, about %.1f GB needed" % (n, n, free0 / 1e9, need / 1e9))
+            continue
+
+        def context(fuse=None):
+            p = Particles(None, dict(shape=[n, n], stateFormat=_capi.TH_STATE_F16))
+            p.setup(2)
+            if fuse is not None:
+                p.option("fuse", fuse)
+            # the packed texels themselves, written in place: positions in [-0.8, 0.8), velocities in +-0.004
+            g = torch.Generator(device="cuda").manual_seed(7)
+            for k in (0, 1):
+                d = C.c_void_p()
+                call("th_state_device_ptr", p._ctx, k, C.byref(d))
+                texels = torch.as_tensor(_Raw(d.value, n * n * 4), device="cuda").view(n * n, 4)
+                chunk = 1 << 24
+                for at in range(0, n * n, chunk):
+                    m = min(chunk, n * n - at)
+                    texels[at:at + m, :2] = torch.randint(-13107, 13107, (m, 2), dtype=torch.int16, device="cuda", generator=g)
+                    vel = (torch.rand((m, 2), device="cuda", generator=g) * 0.008 - 0.004).to(torch.float16)
+                    texels[at:at + m, 2:] = vel.view(torch.int16)
+                call("th_state_device_ptr", p._ctx, k, C.byref(d))      # (written through the address: handed out again)
+            torch.cuda.synchronize()
+            call("th_flow_resize", p._ctx, fw, fh)
+            call("th_flow_upload", p._ctx, flow.ctypes.data_as(_capi._fp))
+            return p
+
+        fused, single = context(), context(fuse=0)
+
+        def step_program(p, prog):
+            def run():
+                p.logic = prog
+                p.step_n(dict(uniforms), time0, dt, steps)
+            return run
+
+        def timed(p, fn, reps):
+            ms = C.c_float(0)
+            call("th_timer_start", p._ctx)
+            for _ in range(reps):
+                fn()
+            call("th_timer_stop", p._ctx, C.byref(ms))
+            return ms.value / reps
+
+        arms = {}
+        for name, prog in programs.items():
+            arms[name + " fused"] = (fused, step_program(fused, prog))
+            arms[name + " single"] = (single, step_program(single, prog))
+        for p, fn in arms.values():
+            timed(p, fn, args.warmup)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()                             # (the fill's temporaries)
+        took = free0 - torch.cuda.mem_get_info()[0]          # both contexts and whatever their calls allocated
+        # launches per call, by the library's own count
+        count = {}
+        for name, (p, fn) in arms.items():
+            ms, k = C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing", p._ctx, 1)
+            fn()
+            call("th_kernel_timing_read", p._ctx, C.byref(ms), C.byref(k))
+            call("th_kernel_timing", p._ctx, 0)
+            count[name] = k.value
+        stream = C.c_void_p()
+        call("th_stream", fused._ctx, C.byref(stream))
+        src, dst = (torch.empty(n * n * 12, dtype=torch.uint8, device="cuda") for _ in range(2))
+        src.zero_(), dst.zero_()
+        torch.cuda.synchronize()
+
+        def copy():
+            e = hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), n * n * 12, HIP_MEMCPY_DEVICE_TO_DEVICE, stream)
+            if e:
+                raise RuntimeError("hipMemcpyAsync: error %d" % e)
+        arms["copy24"] = (fused, copy)
+        timed(fused, copy, args.warmup)
+        rounds = {name: [] for name in arms}
+        for _ in range(args.rounds):
+            for name, (p, fn) in arms.items():
+                rounds[name].append(timed(p, fn, args.reps))
+        out = dict(took_bytes=took, launches=count, arms={})
+        lines.append("%d x %d particles: the process took %.3f GB of device memory for two contexts and their calls" % (n, n, took / 1e9))
+        lines.append("%-24s %10s %10s %10s %10s" % ("arm", "median ms", "min ms", "max ms", "launches"))
+        for name, ms in rounds.items():
+            out["arms"][name] = dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms))
+            lines.append("%-24s %10.4f %10.4f %10.4f %10s" % (name, statistics.median(ms), min(ms), max(ms), count.get(name, "")))
+        for name in programs:
+            a, b, c = out["arms"][name + " fused"], out["arms"][name + " single"], out["arms"]["copy24"]
+            lines.append("%s: fused / single = %.3f (rounds apart: fused max %.4f < single min %.4f: %s); fused / copy24 = %.3f"
+                         % (name, a["median_ms"] / b["median_ms"], a["max_ms"], b["min_ms"], a["max_ms"] < b["min_ms"], a["median_ms"] / c["median_ms"]))
+        result["sizes"][str(n)] = out
+        del src, dst
+        fused.dispose(), single.dispose()
+        torch.cuda.empty_cache()
+    result["query"] = {}
+    probe = Particles(None, dict(shape=[64, 64], stateFormat=_capi.TH_STATE_F16))
+    probe.setup(2)
+    for name, prog in programs.items():
+        result["query"][name] = prog.query(probe)
+        lines.append("th_program_query(%s): th_step_kernel %s" % (name, json.dumps(result["query"][name])))
+    probe.dispose()
+    for prog in programs.values():
+        prog.dispose()
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(result))
+    if args.out and not args.child:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+    return result
+
+
+def packed_compare(args):
+    """the packed arm in child processes, the parent commit's library and this tree's alternating in one session"""
+    here = os.path.join(ROOT, "tendrils_amd", "lib", "libtendrils_hip.so")
+    builds = (("parent", os.path.abspath(args.against)), ("this", here))
+    cmd = [sys.executable, os.path.abspath(__file__), "--packed", "--child", "--steps", str(args.steps), "--reps", str(args.reps),
+           "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--flow", *map(str, args.flow), "--sizes", *map(str, args.sizes)]
+    text, results = [], {name: [] for name, _ in builds}
+    for run in range(args.runs):
+        for name, lib in builds:
+            print("run %d, %s build (%s) ..." % (run + 1, name, lib), flush=True)
+            r = subprocess.run(cmd, env=dict(os.environ, TH_LIB=lib), capture_output=True, text=True, cwd=ROOT, timeout=args.child_timeout)
+            if r.returncode:
+                sys.exit("step_program_bench: the %s build's run failed (exit %d), nothing more is started\n%s\n%s"
+                         % (name, r.returncode, r.stdout[-2000:], r.stderr[-4000:]))
+            body = r.stdout.strip().splitlines()
+            results[name].append(json.loads(body[-1]))
+            text += ["--- %s build, run %d" % (name, run + 1)] + body[:-1]
+    text.append("--- the fused call across the builds (median ms of each run; min - max over all rounds)")
+    for n in map(str, args.sizes):
+        if not all(n in r["sizes"] for rs in results.values() for r in rs):
+            continue
+        for arm in ("drift fused", "flow_only fused"):
+            row = {}
+            for name, rs in results.items():
+                a = [r["sizes"][n]["arms"][arm] for r in rs]
+                row[name] = ([x["median_ms"] for x in a], min(x["min_ms"] for x in a), max(x["max_ms"] for x in a))
+            (pm, plo, phi), (tm, tlo, thi) = row["parent"], row["this"]
+            text.append("%s^2 %-16s parent %s (%.4f - %.4f)   this %s (%.4f - %.4f)   parent / this = %.2f   rounds apart (this max < parent min): %s"
+                        % (n, arm, " / ".join("%.4f" % v for v in pm), plo, phi, " / ".join("%.4f" % v for v in tm), tlo, thi,
+                           statistics.median(pm) / statistics.median(tm), thi < plo))
+        for name, rs in results.items():
+            text.append("%s^2 device memory taken, %s build: %s GB" % (n, name, " / ".join("%.3f" % (r["sizes"][n]["took_bytes"] / 1e9) for r in rs)))
+    for name, rs in results.items():
+        text.append("StepProgram.from_source(flow_only), %s build: %s s" % (name, " / ".join("%.3f" % r["compile_s"]["flow_only"] for r in rs)))
+    text = "\n".join(text)
+    print(text)
+    print(json.dumps(results))
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
 
 
 if __name__ == "__main__":
