@@ -684,6 +684,13 @@ typedef struct th_slot_order_info {
     uint64_t sorts;              /* sorts so far in this context's life */
 } th_slot_order_info;
 th_status th_slot_order(th_context *ctx, th_slot_order_info *out);
+/* (diagnostics, tests) The slot order ring buffer `buffer` is held in, read back: perm[slot] = the particle (texel index within
+ * this context's rows) whose state the slot holds, one word per texel; the order's chunk table, four words a chunk (first slot,
+ * slots, sort class, 0), at most chunk_capacity chunks of it, with the chunk count in *nchunks; and the buffer's texels as they
+ * are stored, in slot order (16 bytes each, 8 on a TH_STATE_F16 ring).  perm, chunks (with nchunks) and slots may each be null.
+ * *sorted = 0, and nothing else written, when the buffer is held in texel order.  Synchronises. */
+th_status th_slot_order_read(th_context *ctx, int32_t buffer, uint32_t *perm, uint32_t *chunks, uint32_t chunk_capacity,
+                             uint32_t *nchunks, void *slots, int32_t *sorted);
 
 /* Which of the two draw() pipelines th_flow_deposit / th_view_draw / th_draw run through (build-defined, invisible in every
  * result: both reproduce GL's primitive order bit for bit).  TH_DRAW_STREAM: fragments produced in stream order from
@@ -761,14 +768,17 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
  *                          (default 0: as many as keep every scratch array of the exchange under about 64 MiB); the same on every rank
  *   TH_OPT_HASH_WINDOW     (TH_HASH_WINDOW) fused th_step_n launches hash the noise lattice over a window of it, without the
  *                          mod 289 of every coordinate, whenever the launch's coordinates provably fit one (1, default); never (0)
- *   TH_OPT_HASH_WINDOW_LAUNCHES  (read-only) fused launches of this context that ran over the window so far */
+ *   TH_OPT_HASH_WINDOW_LAUNCHES  (read-only) fused launches of this context that ran over the window so far
+ *   TH_OPT_DENSE_SORTS     (read-only) plain re-sorts of this context (histogram pass + move: th_step_n's, a packed ring's, the one
+ *                          beside a draw) whose two passes counted every sort class in LDS - flow fields of up to 2047 tiles,
+ *                          1080p among them; larger fields count through a small table per workgroup */
 enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH_OPT_FUSE = 3, TH_OPT_GRAPH = 4,
        TH_OPT_FORCE_GENERIC = 5, TH_OPT_DRAW_REUSE = 6, TH_OPT_BINS_POOL = 7,
 #ifdef TH_TESTING
        TH_OPT_INJECT_FAILURE = 8,
 #endif
        TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12,
-       TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14 };
+       TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14, TH_OPT_DENSE_SORTS = 15 };
 th_status th_option_set(th_context *ctx, int32_t option, int64_t value);
 th_status th_option_get(th_context *ctx, int32_t option, int64_t *value);
 

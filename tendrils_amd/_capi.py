@@ -198,6 +198,8 @@ PROTOTYPES = {
     "th_kernel_timing": (C.c_int32, [_ctx, C.c_int32]),
     "th_kernel_timing_read": (C.c_int32, [_ctx, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "th_slot_order": (C.c_int32, [_ctx, C.POINTER(SlotOrderInfo)]),
+    "th_slot_order_read": (C.c_int32, [_ctx, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.c_void_p, C.POINTER(C.c_int32)]),
     "th_shapes": (C.c_int32, [_ctx, C.POINTER(ShapesInfo)]),
     "th_draw_pipeline": (C.c_int32, [_ctx, C.c_int32]),
     "th_draw_query": (C.c_int32, [_ctx, C.POINTER(DrawInfo)]),

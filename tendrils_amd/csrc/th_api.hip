@@ -595,6 +595,7 @@ th_status th_option_set(th_context *c, int32_t option, int64_t value)
     case TH_OPT_SKIP_UNSEEN: o.skip_unseen = value != 0; break;
     case TH_OPT_HASH_WINDOW: o.hash_window = value != 0; break;
     case TH_OPT_HASH_WINDOW_LAUNCHES: return fail(TH_ERR_INVALID, "TH_OPT_HASH_WINDOW_LAUNCHES is read-only");
+    case TH_OPT_DENSE_SORTS: return fail(TH_ERR_INVALID, "TH_OPT_DENSE_SORTS is read-only");
     case TH_OPT_ASYNC_SORT: o.async_sort = value != 0; if (!o.async_sort) { if (th_status s = asort_drop(c)) return s; } break;
     case TH_OPT_BINS_POOL: TH_REQUIRE(value >= 0 && value < (1ll << 32), "TH_OPT_BINS_POOL out of range"); o.bins_pool = (uint32_t)value; break;
 #ifdef TH_TESTING
@@ -631,6 +632,7 @@ th_status th_option_get(th_context *c, int32_t option, int64_t *value)
     case TH_OPT_SKIP_UNSEEN: *value = o.skip_unseen; break;
     case TH_OPT_HASH_WINDOW: *value = o.hash_window; break;
     case TH_OPT_HASH_WINDOW_LAUNCHES: *value = c->hash_window_launches; break;
+    case TH_OPT_DENSE_SORTS: *value = c->dense_sorts; break;
     case TH_OPT_BINS_POOL: *value = o.bins_pool; break;
 #ifdef TH_TESTING
     case TH_OPT_INJECT_FAILURE: *value = o.inject_failure; break;

@@ -137,6 +137,7 @@ struct th_context {
     DevBuf<float4> lut_block;            // [hash tables | gradient table] ...
     float4 *lut = nullptr;               // ... the gradient table inside it
     DevBuf<float4> win_block;            // [winA | winB | winG]: the same tables extended periodically (th_logic.hpp "over a window")
+    long long dense_sorts = 0;           // plain re-sorts whose passes counted densely in LDS (TH_OPT_DENSE_SORTS)
     long long hash_window_launches = 0;  // fused launches that ran over the window tables (TH_OPT_HASH_WINDOW_LAUNCHES)
     DevBuf<uchar4> frames[2];
     int32_t frw = 0, frh = 0;

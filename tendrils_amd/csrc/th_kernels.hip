@@ -237,11 +237,14 @@ TH_D void stats_none(StatsPartial *slot, bool first)
 // The fused loop.  One LDS block: [permA | permB | gradient table], the hash tables first so that their reads need no base
 // offset - or, WIN, the window tables [winA | winB | winG] (19 680 B: six workgroups per CU hold 118 of 160 KB); `lut` then
 // lies kLutMin entries in front of winG, the addressing the gradient reads have anyway.
-// BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step (to
-// out_prev): f32 carries it along, a register copy per step; a packed ring makes its words at once at the last step (carried
-// through the loop as four more floats the kernel had 101 VGPRs - four waves per SIMD instead of five), and after one step
-// it is the word that came in, whatever that decodes to.  (Peeling the last step off the loop instead leaves the step loop's
-// VALU count as it is (349) and inlines integrate twice: 90 VGPRs against 80 for the f32 kernel, profiles/r7_b_isa.txt.)
+// BUCKETED: tile-sorted slots (p.perm), dealt to the 8 XCD groups in eighths.  The state before the last step leaves for
+// out_prev from inside the loop, under the wave-uniform test for the last step (a scalar branch, taken once per launch; its
+// store address is formed there from an opaque copy of idx, so that no 64-bit address is held through the loop), and the new
+// state overwrites the old one in registers: nothing is carried from step to step but the state itself (carrying the previous
+// state cost the f32 loop four v_mov_b32 per step on its back edge and both kernels registers: profiles/fused_carry_and_sort_isa.txt;
+// integrate()'s cold branch returns in a form that lets the result take the state's registers, th_logic.hpp).  On a packed ring
+// the words are made at the last step, and after one step the previous state is the word that came in, whatever that decodes
+// to.  The loop counts down and runs at least once: the host never launches zero steps (launch_logic_fused).
 // The statistics of a packed ring are those of what its texels decode to - what th_stats reads through its f32 view.
 #define TH_LOGIC_FUSED_LOOP(Fmt)                                                                                              \
     static_assert(!WIN || (NOISE && !FAST), "WIN: NOISE, exact");                                                              \
@@ -273,21 +276,24 @@ TH_D void stats_none(StatsPartial *slot, bool first)
         if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx]);                                              \
     }                                                                                                                         \
     for (; idx < end; idx += stride) {                                                                                        \
-        typename Fmt::Word w = nxt, wprev = w;                                                                                \
+        const typename Fmt::Word w = nxt;                                                                                     \
         const uint32_t pid = BUCKETED ? npid : idx;                                                                           \
         if (idx + stride < end) {                                                                                             \
             nxt = Fmt::load(p.in, idx + stride);                                                                              \
             if constexpr (BUCKETED) npid = __builtin_nontemporal_load(&p.perm[idx + stride]);                                 \
         }                                                                                                                     \
         float4 st = Fmt::decode(w);                                                                                           \
-        for (uint32_t k = 0; k < p.nsteps; ++k) {                                                                             \
-            if constexpr (!Fmt::packed) wprev = Fmt::encode(st);                                                              \
-            else if (k + 1u == p.nsteps && k) wprev = Fmt::encode(st);                                                        \
-            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true, !NOISE, WIN>(p, lut, st, pid, p.times[k], &tabs)); \
-        }                                                                                                                     \
-        if (!Fmt::packed || p.nsteps) w = Fmt::encode(st);                                                                    \
-        Fmt::store(p.out_prev, idx, wprev);                                                                                   \
-        Fmt::store(p.out, idx, w);                                                                                            \
+        uint32_t left = p.nsteps;                                                                                             \
+        do {                                                                                                                  \
+            if (left == 1u) {                                                                                                 \
+                uint32_t at = idx;                                                                                            \
+                asm volatile("" : "+v"(at));                                                                                  \
+                if (Fmt::packed && p.nsteps == 1u) Fmt::store(p.out_prev, at, w);                                             \
+                else Fmt::store(p.out_prev, at, Fmt::encode(st));                                                             \
+            }                                                                                                                 \
+            st = Fmt::quantize(integrate<FAST, NOISE, TARGET, POW2, false, true, !NOISE, WIN>(p, lut, st, pid, p.times[p.nsteps - left], &tabs)); \
+        } while (--left);                                                                                                     \
+        Fmt::store(p.out, idx, Fmt::encode(st));                                                                              \
         if constexpr (STATS) { stats_take(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], st, p.u.speedLimit, first); first = false; } \
     }                                                                                                                         \
     if constexpr (STATS) stats_none(&p.stats_part[blockIdx.x * 4u + (threadIdx.x >> 6)], first);
@@ -317,6 +323,7 @@ int fused_grid(uint32_t count, bool bucketed)
 
 void launch_logic_fused(const LogicParams &p, const LogicVariant &v, hipStream_t s)
 {
+    if (!p.nsteps) return;          // (the step loop runs at least once; th_step.hip launches min(n - done, kMaxFusedSteps) >= 1 steps)
     const bool packed = v.format == StateFormat::packed, bucketed = p.perm != nullptr;
     const int grid = fused_grid(p.count, bucketed);
     lift([&](auto fast, auto noise, auto target, auto pow2, auto bk, auto stats, auto window) {
@@ -607,6 +614,107 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(const TileSortParams 
     }
 }
 
+// ---- the plain passes over a key space that fits LDS -----------------------------------------------------------------------
+// The open-addressed table above fits freshly sorted input - one or two keys per block.  The fused launches re-sort every
+// rebucket_steps (256) steps, by when a particle has drifted several tiles: a 4096-slot block then holds far more than
+// kBinSlots keys, the table is full, and every further run of a wave goes to the global counters - in the scatter with a
+// returning atomic per run, 16 rounds in a row per lane.  Where all 2 * ntiles + 2 bins fit kDenseTileBins words (1080p: 4082),
+// a workgroup counts them densely instead: no probing, no overflow path, and no lane waits for a global round trip of its own.
+//   hist     an LDS add per run of a wave (wave_runs stays: a fresh sort puts 64 lanes on one address), then the threads sweep
+//            the bins and every non-zero one adds once to the block's copy of the global histogram
+//   scatter  a lane's rank inside the block from a returning LDS add; after the barrier every non-zero bin reserves its range
+//            with one atomic on the cursor - all in flight together - and leaves the range's first slot in the bin's own
+//            word; after the second barrier slot = table[key] + rank.  A workgroup's texels stay in registers across the
+//            barriers (reading them again would move 40 % more bytes); key and rank share a word (12 bits each).  A workgroup
+//            moves kDenseScatterSlots = 2048 slots, half a block of the histogram pass: 8 texels a lane - with 16 of them the
+//            f32 kernel needed more than the 128 VGPRs of four waves per SIMD and spilled.
+// Both passes pick the copy replica_of(block) and are only ever launched as a pair over the same blocks (th_order.hip), so they
+// need no block_records.  Larger key spaces run the kernels above unchanged.
+constexpr uint32_t kDenseScatterSlots = 2048;
+static_assert(kDenseTileBins <= (1u << 20) && kDenseScatterSlots <= (1u << 12) && kTileChunk % kDenseScatterSlots == 0, "tile_scatter_dense_kernel: key << 12 | rank");
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void tile_hist_dense_kernel(const TileSortParams b)
+{
+    __shared__ uint32_t count[kDenseTileBins];
+    const uint32_t nbins = 2u * b.g.ntiles + 2u;
+    for (uint32_t k = threadIdx.x; k < nbins; k += 256u) count[k] = 0u;
+    const uint32_t base = blockIdx.x * kTileChunk;
+    float2 pos[kTileChunk / 256u];
+    uint32_t pid[kTileChunk / 256u];
+#pragma unroll
+    for (uint32_t k = 0; k < kTileChunk / 256u; ++k) {
+        const uint32_t s = base + k * 256u + threadIdx.x, at = s < b.count ? s : b.count - 1u;
+        pos[k] = slot_position<PACKED>(b.state, at);
+        pid[k] = b.perm_in ? b.perm_in[at] : at;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kTileChunk / 256u; ++k) {
+        const uint32_t s = base + k * 256u + threadIdx.x;
+        const bool valid = s < b.count;
+        const uint32_t key = valid ? min(tile_key(b.g, pos[k].x, pos[k].y, pid[k]), nbins - 1u) : 0u;
+        const WaveRuns r = wave_runs(key, valid);
+        if (r.head) atomicAdd(&count[key], r.length);
+    }
+    __syncthreads();
+    const uint32_t rep = replica_of(blockIdx.x);
+    for (uint32_t k = threadIdx.x; k < nbins; k += 256u) {
+        const uint32_t n = count[k];
+        if (n) atomicAdd(&b.hist[rep + k], n);
+    }
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(256, 4) void tile_scatter_dense_kernel(const TileSortParams b)
+{
+    using Texel = std::conditional_t<PACKED, v2u, v4f>;          // 8-byte packed texels or RGBA32F
+    constexpr uint32_t kPer = kDenseScatterSlots / 256u;
+    __shared__ uint32_t table[kDenseTileBins];                   // per bin: lanes of this workgroup so far, then the first slot of its range
+    const uint32_t nbins = 2u * b.g.ntiles + 2u;
+    for (uint32_t k = threadIdx.x; k < nbins; k += 256u) table[k] = 0u;
+    const uint32_t base = blockIdx.x * kDenseScatterSlots;
+    const uint32_t *ids = b.perm_in ? b.perm_in : reinterpret_cast<const uint32_t *>(b.state);     // (texel order: a word read anyway)
+    Texel st[kPer];
+    uint32_t pid[kPer], place[kPer];
+#pragma unroll
+    for (uint32_t q = 0; q < kPer; ++q) {
+        const uint32_t s = base + q * 256u + threadIdx.x, at = s < b.count ? s : b.count - 1u;
+        st[q] = __builtin_nontemporal_load(&reinterpret_cast<const Texel *>(b.state)[at]);
+        pid[q] = __builtin_nontemporal_load(&ids[at]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < kPer; ++q) {
+        const uint32_t s = base + q * 256u + threadIdx.x;
+        const bool valid = s < b.count;
+        float px, py;
+        if constexpr (PACKED) { const float4 u = unpack_state(make_uint2(st[q].x, 0u)); px = u.x; py = u.y; }
+        else { px = st[q].x; py = st[q].y; }
+        const uint32_t key = valid ? min(tile_key(b.g, px, py, b.perm_in ? pid[q] : s), nbins - 1u) : 0u;
+        const WaveRuns r = wave_runs(key, valid);
+        uint32_t first = 0;
+        if (r.head) first = atomicAdd(&table[key], r.length);
+        place[q] = key << 12 | (__shfl(first, r.head_lane) + r.rank);
+    }
+    __syncthreads();
+    const uint32_t rep = replica_of(base / kTileChunk);          // (the copy tile_hist counted these slots in)
+    for (uint32_t k = threadIdx.x; k < nbins; k += 256u) {
+        const uint32_t n = table[k];
+        if (n) table[k] = atomicAdd(&b.cursor[rep + k], n);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < kPer; ++q) {
+        const uint32_t s = base + q * 256u + threadIdx.x;
+        if (s < b.count) {
+            const uint32_t d = table[place[q] >> 12] + (place[q] & 0xfffu);
+            reinterpret_cast<Texel *>(b.state_out)[d] = st[q];
+            b.perm_out[d] = b.perm_in ? pid[q] : s;
+        }
+    }
+}
+
 // back to texel order: dst[perm[s]] = src[s]
 template <typename Texel>
 __global__ __launch_bounds__(256) void unpermute_state_kernel(Texel *dst, const Texel *src, const uint32_t *perm, uint32_t n)
@@ -625,6 +733,11 @@ static int tile_grid(uint32_t count) { return (int)((count + kTileChunk - 1) / k
 
 void launch_tile_hist(const TileSortParams &b, hipStream_t s)
 {
+    if (tile_sort_dense(b.g)) {
+        if (b.packed) hipLaunchKernelGGL(tile_hist_dense_kernel<true>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
+        else hipLaunchKernelGGL(tile_hist_dense_kernel<false>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
+        return;
+    }
     if (b.packed) hipLaunchKernelGGL(tile_hist_kernel<true>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
     else hipLaunchKernelGGL(tile_hist_kernel<false>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
 }
@@ -639,6 +752,13 @@ void launch_tile_scan(const TileSortParams &b, hipStream_t s)
 
 void launch_tile_scatter(const TileSortParams &b, hipStream_t s)
 {
+    // (dense: only behind launch_tile_hist over the same blocks - the one way th_order.hip and th_step.hip launch it)
+    if (tile_sort_dense(b.g)) {
+        const uint32_t grid = (b.count + kDenseScatterSlots - 1u) / kDenseScatterSlots;
+        if (b.packed) hipLaunchKernelGGL(tile_scatter_dense_kernel<true>, dim3(grid), dim3(256), 0, s, b);
+        else hipLaunchKernelGGL(tile_scatter_dense_kernel<false>, dim3(grid), dim3(256), 0, s, b);
+        return;
+    }
     if (b.packed) hipLaunchKernelGGL(tile_scatter_kernel<true>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
     else hipLaunchKernelGGL(tile_scatter_kernel<false>, dim3(tile_grid(b.count)), dim3(256), 0, s, b);
 }

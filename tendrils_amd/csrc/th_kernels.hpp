@@ -27,6 +27,8 @@ constexpr int kWinMaxCell = 8958;            // mod289_int(i) is the true residu
 // Tile-sorted slot order (th_kernels.hip "Tile-sorted slot order")
 constexpr uint32_t kTileChunk = 4096;        // slots per workgroup (16 per thread), all of one tile
 constexpr uint32_t kMaxTileBins = 8192;      // sort classes (2 per tile + 2): larger flow fields keep the texel order
+constexpr uint32_t kDenseTileBins = 4096;    // sort classes that tile_hist / tile_scatter count densely in LDS (16 KB a workgroup: 1080p has 4082);
+                                             // between here and kMaxTileBins the open-addressed table of kBinSlots keys counts
 constexpr uint32_t kSortReplicas = 64;       // copies of the global sort counters (power of two)
 constexpr uint32_t kBinSlotsLog2 = 6, kBinSlots = 1u << kBinSlotsLog2;   // LDS table of the tiles one workgroup meets
 
@@ -38,6 +40,7 @@ struct TileGeom {                // how a particle maps to its sort class: the t
 };
 
 struct TileChunk { uint32_t start, count, tile, pad; };
+inline bool tile_sort_dense(const TileGeom &g) { return 2u * g.ntiles + 2u <= kDenseTileBins; }   // launch_tile_hist / _scatter: the dense kernels
 struct ChunkRecord { uint32_t key[kBinSlots], count[kBinSlots]; };   // a chunk's table of (tile, particles) of its next positions
 
 // Kernel argument block of the integrator.  Passed by value: it lands in the
@@ -102,7 +105,7 @@ struct TileSortParams {
     uint32_t *nchunks;
     float4 *state_out;           // tile_scatter only
     uint32_t *perm_out;
-    ChunkRecord *block_records;  // per 4096-slot block of the input: written by tile_hist, used by tile_scatter (may be null)
+    ChunkRecord *block_records;  // per 4096-slot block of the input: written by tile_hist, used by tile_scatter (may be null; the dense kernels touch none)
     uint32_t packed;             // the state is the packed 8-byte form (TH_STATE_F16): state / state_out point at uint2 texels
 };
 

@@ -370,7 +370,11 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
     const float bound = WIN ? p.win_bound : p.pos_bound;
     bool in_domain = __builtin_fabsf(posx) < bound && __builtin_fabsf(posy) < bound;
     if (__builtin_expect(!in_domain, 0)) {
-        if (!(posx != kInert || posy != kInert)) return st;              // inert: pass through (src/logic.frag:52)
+        // (the test reads opaque copies, so that what passes through is the incoming registers themselves and not the constant the
+        // compiler knows them to hold: in a fused loop the result then takes the state's own registers - no copy on the back edge)
+        float ix = posx, iy = posy;
+        asm volatile("" : "+v"(ix), "+v"(iy));
+        if (!(ix != kInert || iy != kInert)) return st;                  // inert: pass through (src/logic.frag:52)
         // A NaN or infinite position component makes every output component NaN in the reference: the first noise
         // coordinate v = pos * noiseScale' is NaN or Inf, s = dot(v, C.yyy) and i = floor(v + s) follow, x0 = v - i + t
         // is NaN (Inf - Inf), the gradient dot products are NaN and 42 * dot(m, NaN) is NaN whatever m is; wander
@@ -379,7 +383,9 @@ TH_D float4 integrate(const LogicParams &p, const float4 *lut, float4 st, uint32
         // DESIGN.md 4); particles that went 0/0 -> NaN (:92-94) would otherwise hold their whole wave on the
         // reference-order path below for good.
         if (!(__builtin_fabsf(posx) < __builtin_inff()) || !(__builtin_fabsf(posy) < __builtin_inff())) {
-            const float q = __builtin_nanf("");
+            // (made in this branch, not ahead of it as a default that would stay live across the reference-order branch below)
+            float q = __builtin_nanf("");
+            asm volatile("" : "+v"(q));
             return make_float4(q, q, q, q);
         }
         // An opaque copy of the particle id, and the texel coordinates again from it: what logic_texel_ref derives from them

@@ -249,6 +249,7 @@ th_status asort_start(th_context *c, const th::TileGeom &g, float4 *src, int src
     th::launch_tile_hist(b, c->side);
     th::launch_tile_scan(b, c->side);
     th::launch_tile_scatter(b, c->side);
+    if (th::tile_sort_dense(g)) ++c->dense_sorts;
     TH_HIP(hipGetLastError());
     TH_HIP(hipEventRecord(c->asort.done, c->side));
     ++c->sorts;
@@ -292,6 +293,7 @@ th_status begin_sort(th_context *c, const th::TileGeom &g, const float4 *state, 
     if (!have_hist) {          // (a COUNT pass whose histogram was never used may have left counts behind)
         TH_HIP(hipMemsetAsync(b.hist, 0, kTileWords / 2 * sizeof(uint32_t), c->stream));
         th::launch_tile_hist(b, c->stream);
+        if (th::tile_sort_dense(g)) ++c->dense_sorts;      // (the caller's launch_tile_scatter takes the same route)
     }
     th::launch_tile_scan(b, c->stream);
     TH_HIP(hipMemsetAsync(c->tile_mem + kTileWords, 0, sizeof(uint32_t), c->stream));    // window misses
@@ -368,6 +370,28 @@ th_status th_slot_order(th_context *c, th_slot_order_info *out)
         TH_HIP(hipStreamSynchronize(c->stream));
         out->window_misses = m;
     }
+    return TH_OK;
+}
+
+th_status th_slot_order_read(th_context *c, int32_t buffer, uint32_t *perm, uint32_t *chunks, uint32_t chunk_capacity, uint32_t *nchunks,
+                             void *slots, int32_t *sorted)
+{
+    if (th_status s = use(c)) return s;
+    TH_REQUIRE(sorted && buffer >= 0 && (size_t)buffer < c->ring.size(), "th_slot_order_read: buffer out of range or null output");
+    TH_REQUIRE(!chunks || nchunks, "th_slot_order_read: chunks without nchunks");
+    const int o = order_of(c, c->ring[(size_t)buffer]);
+    *sorted = o >= 0 ? 1 : 0;
+    if (o < 0) return TH_OK;
+    const th_context::SlotOrder &so = c->orders[(size_t)o];
+    const size_t n = c->texels();
+    TH_HIP(hipStreamSynchronize(c->stream));
+    if (perm) TH_HIP(hipMemcpy(perm, so.perm, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (nchunks) {
+        TH_HIP(hipMemcpy(nchunks, so.nchunks, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const size_t take = std::min<size_t>(std::min<size_t>(*nchunks, chunk_capacity), c->max_chunks);
+        if (chunks && take) TH_HIP(hipMemcpy(chunks, so.chunks, take * sizeof(th::TileChunk), hipMemcpyDeviceToHost));
+    }
+    if (slots) TH_HIP(hipMemcpy(slots, c->ring[(size_t)buffer], n * (c->packed ? sizeof(uint2) : sizeof(float4)), hipMemcpyDeviceToHost));
     return TH_OK;
 }
 
