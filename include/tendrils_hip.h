@@ -364,11 +364,38 @@ th_status th_screen_run(th_context *ctx, th_program *program, const void *unifor
  *                                        stream-ordered built-in pass
  *                      The results are the same bits either way.  Nothing of the pass is reused by the next one, nor of the one
  *                      before by it.  The ring's content is untouched.
- *                      On a row-band shard: TH_ERR_UNSUPPORTED, nothing launched.  TH_ERR_INVALID: another kind's program, more
- *                      than 1024 uniform bytes, null uniforms with a size, a null program, an unknown pass. */
+ *                      On a row-band shard: TH_ERR_UNSUPPORTED, nothing launched (a band's pass goes through the two calls
+ *                      below).  TH_ERR_INVALID: another kind's program, more than 1024 uniform bytes, null uniforms with a
+ *                      size, a null program, an unknown pass.
+ *  th_draw_program_emit       the program pass of a ROW BAND, what th_deposit_emit / th_view_emit are to the built-in stages: this
+ *                      band's fragments with the program as their vertex stage, keyed (owner, texel, global stream index) and
+ *                      parted by owner (th_deposit_set_owners); *count, *keys_dev, *colors_dev as th_deposit_emit hands them
+ *                      out, valid until the context's next draw call.  The owner blends what it received with th_deposit_merge
+ *                      (TH_PASS_FLOW) or th_view_merge (TH_PASS_VIEW): for the owned texels the unsharded th_draw_program_run
+ *                      bit for bit.  A whole-texture context is the band of all rows.  th_vertex_pass is field for field what
+ *                      the unsharded run hands the program for the same particle: vertex, line, dataRes, geomRes speak of the
+ *                      WHOLE texture, uv and state are the global stream's - a lookup that lands on the row above or below the
+ *                      band reads the neighbour's edge row (th_deposit_set_halo); where nobody supplied it the call fails with
+ *                      th_deposit_emit's TH_ERR_UNSUPPORTED and hands out nothing.  Always stream-ordered: the ring goes to
+ *                      texel order (a packed ring is seen through f32 copies); its content is untouched.  TH_ERR_INVALID as
+ *                      th_draw_program_run, and: null outputs, a target of more than 2^24 texels.
+ *  th_draw_program_sharded    what th_draw_sharded (below) is to the built-in stages: draw() of a row-band shard with a program
+ *                      in one pass or both, the exchange issued by the library (every rank, collectively; needs th_comm_init;
+ *                      balanced bands, <= 32 ranks).  Edge rows to the neighbours, then the flow pass, then - with view_program
+ *                      or r - the view pass, each: emit -> fragment all-to-all by texel owner -> merge -> all-gather of the
+ *                      owned ranges.  A null program selects the built-in stage of that pass, with u / r (then not null).
+ *                      Always pass by pass and stream-ordered: two programs need not agree on where the lines are.
+ *                      *fragments / *view_fragments (optional): what this band emitted in each pass.  A rank that fails on its
+ *                      own - loading the program, its vertex buffer, the launch, a missing halo row - ends the draw on every
+ *                      rank before anything is blended: that rank returns its error, the others name it.  TH_ERR_INVALID,
+ *                      nothing launched or exchanged: both programs null (th_draw_sharded is the call), another kind's
+ *                      program, more than 1024 uniform bytes, null uniforms with a size, no communicator, more than 32 ranks. */
 th_status th_draw_program_compile(const char *source, const char *name, th_program **out);
 th_status th_draw_program_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
                               int32_t pass /* TH_PASS_FLOW | TH_PASS_VIEW */, uint64_t *fragments);
+th_status th_draw_program_emit(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes,
+                               int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev);
+/* (th_draw_program_sharded is declared beside th_draw_sharded, below: it takes the view pass's uniforms) */
 
 /* -- step programs: n steps of an integrator the CALLER wrote, fused in one launch -----------------------------------
  * new Tendrils(gl, { logicShader }) takes a caller's integrator (src/index.js:70, 107-113).  As a state program (above) it
@@ -662,6 +689,11 @@ th_status th_export_view_lines(th_context *ctx, const th_render_uniforms *u, flo
  * groups, ncclAllGather) - once for both passes (th_draw_emit / th_draw_merge below) when they draw with the same line
  * width, else pass by pass.  r = NULL: the flow pass only.  Same results as the primitives driven by a host. */
 th_status th_draw_sharded(th_context *ctx, const th_deposit_uniforms *u, const th_render_uniforms *r, uint64_t *fragments);
+/* ... with a draw program as the vertex stage of one pass or both ("draw programs", above) */
+th_status th_draw_program_sharded(th_context *ctx,
+                                  th_program *flow_program, const void *flow_uniforms, uint32_t flow_bytes, const th_deposit_uniforms *du,
+                                  th_program *view_program, const void *view_uniforms, uint32_t view_bytes, const th_render_uniforms *ru,
+                                  uint64_t *fragments, uint64_t *view_fragments);
 th_status th_view_emit(th_context *ctx, const th_render_uniforms *u, uint64_t *count, void **keys_dev, void **colors_dev);
 th_status th_view_merge(th_context *ctx, const void *keys_dev, const void *colors_dev, uint64_t count);
 th_status th_view_device_ptr(th_context *ctx, void **dptr);

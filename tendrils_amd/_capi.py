@@ -235,6 +235,11 @@ PROTOTYPES = {
                                   C.c_int32]),
     "th_draw_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_draw_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "th_draw_program_emit": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p)]),
+    "th_draw_program_sharded": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DepositUniforms),
+                                            C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RenderUniforms),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "th_step_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_step_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32]),
     "th_step_program_view_size": (C.c_int32, [_ctx, C.POINTER(C.c_float)]),

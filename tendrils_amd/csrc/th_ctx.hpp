@@ -99,6 +99,7 @@ struct ProgramModule {
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
+    hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines)
     hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
@@ -500,6 +501,13 @@ th_status refuse_band(const th_context *c, const char *what, const char *instead
 th_status shared_uniforms(const th_deposit_uniforms *du, const th_render_uniforms *ru);  // the passes of one draw agree on what they draw
 th_deposit_uniforms deposit_uniforms_of(const th_render_uniforms &u);
 th_status missing_halo(const th_context *c);          // the error of a band's line that reads a row nobody supplied
+
+// ---- th_shard.hip ----------------------------------------------------------------------------------------------------
+// the sharded deposit's keys hold 24 texel bits: `target` ("flow", "view") names what is too large for them
+th_status texels_fit_keys(const th_context *c, const char *target);
+// the tail of every emit of a row band: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed
+// (owner, texel, global stream index) and parted by owner; synchronises (the caller hands the buffers to a collective)
+th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev);
 
 // One pass of a local draw: prepare(p, first, &bins) readies `p` for an attempt - the first may take the bins - and says which
 // pipeline it takes; a binned pass that gives up before blending is repeated in stream order, and so are the other passes of its frame.

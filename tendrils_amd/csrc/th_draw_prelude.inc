@@ -150,4 +150,58 @@ extern "C" __global__ __launch_bounds__(256) void th_draw_vertex_slots_kernel(co
         }
     }
 }
+
+// The same stage over a ROW BAND (th_draw_program_emit: a context that holds rows row0 .. row0 + rows of the W x H texture;
+// the whole texture is the band of all rows).  The record is its own: a th_draw_args at its head - what th_flow / th_colormap
+// read through v.args; H the WHOLE texture's height, count = 2 W rows, the band's stream vertices, cur / prev the band's rows -
+// and behind it what only a band has.
+struct th_draw_band_args {
+    th_draw_args a;
+    const float4 *halo_lo, *halo_hi;   // row row0 - 1 / row0 + rows of the neighbouring bands, as th_deposit_set_halo takes them:
+                                       // W texels of buffers[0], then W of buffers[1] (null: nobody supplied it)
+    unsigned *oob;                     // set to 1 when a lookup lands on a row that neither the band nor a halo row holds
+    unsigned row0, rows;
+};
+static_assert(sizeof(th_draw_band_args) == 128, "th_draw_band_args: layout shared with th_drawprog.hip");
+// One lane per stream vertex of the band, as th_draw_vertex_kernel: lane `idx` is vertex e = idx & 1 of the line of the band's
+// texel idx >> 1 and writes record `idx` - where the raster stage reads it, by LOCAL row (dep_vertex_read) - in two 16-byte
+// stores; the state comes in as one 16-byte load.  What the program sees is the GLOBAL stream: j = 2 (row0 + local row) + e,
+// line = column H + global row, dataRes / geomRes the whole texture's - field for field what the unsharded kernel hands it for
+// the same particle.  th_stream_lookup counts the row it lands on from row0: -1 and `rows` are the neighbours' edge rows, read
+// from the halo rows (chosen as dep_fetch chooses, th_raster.hpp); where that row is absent the flag is raised - the pass is
+// refused - and the load goes to the band's nearest row instead: never out of bounds.  No LDS, no atomics.
+extern "C" __global__ __launch_bounds__(256) void th_draw_vertex_band_kernel(const th_draw_band_args b, const th_program_uniform_block u)
+{
+    const th_draw_args &a = b.a;
+    th_vertex_pass v;
+    v.dataRes = make_float2((float)a.W, (float)a.H);
+    v.geomRes = make_float2((float)a.W, (float)(2u * a.H));
+    v.uniforms = u.bytes;
+    v.args = &b.a;
+    float4 *records = static_cast<float4 *>(a.vertices);
+    for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < a.count; idx += gridDim.x * 256u) {
+        const unsigned t = idx >> 1, local = t / a.W, col = t - local * a.W;
+        const unsigned row = b.row0 + local;
+        const unsigned j = 2u * row + (idx & 1u);
+        const th_stream_at<float4> s = th_stream_lookup(col, j, a.inv_x, a.inv_y, (int)a.W, (int)a.H, b.row0, a.cur, a.prev);
+        v.uv = make_float2(s.uvx, s.uvy);
+        v.from_current = s.from_cur;
+        // (one unconditional load from a selected address, as dep_fetch)
+        const int held = s.row < 0 ? 0 : (s.row < (int)b.rows ? s.row : (int)b.rows - 1);
+        const float4 *from = s.tex + ((size_t)held * a.W + (size_t)s.col);
+        if (held != s.row) {
+            const float4 *halo = s.row == -1 ? b.halo_lo : (s.row == (int)b.rows ? b.halo_hi : nullptr);
+            if (halo) from = halo + (s.from_cur ? 0u : a.W) + s.col;
+            else *b.oob = 1u;
+        }
+        const th_float4_load t4 = *reinterpret_cast<const th_float4_load *>(from);
+        v.state = make_float4(t4.x, t4.y, t4.z, t4.w);
+        v.column = col;
+        v.vertex = j;
+        v.line = col * a.H + row;
+        const th_vertex o = th_vertex_main(v);
+        records[2u * (size_t)idx] = make_float4(o.position.x, o.position.y, __uint_as_float(o.live ? 1u : 0u), 0.0f);
+        records[2u * (size_t)idx + 1u] = o.color;
+    }
+}
 )TH_PRELUDE"

@@ -46,6 +46,28 @@ using KernArgs = ProgramKernArgs<DrawArgs>;
 static_assert(sizeof(DrawArgs) == 96 && offsetof(DrawArgs, perm) == 88 && offsetof(KernArgs, u) == 96 && sizeof(KernArgs) == 96 + kUniformBytes,
               "launch record: layout shared with th_draw_prelude.inc");
 
+// ... and a row band's (th_draw_band_args: a th_draw_args at its head, then what only a band has)
+struct BandArgs {
+    DrawArgs a;
+    const float4 *halo_lo, *halo_hi;
+    uint32_t *oob;
+    uint32_t row0, rows;
+};
+using BandKernArgs = ProgramKernArgs<BandArgs>;
+static_assert(sizeof(BandArgs) == 128 && offsetof(BandArgs, halo_lo) == 96 && offsetof(BandArgs, row0) == 120 && offsetof(BandKernArgs, u) == 128 &&
+              sizeof(BandKernArgs) == 128 + kUniformBytes, "a band's launch record: layout shared with th_draw_prelude.inc");
+
+// what the records of all three vertex kernels say alike: the buffer they fill, what th_flow / th_colormap tap, the stream's scales
+// and shape (H: the whole texture's), `lines` lines of the rows this context holds
+void record_shared(const th_context *c, const th::DepositParams &p, size_t lines, DrawArgs &a)
+{
+    a.vertices = c->draw_vertices.get();
+    a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
+    a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
+    a.inv_x = p.inv_x; a.inv_y = p.inv_y;
+    a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
+}
+
 }  // namespace
 
 extern "C" {
@@ -69,6 +91,7 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
     if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;      // (the view pass writes no state and no flow: th_view_draw)
     if (th_status s = program_run_args(prog, kDrawProgram, "th_draw_program_run", uniforms, uniform_bytes)) return s;
     TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
+    // (this LOCAL pass has no exchange to go through; a band's program pass is th_draw_program_emit / th_draw_program_sharded)
     if (th_status s = refuse_band(c, "draw program", "a band's pass goes through the owners' exchange, which carries the built-in stages alone")) return s;
     const size_t lines = c->texels();
     TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a %dx%d particle texture is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
@@ -103,11 +126,7 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
             if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
             a.cur = cur; a.prev = prev;
         }
-        a.vertices = c->draw_vertices.get();
-        a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
-        a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
-        a.inv_x = p.inv_x; a.inv_y = p.inv_y;
-        a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
+        record_shared(c, p, lines, a);
         k.set_uniforms(uniforms, uniform_bytes);
         if (lanes) {
             // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
@@ -120,6 +139,55 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
     });
     c->drawn.valid = false;
     return ran;
+}
+
+// The program pass of a row band - what th_deposit_emit / th_view_emit are to the built-in stages (th_shard.hip): this band's
+// fragments with the program as their vertex stage, keyed and parted by owner for th_deposit_merge (flow) / th_view_merge (view).
+// Always stream-ordered: the ring goes to texel order, th_draw_vertex_band_kernel fills the vertex buffer by local row with
+// what the program makes of the GLOBAL stream (the neighbours' edge rows from the halo rows), the stream-ordered raster stage
+// draws from the buffer.  A row that neither the band nor a halo row holds - asked for by the vertex kernel or by the raster
+// stage, on the same word - is the error of th_deposit_emit, and nothing is handed out.
+th_status th_draw_program_emit(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t pass,
+                               uint64_t *count, void **keys_dev, void **colors_dev)
+{
+    if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;
+    if (th_status s = program_run_args(prog, kDrawProgram, "th_draw_program_emit", uniforms, uniform_bytes)) return s;
+    TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
+    TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
+    if (th_status s = texels_fit_keys(c, pass == TH_PASS_VIEW ? "view" : "flow")) return s;
+    const size_t lines = c->texels();
+    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a band of %dx%d particles is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
+    *count = 0; *keys_dev = nullptr; *colors_dev = nullptr;
+    c->drawn.valid = false;
+    ProgramModule *m = nullptr;
+    if (th_status s = program_loaded(c, prog, &m)) return s;
+    const th_deposit_uniforms none{};                   // (viewSize, time, speedLimit are the program's own business: th_draw_program_run)
+    th::DepositParams p;
+    if (th_status s = deposit_prepare(c, &none, p)) return s;          // (texel order; the out-of-band word is cleared)
+    if (pass == TH_PASS_VIEW) p.mode = 1;
+    p.line_half = 0.5f * drawn_line_width(c, pass);
+    if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
+    p.vertices = c->draw_vertices;
+    BandKernArgs k{};
+    DrawArgs &a = k.a.a;
+    float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as the halo rows are)
+    if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
+    if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
+    a.cur = cur; a.prev = prev;
+    record_shared(c, p, lines, a);                     // (count: the band's vertices)
+    k.a.halo_lo = p.halo_lo; k.a.halo_hi = p.halo_hi; k.a.oob = p.oob;
+    k.a.row0 = p.row0; k.a.rows = p.rows;
+    k.set_uniforms(uniforms, uniform_bytes);
+    if (lines) {
+        LaunchTimer timer;                              // (th_kernel_timing: the vertex kernel alone)
+        if (th_status s = timer.begin(c)) return s;
+        if (th_status s = program_launch(c, m->fn_band, 2 * lines, k)) return s;
+        if (th_status s = timer.end(c)) return s;
+    }
+    const th_status emitted = emit_parted(c, p, count, keys_dev, colors_dev);
+    if (emitted == TH_OK) { c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = *count; c->last_draw.crowded_fragments = 0; }
+    c->drawn.valid = false;
+    return emitted;
 }
 
 }  // extern "C"

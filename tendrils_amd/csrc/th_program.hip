@@ -128,7 +128,7 @@ void ProgramModule::reset()
 {
     if (module) (void)hipModuleUnload(module);
     program_release(prog);
-    module = nullptr; fn = nullptr; fn_slots = nullptr; fn_packed = nullptr; prog = nullptr;
+    module = nullptr; fn = nullptr; fn_slots = nullptr; fn_band = nullptr; fn_packed = nullptr; prog = nullptr;
 }
 
 const char *program_kind_name(ProgramKind kind)
@@ -156,6 +156,7 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     TH_HIP(hipModuleLoadData(&m->module, prog->code.data()));
     TH_HIP(hipModuleGetFunction(&m->fn, m->module, kKernelNames[prog->kind]));
     if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_draw_vertex_slots_kernel"));
+    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_draw_vertex_band_kernel"));
     if (prog->kind == kStepProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_step_packed_kernel"));
     m->prog = prog;
     prog->refs.fetch_add(1);

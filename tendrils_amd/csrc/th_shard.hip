@@ -4,19 +4,9 @@
 
 using namespace thi;
 
-extern "C" {
+namespace thi {
 
-th_status th_deposit_set_owners(th_context *c, int32_t world)
-{
-    TH_REQUIRE(c, "null context");
-    // (the owner's merge walks up to 32 source bands per texel - th_deposit.hip: kMaxBands: more ranks than that could only be
-    // refused after the blend had begun)
-    TH_REQUIRE(world >= 1 && world <= 32, "owner count %d outside [1, 32]", world);
-    c->dep_owners = (uint32_t)world;
-    return TH_OK;
-}
-
-static th_status texels_fit_keys(const th_context *c, const char *target)
+th_status texels_fit_keys(const th_context *c, const char *target)
 {
     TH_REQUIRE((uint64_t)c->fw * c->fh <= (uint64_t)th::kTexelMask + 1u, "the sharded deposit keys hold 24 texel bits: %s %dx%d is too large", target, c->fw, c->fh);
     return TH_OK;
@@ -24,7 +14,7 @@ static th_status texels_fit_keys(const th_context *c, const char *target)
 
 // the tail of the three emits: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed (owner,
 // texel, global stream index) and parted by owner
-static th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev)
+th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev)
 {
     th::launch_deposit_count(p, c->stream);
     uint32_t total = 0;
@@ -52,6 +42,20 @@ static th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *coun
     }
     TH_HIP(hipGetLastError());
     TH_HIP(hipStreamSynchronize(c->stream));               // the caller hands the buffers to a collective on its own stream
+    return TH_OK;
+}
+
+}  // namespace thi
+
+extern "C" {
+
+th_status th_deposit_set_owners(th_context *c, int32_t world)
+{
+    TH_REQUIRE(c, "null context");
+    // (the owner's merge walks up to 32 source bands per texel - th_deposit.hip: kMaxBands: more ranks than that could only be
+    // refused after the blend had begun)
+    TH_REQUIRE(world >= 1 && world <= 32, "owner count %d outside [1, 32]", world);
+    c->dep_owners = (uint32_t)world;
     return TH_OK;
 }
 
@@ -303,19 +307,19 @@ static th_status exchange_fragments(th_context *c, const void *keys, const void 
 }
 
 // One pass: this band's fragments parted by owner -> all-to-all -> the owner's merge -> all-gather of the owned ranges.
-// du alone: the flow pass; ru alone: the view pass; both: both passes over one rasterisation and one exchange (two all-gathers)
-static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
+// view alone: the view pass; both: both passes over one rasterisation and one exchange (two all-gathers); neither: the flow pass.
+// emit(&count, &keys, &colors): stage 1, this band's fragments parted by owner - a built-in emit, or a draw program's
+// (th_draw_program_emit): whatever fails inside it fails on this rank alone, and travels with the counts
+extern "C++" template <class Emit>
+static th_status sharded_pass(th_context *c, bool view, bool both, Emit emit, uint64_t *fragments)
 {
     const int world = c->comm_world, rank = c->comm_rank;
-    const bool view = ru != nullptr, both = ru != nullptr && du != nullptr;
     const size_t color_bytes = both ? 2 * sizeof(float4) : sizeof(float4);
     uint64_t count = 0;
     void *keys = nullptr, *colors = nullptr;
     // stage 1 - rasterise and part by owner
     th_status mine = injected(c, 2);
-    if (mine == TH_OK)
-        mine = both ? th_draw_emit(c, du, ru, &count, &keys, &colors)
-                    : (view ? th_view_emit(c, ru, &count, &keys, &colors) : th_deposit_emit(c, du, &count, &keys, &colors));
+    if (mine == TH_OK) mine = emit(&count, &keys, &colors);
     // (exchange_counts would pass kRetryInStreamOrder on as a wish for this very pass: no emit returns it, and if one ever did it is a failure here)
     if (mine == kRetryInStreamOrder) mine = fail(TH_ERR_HIP, "the stream-ordered emit asked for the stream-ordered pass");
     if (fragments) *fragments = mine == TH_OK ? count : 0;
@@ -351,6 +355,16 @@ static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, cons
     std::vector<size_t> lo((size_t)world), hi((size_t)world);
     for (int r = 0; r < world; ++r) { lo[(size_t)r] = std::min(texels, (size_t)r * chunk); hi[(size_t)r] = std::min(texels, ((size_t)r + 1) * chunk); }
     return gather_owned(c, view, both, lo, hi);
+}
+
+// du alone: the flow pass; ru alone: the view pass; both: both passes in one - with the built-in stages
+static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
+{
+    const bool view = ru != nullptr, both = ru != nullptr && du != nullptr;
+    return sharded_pass(c, view, both, [&](uint64_t *count, void **keys, void **colors) -> th_status {
+        return both ? th_draw_emit(c, du, ru, count, keys, colors)
+                    : (view ? th_view_emit(c, ru, count, keys, colors) : th_deposit_emit(c, du, count, keys, colors));
+    }, fragments);
 }
 
 // ---- the same pass through the BINS, in its parts ------------------------------------------------------------------------------
@@ -612,6 +626,44 @@ th_status th_draw_sharded(th_context *c, const th_deposit_uniforms *du, const th
     // (no synchronize: like every other entry point the call enqueues and returns - the all-gathers of the owned ranges are
     // on the context's stream, and so is whatever the host asks for next)
     return TH_OK;
+}
+
+// th_draw_sharded with a caller's vertex stage in one pass or in both (th_drawprog.hip: th_draw_program_emit): always pass by
+// pass and always stream-ordered - two programs need not agree on where the lines are, so there is no paired rasterisation, and
+// the bins of a sharded pass carry the built-in stages alone.  A null program: the built-in stage of that pass.  Only the emit
+// of sharded_pass differs; what a program's emit can fail at on one rank alone - loading the program, growing the vertex
+// buffer, the launch, a halo row nobody holds - reaches every rank with the counts, as a built-in emit's failure does.
+th_status th_draw_program_sharded(th_context *c, th_program *flow_program, const void *flow_uniforms, uint32_t flow_bytes, const th_deposit_uniforms *du,
+                                  th_program *view_program, const void *view_uniforms, uint32_t view_bytes, const th_render_uniforms *ru,
+                                  uint64_t *fragments, uint64_t *view_fragments)
+{
+    if (th_status s = use(c)) return s;
+    TH_REQUIRE(flow_program || view_program, "th_draw_program_sharded without a program: th_draw_sharded draws with the built-in stages");
+    if (flow_program) { if (th_status s = program_run_args(flow_program, kDrawProgram, "th_draw_program_sharded", flow_uniforms, flow_bytes)) return s; }
+    else TH_REQUIRE(du, "null uniforms: without a flow program the flow pass is the built-in stage's");
+    if (view_program) if (th_status s = program_run_args(view_program, kDrawProgram, "th_draw_program_sharded", view_uniforms, view_bytes)) return s;
+    TH_REQUIRE(c->comm, "th_draw_program_sharded needs the job's communicator (th_comm_init)");
+    TH_REQUIRE(c->comm_world <= 32, "the owners' merge handles up to 32 ranks");
+    if (th_status s = texels_fit_keys(c, "target")) return s;          // (the same on every rank: a host error, not a rank-local one)
+    const int world = c->comm_world;
+    const bool view = view_program != nullptr || ru != nullptr;
+    if (fragments) *fragments = 0;
+    if (view_fragments) *view_fragments = 0;
+    c->last_draw.sent_bytes = c->last_draw.received_bytes = 0;
+    if (th_status s = sharded_draw_fixed(c, view)) return s;
+    // the neighbours' edge rows, always: which rows a program's lines read is the stream's business, as for the built-in stages
+    c->halo_lo = c->halo_hi = nullptr;
+    if (world > 1) if (th_status s = halo_exchange_stream(c)) return s;
+    c->dep_owners = (uint32_t)world;
+    if (th_status s = sharded_pass(c, false, false, [&](uint64_t *count, void **keys, void **colors) -> th_status {
+            return flow_program ? th_draw_program_emit(c, flow_program, flow_uniforms, flow_bytes, TH_PASS_FLOW, count, keys, colors)
+                                : th_deposit_emit(c, du, count, keys, colors);
+        }, fragments)) return s;
+    if (!view) return TH_OK;
+    return sharded_pass(c, true, false, [&](uint64_t *count, void **keys, void **colors) -> th_status {
+        return view_program ? th_draw_program_emit(c, view_program, view_uniforms, view_bytes, TH_PASS_VIEW, count, keys, colors)
+                            : th_view_emit(c, ru, count, keys, colors);
+    }, view_fragments);
 }
 
 // ---- one process per GPU: the communicator of the job's ranks and the path's collective (th_comm.hip) --------------------

@@ -236,6 +236,30 @@ def merge_view_fragments(tendrils, keys, colors):
                    C.c_uint64(keys.numel()))
 
 
+def _program_block(program, uniforms):
+    """(program handle, byref of its packed uniform block or None, the block's size) - Tendrils._draw_program's arguments"""
+    from .particles import DrawProgram
+    if not isinstance(program, DrawProgram) or not program.handle:
+        raise TypeError("draw: %r is no compiled DrawProgram" % (program,))
+    block = program.pack(uniforms)
+    return program.handle, block, (None if block is None else C.byref(block)), (0 if block is None else C.sizeof(block))
+
+
+def emit_program_fragments(tendrils, program, which, uniforms):
+    """th_draw_program_emit on this rank's context -> (keys int64[n], colors float32[n, 4]) views (or empty tensors): the
+    fragments of this band's lines with `program` (a DrawProgram) as the vertex stage of pass `which` (TH_PASS_FLOW: merge
+    with merge_fragments; TH_PASS_VIEW: with merge_view_fragments), parted by owner like the built-in stages'.  `uniforms`:
+    the dict the program's block is packed from (Tendrils.draw_program_uniforms())."""
+    import torch
+    from . import _capi
+    handle, _block, ref, size = _program_block(program, uniforms)
+    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
+    _capi.call("th_draw_program_emit", tendrils.particles._ctx, handle, ref, size, int(which), C.byref(n), C.byref(kp), C.byref(cp))
+    if n.value == 0:
+        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
+    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+
+
 def emit_draw_fragments(tendrils):
     """th_draw_emit -> (keys int64[n], colors float32[n, 8]): both passes' fragments of this band's lines in one - the flow
     pass's varying and the view pass's colour side by side -, parted by owner.  Needs both passes to draw with one line width."""
@@ -339,16 +363,10 @@ def _gather_owned(dist, plane, texels):
     torch.cuda.synchronize()
 
 
-def draw_sharded(dist, tendrils, view=False):
-    """Tendrils.draw() for a row-band shard of a torch.distributed job (backend nccl = RCCL): the flow pass and - `view` -
-    the view pass (after the clear / fade the caller applied to its copy of the view buffer, the same on every rank).
-    One exchange step per pass: fragment all-to-all by texel owner, then an all-gather of the owned ranges."""
+def _exchange_halos(dist, tendrils):
+    """the neighbouring bands' edge rows of both state buffers into this context (set_halo)"""
     import torch
     world, rank = dist.get_world_size(), dist.get_rank()
-    fw, fh = tendrils.flow.shape
-    texels = fw * fh
-    # edge rows of both state buffers to the neighbouring bands (the fp32 row lookup of the vertex stream can land
-    # one row beside a line's own row for some texture heights)
     lo = hi = None
     if tendrils._state_format == 0 and world > 1:                # f32 ring (a packed band keeps to its own rows)
         edges = edge_rows(tendrils)                              # [2 (first, last), 2 (cur, prev), W, 4]
@@ -358,6 +376,73 @@ def draw_sharded(dist, tendrils, view=False):
         hi = every[rank + 1, 0].contiguous() if rank + 1 < world else None
         torch.cuda.synchronize()
     set_halo(tendrils, lo, hi)
+
+
+def _has_draw_program(tendrils):
+    return getattr(tendrils, "flowShader", None) is not None or getattr(tendrils, "renderShader", None) is not None
+
+
+def draw_sharded_programs(dist, tendrils, view=False):
+    """draw() of a row-band shard with tendrils.flowShader / renderShader (DrawPrograms) as the vertex stage of their passes:
+    always pass by pass - the program's emit where a shader is set, the built-in one where none is -, the exchange by
+    `dist` (a torch.distributed job) or, dist = None, by the library over its own communicator (th_draw_program_sharded;
+    needs sharding.comm_init).  Both programs get Tendrils.draw_program_uniforms(), what the unsharded draw() hands them.
+    Returns (fragments, view_fragments) of this band."""
+    from . import _capi
+    uniforms = tendrils.draw_program_uniforms()
+    flow_shader, view_shader = tendrils.flowShader, (tendrils.renderShader if view else None)
+    if dist is None:
+        none = (None, None, None, 0)
+        fp, fblock, fref, fsize = _program_block(flow_shader, uniforms) if flow_shader is not None else none
+        vp, vblock, vref, vsize = _program_block(view_shader, uniforms) if view_shader is not None else none
+        d = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
+        d.viewSize[0], d.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
+        u = tendrils.render_uniforms() if view else None
+        n, vn = C.c_uint64(0), C.c_uint64(0)
+        if fp is None and vp is None:              # (a render shader without a view pass: the built-in flow pass is all there is)
+            _capi.call("th_draw_sharded", tendrils.particles._ctx, C.byref(d), None, C.byref(n))
+            return int(n.value), 0
+        _capi.call("th_draw_program_sharded", tendrils.particles._ctx, fp, fref, fsize, C.byref(d),
+                   vp, vref, vsize, C.byref(u) if view else None, C.byref(n), C.byref(vn))
+        return int(n.value), int(vn.value)
+    world = dist.get_world_size()
+    texels = tendrils.flow.shape[0] * tendrils.flow.shape[1]
+    _exchange_halos(dist, tendrils)
+    set_owners(tendrils, world)
+    if flow_shader is not None:
+        keys, colors = emit_program_fragments(tendrils, flow_shader, _capi.TH_PASS_FLOW, uniforms)
+    else:
+        keys, colors = emit_fragments(tendrils)
+    fragments = int(keys.numel())
+    rkeys, rcolors = _exchange(dist, keys, colors, texels)
+    merge_fragments(tendrils, rkeys, rcolors)
+    _gather_owned(dist, flow_view(tendrils), texels)
+    if not view:
+        return fragments, 0
+    if view_shader is not None:
+        keys, colors = emit_program_fragments(tendrils, view_shader, _capi.TH_PASS_VIEW, uniforms)
+    else:
+        keys, colors = emit_view_fragments(tendrils)
+    view_fragments = int(keys.numel())
+    rkeys, rcolors = _exchange(dist, keys, colors, texels)
+    merge_view_fragments(tendrils, rkeys, rcolors)
+    _gather_owned(dist, view_view(tendrils), texels)
+    return fragments, view_fragments
+
+
+def draw_sharded(dist, tendrils, view=False):
+    """Tendrils.draw() for a row-band shard of a torch.distributed job (backend nccl = RCCL): the flow pass and - `view` -
+    the view pass (after the clear / fade the caller applied to its copy of the view buffer, the same on every rank).
+    One exchange step per pass: fragment all-to-all by texel owner, then an all-gather of the owned ranges.
+    With tendrils.flowShader / renderShader set: draw_sharded_programs."""
+    if _has_draw_program(tendrils):
+        return draw_sharded_programs(dist, tendrils, view)[0]
+    world = dist.get_world_size()
+    fw, fh = tendrils.flow.shape
+    texels = fw * fh
+    # edge rows of both state buffers to the neighbouring bands (the fp32 row lookup of the vertex stream can land
+    # one row beside a line's own row for some texture heights)
+    _exchange_halos(dist, tendrils)
     set_owners(tendrils, world)
     if view and same_line_widths(tendrils):
         # both passes draw the same lines: one rasterisation, one exchange of fragments carrying both varyings, two all-gathers
@@ -383,8 +468,11 @@ def draw_sharded(dist, tendrils, view=False):
 
 def draw_sharded_native(tendrils, view=False):
     """The same draw() with the exchange issued by the LIBRARY over its own communicator (th_draw_sharded; needs
-    sharding.comm_init): what a Node process per GPU calls as drawSharded - no torch.distributed in the data path."""
+    sharding.comm_init): what a Node process per GPU calls as drawSharded - no torch.distributed in the data path.
+    With tendrils.flowShader / renderShader set: th_draw_program_sharded (draw_sharded_programs)."""
     from . import _capi
+    if _has_draw_program(tendrils):
+        return draw_sharded_programs(None, tendrils, view)[0]
     d = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
     d.viewSize[0], d.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
     n = C.c_uint64(0)

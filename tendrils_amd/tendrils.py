@@ -542,6 +542,24 @@ class Tendrils:
              0 if block is None else C.sizeof(block), which, C.byref(n))
         return int(n.value)
 
+    def _sharded(self):
+        """this context is a row-band shard: of a torch.distributed job, or a band narrower than the texture"""
+        row0, rows, gh = self._band
+        return self.dist is not None or bool(rows and rows != (gh or self.state["rootNum"]))
+
+    def draw_program_uniforms(self):
+        """what draw() hands a flowShader / renderShader, on one GPU and on a row band alike (src/index.js:284-293): the state,
+        time, viewSize, viewRes, colorMapRes - and dataRes, geomRes (src/particles.js:149-155) of the WHOLE particle texture -
+        with self.uniforms["render"] on top; each program's block is packed from it by field name"""
+        p = self.particles
+        height = self._band[2] or p.shape[1]
+        whole = height != p.shape[1]
+        uniforms = dict(self.state, time=float(self.timer.time), viewSize=self.viewSize, viewRes=self.viewRes,
+                        dataRes=[p.shape[0], height] if whole else p.shape,
+                        geomRes=[p.shape[0], 2 * height] if whole else p.geomShape, colorMapRes=self.colorMap.shape)
+        uniforms.update(self.uniforms["render"])
+        return uniforms
+
     def _draw_programs(self):
         """draw() with a caller's vertex stage in one pass or both (src/index.js:278-340): the flow pass, then - with
         renderView - the clear, the fade and the view pass; each pass runs its program or, where there is none, the library's
@@ -551,9 +569,20 @@ class Tendrils:
         context would (Particles.draw_pipeline / TH_DRAW: binned where the shape and the ring allow it, else stream-ordered -
         include/tendrils_hip.h "draw programs"); through the bins a tile-sorted ring stays sorted, so step(); draw() keeps it."""
         p = self.particles
-        uniforms = dict(self.state, time=float(self.timer.time), viewSize=self.viewSize, viewRes=self.viewRes,
-                        dataRes=p.shape, geomRes=p.geomShape, colorMapRes=self.colorMap.shape)
-        uniforms.update(self.uniforms["render"])
+        uniforms = self.draw_program_uniforms()
+        if self._sharded():
+            # a row band: the passes go through the owners' exchange (sharding.draw_sharded_programs) - the host's, of a
+            # torch.distributed job, or the library's own (th_draw_program_sharded); every rank calls draw() together.  Every
+            # rank holds the whole view buffer: the bind, the clear and the fade are the same everywhere, and come first
+            from .sharding import draw_sharded_programs
+            if self.renderView:
+                self._bind_view(self.buffers[0] if self.buffers else None)
+                if self.state["autoClearView"]:
+                    self.clearView()
+                if self.state["autoFade"]:
+                    self.drawFade()
+            self.fragments, self.view_fragments = draw_sharded_programs(self.dist, self, view=self.renderView)
+            return self
         if self.flowShader is not None:
             self.fragments = self._draw_program(self.flowShader, _capi.TH_PASS_FLOW, uniforms)
         else:
