@@ -397,6 +397,64 @@ th_status th_draw_program_emit(th_context *ctx, th_program *program, const void 
                                int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev);
 /* (th_draw_program_sharded is declared beside th_draw_sharded, below: it takes the view pass's uniforms) */
 
+/* -- fragment programs: the fragment stage of a draw() pass the CALLER wrote ----------------------------------------
+ * The other half of the reference's shader pairs - flowShader: [flowVert, flowFrag], renderShader: [renderVert, renderFrag]
+ * (src/index.js:70-71, 114-120): where a per-texel effect belongs - a vignette on the flow deposit, a mask or tint looked up by
+ * window position, alpha shaped per texel.  HIP source defining one device function,
+ *     __device__ float4 th_fragment_main(const th_fragment_pass &f);   - main() of the fragment shader; returns gl_FragColor
+ * compiled exactly as a user program is (same hiprtc, same flags, same `#line 1 "<name>"`, same th_program_log()) behind a
+ * prelude of its own (tendrils_amd/csrc/th_fragment_prelude.inc) that declares:
+ *   th_fragment_pass   x, y (the window texel of the target: gl_FragCoord.xy = (x + 0.5, y + 0.5), also there as the float2
+ *                      coord), viewRes (the target's width and height), color (the varying, as the library interpolated it
+ *                      along the line's snapped endpoints: what a pass without this stage blends), pass (TH_PASS_FLOW |
+ *                      TH_PASS_VIEW), uniforms (th_uniforms<T>(f): the caller's block, up to 1024 bytes)
+ *   th_flow(f, u, v), th_flow_res(f)           texture2D(flow, (u, v)): NEAREST, CLAMP_TO_EDGE - the field as it was BEFORE this
+ *                              pass, also in a pass that draws into it (every fragment runs before anything blends)
+ *   th_colormap(f, u, v), th_colormap_res(f)   ... of the colour map; no map held: the 1 x 1 zero texture
+ * Every accessor clamps: a program that reads through them alone cannot read out of bounds.  NOT offered: the destination
+ * texel (GL has none either), `discard`, the identity or geometry of the fragment's line, th_particles - a source that names
+ * an accessor it does not have fails to compile, on the caller's own line.  A fragment that wants to leave its texel alone
+ * returns alpha 0 WITH FINITE COLOUR: the blend is dst = src * a + dst * (1 - a), and 0 * inf is NaN.
+ * The stage runs once per fragment, over the array the stream-ordered pipeline holds between its emit and its sort, in place;
+ * everything before it (the vertex stage, the raster) and behind it (the sort, the blend in primitive order) is the code of a
+ * pass without it.  A pass with a fragment stage is therefore ALWAYS stream-ordered, whatever th_draw_pipeline / TH_DRAW say:
+ * the ring goes to texel order and is held there as after any stream-ordered pass (a packed ring is read as the library's own
+ * stage reads it, through f32 copies under a vertex program), its content is untouched; the policy's frame count does not see the
+ * pass; th_draw_query reports TH_DRAW_STREAM and the pass's fragments; nothing of the pass is reused by the next one, nor of
+ * the one before by it.  Not built: the stage in the binned pipeline, in th_draw's one-rasterisation form, and in the
+ * library-issued exchanges (th_draw_sharded, th_draw_program_sharded).
+ *  th_fragment_program_compile    as th_program_compile (a source without th_fragment_main does not compile).  The handle is a
+ *                      th_program of a fifth kind: th_program_destroy / _query / _log serve all five (_query: th_fragment_kernel);
+ *                      th_program_run, th_screen_run, th_draw_program_run / _emit / _sharded and th_step_program_run refuse it, and
+ *                      the slots of th_draw_stages refuse each other's and every other kind (TH_ERR_INVALID, both kinds named,
+ *                      nothing launched).
+ *  th_draw_stages      the stages of one pass: `vertex` a draw program with its block, or NULL - the library's vertex stage, with
+ *                      `builtin` its uniforms (a th_deposit_uniforms for TH_PASS_FLOW, a th_render_uniforms for TH_PASS_VIEW);
+ *                      `fragment` a fragment program with its block, or NULL: gl_FragColor = color.
+ *  th_draw_stages_run  one pass of draw() with these stages: th_draw_program_run (vertex set) or th_flow_deposit / th_view_draw
+ *                      (vertex NULL) with the fragment stage in; with fragment NULL it IS th_draw_program_run.  *fragments
+ *                      (optional): the fragments blended.  A pass without fragments launches no fragment kernel.  th_kernel_timing
+ *                      puts an event pair around the fragment kernel (and, as ever, the vertex kernel of a draw program).  On a
+ *                      row-band shard: TH_ERR_UNSUPPORTED, nothing launched.
+ *  th_draw_stages_emit the pass of a ROW BAND with these stages: th_draw_program_emit (vertex set) or th_deposit_emit /
+ *                      th_view_emit (vertex NULL) with the fragment stage in - it runs on this band's fragments before they are
+ *                      parted by owner; x, y are the texel of the WHOLE target.  *count, *keys_dev, *colors_dev as th_deposit_emit
+ *                      hands them out; th_deposit_merge (TH_PASS_FLOW) / th_view_merge (TH_PASS_VIEW) blend them: for the owned
+ *                      texels th_draw_stages_run of the unsharded state bit for bit.  A whole-texture context is the band of all
+ *                      rows.  Errors of the call it stands for, and: null outputs.
+ *  TH_ERR_INVALID from both, nothing launched: both stages NULL (th_flow_deposit / th_view_draw, th_deposit_emit / th_view_emit
+ *                      are the calls), a program of another kind in either slot, more than 1024 uniform bytes in either block,
+ *                      null uniforms with a size, a size without a program, vertex NULL without `builtin`, an unknown pass, null
+ *                      stages. */
+typedef struct th_draw_stages {
+    th_program *vertex;   const void *vertex_uniforms;   uint32_t vertex_uniform_bytes;     /* a draw program, or NULL: the library's stage with `builtin` */
+    th_program *fragment; const void *fragment_uniforms; uint32_t fragment_uniform_bytes;   /* a fragment program, or NULL: gl_FragColor = color */
+    const void *builtin;  /* vertex == NULL: th_deposit_uniforms (TH_PASS_FLOW) / th_render_uniforms (TH_PASS_VIEW) */
+} th_draw_stages;
+th_status th_fragment_program_compile(const char *source, const char *name, th_program **out);
+th_status th_draw_stages_run(th_context *ctx, const th_draw_stages *stages, int32_t pass /* TH_PASS_FLOW | TH_PASS_VIEW */, uint64_t *fragments);
+th_status th_draw_stages_emit(th_context *ctx, const th_draw_stages *stages, int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev);
+
 /* -- step programs: n steps of an integrator the CALLER wrote, fused in one launch -----------------------------------
  * new Tendrils(gl, { logicShader }) takes a caller's integrator (src/index.js:70, 107-113).  As a state program (above) it
  * runs, but one launch per step; a step program is the same pass under ONE restriction, which is what th_step_n's fusion rests

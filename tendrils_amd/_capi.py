@@ -109,6 +109,13 @@ class ProgramInfo(C.Structure):
                 ("code_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DrawStages(C.Structure):
+    """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
+    _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
+                ("fragment", C.c_void_p), ("fragment_uniforms", C.c_void_p), ("fragment_uniform_bytes", C.c_uint32),
+                ("builtin", C.c_void_p)]
+
+
 class FlowLineUniforms(C.Structure):
     _fields_ = [("speed", C.c_float), ("rad", C.c_float), ("crestShape", C.c_float), ("speedLimit", C.c_float),
                 ("viewSize", C.c_float * 2)]
@@ -240,6 +247,10 @@ PROTOTYPES = {
     "th_draw_program_sharded": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(DepositUniforms),
                                             C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RenderUniforms),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "th_fragment_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "th_draw_stages_run": (C.c_int32, [_ctx, C.POINTER(DrawStages), C.c_int32, C.POINTER(C.c_uint64)]),
+    "th_draw_stages_emit": (C.c_int32, [_ctx, C.POINTER(DrawStages), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p)]),
     "th_step_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_step_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32]),
     "th_step_program_view_size": (C.c_int32, [_ctx, C.POINTER(C.c_float)]),

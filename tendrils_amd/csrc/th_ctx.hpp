@@ -80,7 +80,7 @@ struct th_options {
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
 // anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
 namespace thi {
-enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile
+enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3, kFragmentProgram = 4 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile / th_fragment_program_compile
 }
 struct th_program {
     thi::ProgramKind kind = thi::kStateProgram;
@@ -97,15 +97,28 @@ namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel
+    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel / th_fragment_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
-    hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines)
+    hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines); a fragment
+                                         // program's second: th_fragment_band_kernel (the fragments of an emit, under their 64-bit keys)
     hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
     ~ProgramModule() { reset(); }
     void reset();                        // th_program.hip
+};
+}  // namespace thi
+
+// A caller's fragment stage as one draw call carries it (th_fragprog.hip: th_draw_stages_run / _emit): on the context for the
+// duration of the call, so that the pass underneath - whichever entry point prepares it - finds it where its fragments lie
+// (deposit_run, emit_parted) without a field more in th::DepositParams.
+namespace thi {
+struct FragmentStage {
+    ProgramModule *module;
+    const void *uniforms;
+    uint32_t uniform_bytes;
+    int32_t pass;
 };
 }  // namespace thi
 
@@ -230,6 +243,7 @@ struct th_context {
     DevBuf<float4> edge_rows;            // th_draw_sharded through the bins: this band's edge rows gathered into texel order (4 x W)
     int draw_pipeline = TH_DRAW_AUTO;    // th_draw_pipeline
     th_draw_info last_draw{};            // th_draw_query
+    const thi::FragmentStage *frag_stage = nullptr;      // the caller's fragment stage of the draw call under way (th_fragprog.hip), else null
     long long draws = 0;                          // (`draws` counts frames: the passes drawn at one total_steps share a count ...
     long long draw_frame_step = -1;               //  ... and a pipeline: th_draw.hip, draw_uses_bins)
     int frame_bins = -1;
@@ -428,6 +442,10 @@ th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *re
 template <class Args> th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, ProgramKernArgs<Args> &k) { return program_launch(c, fn, lanes, &k, sizeof k); }
 // ... on a grid of the caller's (256-lane workgroups): a step program over tile-sorted slots takes the built-in fused launch's
 th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes);
+// ---- th_fragprog.hip -------------------------------------------------------------------------------------------------
+// c->frag_stage over the `total` fragments (not 0) the scatter of the (prepared) pass `p` has just written: p.keys64 / p.keys and
+// p.colors, fragment i in place i of both - before anything sorts or parts them
+th_status fragment_stage_run(th_context *c, const th::DepositParams &p, uint32_t total);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
 // an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format

@@ -92,6 +92,7 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
     TH_REQUIRE(u, "null uniforms");
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
     if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
+    if (c->frag_stage) want_bins = false;       // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count)
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -398,7 +399,8 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragme
     // Same state, same view, same resolution as the pass before (the view pass after the flow pass of one draw()): the
     // lines cover the same texels in the same order - counts, offsets, records and the sorted order of the fragments are
     // still there, only the varyings differ.  (TH_DRAW_REUSE=0: every pass on its own.)
-    const bool reuse = c->opt.draw_reuse && p.mode != 2 && c->drawn.valid && !c->drawn.binned && c->drawn.view_x == p.view_x && c->drawn.view_y == p.view_y &&
+    // (A caller's fragment stage runs over the array the scatter writes, key beside varying: such a pass reuses nothing.)
+    const bool reuse = c->opt.draw_reuse && !c->frag_stage && p.mode != 2 && c->drawn.valid && !c->drawn.binned && c->drawn.view_x == p.view_x && c->drawn.view_y == p.view_y &&
                        c->drawn.line_half == p.line_half;
     uint32_t total = 0;
     if (reuse) total = c->drawn.total;
@@ -421,6 +423,7 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragme
         const int bits = th::deposit_key_bits(p);
         if (th_status s = deposit_temp(c, th::radix_sort_temp_bytes(total, 0, bits))) return s;
         th::launch_deposit_scatter(p, c->stream);
+        if (c->frag_stage) if (th_status s = fragment_stage_run(c, p, total)) return s;
         const bool in_a = th::launch_radix_sort_u32(p.keys, p.slots, p.keys_sorted, p.slots_sorted, total, 0, bits, c->dep_temp, true, c->stream) == 0;
         if (in_a) { p.keys_sorted = c->dep_u32[0]; p.slots_sorted = c->dep_u32[1]; }        // an even number of passes ends in the (a) buffers
         c->drawn.valid = true; c->drawn.binned = false; c->drawn.view_x = p.view_x; c->drawn.view_y = p.view_y; c->drawn.line_half = p.line_half; c->drawn.total = total; c->drawn.sorted_in_a = in_a;

@@ -1,0 +1,122 @@
+R"TH_PRELUDE(// th_fragment_prelude.inc - what th_fragment_program_compile puts in front of a fragment program, after the text of
+// th_taps.inc (th_fragprog.hip embeds this file as text: the first and the last line make it one raw string literal).
+// Self-contained: no project header, only what hiprtc's built-in headers give.  Compiled with the product's arithmetic flags
+// (-ffp-contract=off: a*b+c stays two rounded fp32 operations, as in the reference's shaders).
+//
+// A fragment program defines ONE device function,
+//     __device__ float4 th_fragment_main(const th_fragment_pass &f);
+// main() of the fragment shader of one pass of draw() (the second of renderShader: [vert, frag] / flowShader: [vert, frag]): it
+// is called once per fragment the pass's lines cover and returns gl_FragColor, which the library blends into the target in
+// primitive order (SRC_ALPHA / ONE_MINUS_SRC_ALPHA) as it blends the varying of a pass without this stage.  There is no
+// destination texel to read (GL has none either), no `discard`, nothing of the line the fragment belongs to and nothing of the
+// particles: a source that names th_particles does not compile.  A fragment that wants to leave its texel alone returns
+// alpha 0 WITH FINITE COLOUR: the blend is dst = src * a + dst * (1 - a), and 0 * inf or 0 * NaN is NaN.
+//
+// th_fragment_args is the launch record th_fragprog.hip fills (same layout there; the static_asserts pin the sizes).
+#define TH_PASS_FLOW 0
+#define TH_PASS_VIEW 1
+struct th_fragment_args {
+    const void *keys;            // per fragment: th_fragment_kernel - 32-bit texel keys; th_fragment_band_kernel - 64-bit
+                                 // owner << 56 | texel << 32 | stream index
+    float4 *colors;              // per fragment, in the keys' order: the varying in, gl_FragColor out
+    const float4 *flow;          // fw x fh, as it was before this pass
+    const float4 *colormap;      // cw x ch (null: none is held)
+    unsigned total;              // fragments of the pass
+    int fw, fh, cw, ch;          // (the target, flow field or view image, is fw x fh)
+    int pass;
+    unsigned div_mul, div_shift; // texel / fw for every texel < 2^32: m = floor(2^32 (2^l - fw) / fw) + 1 with l = ceil(log2 fw),
+                                 // t = mulhi(m, n), q = (t + ((n - t) >> min(l, 1))) >> max(l - 1, 0); div_shift = sh1 | sh2 << 8
+};
+static_assert(sizeof(th_fragment_args) == 64, "th_fragment_args: layout shared with th_fragprog.hip");
+struct __attribute__((aligned(16))) th_program_uniform_block { unsigned char bytes[1024]; };
+
+struct th_fragment_pass {
+    unsigned x, y;               // the window texel of the target: column, row (row 0 is the target's first row)
+    float2 coord;                // gl_FragCoord.xy: (x + 0.5, y + 0.5)
+    float2 viewRes;              // the target's width and height
+    float4 color;                // the varying, as the library interpolated it along the line's snapped endpoints
+    int pass;                    // TH_PASS_FLOW | TH_PASS_VIEW
+    const void *uniforms;        // the caller's uniform block (th_uniforms<T>(f))
+    const th_fragment_args *args;
+};
+
+__device__ float4 th_fragment_main(const th_fragment_pass &f);
+
+// the caller's uniform block as its own struct (the same struct, field for field, as the host packs)
+template <class T> __device__ __forceinline__ const T &th_uniforms(const th_fragment_pass &f)
+{
+    static_assert(sizeof(T) <= sizeof(th_program_uniform_block), "a uniform block holds at most 1024 bytes");
+    return *static_cast<const T *>(f.uniforms);
+}
+
+// texture2D(flow, (u, v)) / texture2D(colorMap, (u, v)): NEAREST, CLAMP_TO_EDGE, always inside the texture (th_taps.inc).  The
+// flow is the field as it was BEFORE this pass, also in a pass that draws into it: every fragment has run before anything blends.
+__device__ __forceinline__ float4 th_flow(const th_fragment_pass &f, float u, float v)
+{
+    const th_fragment_args &a = *f.args;
+    return a.flow[(size_t)th_tap_nearest(v, a.fh) * a.fw + th_tap_nearest(u, a.fw)];
+}
+__device__ __forceinline__ float2 th_flow_res(const th_fragment_pass &f) { return make_float2((float)f.args->fw, (float)f.args->fh); }
+// no colour map held: the 1 x 1 zero texture, as the built-in view stage reads it
+__device__ __forceinline__ float4 th_colormap(const th_fragment_pass &f, float u, float v)
+{
+    const th_fragment_args &a = *f.args;
+    if (!a.colormap) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return a.colormap[(size_t)th_tap_nearest(v, a.ch) * a.cw + th_tap_nearest(u, a.cw)];
+}
+__device__ __forceinline__ float2 th_colormap_res(const th_fragment_pass &f)
+{
+    const th_fragment_args &a = *f.args;
+    return a.colormap ? make_float2((float)a.cw, (float)a.ch) : make_float2(1.0f, 1.0f);
+}
+
+// One fragment: its texel split into (x, y) with the record's multiplier (five integer operations, no division), ONE 16-byte
+// load of colors[at], the program, ONE 16-byte store back.
+typedef float th_float4_load __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void th_fragment_lane(th_fragment_pass &f, const th_fragment_args &a, unsigned texel, unsigned at)
+{
+    const unsigned t = __umulhi(a.div_mul, texel);
+    const unsigned y = (t + ((texel - t) >> (a.div_shift & 0xffu))) >> (a.div_shift >> 8);
+    const unsigned x = texel - y * (unsigned)a.fw;
+    f.x = x; f.y = y;
+    f.coord = make_float2((float)x + 0.5f, (float)y + 0.5f);
+    th_float4_load *slot = reinterpret_cast<th_float4_load *>(a.colors + at);
+    const th_float4_load c = *slot;
+    f.color = make_float4(c.x, c.y, c.z, c.w);
+    const float4 o = th_fragment_main(f);
+    th_float4_load out;
+    out.x = o.x; out.y = o.y; out.z = o.z; out.w = o.w;
+    *slot = out;
+}
+__device__ __forceinline__ th_fragment_pass th_fragment_pass_of(const th_fragment_args &a, const th_program_uniform_block &u)
+{
+    th_fragment_pass f;
+    f.viewRes = make_float2((float)a.fw, (float)a.fh);
+    f.pass = a.pass;
+    f.uniforms = u.bytes;
+    f.args = &a;
+    return f;
+}
+
+// The harness: one lane per fragment of the pass, 256-thread workgroups, grid-stride (total < 2^31).  A wave reads 256 bytes of
+// keys and 1 KiB of varyings, contiguous, and writes that KiB back where it read it; the record is the kernel's argument (scalar
+// loads).  No LDS, no atomics; nothing is written but colors[at], at < total.
+extern "C" __global__ __launch_bounds__(256) void th_fragment_kernel(const th_fragment_args a, const th_program_uniform_block u)
+{
+    th_fragment_pass f = th_fragment_pass_of(a, u);
+    const unsigned *keys = static_cast<const unsigned *>(a.keys);
+    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
+        th_fragment_lane(f, a, keys[at], at);
+}
+
+// The same stage over the fragments of an emit (th_draw_stages_emit), under their 64-bit keys: the texel is bits 32 .. 55 - of
+// the WHOLE target, whatever rows of the particle texture the context holds.  An entry point of its own and no switch in one
+// kernel: each loop loads keys of one width, and neither carries the other's registers.
+extern "C" __global__ __launch_bounds__(256) void th_fragment_band_kernel(const th_fragment_args a, const th_program_uniform_block u)
+{
+    th_fragment_pass f = th_fragment_pass_of(a, u);
+    const unsigned long long *keys = static_cast<const unsigned long long *>(a.keys);
+    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
+        th_fragment_lane(f, a, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
+}
+)TH_PRELUDE"

@@ -1,0 +1,157 @@
+// th_fragprog.hip - fragment programs: a caller's fragment stage in one pass of draw().  The second half of the reference's
+// shader pairs, new Tendrils(gl, { flowShader: [vert, frag], renderShader: [vert, frag] }) (src/index.js:70-71, 114-120);
+// th_drawprog.hip has the first.  The caller's fragment shader is HIP source for one device function, th_fragment_main
+// (th_fragment_prelude.inc), compiled for gfx950 at run time like the other kinds (th_program.hip: program_compile).  It runs
+// once per fragment, in place over the array the stream-ordered pipeline holds between its emit and its sort - texel key beside
+// interpolated varying -, so nothing of the raster or blend kernels knows of it: the entry points here put the stage on the
+// context for the duration of one call (c->frag_stage), run the pass through the entry point that draws it without the stage,
+// and deposit_run (th_draw.hip) / emit_parted (th_shard.hip) call fragment_stage_run where the fragments lie.
+#include "th_ctx.hpp"
+
+using namespace thi;
+
+namespace {
+
+// the tap rules as text (th_taps.inc: the library's kernels compile the same lines), then the prelude
+#define TH_TAPS(...) #__VA_ARGS__
+const char kTaps[] =
+#include "th_taps.inc"
+    ;
+#undef TH_TAPS
+const char kPrelude[] =
+#include "th_fragment_prelude.inc"
+    ;
+
+// the launch record (th_fragment_prelude.inc: th_fragment_args, th_program_uniform_block - the same layout)
+struct FragmentArgs {
+    const void *keys;
+    float4 *colors;
+    const float4 *flow, *colormap;
+    uint32_t total;
+    int32_t fw, fh, cw, ch;
+    int32_t pass;
+    uint32_t div_mul, div_shift;
+};
+using KernArgs = ProgramKernArgs<FragmentArgs>;
+static_assert(sizeof(FragmentArgs) == 64 && offsetof(FragmentArgs, total) == 32 && offsetof(FragmentArgs, div_mul) == 56 && offsetof(KernArgs, u) == 64 &&
+              sizeof(KernArgs) == 64 + kUniformBytes, "launch record: layout shared with th_fragment_prelude.inc");
+
+// n / d for every 32-bit n by one multiplication (Granlund & Montgomery 1994, the round-up form): the multiplier and both shifts
+void divide_by(uint32_t d, uint32_t &mul, uint32_t &shifts)
+{
+    uint32_t l = 0;
+    while (((uint64_t)1 << l) < d) ++l;
+    mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << l) - d)) / d + 1u);
+    shifts = (l < 1u ? l : 1u) | ((l > 1u ? l - 1u : 0u) << 8);
+}
+
+// a slot of th_draw_stages: null, or a program of `kind` with its block
+th_status stage_args(const th_program *prog, ProgramKind kind, const char *entry, const char *slot, const void *uniforms, uint32_t uniform_bytes)
+{
+    if (!prog) {
+        TH_REQUIRE(uniform_bytes == 0, "%s: %u %s uniform bytes and no %s program", entry, uniform_bytes, slot, slot);
+        return TH_OK;
+    }
+    TH_REQUIRE(prog->kind == kind, "%s takes a %s as its %s stage: '%s' is a %s", entry, program_kind_name(kind), slot, prog->name.c_str(), program_kind_name(prog->kind));
+    TH_REQUIRE(uniform_bytes <= kUniformBytes, "%s uniform block of %u bytes (at most %u)", slot, uniform_bytes, kUniformBytes);
+    TH_REQUIRE(uniforms || uniform_bytes == 0, "null %s uniforms", slot);
+    return TH_OK;
+}
+
+// what both entry points refuse before anything is launched
+th_status stages_args(const th_context *c, const th_draw_stages *s, int32_t pass, const char *entry, const char *builtin_calls)
+{
+    TH_REQUIRE(c, "null context");
+    TH_REQUIRE(s, "null stages");
+    TH_REQUIRE(s->vertex || s->fragment, "%s with neither a vertex nor a fragment program: the library's own stages are %s", entry, builtin_calls);
+    if (th_status st = stage_args(s->vertex, kDrawProgram, entry, "vertex", s->vertex_uniforms, s->vertex_uniform_bytes)) return st;
+    if (th_status st = stage_args(s->fragment, kFragmentProgram, entry, "fragment", s->fragment_uniforms, s->fragment_uniform_bytes)) return st;
+    TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
+    TH_REQUIRE(s->vertex || s->builtin, "%s without a vertex program needs `builtin`: the %s of the library's vertex stage", entry,
+               pass == TH_PASS_VIEW ? "th_render_uniforms" : "th_deposit_uniforms");
+    return TH_OK;
+}
+
+// the stage on the context while one call runs
+struct StageScope {
+    th_context *c;
+    FragmentStage stage{};
+    explicit StageScope(th_context *ctx) : c(ctx) {}
+    th_status begin(const th_draw_stages *s, int32_t pass)
+    {
+        if (!s->fragment) return TH_OK;
+        if (th_status st = program_loaded(c, s->fragment, &stage.module)) return st;
+        stage.uniforms = s->fragment_uniforms; stage.uniform_bytes = s->fragment_uniform_bytes; stage.pass = pass;
+        c->frag_stage = &stage;
+        return TH_OK;
+    }
+    ~StageScope() { c->frag_stage = nullptr; }
+};
+
+}  // namespace
+
+th_status thi::fragment_stage_run(th_context *c, const th::DepositParams &p, uint32_t total)
+{
+    const FragmentStage &stage = *c->frag_stage;
+    KernArgs k{};
+    FragmentArgs &a = k.a;
+    a.keys = p.keys64 ? static_cast<const void *>(p.keys64) : static_cast<const void *>(p.keys);
+    a.colors = p.colors;
+    a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
+    a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
+    a.total = total;
+    a.pass = stage.pass;
+    divide_by((uint32_t)c->fw, a.div_mul, a.div_shift);
+    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+    LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
+    if (th_status s = timer.begin(c)) return s;
+    if (th_status s = program_launch(c, p.keys64 ? stage.module->fn_band : stage.module->fn, total, k)) return s;
+    return timer.end(c);
+}
+
+extern "C" {
+
+th_status th_fragment_program_compile(const char *source, const char *name, th_program **out)
+{
+    return program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
+}
+
+// One pass of draw() with the stages of `s`: the entry point that draws the pass without a fragment stage - th_draw_program_run
+// with a vertex program, th_flow_deposit / th_view_draw with the library's vertex stage - runs it, and finds the fragment stage
+// on the context: deposit_prepare then leaves the bins and the frame's pipeline count alone, deposit_run reuses nothing and calls
+// the stage between its scatter and its sort.  What such a pass leaves of its lines (c->drawn) is no other pass's to reuse.
+th_status th_draw_stages_run(th_context *c, const th_draw_stages *s, int32_t pass, uint64_t *fragments)
+{
+    if (th_status st = stages_args(c, s, pass, "th_draw_stages_run", "th_flow_deposit / th_view_draw")) return st;
+    if (th_status st = use(c, pass == TH_PASS_VIEW)) return st;
+    if (th_status st = refuse_band(c, "draw stages", "a band's pass goes through th_draw_stages_emit and the owners' exchange")) return st;
+    StageScope scope(c);
+    if (th_status st = scope.begin(s, pass)) return st;
+    if (s->fragment) c->drawn.valid = false;
+    const th_status ran = s->vertex         ? th_draw_program_run(c, s->vertex, s->vertex_uniforms, s->vertex_uniform_bytes, pass, fragments)
+                        : pass == TH_PASS_VIEW ? th_view_draw(c, static_cast<const th_render_uniforms *>(s->builtin), fragments)
+                                               : th_flow_deposit(c, static_cast<const th_deposit_uniforms *>(s->builtin), fragments);
+    if (s->fragment) c->drawn.valid = false;
+    return ran;
+}
+
+// ... and of a row band (a whole-texture context: the band of all rows): th_draw_program_emit / th_deposit_emit / th_view_emit
+// with the stage on the context - emit_parted calls it behind its scatter, before it parts the fragments by owner.
+th_status th_draw_stages_emit(th_context *c, const th_draw_stages *s, int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev)
+{
+    if (th_status st = stages_args(c, s, pass, "th_draw_stages_emit", "th_deposit_emit / th_view_emit")) return st;
+    TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
+    if (th_status st = use(c, pass == TH_PASS_VIEW)) return st;
+    *count = 0; *keys_dev = nullptr; *colors_dev = nullptr;
+    StageScope scope(c);
+    if (th_status st = scope.begin(s, pass)) return st;
+    if (s->fragment) c->drawn.valid = false;
+    const th_status emitted = s->vertex      ? th_draw_program_emit(c, s->vertex, s->vertex_uniforms, s->vertex_uniform_bytes, pass, count, keys_dev, colors_dev)
+                            : pass == TH_PASS_VIEW ? th_view_emit(c, static_cast<const th_render_uniforms *>(s->builtin), count, keys_dev, colors_dev)
+                                                   : th_deposit_emit(c, static_cast<const th_deposit_uniforms *>(s->builtin), count, keys_dev, colors_dev);
+    if (emitted == TH_OK) { c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = *count; c->last_draw.crowded_fragments = 0; }
+    if (s->fragment) c->drawn.valid = false;
+    return emitted;
+}
+
+}  // extern "C"

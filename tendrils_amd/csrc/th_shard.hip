@@ -27,6 +27,8 @@ th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void
     p.owners = c->dep_owners;
     p.owner_chunk = (uint32_t)(((uint64_t)c->fw * c->fh + p.owners - 1u) / p.owners);
     th::launch_deposit_scatter(p, c->stream);
+    // (a caller's fragment stage, th_draw_stages_emit: here keys64[i] and colors[i] still name the same fragment)
+    if (c->frag_stage) if (th_status s = fragment_stage_run(c, p, total)) return s;
     *keys_dev = c->dep_u64[0]; *colors_dev = c->dep_colors;
     if (p.owners > 1u) {
         // the fragment array is in this band's stream order: ONE stable pass on the owner bits parts it by destination

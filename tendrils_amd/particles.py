@@ -107,6 +107,54 @@ class DrawProgram(Program):
     COMPILE, SOURCE_KIND = "th_draw_program_compile", "draw"
 
 
+class FragmentProgram(Program):
+    """A fragment program (include/tendrils_hip.h "fragment programs"): from_source() takes HIP source defining
+    `__device__ float4 th_fragment_main(const th_fragment_pass &f)` - the fragment shader of one pass of draw(), called once per
+    fragment with its window texel and the interpolated varying; what it returns is blended - and is otherwise
+    Program.from_source: compiled once, for gfx950, no GPU needed; TendrilsHipError with the compiler's output; pack(), query()
+    and dispose() as there.  Tendrils runs it as the second of a flowShader / renderShader pair (or alone: with the library's
+    vertex stage); such a pass is always stream-ordered."""
+    COMPILE, SOURCE_KIND = "th_fragment_program_compile", "fragment"
+
+
+def shader_stages(shader):
+    """(vertex, fragment) of a flowShader / renderShader: None, a DrawProgram (the vertex stage), a FragmentProgram (the fragment
+    stage, with the library's vertex stage) or the reference's pair [vert, frag] (src/index.js:70-71), either of which may be None"""
+    if shader is None:
+        return None, None
+    if isinstance(shader, FragmentProgram):
+        return None, shader
+    if isinstance(shader, (tuple, list)):
+        if len(shader) != 2:
+            raise TypeError("draw: a shader pair is (vertex, fragment): %r" % (shader,))
+        vertex, fragment = shader
+    else:
+        vertex, fragment = shader, None
+    if vertex is not None and (not isinstance(vertex, DrawProgram) or not vertex.handle):
+        raise TypeError("draw: %r is no compiled DrawProgram" % (vertex,))
+    if fragment is not None and (not isinstance(fragment, FragmentProgram) or not fragment.handle):
+        raise TypeError("draw: %r is no compiled FragmentProgram" % (fragment,))
+    return vertex, fragment
+
+
+def draw_stages(vertex, fragment, uniforms, builtin):
+    """(th_draw_stages, what it points to - to be kept alive across the call) of one pass: each program's block packed by field
+    name from `uniforms`; `builtin`: the library's vertex-stage uniforms (a ctypes structure), read when vertex is None"""
+    stages, keep = _capi.DrawStages(), [builtin]
+    for slot, program in (("vertex", vertex), ("fragment", fragment)):
+        if program is None:
+            continue
+        block = program.pack(uniforms)
+        keep.append(block)
+        setattr(stages, slot, program.handle)
+        if block is not None:
+            setattr(stages, slot + "_uniforms", C.cast(C.pointer(block), C.c_void_p))
+            setattr(stages, slot + "_uniform_bytes", C.sizeof(block))
+    if vertex is None:
+        stages.builtin = C.cast(C.pointer(builtin), C.c_void_p)
+    return stages, keep
+
+
 class StepProgram(Program):
     """A step program (include/tendrils_hip.h "step programs"): from_source() takes HIP source defining
     `__device__ float4 th_step_main(const th_step_pass &s)` - one step of one particle's integrator, which reads nothing of the

@@ -260,6 +260,23 @@ def emit_program_fragments(tendrils, program, which, uniforms):
     return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
 
 
+def emit_stage_fragments(tendrils, vertex, fragment, which, uniforms):
+    """th_draw_stages_emit on this rank's context -> (keys int64[n], colors float32[n, 4]) views (or empty tensors): the
+    fragments of this band's lines with `fragment` (a FragmentProgram) run over them, behind `vertex` (a DrawProgram; None: the
+    library's vertex stage of pass `which`), parted by owner; merged like every other pass's (merge_fragments /
+    merge_view_fragments)."""
+    import torch
+    from . import _capi
+    from .particles import draw_stages
+    builtin = tendrils.render_uniforms() if which == _capi.TH_PASS_VIEW else tendrils.deposit_uniforms()
+    stages, _keep = draw_stages(vertex, fragment, uniforms, builtin)
+    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
+    _capi.call("th_draw_stages_emit", tendrils.particles._ctx, C.byref(stages), int(which), C.byref(n), C.byref(kp), C.byref(cp))
+    if n.value == 0:
+        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
+    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+
+
 def emit_draw_fragments(tendrils):
     """th_draw_emit -> (keys int64[n], colors float32[n, 8]): both passes' fragments of this band's lines in one - the flow
     pass's varying and the view pass's colour side by side -, parted by owner.  Needs both passes to draw with one line width."""
@@ -379,19 +396,26 @@ def _exchange_halos(dist, tendrils):
 
 
 def _has_draw_program(tendrils):
-    return getattr(tendrils, "flowShader", None) is not None or getattr(tendrils, "renderShader", None) is not None
+    from .particles import shader_stages
+    return any(stage is not None for which in ("flowShader", "renderShader") for stage in shader_stages(getattr(tendrils, which, None)))
 
 
 def draw_sharded_programs(dist, tendrils, view=False):
-    """draw() of a row-band shard with tendrils.flowShader / renderShader (DrawPrograms) as the vertex stage of their passes:
+    """draw() of a row-band shard with tendrils.flowShader / renderShader as the stages of their passes (a DrawProgram: the vertex
+    stage; a FragmentProgram or a pair with one: only with `dist`, the host's exchange, around th_draw_stages_emit):
     always pass by pass - the program's emit where a shader is set, the built-in one where none is -, the exchange by
     `dist` (a torch.distributed job) or, dist = None, by the library over its own communicator (th_draw_program_sharded;
     needs sharding.comm_init).  Both programs get Tendrils.draw_program_uniforms(), what the unsharded draw() hands them.
     Returns (fragments, view_fragments) of this band."""
     from . import _capi
+    from .particles import shader_stages
     uniforms = tendrils.draw_program_uniforms()
-    flow_shader, view_shader = tendrils.flowShader, (tendrils.renderShader if view else None)
+    (flow_shader, flow_fragment), (view_shader, view_fragment) = shader_stages(tendrils.flowShader), shader_stages(tendrils.renderShader if view else None)
     if dist is None:
+        if flow_fragment is not None or view_fragment is not None:
+            raise NotImplementedError("draw: the library-issued exchange (th_draw_program_sharded / th_draw_sharded) carries no fragment stage - "
+                                      "run the bands under a torch.distributed job (Tendrils(dist=...): sharding.draw_sharded_programs "
+                                      "around th_draw_stages_emit)")
         none = (None, None, None, 0)
         fp, fblock, fref, fsize = _program_block(flow_shader, uniforms) if flow_shader is not None else none
         vp, vblock, vref, vsize = _program_block(view_shader, uniforms) if view_shader is not None else none
@@ -409,7 +433,9 @@ def draw_sharded_programs(dist, tendrils, view=False):
     texels = tendrils.flow.shape[0] * tendrils.flow.shape[1]
     _exchange_halos(dist, tendrils)
     set_owners(tendrils, world)
-    if flow_shader is not None:
+    if flow_fragment is not None:
+        keys, colors = emit_stage_fragments(tendrils, flow_shader, flow_fragment, _capi.TH_PASS_FLOW, uniforms)
+    elif flow_shader is not None:
         keys, colors = emit_program_fragments(tendrils, flow_shader, _capi.TH_PASS_FLOW, uniforms)
     else:
         keys, colors = emit_fragments(tendrils)
@@ -419,7 +445,9 @@ def draw_sharded_programs(dist, tendrils, view=False):
     _gather_owned(dist, flow_view(tendrils), texels)
     if not view:
         return fragments, 0
-    if view_shader is not None:
+    if view_fragment is not None:
+        keys, colors = emit_stage_fragments(tendrils, view_shader, view_fragment, _capi.TH_PASS_VIEW, uniforms)
+    elif view_shader is not None:
         keys, colors = emit_program_fragments(tendrils, view_shader, _capi.TH_PASS_VIEW, uniforms)
     else:
         keys, colors = emit_view_fragments(tendrils)

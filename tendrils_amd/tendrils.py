@@ -4,7 +4,8 @@ spawnShader(), resize(), and draw() = the flow pass + the view pass (the particl
 render shader's colours into an RGBA8 image of the drawing buffer: `view`, read with read_view()).
 The demo's last pass - a shader of its own over the finished view (src/screen) - is screenShader() with a caller's
 ScreenProgram; the reference's own blur shader is outside this build.  The constructor's flowShader / renderShader options
-take a caller's DrawProgram: the vertex stage of the flow pass / the view pass of draw().
+take a caller's DrawProgram - the vertex stage of the flow pass / the view pass of draw() -, a FragmentProgram - the fragment
+stage, behind the library's vertex stage - or the reference's pair (vertex, fragment).
 """
 import ctypes as C
 import math
@@ -13,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, StepProgram, run_pass
+from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, StepProgram, draw_stages, run_pass, shader_stages
 from .timer import Timer
 
 
@@ -224,7 +225,8 @@ class Tendrils:
         self.logicShader = None
         self._logic_option = params.get("logicShader")         # new Tendrils(gl, { logicShader }): the caller's integrator
         # new Tendrils(gl, { flowShader, renderShader }) (src/index.js:70-71, 114-120): a caller's DrawProgram as the vertex stage
-        # of the flow pass / the view pass of draw(); None = the library's own stage.  Assignable, as there.
+        # of the flow pass / the view pass of draw(); None = the library's own stage.  Assignable, as there.  Also: a
+        # FragmentProgram (the fragment stage; the library's vertex stage) or the pair (vertex or None, fragment or None).
         self.flowShader = params.get("flowShader")
         self.renderShader = params.get("renderShader")
         self.uniforms = dict(render={}, update={})
@@ -489,7 +491,7 @@ class Tendrils:
         asks for).  Both passes draw the same lines: one call rasterises and sorts them once (th_draw) when they draw them
         with the same width."""
         self.line_widths()
-        if self.flowShader is not None or self.renderShader is not None:
+        if any(stage is not None for stage in shader_stages(self.flowShader) + shader_stages(self.renderShader)):
             return self._draw_programs()
         if self.dist is not None:          # row-band shard of a torch.distributed job: emit / exchange / merge, pass by pass
             from .sharding import draw_sharded
@@ -542,6 +544,21 @@ class Tendrils:
              0 if block is None else C.sizeof(block), which, C.byref(n))
         return int(n.value)
 
+    def _draw_stages(self, vertex, fragment, which, uniforms):
+        """one pass with a caller's fragment stage behind `vertex` (a DrawProgram; None: the library's vertex stage):
+        th_draw_stages_run - always stream-ordered"""
+        builtin = self.render_uniforms() if which == _capi.TH_PASS_VIEW else self.deposit_uniforms()
+        stages, _keep = draw_stages(vertex, fragment, uniforms, builtin)
+        n = C.c_uint64(0)
+        call("th_draw_stages_run", self.particles._ctx, C.byref(stages), which, C.byref(n))
+        return int(n.value)
+
+    def deposit_uniforms(self):
+        """the library's flow stage's uniforms of this frame (th_deposit_uniforms)"""
+        d = _capi.DepositUniforms(time=float(self.timer.time), speedLimit=float(self.state["speedLimit"]))
+        d.viewSize[0], d.viewSize[1] = float(self.viewSize[0]), float(self.viewSize[1])
+        return d
+
     def _sharded(self):
         """this context is a row-band shard: of a torch.distributed job, or a band narrower than the texture"""
         row0, rows, gh = self._band
@@ -561,9 +578,9 @@ class Tendrils:
         return uniforms
 
     def _draw_programs(self):
-        """draw() with a caller's vertex stage in one pass or both (src/index.js:278-340): the flow pass, then - with
-        renderView - the clear, the fade and the view pass; each pass runs its program or, where there is none, the library's
-        own stage.  Both programs get what the reference hands both shaders (src/index.js:284-293): the state, time, viewSize,
+        """draw() with a caller's stages in one pass or both (src/index.js:278-340): the flow pass, then - with
+        renderView - the clear, the fade and the view pass; each pass runs its programs or, where there is none, the library's
+        own stage.  A pass with a fragment stage goes through th_draw_stages_run and is always stream-ordered.  Both programs get what the reference hands both shaders (src/index.js:284-293): the state, time, viewSize,
         viewRes, colorMapRes - and dataRes, geomRes (src/particles.js:149-155) - with self.uniforms["render"] on top, packed
         into each program's uniform block by field name.  A program pass takes the pipeline the library's own pass of this
         context would (Particles.draw_pipeline / TH_DRAW: binned where the shape and the ring allow it, else stream-ordered -
@@ -583,8 +600,11 @@ class Tendrils:
                     self.drawFade()
             self.fragments, self.view_fragments = draw_sharded_programs(self.dist, self, view=self.renderView)
             return self
-        if self.flowShader is not None:
-            self.fragments = self._draw_program(self.flowShader, _capi.TH_PASS_FLOW, uniforms)
+        vertex, fragment = shader_stages(self.flowShader)
+        if fragment is not None:
+            self.fragments = self._draw_stages(vertex, fragment, _capi.TH_PASS_FLOW, uniforms)
+        elif vertex is not None:
+            self.fragments = self._draw_program(vertex, _capi.TH_PASS_FLOW, uniforms)
         else:
             self.fragments = p.deposit_flow(self.viewSize, self.timer.time, self.state["speedLimit"])
         if not self.renderView:
@@ -594,8 +614,11 @@ class Tendrils:
             self.clearView()
         if self.state["autoFade"]:
             self.drawFade()
-        if self.renderShader is not None:
-            self.view_fragments = self._draw_program(self.renderShader, _capi.TH_PASS_VIEW, uniforms)
+        vertex, fragment = shader_stages(self.renderShader)
+        if fragment is not None:
+            self.view_fragments = self._draw_stages(vertex, fragment, _capi.TH_PASS_VIEW, uniforms)
+        elif vertex is not None:
+            self.view_fragments = self._draw_program(vertex, _capi.TH_PASS_VIEW, uniforms)
         else:
             u, n = self.render_uniforms(), C.c_uint64(0)
             call("th_view_draw", p._ctx, C.byref(u), C.byref(n))

@@ -1,0 +1,192 @@
+"""GPU time of a draw() pass with a caller's fragment stage (tendrils_amd/csrc/th_fragprog.hip, th_fragment_prelude.inc) against
+the same pass without it, and of the fragment kernel alone against a copy of the bytes it moves, on one MI355X.
+
+One process, one context: 4096^2 particles in the C3 state of benchlib after a few steps (every line a texel or two long) on a
+1920 x 1080 target, the stream-ordered pipeline with reuse off on every arm (a pass with a fragment stage never reuses).  Arms,
+all the flow pass with the library's vertex stage:
+  plain       th_flow_deposit
+  identity    th_draw_stages_run with `return f.color` - the compiler proves the store writes what the load read and drops both:
+              the kernel of this program is empty, and the arm shows what the stage costs a pass beside its kernel (the launch)
+  gain        ... with `color * uniform`: the 16-byte load and the 16-byte store, no use of x, y - the key load is dropped
+  stripe      ... with `color * ((x + 3 y) & 1 ? uniform : 1)`: the key load and the split into x, y beside them, no tap - what the
+              split costs shows against gain and against the copy of its 36 bytes
+  vignette    ... with the program of the tests (tests/test_fragment_program_build.py: VIGNETTE): key, x and y, a colour-map tap
+The kernel alone is th_kernel_timing's event pair around its launch; copy(N) is a device-to-device copy that reads and writes N
+bytes a fragment in all (32: what gain's kernel moves; 36: vignette's, beside its taps of a map that stays in cache).
+Each pass figure is GPU ms per call between two events on the context's stream around --reps calls, after --warmup calls; the arms
+alternate for --rounds rounds and the median round is reported with the spread.  th_program_query's registers / scratch / code
+size go out with the figures.
+
+Usage: python tools/fragment_program_bench.py [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))          # the test programs are the tests' (one copy)
+
+GAIN = """struct GainUniforms { float gain; };
+__device__ float4 th_fragment_main(const th_fragment_pass &f)
+{
+    const float g = th_uniforms<GainUniforms>(f).gain;
+    return make_float4(f.color.x * g, f.color.y * g, f.color.z, f.color.w * g);
+}
+"""
+
+STRIPE = """struct GainUniforms { float gain; };
+__device__ float4 th_fragment_main(const th_fragment_pass &f)
+{
+    const float g = ((f.x + 3u * f.y) & 1u) ? th_uniforms<GainUniforms>(f).gain : 1.0f;
+    return make_float4(f.color.x * g, f.color.y * g, f.color.z, f.color.w * g);
+}
+"""
+
+
+class GainUniforms(C.Structure):
+    _fields_ = [("gain", C.c_float)]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--root", type=int, default=4096)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("fragment_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import FragmentProgram, draw_stages
+    from tendrils_amd.tendrils import View
+    from test_fragment_program_build import IDENTITY, VIGNETTE, FragUniforms
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    programs = dict(identity=FragmentProgram.from_source(IDENTITY, name="identity"),
+                    gain=FragmentProgram.from_source(GAIN, GainUniforms, "gain"),
+                    stripe=FragmentProgram.from_source(STRIPE, GainUniforms, "stripe"),
+                    vignette=FragmentProgram.from_source(VIGNETTE, FragUniforms, "vignette"))
+    t = ta.Tendrils(View(w, h))
+    t.resize()
+    t.setup(n)
+    p, ctx = t.particles, t.particles._ctx
+    p.upload_texels(workload.synth_state(0))
+    t.colorMap.set_pixels(np.random.default_rng(7).uniform(0, 1, (64, 64, 4)).astype(np.float32))
+    t.timer.time = 1000.0
+    for _ in range(3):                               # the C3 state a few frames in: buffers[1] -> buffers[0] are the lines
+        t.timer.tick()
+        t.step()
+    p.draw_pipeline("stream")
+    p.option("draw_reuse", 0)
+    t.line_widths()
+    uniforms = dict(t.state, gain=0.5, tint=[0.5, 0.25, 0.75, 0.875], invRes=[1.0 / w, 1.0 / h], edge=3.5 / (w * w + h * h))
+    d = t.deposit_uniforms()
+    held = {name: draw_stages(None, prog, uniforms, d) for name, prog in programs.items()}
+    frags = {}
+
+    def plain():
+        count = C.c_uint64(0)
+        call("th_flow_deposit", ctx, C.byref(d), C.byref(count))
+        frags["plain"] = count.value
+
+    def staged(name):
+        def run():
+            count = C.c_uint64(0)
+            call("th_draw_stages_run", ctx, C.byref(held[name][0]), 0, C.byref(count))
+            frags[name] = count.value
+        return run
+
+    arms = dict(plain=plain, identity=staged("identity"), gain=staged("gain"), stripe=staged("stripe"), vignette=staged("vignette"))
+
+    def timed(name, fn, reps):
+        """(GPU ms per call, mean ms of the fragment kernel alone or None)"""
+        ms, kernel = C.c_float(0), None
+        if name != "plain":
+            call("th_kernel_timing", ctx, 1)
+        call("th_timer_start", ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", ctx, C.byref(ms))
+        if name != "plain":
+            mean, launches = C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+            call("th_kernel_timing", ctx, 0)
+            assert launches.value == reps, (launches.value, reps)
+            kernel = mean.value
+        return ms.value / reps, kernel
+
+    for name, fn in arms.items():
+        timed(name, fn, args.warmup)
+    total = frags["plain"]
+    assert all(v == total for v in frags.values()), frags
+    copies = {}
+    for moved in (32, 36):                           # half read, half written (torch's stream, its own events)
+        src = torch.empty(total * moved // 2, dtype=torch.uint8, device="cuda")
+        copies[moved] = (src, torch.empty_like(src))
+
+    def copy_ms(moved, reps):
+        src, dst = copies[moved]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for moved in copies:
+        copy_ms(moved, args.warmup)
+    rounds = {}
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            ms, kernel = timed(name, fn, args.reps)
+            rounds.setdefault("pass(%s)" % name, []).append(ms)
+            if kernel is not None:
+                rounds.setdefault("kernel(%s)" % name, []).append(kernel)
+        for moved in copies:
+            rounds.setdefault("copy(%d)" % moved, []).append(copy_ms(moved, args.reps))
+
+    queries = {name: prog.query(p) for name, prog in programs.items()}
+    bytes_of = {"kernel(gain)": 32, "kernel(stripe)": 36, "kernel(vignette)": 36, "copy(32)": 32, "copy(36)": 36}
+    lines = ["fragment stage in the flow pass, %d^2 particles (C3 state, 3 steps in) into %d x %d, stream-ordered pipeline, reuse off; "
+             "%d rounds of %d calls, arms alternating; GPU ms per call (events on the stream)" % (n, w, h, args.rounds, args.reps),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "fragments per pass: %d" % total,
+             "%-20s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)")]
+    med = {}
+    for name, ms in rounds.items():
+        med[name] = statistics.median(ms)
+        gbps = "%.1f" % (bytes_of[name] * total / med[name] / 1e6) if name in bytes_of else "-"
+        lines.append("%-20s %10.4f %10.4f %10.4f %14s" % (name, med[name], min(ms), max(ms), gbps))
+    lines.append("pass(identity) / pass(plain) = %.3f;  pass(gain) / pass(plain) = %.3f;  pass(stripe) / pass(plain) = %.3f;  pass(vignette) / pass(plain) = %.3f  (time ratios)"
+                 % tuple(med["pass(%s)" % k] / med["pass(plain)"] for k in ("identity", "gain", "stripe", "vignette")))
+    lines.append("kernel(gain) / copy(32) = %.3f;  kernel(stripe) / copy(36) = %.3f;  kernel(vignette) / copy(36) = %.3f  (time ratios, the same bytes a fragment)"
+                 % (med["kernel(gain)"] / med["copy(32)"], med["kernel(stripe)"] / med["copy(36)"], med["kernel(vignette)"] / med["copy(36)"]))
+    for name, info in queries.items():
+        lines.append("th_program_query(%s): %s" % (name, json.dumps(info)))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(dict(root=n, width=w, height=h, reps=args.reps, rounds=args.rounds, fragments=total, query=queries, median_ms=med)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    t.dispose()
+    for prog in programs.values():
+        prog.dispose()
+
+
+if __name__ == "__main__":
+    main()
