@@ -110,16 +110,24 @@ struct ProgramModule {
 };
 }  // namespace thi
 
-// A caller's fragment stage as one draw call carries it (th_fragprog.hip: th_draw_stages_run / _emit): on the context for the
-// duration of the call, so that the pass underneath - whichever entry point prepares it - finds it where its fragments lie
-// (deposit_run, emit_parted) without a field more in th::DepositParams.
+// A caller's fragment stage as one pass carries it (th_fragprog.hip: th_draw_stages_run / _emit load the module): an argument from
+// the pass's entry point down to where its fragments lie (deposit_run, emit_parted), null when the pass has none - beside
+// th::DepositParams, which is a kernel's argument and knows nothing of it.
 namespace thi {
 struct FragmentStage {
     ProgramModule *module;
-    const void *uniforms;
-    uint32_t uniform_bytes;
+    const void *uniforms; uint32_t uniform_bytes;
     int32_t pass;
 };
+// One pass of draw() as its entry point describes it, for pass_run (a whole texture) and pass_emit (a row band; th_draw.hip); both passes in one (th_draw, th_draw_emit) prepare themselves
+struct PassSpec {
+    int32_t pass = TH_PASS_FLOW;                                                         // TH_PASS_FLOW / TH_PASS_VIEW
+    th_program *vertex = nullptr; const void *uniforms = nullptr; uint32_t uniform_bytes = 0;      // the vertex stage: a draw program and its block, or null:
+    const void *builtin = nullptr;                                                       // ... the library's own, with its th_deposit_uniforms (flow) / th_render_uniforms (view)
+    const FragmentStage *fragment = nullptr;                                             // the fragment stage, or null
+};
+inline PassSpec builtin_pass(int32_t pass, const void *uniforms) { PassSpec s; s.pass = pass; s.builtin = uniforms; return s; }
+inline PassSpec program_pass(int32_t pass, th_program *prog, const void *u, uint32_t bytes) { PassSpec s; s.pass = pass; s.vertex = prog; s.uniforms = u; s.uniform_bytes = bytes; return s; }
 }  // namespace thi
 
 // One captured th_step_n sequence (see th_step_n).
@@ -243,7 +251,6 @@ struct th_context {
     DevBuf<float4> edge_rows;            // th_draw_sharded through the bins: this band's edge rows gathered into texel order (4 x W)
     int draw_pipeline = TH_DRAW_AUTO;    // th_draw_pipeline
     th_draw_info last_draw{};            // th_draw_query
-    const thi::FragmentStage *frag_stage = nullptr;      // the caller's fragment stage of the draw call under way (th_fragprog.hip), else null
     long long draws = 0;                          // (`draws` counts frames: the passes drawn at one total_steps share a count ...
     long long draw_frame_step = -1;               //  ... and a pipeline: th_draw.hip, draw_uses_bins)
     int frame_bins = -1;
@@ -442,10 +449,14 @@ th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *re
 template <class Args> th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, ProgramKernArgs<Args> &k) { return program_launch(c, fn, lanes, &k, sizeof k); }
 // ... on a grid of the caller's (256-lane workgroups): a step program over tile-sorted slots takes the built-in fused launch's
 th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes);
+// ---- th_drawprog.hip -------------------------------------------------------------------------------------------------
+// s.vertex over the lines of the (prepared) pass `p`, into the vertex buffer its raster stage draws from: a local pass's over the order its pipeline walks (bins: the slots), a band's by local row
+th_status vertex_stage_run(th_context *c, const PassSpec &s, th::DepositParams &p, bool bins);
+th_status vertex_stage_band(th_context *c, const PassSpec &s, th::DepositParams &p);
 // ---- th_fragprog.hip -------------------------------------------------------------------------------------------------
-// c->frag_stage over the `total` fragments (not 0) the scatter of the (prepared) pass `p` has just written: p.keys64 / p.keys and
+// `stage` over the `total` fragments (not 0) the scatter of the (prepared) pass `p` has just written: p.keys64 / p.keys and
 // p.colors, fragment i in place i of both - before anything sorts or parts them
-th_status fragment_stage_run(th_context *c, const th::DepositParams &p, uint32_t total);
+th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
 // an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format
@@ -488,18 +499,19 @@ th_status fused_slots(th_context *c, bool may_sort, const th::TileGeom &g);
 int deposit_texel_bits(const th_context *c);
 float drawn_line_width(const th_context *c, int pass);
 // program: the pass of a caller's draw program (th_drawprog.hip) - its binned form walks the vertex records in texel order over
-// a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list)
-th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false);
+// a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list); stage: the
+// pass's fragment stage, or null - with one the pass is stream-ordered, and no frame of the policy's count
+th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false, const FragmentStage *stage = nullptr);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
 th_status deposit_temp(th_context *c, size_t need);
-// the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, sort by texel, blend
-th_status deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments);
+// the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, `stage` (or null) over the fragments, sort by texel, blend
+th_status deposit_run(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *fragments);
 // ... and the binned one (program: p.vertices holds a draw program's records).  kRetryInStreamOrder: see below
 th_status deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program = false);
 th_status view_storage(th_context *c);
 void view_fields(th_context *c, const th_render_uniforms *u, th::DepositParams &p);
-th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr);
+th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, const FragmentStage *stage = nullptr);
 // the binned pipeline in parts (deposit_run_bins = emit + finish; row-band shards put the owners' exchange in between)
 constexpr th_status kRetryInStreamOrder = -1;        // (internal) the binned pass gave up before it touched a target
 th_status bins_store_for(th_context *c, th::DepositParams &p, uint32_t at_least);
@@ -515,28 +527,33 @@ bool binned_shards(const th_context *c);              // a sharded draw() of thi
 th_status deposit_prepare_bins(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p);
 // what the entry points of a draw say alike
 void draw_moves_nothing(th_context *c);               // a local draw: nothing travels between ranks (th_draw_query)
+inline void draw_streamed(th_context *c, uint64_t n) { c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = n; c->last_draw.crowded_fragments = 0; }      // (th_draw_query of a stream-ordered pass)
 th_status refuse_band(const th_context *c, const char *what, const char *instead);       // TH_OK on a whole texture
 th_status shared_uniforms(const th_deposit_uniforms *du, const th_render_uniforms *ru);  // the passes of one draw agree on what they draw
 th_deposit_uniforms deposit_uniforms_of(const th_render_uniforms &u);
 th_status missing_halo(const th_context *c);          // the error of a band's line that reads a row nobody supplied
+// The pass `s` behind its entry point's own checks: drawn on a whole texture through draw_pass - the policy, the bins, the retry -,
+// or emitted on a row band (a whole-texture context: the band of all rows) - prepared, its vertex kernel if it has one, emit_parted
+th_status pass_run(th_context *c, const PassSpec &s, uint64_t *fragments);
+th_status pass_emit(th_context *c, const PassSpec &s, uint64_t *count, void **keys_dev, void **colors_dev);
 
 // ---- th_shard.hip ----------------------------------------------------------------------------------------------------
 // the sharded deposit's keys hold 24 texel bits: `target` ("flow", "view") names what is too large for them
 th_status texels_fit_keys(const th_context *c, const char *target);
 // the tail of every emit of a row band: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed
-// (owner, texel, global stream index) and parted by owner; synchronises (the caller hands the buffers to a collective)
-th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev);
+// (owner, texel, global stream index), `stage` (or null) over them, parted by owner; synchronises (the caller hands the buffers to a collective)
+th_status emit_parted(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *count, void **keys_dev, void **colors_dev);
 
 // One pass of a local draw: prepare(p, first, &bins) readies `p` for an attempt - the first may take the bins - and says which
-// pipeline it takes; a binned pass that gives up before blending is repeated in stream order, and so are the other passes of its frame.
+// pipeline it takes (never the bins with `stage`); a binned pass that gives up before blending is repeated in stream order, and so are the other passes of its frame.
 template <class Prepare>
-th_status draw_pass(th_context *c, uint64_t *fragments, bool program, Prepare prepare)
+th_status draw_pass(th_context *c, uint64_t *fragments, bool program, const FragmentStage *stage, Prepare prepare)
 {
     for (int attempt = 0;; ++attempt) {
         th::DepositParams p;
         bool bins = false;
         if (th_status s = prepare(p, attempt == 0, &bins)) return s;
-        if (!bins) return deposit_run(c, p, fragments);
+        if (!bins) return deposit_run(c, p, stage, fragments);
         const th_status s = deposit_run_bins(c, p, fragments, program);
         if (s != kRetryInStreamOrder) return s;
         c->frame_bins = 0;                  // (the other passes of this frame as well)

@@ -87,12 +87,12 @@ th_status deposit_prepare_bins(th_context *c, const th_deposit_uniforms *u, th::
     return prepare_pass(c, u, p, Walk::slots);
 }
 
-th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins, bool program)
+th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins, bool program, const FragmentStage *stage)
 {
     TH_REQUIRE(u, "null uniforms");
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
     if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
-    if (c->frag_stage) want_bins = false;       // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count)
+    if (stage) want_bins = false;               // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count)
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -344,11 +344,11 @@ th_deposit_uniforms deposit_uniforms_of(const th_render_uniforms &u)
     return d;
 }
 
-th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins)
+th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins, bool *bins, const FragmentStage *stage)
 {
     TH_REQUIRE(u, "null uniforms");
     const th_deposit_uniforms d = deposit_uniforms_of(*u);
-    if (th_status s = deposit_prepare(c, &d, p, want_bins, bins)) return s;
+    if (th_status s = deposit_prepare(c, &d, p, want_bins, bins, false, stage)) return s;
     p.mode = 1;
     p.line_half = 0.5f * drawn_line_width(c, TH_PASS_VIEW);
     view_fields(c, u, p);
@@ -394,13 +394,13 @@ static th_status export_run(th_context *c, th::DepositParams &p, float *lines, u
 }
 
 // the fragments of the (prepared) pass `p`: count, emit, sort by texel, blend
-th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragments)
+th_status thi::deposit_run(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *fragments)
 {
     // Same state, same view, same resolution as the pass before (the view pass after the flow pass of one draw()): the
     // lines cover the same texels in the same order - counts, offsets, records and the sorted order of the fragments are
     // still there, only the varyings differ.  (TH_DRAW_REUSE=0: every pass on its own.)
     // (A caller's fragment stage runs over the array the scatter writes, key beside varying: such a pass reuses nothing.)
-    const bool reuse = c->opt.draw_reuse && !c->frag_stage && p.mode != 2 && c->drawn.valid && !c->drawn.binned && c->drawn.view_x == p.view_x && c->drawn.view_y == p.view_y &&
+    const bool reuse = c->opt.draw_reuse && !stage && p.mode != 2 && c->drawn.valid && !c->drawn.binned && c->drawn.view_x == p.view_x && c->drawn.view_y == p.view_y &&
                        c->drawn.line_half == p.line_half;
     uint32_t total = 0;
     if (reuse) total = c->drawn.total;
@@ -410,7 +410,7 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragme
         if (th_status s = deposit_scan_total(c, p, &total)) return s;
     }
     if (fragments) *fragments = total;
-    c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = total; c->last_draw.crowded_fragments = 0;
+    draw_streamed(c, total);
     if (total == 0) return TH_OK;
     if (!reuse) if (th_status s = deposit_reserve(c, total, false, p.mode == 2)) return s;
     p.keys = c->dep_u32[0]; p.slots = c->dep_u32[1]; p.keys_sorted = c->dep_u32[2]; p.slots_sorted = c->dep_u32[3];
@@ -423,7 +423,7 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, uint64_t *fragme
         const int bits = th::deposit_key_bits(p);
         if (th_status s = deposit_temp(c, th::radix_sort_temp_bytes(total, 0, bits))) return s;
         th::launch_deposit_scatter(p, c->stream);
-        if (c->frag_stage) if (th_status s = fragment_stage_run(c, p, total)) return s;
+        if (stage) if (th_status s = fragment_stage_run(c, *stage, p, total)) return s;
         const bool in_a = th::launch_radix_sort_u32(p.keys, p.slots, p.keys_sorted, p.slots_sorted, total, 0, bits, c->dep_temp, true, c->stream) == 0;
         if (in_a) { p.keys_sorted = c->dep_u32[0]; p.slots_sorted = c->dep_u32[1]; }        // an even number of passes ends in the (a) buffers
         c->drawn.valid = true; c->drawn.binned = false; c->drawn.view_x = p.view_x; c->drawn.view_y = p.view_y; c->drawn.line_half = p.line_half; c->drawn.total = total; c->drawn.sorted_in_a = in_a;
@@ -729,6 +729,50 @@ th_status thi::deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *f
     return bins_pass_finish(c, p, fragments, early);
 }
 
+// ---- one pass, as its entry point describes it (PassSpec) ------------------------------------------------------------------------
+// `p` readied for the pass, in front of its vertex kernel (want_bins, bins: as draw_pass hands them; an emit has neither)
+static th_status pass_prepare(th_context *c, const PassSpec &s, th::DepositParams &p, bool want_bins, bool *bins)
+{
+    if (s.vertex) {
+        const th_deposit_uniforms none{};                   // (viewSize, time, speedLimit are the program's own business)
+        return deposit_prepare(c, &none, p, want_bins, bins, true, s.fragment);
+    }
+    if (s.pass == TH_PASS_VIEW) return view_params(c, static_cast<const th_render_uniforms *>(s.builtin), p, want_bins, bins, s.fragment);
+    return deposit_prepare(c, static_cast<const th_deposit_uniforms *>(s.builtin), p, want_bins, bins, false, s.fragment);
+}
+
+// Through the pipeline the built-in pass of this context would take (deposit_prepare: the policy, the frame's one-pipeline rule, the
+// gate; a fragment stage: stream-ordered).  With a vertex program, binned: the ring stays in the order it is held in, the vertex
+// kernel fills the texel-indexed vertex buffer - over a sorted ring one lane per SLOT, the state read where it lies - and the bins
+// walk the records in texel order; stream: the ring goes to texel order (held for a while), one lane per vertex - every attempt runs the vertex kernel.  A caller's stage
+// made or coloured the lines: what a built-in pass left of its own (c->drawn) is not such a pass's, nor such a pass's a built-in's.
+th_status thi::pass_run(th_context *c, const PassSpec &s, uint64_t *fragments)
+{
+    const bool view = s.pass == TH_PASS_VIEW, own_lines = s.vertex || s.fragment;
+    if (own_lines) c->drawn.valid = false;
+    if (view) if (th_status st = view_storage(c)) return st;
+    const th_status ran = draw_pass(c, fragments, s.vertex != nullptr, s.fragment, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
+        if (th_status st = pass_prepare(c, s, p, first, bins)) return st;
+        if (view) p.view = c->view;
+        return s.vertex ? vertex_stage_run(c, s, p, *bins) : TH_OK;
+    });
+    if (own_lines) c->drawn.valid = false;          // (deposit_run has said what it left: true of a built-in pass alone)
+    return ran;
+}
+
+// always stream-ordered: the ring goes to texel order (deposit_prepare clears the out-of-band word), a vertex program fills the vertex buffer by local row, the tail of every emit
+// keys and parts the fragments.  A row that neither the band nor a halo row holds - asked for by the vertex kernel or by the raster stage, on the same word - is one error, and nothing is handed out.
+th_status thi::pass_emit(th_context *c, const PassSpec &s, uint64_t *count, void **keys_dev, void **colors_dev)
+{
+    if (s.vertex || s.fragment) c->drawn.valid = false;
+    if (th_status st = texels_fit_keys(c, s.pass == TH_PASS_VIEW ? "view" : "flow")) return st;
+    if (s.vertex) { *count = 0; *keys_dev = nullptr; *colors_dev = nullptr; }        // (what a failure of the vertex stage hands out)
+    th::DepositParams p;
+    if (th_status st = pass_prepare(c, s, p, false, nullptr)) return st;
+    if (s.vertex) if (th_status st = vertex_stage_band(c, s, p)) return st;
+    return emit_parted(c, p, s.fragment, count, keys_dev, colors_dev);
+}
+
 extern "C" {
 
 th_status th_export_lines(th_context *c, const th_deposit_uniforms *u, float *lines, uint64_t capacity, uint64_t *count)
@@ -745,7 +789,7 @@ th_status th_flow_deposit(th_context *c, const th_deposit_uniforms *u, uint64_t 
     if (th_status s = use(c)) return s;
     draw_moves_nothing(c);
     if (th_status s = refuse_band(c, "flow deposit", "use th_deposit_emit / th_deposit_merge with the exchange of tendrils_amd/sharding.py")) return s;
-    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) { return deposit_prepare(c, u, p, first, bins); });
+    return pass_run(c, builtin_pass(TH_PASS_FLOW, u), fragments);
 }
 
 // Both passes of Tendrils.draw() (src/index.js:278-337) in one: the lines are rasterised, scanned, emitted and sorted once,
@@ -761,11 +805,11 @@ th_status th_draw(th_context *c, const th_deposit_uniforms *du, const th_render_
     if (th_status s = refuse_band(c, "draw", "the passes go through th_deposit_emit / th_deposit_merge and th_view_emit / th_view_merge with the owners' exchange in between")) return s;
     if (th_status s = shared_uniforms(du, ru)) return s;
     if (drawn_line_width(c, TH_PASS_FLOW) != drawn_line_width(c, TH_PASS_VIEW)) {       // two widths: two rasterisations
-        if (th_status s = th_flow_deposit(c, du, fragments)) return s;
-        return th_view_draw(c, ru, nullptr);
+        if (th_status s = pass_run(c, builtin_pass(TH_PASS_FLOW, du), fragments)) return s;
+        return pass_run(c, builtin_pass(TH_PASS_VIEW, ru), nullptr);
     }
     if (th_status s = view_storage(c)) return s;
-    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
+    return draw_pass(c, fragments, false, nullptr, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
         if (th_status s = deposit_prepare(c, du, p, first, bins)) return s;
         p.mode = 2;
         view_fields(c, ru, p);
@@ -779,12 +823,7 @@ th_status th_view_draw(th_context *c, const th_render_uniforms *u, uint64_t *fra
     if (th_status s = use(c, true)) return s;
     draw_moves_nothing(c);
     if (th_status s = refuse_band(c, "view pass", "use th_view_emit / th_view_merge with the owners' exchange in between")) return s;
-    if (th_status s = view_storage(c)) return s;
-    return draw_pass(c, fragments, false, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
-        if (th_status s = view_params(c, u, p, first, bins)) return s;
-        p.view = c->view;
-        return TH_OK;
-    });
+    return pass_run(c, builtin_pass(TH_PASS_VIEW, u), fragments);
 }
 
 th_status th_view_fill(th_context *c, const float rgba[4])

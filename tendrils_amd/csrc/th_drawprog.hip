@@ -68,7 +68,74 @@ void record_shared(const th_context *c, const th::DepositParams &p, size_t lines
     a.W = p.W; a.H = p.H; a.count = (uint32_t)(2 * lines);
 }
 
+// what every vertex kernel needs and the raster stage of `p` then reads: the module, the pass's mode and line width, the vertex buffer
+th_status vertex_buffer(th_context *c, const PassSpec &s, th::DepositParams &p, size_t lines, ProgramModule **m)
+{
+    if (th_status st = program_loaded(c, s.vertex, m)) return st;
+    if (s.pass == TH_PASS_VIEW) p.mode = 1;
+    p.line_half = 0.5f * drawn_line_width(c, s.pass);
+    if (th_status st = c->draw_vertices.reserve(4 * lines, 4 * lines)) return st;
+    p.vertices = c->draw_vertices;
+    return TH_OK;
+}
+
+// the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
+template <class Record> th_status vertex_launch(th_context *c, hipFunction_t fn, size_t lanes, Record &k)
+{
+    if (!lanes) return TH_OK;
+    LaunchTimer timer;                                  // (th_kernel_timing: the vertex kernel alone)
+    if (th_status st = timer.begin(c)) return st;
+    if (th_status st = program_launch(c, fn, lanes, k)) return st;
+    return timer.end(c);
+}
+
 }  // namespace
+
+th_status thi::vertex_stage_run(th_context *c, const PassSpec &s, th::DepositParams &p, bool bins)
+{
+    const size_t lines = c->texels();
+    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a %dx%d particle texture is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
+    ProgramModule *m = nullptr;
+    if (th_status st = vertex_buffer(c, s, p, lines, &m)) return st;
+    KernArgs k{};
+    DrawArgs &a = k.a;
+    hipFunction_t fn = m->fn;
+    size_t lanes = 2 * lines;                           // (one per stream vertex)
+    const int order = bins ? order_of(c, c->ring[0]) : -1;
+    if (order >= 0) {
+        // over sorted slots (f32 texels, both buffers in ONE order: the gate, align_slot_orders): one lane per slot
+        a.cur = c->ring[0]; a.prev = c->ring[1]; a.perm = c->orders[(size_t)order].perm;
+        fn = m->fn_slots; lanes = lines;
+    } else {
+        float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
+        if (th_status st = unpacked_view(c, c->ring[0], 0, &cur)) return st;
+        if (th_status st = unpacked_view(c, c->ring[1], 1, &prev)) return st;
+        a.cur = cur; a.prev = prev;
+    }
+    record_shared(c, p, lines, a);
+    k.set_uniforms(s.uniforms, s.uniform_bytes);
+    return vertex_launch(c, fn, lanes, k);
+}
+
+// by local row, what the program makes of the GLOBAL stream (the neighbours' edge rows from the halo rows): th_draw_vertex_band_kernel
+th_status thi::vertex_stage_band(th_context *c, const PassSpec &s, th::DepositParams &p)
+{
+    const size_t lines = c->texels();
+    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a band of %dx%d particles is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
+    ProgramModule *m = nullptr;
+    if (th_status st = vertex_buffer(c, s, p, lines, &m)) return st;
+    BandKernArgs k{};
+    DrawArgs &a = k.a.a;
+    float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as the halo rows are)
+    if (th_status st = unpacked_view(c, c->ring[0], 0, &cur)) return st;
+    if (th_status st = unpacked_view(c, c->ring[1], 1, &prev)) return st;
+    a.cur = cur; a.prev = prev;
+    record_shared(c, p, lines, a);                     // (count: the band's vertices)
+    k.a.halo_lo = p.halo_lo; k.a.halo_hi = p.halo_hi; k.a.oob = p.oob;
+    k.a.row0 = p.row0; k.a.rows = p.rows;
+    k.set_uniforms(s.uniforms, s.uniform_bytes);
+    return vertex_launch(c, m->fn_band, 2 * lines, k);
+}
 
 extern "C" {
 
@@ -77,15 +144,8 @@ th_status th_draw_program_compile(const char *source, const char *name, th_progr
     return program_compile(kDrawProgram, std::string(kTaps) + "\n" + kStream + "\n" + kPrelude, source, name, out);
 }
 
-// One pass of draw() with the program as its vertex stage, through the pipeline the built-in pass of this context would take
-// (deposit_prepare: the policy, the frame's one-pipeline rule, the gate), as th_flow_deposit / th_view_draw go about it.
-//   binned: the ring stays in the order it is held in.  The vertex kernel fills the texel-indexed vertex buffer - over a sorted
-//           ring one lane per SLOT, the state read where it lies (th_draw_vertex_slots_kernel) - and the bins walk the records
-//           in texel order.  A pass that gives up before blending is repeated in stream order, from its start.
-//   stream: the ring goes to texel order as for a stream-ordered built-in pass (held for a while), the vertex kernel runs one
-//           lane per vertex, the stream-ordered pipeline draws from the buffer.
-// The counts and the sorted order a built-in pass left (c->drawn) are not this pass's, nor this pass's a built-in's: invalid
-// before and after.
+// One pass of draw() with the program as its vertex stage, through the pipeline the built-in pass of this context would take, as
+// th_flow_deposit / th_view_draw go about it (th_draw.hip: pass_run).
 th_status th_draw_program_run(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t pass, uint64_t *fragments)
 {
     if (th_status s = use(c, pass == TH_PASS_VIEW)) return s;      // (the view pass writes no state and no flow: th_view_draw)
@@ -93,60 +153,12 @@ th_status th_draw_program_run(th_context *c, th_program *prog, const void *unifo
     TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
     // (this LOCAL pass has no exchange to go through; a band's program pass is th_draw_program_emit / th_draw_program_sharded)
     if (th_status s = refuse_band(c, "draw program", "a band's pass goes through the owners' exchange, which carries the built-in stages alone")) return s;
-    const size_t lines = c->texels();
-    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a %dx%d particle texture is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
-    c->drawn.valid = false;
     draw_moves_nothing(c);
-    ProgramModule *m = nullptr;
-    if (th_status s = program_loaded(c, prog, &m)) return s;
-    if (pass == TH_PASS_VIEW) if (th_status s = view_storage(c)) return s;
-    // every attempt of the pass (draw_pass: a binned one that gives up before blending is repeated in stream order, from its start)
-    // runs the vertex kernel over the order its pipeline walks
-    const th_status ran = draw_pass(c, fragments, true, [&](th::DepositParams &p, bool first, bool *use_bins) -> th_status {
-        // what the built-in vertex stage takes from its uniforms - viewSize, time, speedLimit - is the program's own business here
-        const th_deposit_uniforms none{};
-        if (th_status s = deposit_prepare(c, &none, p, first, use_bins, true)) return s;
-        const bool bins = *use_bins;
-        if (pass == TH_PASS_VIEW) { p.mode = 1; p.view = c->view; }
-        p.line_half = 0.5f * drawn_line_width(c, pass);
-        if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
-        p.vertices = c->draw_vertices;
-        KernArgs k{};
-        DrawArgs &a = k.a;
-        hipFunction_t fn = m->fn;
-        uint32_t lanes = (uint32_t)(2 * lines);         // (one per stream vertex)
-        const int order = bins ? order_of(c, c->ring[0]) : -1;
-        if (order >= 0) {
-            // over sorted slots (f32 texels, both buffers in ONE order: the gate, align_slot_orders): one lane per slot
-            a.cur = c->ring[0]; a.prev = c->ring[1]; a.perm = c->orders[(size_t)order].perm;
-            fn = m->fn_slots; lanes = (uint32_t)lines;
-        } else {
-            float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
-            if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
-            if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
-            a.cur = cur; a.prev = prev;
-        }
-        record_shared(c, p, lines, a);
-        k.set_uniforms(uniforms, uniform_bytes);
-        if (lanes) {
-            // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
-            LaunchTimer timer;                              // (th_kernel_timing: the vertex kernel alone)
-            if (th_status s = timer.begin(c)) return s;
-            if (th_status s = program_launch(c, fn, lanes, k)) return s;
-            if (th_status s = timer.end(c)) return s;
-        }
-        return TH_OK;
-    });
-    c->drawn.valid = false;
-    return ran;
+    return pass_run(c, program_pass(pass, prog, uniforms, uniform_bytes), fragments);
 }
 
-// The program pass of a row band - what th_deposit_emit / th_view_emit are to the built-in stages (th_shard.hip): this band's
-// fragments with the program as their vertex stage, keyed and parted by owner for th_deposit_merge (flow) / th_view_merge (view).
-// Always stream-ordered: the ring goes to texel order, th_draw_vertex_band_kernel fills the vertex buffer by local row with
-// what the program makes of the GLOBAL stream (the neighbours' edge rows from the halo rows), the stream-ordered raster stage
-// draws from the buffer.  A row that neither the band nor a halo row holds - asked for by the vertex kernel or by the raster
-// stage, on the same word - is the error of th_deposit_emit, and nothing is handed out.
+// The program pass of a row band - what th_deposit_emit / th_view_emit are to the built-in stages (th_shard.hip: pass_emit), keyed
+// and parted by owner for th_deposit_merge (flow) / th_view_merge (view).  Unlike those two it tells th_draw_query what it emitted.
 th_status th_draw_program_emit(th_context *c, th_program *prog, const void *uniforms, uint32_t uniform_bytes, int32_t pass,
                                uint64_t *count, void **keys_dev, void **colors_dev)
 {
@@ -154,39 +166,8 @@ th_status th_draw_program_emit(th_context *c, th_program *prog, const void *unif
     if (th_status s = program_run_args(prog, kDrawProgram, "th_draw_program_emit", uniforms, uniform_bytes)) return s;
     TH_REQUIRE(pass == TH_PASS_FLOW || pass == TH_PASS_VIEW, "unknown pass %d", pass);
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    if (th_status s = texels_fit_keys(c, pass == TH_PASS_VIEW ? "view" : "flow")) return s;
-    const size_t lines = c->texels();
-    TH_REQUIRE(2 * (uint64_t)lines <= 0x7fffffffull, "a band of %dx%d particles is beyond what a draw program's vertex kernel indexes", c->cfg.width, c->cfg.height);
-    *count = 0; *keys_dev = nullptr; *colors_dev = nullptr;
-    c->drawn.valid = false;
-    ProgramModule *m = nullptr;
-    if (th_status s = program_loaded(c, prog, &m)) return s;
-    const th_deposit_uniforms none{};                   // (viewSize, time, speedLimit are the program's own business: th_draw_program_run)
-    th::DepositParams p;
-    if (th_status s = deposit_prepare(c, &none, p)) return s;          // (texel order; the out-of-band word is cleared)
-    if (pass == TH_PASS_VIEW) p.mode = 1;
-    p.line_half = 0.5f * drawn_line_width(c, pass);
-    if (th_status s = c->draw_vertices.reserve(4 * lines, 4 * lines)) return s;
-    p.vertices = c->draw_vertices;
-    BandKernArgs k{};
-    DrawArgs &a = k.a.a;
-    float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as the halo rows are)
-    if (th_status s = unpacked_view(c, c->ring[0], 0, &cur)) return s;
-    if (th_status s = unpacked_view(c, c->ring[1], 1, &prev)) return s;
-    a.cur = cur; a.prev = prev;
-    record_shared(c, p, lines, a);                     // (count: the band's vertices)
-    k.a.halo_lo = p.halo_lo; k.a.halo_hi = p.halo_hi; k.a.oob = p.oob;
-    k.a.row0 = p.row0; k.a.rows = p.rows;
-    k.set_uniforms(uniforms, uniform_bytes);
-    if (lines) {
-        LaunchTimer timer;                              // (th_kernel_timing: the vertex kernel alone)
-        if (th_status s = timer.begin(c)) return s;
-        if (th_status s = program_launch(c, m->fn_band, 2 * lines, k)) return s;
-        if (th_status s = timer.end(c)) return s;
-    }
-    const th_status emitted = emit_parted(c, p, count, keys_dev, colors_dev);
-    if (emitted == TH_OK) { c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = *count; c->last_draw.crowded_fragments = 0; }
-    c->drawn.valid = false;
+    const th_status emitted = pass_emit(c, program_pass(pass, prog, uniforms, uniform_bytes), count, keys_dev, colors_dev);
+    if (emitted == TH_OK) draw_streamed(c, *count);
     return emitted;
 }
 

@@ -3,9 +3,9 @@
 // th_drawprog.hip has the first.  The caller's fragment shader is HIP source for one device function, th_fragment_main
 // (th_fragment_prelude.inc), compiled for gfx950 at run time like the other kinds (th_program.hip: program_compile).  It runs
 // once per fragment, in place over the array the stream-ordered pipeline holds between its emit and its sort - texel key beside
-// interpolated varying -, so nothing of the raster or blend kernels knows of it: the entry points here put the stage on the
-// context for the duration of one call (c->frag_stage), run the pass through the entry point that draws it without the stage,
-// and deposit_run (th_draw.hip) / emit_parted (th_shard.hip) call fragment_stage_run where the fragments lie.
+// interpolated varying -, so nothing of the raster or blend kernels knows of it: the entry points here load the stage and describe
+// the pass with it (PassSpec::fragment) to the body every pass goes through (th_draw.hip: pass_run / pass_emit); it travels down as
+// an argument, and deposit_run (th_draw.hip) / emit_parted (th_shard.hip) call fragment_stage_run where the fragments lie.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -72,27 +72,21 @@ th_status stages_args(const th_context *c, const th_draw_stages *s, int32_t pass
     return TH_OK;
 }
 
-// the stage on the context while one call runs
-struct StageScope {
-    th_context *c;
-    FragmentStage stage{};
-    explicit StageScope(th_context *ctx) : c(ctx) {}
-    th_status begin(const th_draw_stages *s, int32_t pass)
-    {
-        if (!s->fragment) return TH_OK;
-        if (th_status st = program_loaded(c, s->fragment, &stage.module)) return st;
-        stage.uniforms = s->fragment_uniforms; stage.uniform_bytes = s->fragment_uniform_bytes; stage.pass = pass;
-        c->frag_stage = &stage;
-        return TH_OK;
-    }
-    ~StageScope() { c->frag_stage = nullptr; }
-};
+// the pass th_draw_stages names: its vertex slot, and its fragment stage as this context loaded it (`stage`: the caller's storage)
+th_status stages_pass(th_context *c, const th_draw_stages *s, int32_t pass, FragmentStage &stage, PassSpec &spec)
+{
+    spec = s->vertex ? program_pass(pass, s->vertex, s->vertex_uniforms, s->vertex_uniform_bytes) : builtin_pass(pass, s->builtin);
+    if (!s->fragment) return TH_OK;
+    if (th_status st = program_loaded(c, s->fragment, &stage.module)) return st;
+    stage.uniforms = s->fragment_uniforms; stage.uniform_bytes = s->fragment_uniform_bytes; stage.pass = pass;
+    spec.fragment = &stage;
+    return TH_OK;
+}
 
 }  // namespace
 
-th_status thi::fragment_stage_run(th_context *c, const th::DepositParams &p, uint32_t total)
+th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total)
 {
-    const FragmentStage &stage = *c->frag_stage;
     KernArgs k{};
     FragmentArgs &a = k.a;
     a.keys = p.keys64 ? static_cast<const void *>(p.keys64) : static_cast<const void *>(p.keys);
@@ -116,41 +110,33 @@ th_status th_fragment_program_compile(const char *source, const char *name, th_p
     return program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
 }
 
-// One pass of draw() with the stages of `s`: the entry point that draws the pass without a fragment stage - th_draw_program_run
-// with a vertex program, th_flow_deposit / th_view_draw with the library's vertex stage - runs it, and finds the fragment stage
-// on the context: deposit_prepare then leaves the bins and the frame's pipeline count alone, deposit_run reuses nothing and calls
-// the stage between its scatter and its sort.  What such a pass leaves of its lines (c->drawn) is no other pass's to reuse.
+// One pass of draw() with the stages of `s`, through the body every local pass goes through (pass_run): with a fragment stage
+// deposit_prepare leaves the bins and the frame's pipeline count alone, deposit_run reuses nothing and calls the stage between
+// its scatter and its sort.  What such a pass leaves of its lines (c->drawn) is no other pass's to reuse.
 th_status th_draw_stages_run(th_context *c, const th_draw_stages *s, int32_t pass, uint64_t *fragments)
 {
     if (th_status st = stages_args(c, s, pass, "th_draw_stages_run", "th_flow_deposit / th_view_draw")) return st;
     if (th_status st = use(c, pass == TH_PASS_VIEW)) return st;
     if (th_status st = refuse_band(c, "draw stages", "a band's pass goes through th_draw_stages_emit and the owners' exchange")) return st;
-    StageScope scope(c);
-    if (th_status st = scope.begin(s, pass)) return st;
-    if (s->fragment) c->drawn.valid = false;
-    const th_status ran = s->vertex         ? th_draw_program_run(c, s->vertex, s->vertex_uniforms, s->vertex_uniform_bytes, pass, fragments)
-                        : pass == TH_PASS_VIEW ? th_view_draw(c, static_cast<const th_render_uniforms *>(s->builtin), fragments)
-                                               : th_flow_deposit(c, static_cast<const th_deposit_uniforms *>(s->builtin), fragments);
-    if (s->fragment) c->drawn.valid = false;
-    return ran;
+    FragmentStage stage{}; PassSpec spec;
+    if (th_status st = stages_pass(c, s, pass, stage, spec)) return st;
+    draw_moves_nothing(c);
+    return pass_run(c, spec, fragments);
 }
 
-// ... and of a row band (a whole-texture context: the band of all rows): th_draw_program_emit / th_deposit_emit / th_view_emit
-// with the stage on the context - emit_parted calls it behind its scatter, before it parts the fragments by owner.
+// ... and of a row band (a whole-texture context: the band of all rows), through pass_emit: emit_parted calls the stage behind its
+// scatter, before it parts the fragments by owner.  Like th_draw_program_emit it tells th_draw_query what it emitted.  (use(): the
+// view pass keeps what a step left for the draw only with a vertex program - as th_draw_program_emit does and th_view_emit does not)
 th_status th_draw_stages_emit(th_context *c, const th_draw_stages *s, int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev)
 {
     if (th_status st = stages_args(c, s, pass, "th_draw_stages_emit", "th_deposit_emit / th_view_emit")) return st;
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    if (th_status st = use(c, pass == TH_PASS_VIEW)) return st;
+    if (th_status st = use(c, pass == TH_PASS_VIEW && s->vertex)) return st;
     *count = 0; *keys_dev = nullptr; *colors_dev = nullptr;
-    StageScope scope(c);
-    if (th_status st = scope.begin(s, pass)) return st;
-    if (s->fragment) c->drawn.valid = false;
-    const th_status emitted = s->vertex      ? th_draw_program_emit(c, s->vertex, s->vertex_uniforms, s->vertex_uniform_bytes, pass, count, keys_dev, colors_dev)
-                            : pass == TH_PASS_VIEW ? th_view_emit(c, static_cast<const th_render_uniforms *>(s->builtin), count, keys_dev, colors_dev)
-                                                   : th_deposit_emit(c, static_cast<const th_deposit_uniforms *>(s->builtin), count, keys_dev, colors_dev);
-    if (emitted == TH_OK) { c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = *count; c->last_draw.crowded_fragments = 0; }
-    if (s->fragment) c->drawn.valid = false;
+    FragmentStage stage{}; PassSpec spec;
+    if (th_status st = stages_pass(c, s, pass, stage, spec)) return st;
+    const th_status emitted = pass_emit(c, spec, count, keys_dev, colors_dev);
+    if (emitted == TH_OK) draw_streamed(c, *count);
     return emitted;
 }
 

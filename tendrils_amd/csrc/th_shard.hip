@@ -12,9 +12,9 @@ th_status texels_fit_keys(const th_context *c, const char *target)
     return TH_OK;
 }
 
-// the tail of the three emits: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed (owner,
-// texel, global stream index) and parted by owner
-th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void **keys_dev, void **colors_dev)
+// the tail of every emit: the fragments of the (prepared) pass `p` - this band's lines - counted, scanned, keyed (owner,
+// texel, global stream index), handed to the pass's fragment stage if it has one, and parted by owner
+th_status emit_parted(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *count, void **keys_dev, void **colors_dev)
 {
     th::launch_deposit_count(p, c->stream);
     uint32_t total = 0;
@@ -28,7 +28,7 @@ th_status emit_parted(th_context *c, th::DepositParams &p, uint64_t *count, void
     p.owner_chunk = (uint32_t)(((uint64_t)c->fw * c->fh + p.owners - 1u) / p.owners);
     th::launch_deposit_scatter(p, c->stream);
     // (a caller's fragment stage, th_draw_stages_emit: here keys64[i] and colors[i] still name the same fragment)
-    if (c->frag_stage) if (th_status s = fragment_stage_run(c, p, total)) return s;
+    if (stage) if (th_status s = fragment_stage_run(c, *stage, p, total)) return s;
     *keys_dev = c->dep_u64[0]; *colors_dev = c->dep_colors;
     if (p.owners > 1u) {
         // the fragment array is in this band's stream order: ONE stable pass on the owner bits parts it by destination
@@ -65,10 +65,7 @@ th_status th_deposit_emit(th_context *c, const th_deposit_uniforms *u, uint64_t 
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    if (th_status s = texels_fit_keys(c, "flow")) return s;
-    th::DepositParams p;
-    if (th_status s = deposit_prepare(c, u, p)) return s;
-    return emit_parted(c, p, count, keys_dev, colors_dev);
+    return pass_emit(c, builtin_pass(TH_PASS_FLOW, u), count, keys_dev, colors_dev);
 }
 
 // the view pass of a row-band shard: the same lines with the render shader's colours
@@ -76,17 +73,13 @@ th_status th_view_emit(th_context *c, const th_render_uniforms *u, uint64_t *cou
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(count && keys_dev && colors_dev, "null outputs");
-    if (th_status s = texels_fit_keys(c, "view")) return s;
-    th::DepositParams p;
-    if (th_status s = view_params(c, u, p)) return s;
-    return emit_parted(c, p, count, keys_dev, colors_dev);
+    return pass_emit(c, builtin_pass(TH_PASS_VIEW, u), count, keys_dev, colors_dev);
 }
 
 // both passes of a row-band shard's draw() in one: every fragment with the flow pass's varying and the view pass's colour
 // side by side (32 bytes), rasterised, parted and - by the host or th_draw_sharded - exchanged once
-th_status th_draw_emit(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *count, void **keys_dev, void **colors_dev)
+static th_status draw_emit(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *count, void **keys_dev, void **colors_dev)
 {
-    if (th_status s = use(c)) return s;
     TH_REQUIRE(du && ru && count && keys_dev && colors_dev, "null argument");
     if (th_status s = texels_fit_keys(c, "target")) return s;
     if (th_status s = shared_uniforms(du, ru)) return s;
@@ -97,7 +90,13 @@ th_status th_draw_emit(th_context *c, const th_deposit_uniforms *du, const th_re
     if (th_status s = deposit_prepare(c, du, p)) return s;
     p.mode = 2;
     view_fields(c, ru, p);
-    return emit_parted(c, p, count, keys_dev, colors_dev);
+    return emit_parted(c, p, nullptr, count, keys_dev, colors_dev);
+}
+
+th_status th_draw_emit(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *count, void **keys_dev, void **colors_dev)
+{
+    if (th_status s = use(c)) return s;
+    return draw_emit(c, du, ru, count, keys_dev, colors_dev);
 }
 
 th_status th_deposit_set_halo(th_context *c, const void *lo_dev, const void *hi_dev)
@@ -137,25 +136,17 @@ static th_status merge_parted(th_context *c, const void *keys_dev, const void *c
     return TH_OK;
 }
 
-th_status th_deposit_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count)
+// ... as the three entry points and th_draw_sharded's passes go about it: a merge into the view buffer writes no state and no flow
+static th_status merge_pass(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count, int target)
 {
-    if (th_status s = use(c)) return s;
-    return merge_parted(c, keys_dev, colors_dev, count, 0);
+    if (th_status s = use(c, target != 0)) return s;
+    if (target != 0) if (th_status s = view_storage(c)) return s;
+    return merge_parted(c, keys_dev, colors_dev, count, target);
 }
 
-th_status th_view_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count)
-{
-    if (th_status s = use(c, true)) return s;
-    if (th_status s = view_storage(c)) return s;
-    return merge_parted(c, keys_dev, colors_dev, count, 1);
-}
-
-th_status th_draw_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count)
-{
-    if (th_status s = use(c, true)) return s;
-    if (th_status s = view_storage(c)) return s;
-    return merge_parted(c, keys_dev, colors_dev, count, 2);
-}
+th_status th_deposit_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count) { return merge_pass(c, keys_dev, colors_dev, count, 0); }
+th_status th_view_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count) { return merge_pass(c, keys_dev, colors_dev, count, 1); }
+th_status th_draw_merge(th_context *c, const void *keys_dev, const void *colors_dev, uint64_t count) { return merge_pass(c, keys_dev, colors_dev, count, 2); }
 
 // ---- draw() of a row-band shard, the exchange issued by the library over its own communicator ---------------------------------
 // A rank that fails on its own (a line that needs a halo row nobody supplied, an allocation) must not leave the others
@@ -309,23 +300,22 @@ static th_status exchange_fragments(th_context *c, const void *keys, const void 
 }
 
 // One pass: this band's fragments parted by owner -> all-to-all -> the owner's merge -> all-gather of the owned ranges.
-// view alone: the view pass; both: both passes over one rasterisation and one exchange (two all-gathers); neither: the flow pass.
-// emit(&count, &keys, &colors): stage 1, this band's fragments parted by owner - a built-in emit, or a draw program's
-// (th_draw_program_emit): whatever fails inside it fails on this rank alone, and travels with the counts
-extern "C++" template <class Emit>
-static th_status sharded_pass(th_context *c, bool view, bool both, Emit emit, uint64_t *fragments)
+// spec: the flow pass or the view pass, with the built-in vertex stage or a draw program's; null: both passes with the built-in stages of du and ru
+// over one rasterisation and one exchange (two all-gathers).  Whatever fails inside the emit (stage 1) fails on this rank alone, and travels with the counts
+static th_status sharded_pass(th_context *c, const PassSpec *spec, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
 {
+    const bool both = !spec, view = both || spec->pass == TH_PASS_VIEW;
     const int world = c->comm_world, rank = c->comm_rank;
     const size_t color_bytes = both ? 2 * sizeof(float4) : sizeof(float4);
     uint64_t count = 0;
     void *keys = nullptr, *colors = nullptr;
     // stage 1 - rasterise and part by owner
     th_status mine = injected(c, 2);
-    if (mine == TH_OK) mine = emit(&count, &keys, &colors);
+    if (mine == TH_OK) mine = both ? draw_emit(c, du, ru, &count, &keys, &colors) : pass_emit(c, *spec, &count, &keys, &colors);
     // (exchange_counts would pass kRetryInStreamOrder on as a wish for this very pass: no emit returns it, and if one ever did it is a failure here)
     if (mine == kRetryInStreamOrder) mine = fail(TH_ERR_HIP, "the stream-ordered emit asked for the stream-ordered pass");
     if (fragments) *fragments = mine == TH_OK ? count : 0;
-    c->last_draw.pipeline = TH_DRAW_STREAM; c->last_draw.fragments = mine == TH_OK ? count : 0; c->last_draw.crowded_fragments = 0;
+    draw_streamed(c, mine == TH_OK ? count : 0);
     const bool on_device = mine == TH_OK && count;
     if (on_device) {
         th::launch_owner_bounds(static_cast<const unsigned long long *>(keys), (uint32_t)count, (uint32_t)world, c->x_counts + kXBounds, c->stream);
@@ -350,23 +340,12 @@ static th_status sharded_pass(th_context *c, bool view, bool both, Emit emit, ui
     if (th_status s = agree_status(c, mine, "making room for the fragments it owns")) return s;
     // stage 3 - the exchange, the merge, the owned ranges back to everybody
     if (th_status s = exchange_fragments(c, keys, colors, color_bytes, x)) return s;
-    if (th_status s = both ? th_draw_merge(c, c->x_keys, c->x_colors, total)
-                           : (view ? th_view_merge(c, c->x_keys, c->x_colors, total) : th_deposit_merge(c, c->x_keys, c->x_colors, total))) return s;
+    if (th_status s = merge_pass(c, c->x_keys, c->x_colors, total, both ? 2 : (view ? 1 : 0))) return s;
     // the owners' texel ranges of the target(s) to every rank, in place
     const size_t texels = (size_t)c->fw * c->fh, chunk = (texels + (size_t)world - 1) / (size_t)world;
     std::vector<size_t> lo((size_t)world), hi((size_t)world);
     for (int r = 0; r < world; ++r) { lo[(size_t)r] = std::min(texels, (size_t)r * chunk); hi[(size_t)r] = std::min(texels, ((size_t)r + 1) * chunk); }
     return gather_owned(c, view, both, lo, hi);
-}
-
-// du alone: the flow pass; ru alone: the view pass; both: both passes in one - with the built-in stages
-static th_status sharded_pass(th_context *c, const th_deposit_uniforms *du, const th_render_uniforms *ru, uint64_t *fragments)
-{
-    const bool view = ru != nullptr, both = ru != nullptr && du != nullptr;
-    return sharded_pass(c, view, both, [&](uint64_t *count, void **keys, void **colors) -> th_status {
-        return both ? th_draw_emit(c, du, ru, count, keys, colors)
-                    : (view ? th_view_emit(c, ru, count, keys, colors) : th_deposit_emit(c, du, count, keys, colors));
-    }, fragments);
 }
 
 // ---- the same pass through the BINS, in its parts ------------------------------------------------------------------------------
@@ -616,7 +595,8 @@ th_status th_draw_sharded(th_context *c, const th_deposit_uniforms *du, const th
             const th_status s = sharded_pass_bins(c, d, r, n);
             if (s != kRetryInStreamOrder) return s;          // (on every rank together: the stream-ordered pass instead)
         }
-        return sharded_pass(c, d, r, n);
+        const PassSpec one = r ? builtin_pass(TH_PASS_VIEW, r) : builtin_pass(TH_PASS_FLOW, d);      // (d alone: the flow pass; r alone: the view pass)
+        return sharded_pass(c, d && r ? nullptr : &one, d, r, n);
     };
     if (ru && drawn_line_width(c, TH_PASS_FLOW) == drawn_line_width(c, TH_PASS_VIEW)) {
         // both passes draw the same lines: one rasterisation, one exchange of fragments carrying both varyings
@@ -657,15 +637,11 @@ th_status th_draw_program_sharded(th_context *c, th_program *flow_program, const
     c->halo_lo = c->halo_hi = nullptr;
     if (world > 1) if (th_status s = halo_exchange_stream(c)) return s;
     c->dep_owners = (uint32_t)world;
-    if (th_status s = sharded_pass(c, false, false, [&](uint64_t *count, void **keys, void **colors) -> th_status {
-            return flow_program ? th_draw_program_emit(c, flow_program, flow_uniforms, flow_bytes, TH_PASS_FLOW, count, keys, colors)
-                                : th_deposit_emit(c, du, count, keys, colors);
-        }, fragments)) return s;
+    const PassSpec flow = flow_program ? program_pass(TH_PASS_FLOW, flow_program, flow_uniforms, flow_bytes) : builtin_pass(TH_PASS_FLOW, du);
+    if (th_status s = sharded_pass(c, &flow, nullptr, nullptr, fragments)) return s;
     if (!view) return TH_OK;
-    return sharded_pass(c, true, false, [&](uint64_t *count, void **keys, void **colors) -> th_status {
-        return view_program ? th_draw_program_emit(c, view_program, view_uniforms, view_bytes, TH_PASS_VIEW, count, keys, colors)
-                            : th_view_emit(c, ru, count, keys, colors);
-    }, view_fragments);
+    const PassSpec seen = view_program ? program_pass(TH_PASS_VIEW, view_program, view_uniforms, view_bytes) : builtin_pass(TH_PASS_VIEW, ru);
+    return sharded_pass(c, &seen, nullptr, nullptr, view_fragments);
 }
 
 // ---- one process per GPU: the communicator of the job's ranks and the path's collective (th_comm.hip) --------------------

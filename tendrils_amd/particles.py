@@ -137,6 +137,22 @@ def shader_stages(shader):
     return vertex, fragment
 
 
+def program_block(program, uniforms):
+    """(the program's handle, its uniform block packed by field name from `uniforms` - None: it has none -, the block's size):
+    how every draw call hands a program over; the caller keeps the block alive across the call"""
+    block = program.pack(uniforms)
+    return program.handle, block, (0 if block is None else C.sizeof(block))
+
+
+def draw_program_args(program, uniforms):
+    """((program, uniforms, uniform_bytes) as th_draw_program_run / _emit / _sharded take a DrawProgram, its block - to be kept
+    alive across the call)"""
+    if not isinstance(program, DrawProgram) or not program.handle:
+        raise TypeError("draw: %r is no compiled DrawProgram" % (program,))
+    handle, block, size = program_block(program, uniforms)
+    return (handle, None if block is None else C.byref(block), size), block
+
+
 def draw_stages(vertex, fragment, uniforms, builtin):
     """(th_draw_stages, what it points to - to be kept alive across the call) of one pass: each program's block packed by field
     name from `uniforms`; `builtin`: the library's vertex-stage uniforms (a ctypes structure), read when vertex is None"""
@@ -144,15 +160,22 @@ def draw_stages(vertex, fragment, uniforms, builtin):
     for slot, program in (("vertex", vertex), ("fragment", fragment)):
         if program is None:
             continue
-        block = program.pack(uniforms)
+        handle, block, size = program_block(program, uniforms)
         keep.append(block)
-        setattr(stages, slot, program.handle)
+        setattr(stages, slot, handle)
         if block is not None:
             setattr(stages, slot + "_uniforms", C.cast(C.pointer(block), C.c_void_p))
-            setattr(stages, slot + "_uniform_bytes", C.sizeof(block))
+            setattr(stages, slot + "_uniform_bytes", size)
     if vertex is None:
         stages.builtin = C.cast(C.pointer(builtin), C.c_void_p)
     return stages, keep
+
+
+def deposit_uniforms(view_size, time, speed_limit):
+    """th_deposit_uniforms: what the library's flow stage takes of a frame - the one place that builds them"""
+    u = _capi.DepositUniforms(time=float(time), speedLimit=float(speed_limit))
+    u.viewSize[0], u.viewSize[1] = float(view_size[0]), float(view_size[1])
+    return u
 
 
 class StepProgram(Program):
@@ -371,16 +394,14 @@ class Particles:
     def deposit_flow(self, view_size, time, speed_limit):
         """The flow pass of Tendrils.draw(): (previous -> current) lines blended into the flow texture
         (src/index.js:295-303, src/particles.js:147-158).  Returns the number of fragments."""
-        u = _capi.DepositUniforms(time=float(time), speedLimit=float(speed_limit))
-        u.viewSize[0], u.viewSize[1] = float(view_size[0]), float(view_size[1])
+        u = deposit_uniforms(view_size, time, speed_limit)
         n = C.c_uint64(0)
         call("th_flow_deposit", self._ctx, C.byref(u), C.byref(n))
         return int(n.value)
 
     def export_lines(self, view_size, time, speed_limit):
         """The line list of draw() ([n, 12] float32: p0.xy, p1.xy, c0, c1 in stream order) for offline rendering."""
-        u = _capi.DepositUniforms(time=float(time), speedLimit=float(speed_limit))
-        u.viewSize[0], u.viewSize[1] = float(view_size[0]), float(view_size[1])
+        u = deposit_uniforms(view_size, time, speed_limit)
         n = C.c_uint64(0)
         call("th_export_lines", self._ctx, C.byref(u), None, 0, C.byref(n))
         out = np.empty((int(n.value), 12), np.float32)

@@ -158,18 +158,26 @@ def set_owners(tendrils, world):
     _capi.call("th_deposit_set_owners", tendrils.particles._ctx, int(world))
 
 
+def fragment_views(count, keys_ptr, colors_ptr, width):
+    """what an emit handed out as (keys int64[n], colors float32[n, width]) views of the library's memory (or empty tensors)"""
+    import torch
+    if count == 0:
+        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, width), dtype=torch.float32, device="cuda")
+    return device_view(keys_ptr, (count,), "<i8"), device_view(colors_ptr, (count, width), "<f4")
+
+
+def _emit(name, tendrils, *args, width=4):
+    """the emit `name` of this rank's context with `args` in front of its three outputs -> fragment_views"""
+    from . import _capi
+    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
+    _capi.call(name, tendrils.particles._ctx, *args, C.byref(n), C.byref(kp), C.byref(cp))
+    return fragment_views(n.value, kp.value, cp.value, width)
+
+
 def emit_fragments(tendrils):
     """th_deposit_emit on this rank's context -> (keys int64[n], colors float32[n, 4]) views (or empty tensors)."""
-    import torch
-    from . import _capi
-    p = tendrils.particles
-    u = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
-    u.viewSize[0], u.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
-    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
-    _capi.call("th_deposit_emit", p._ctx, C.byref(u), C.byref(n), C.byref(kp), C.byref(cp))
-    if n.value == 0:
-        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
-    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+    u = tendrils.deposit_uniforms()
+    return _emit("th_deposit_emit", tendrils, C.byref(u))
 
 
 def edge_rows(tendrils):
@@ -218,14 +226,8 @@ def flow_view(tendrils):
 def emit_view_fragments(tendrils):
     """th_view_emit on this rank's context -> (keys int64[n], colors float32[n, 4]) views (or empty tensors): the view
     pass's fragments of this band's lines, parted by owner like the flow pass's."""
-    import torch
-    from . import _capi
     u = tendrils.render_uniforms()
-    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
-    _capi.call("th_view_emit", tendrils.particles._ctx, C.byref(u), C.byref(n), C.byref(kp), C.byref(cp))
-    if n.value == 0:
-        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
-    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+    return _emit("th_view_emit", tendrils, C.byref(u))
 
 
 def merge_view_fragments(tendrils, keys, colors):
@@ -236,28 +238,14 @@ def merge_view_fragments(tendrils, keys, colors):
                    C.c_uint64(keys.numel()))
 
 
-def _program_block(program, uniforms):
-    """(program handle, byref of its packed uniform block or None, the block's size) - Tendrils._draw_program's arguments"""
-    from .particles import DrawProgram
-    if not isinstance(program, DrawProgram) or not program.handle:
-        raise TypeError("draw: %r is no compiled DrawProgram" % (program,))
-    block = program.pack(uniforms)
-    return program.handle, block, (None if block is None else C.byref(block)), (0 if block is None else C.sizeof(block))
-
-
 def emit_program_fragments(tendrils, program, which, uniforms):
     """th_draw_program_emit on this rank's context -> (keys int64[n], colors float32[n, 4]) views (or empty tensors): the
     fragments of this band's lines with `program` (a DrawProgram) as the vertex stage of pass `which` (TH_PASS_FLOW: merge
     with merge_fragments; TH_PASS_VIEW: with merge_view_fragments), parted by owner like the built-in stages'.  `uniforms`:
     the dict the program's block is packed from (Tendrils.draw_program_uniforms())."""
-    import torch
-    from . import _capi
-    handle, _block, ref, size = _program_block(program, uniforms)
-    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
-    _capi.call("th_draw_program_emit", tendrils.particles._ctx, handle, ref, size, int(which), C.byref(n), C.byref(kp), C.byref(cp))
-    if n.value == 0:
-        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
-    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+    from .particles import draw_program_args
+    args, _keep = draw_program_args(program, uniforms)
+    return _emit("th_draw_program_emit", tendrils, *args, int(which))
 
 
 def emit_stage_fragments(tendrils, vertex, fragment, which, uniforms):
@@ -265,31 +253,18 @@ def emit_stage_fragments(tendrils, vertex, fragment, which, uniforms):
     fragments of this band's lines with `fragment` (a FragmentProgram) run over them, behind `vertex` (a DrawProgram; None: the
     library's vertex stage of pass `which`), parted by owner; merged like every other pass's (merge_fragments /
     merge_view_fragments)."""
-    import torch
     from . import _capi
     from .particles import draw_stages
     builtin = tendrils.render_uniforms() if which == _capi.TH_PASS_VIEW else tendrils.deposit_uniforms()
     stages, _keep = draw_stages(vertex, fragment, uniforms, builtin)
-    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
-    _capi.call("th_draw_stages_emit", tendrils.particles._ctx, C.byref(stages), int(which), C.byref(n), C.byref(kp), C.byref(cp))
-    if n.value == 0:
-        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 4), dtype=torch.float32, device="cuda")
-    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 4), "<f4")
+    return _emit("th_draw_stages_emit", tendrils, C.byref(stages), int(which))
 
 
 def emit_draw_fragments(tendrils):
     """th_draw_emit -> (keys int64[n], colors float32[n, 8]): both passes' fragments of this band's lines in one - the flow
     pass's varying and the view pass's colour side by side -, parted by owner.  Needs both passes to draw with one line width."""
-    import torch
-    from . import _capi
-    d = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
-    d.viewSize[0], d.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
-    u = tendrils.render_uniforms()
-    n, kp, cp = C.c_uint64(0), C.c_void_p(), C.c_void_p()
-    _capi.call("th_draw_emit", tendrils.particles._ctx, C.byref(d), C.byref(u), C.byref(n), C.byref(kp), C.byref(cp))
-    if n.value == 0:
-        return torch.empty(0, dtype=torch.int64, device="cuda"), torch.empty((0, 8), dtype=torch.float32, device="cuda")
-    return device_view(kp.value, (n.value,), "<i8"), device_view(cp.value, (n.value, 8), "<f4")
+    d, u = tendrils.deposit_uniforms(), tendrils.render_uniforms()
+    return _emit("th_draw_emit", tendrils, C.byref(d), C.byref(u), width=8)
 
 
 def merge_draw_fragments(tendrils, keys, colors):
@@ -400,6 +375,29 @@ def _has_draw_program(tendrils):
     return any(stage is not None for which in ("flowShader", "renderShader") for stage in shader_stages(getattr(tendrils, which, None)))
 
 
+def _through_owners(dist, tendrils, keys, colors, merge, planes):
+    """a pass's trip through the owners: every part of what this band emitted to its owner (all-to-all), the owner's `merge`,
+    the owned ranges of each of `planes` (flow_view, view_view) back to every rank; returns the fragments this band emitted"""
+    texels = tendrils.flow.shape[0] * tendrils.flow.shape[1]
+    rkeys, rcolors = _exchange(dist, keys, colors, texels)
+    merge(tendrils, rkeys, rcolors)
+    for plane in planes:
+        _gather_owned(dist, plane(tendrils), texels)
+    return int(keys.numel())
+
+
+def _emit_pass(tendrils, which, stages, uniforms):
+    """this band's fragments of pass `which` with `stages` = (vertex, fragment): the fragment stage's emit, else the vertex
+    program's, else the built-in one"""
+    from . import _capi
+    vertex, fragment = stages
+    if fragment is not None:
+        return emit_stage_fragments(tendrils, vertex, fragment, which, uniforms)
+    if vertex is not None:
+        return emit_program_fragments(tendrils, vertex, which, uniforms)
+    return emit_view_fragments(tendrils) if which == _capi.TH_PASS_VIEW else emit_fragments(tendrils)
+
+
 def draw_sharded_programs(dist, tendrils, view=False):
     """draw() of a row-band shard with tendrils.flowShader / renderShader as the stages of their passes (a DrawProgram: the vertex
     stage; a FragmentProgram or a pair with one: only with `dist`, the host's exchange, around th_draw_stages_emit):
@@ -408,54 +406,40 @@ def draw_sharded_programs(dist, tendrils, view=False):
     needs sharding.comm_init).  Both programs get Tendrils.draw_program_uniforms(), what the unsharded draw() hands them.
     Returns (fragments, view_fragments) of this band."""
     from . import _capi
-    from .particles import shader_stages
+    from .particles import draw_program_args, shader_stages
     uniforms = tendrils.draw_program_uniforms()
-    (flow_shader, flow_fragment), (view_shader, view_fragment) = shader_stages(tendrils.flowShader), shader_stages(tendrils.renderShader if view else None)
+    stages = shader_stages(tendrils.flowShader), shader_stages(tendrils.renderShader if view else None)
     if dist is None:
+        (flow_shader, flow_fragment), (view_shader, view_fragment) = stages
         if flow_fragment is not None or view_fragment is not None:
             raise NotImplementedError("draw: the library-issued exchange (th_draw_program_sharded / th_draw_sharded) carries no fragment stage - "
                                       "run the bands under a torch.distributed job (Tendrils(dist=...): sharding.draw_sharded_programs "
                                       "around th_draw_stages_emit)")
-        none = (None, None, None, 0)
-        fp, fblock, fref, fsize = _program_block(flow_shader, uniforms) if flow_shader is not None else none
-        vp, vblock, vref, vsize = _program_block(view_shader, uniforms) if view_shader is not None else none
-        d = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
-        d.viewSize[0], d.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
-        u = tendrils.render_uniforms() if view else None
+        if flow_shader is None and view_shader is None:      # (a render shader without a view pass: the built-in flow pass is all there is)
+            return _draw_sharded_builtin(tendrils, False), 0
+        none = ((None, None, 0), None)
+        flow_args, _flow_block = draw_program_args(flow_shader, uniforms) if flow_shader is not None else none
+        view_args, _view_block = draw_program_args(view_shader, uniforms) if view_shader is not None else none
+        d, u = tendrils.deposit_uniforms(), tendrils.render_uniforms() if view else None
         n, vn = C.c_uint64(0), C.c_uint64(0)
-        if fp is None and vp is None:              # (a render shader without a view pass: the built-in flow pass is all there is)
-            _capi.call("th_draw_sharded", tendrils.particles._ctx, C.byref(d), None, C.byref(n))
-            return int(n.value), 0
-        _capi.call("th_draw_program_sharded", tendrils.particles._ctx, fp, fref, fsize, C.byref(d),
-                   vp, vref, vsize, C.byref(u) if view else None, C.byref(n), C.byref(vn))
+        _capi.call("th_draw_program_sharded", tendrils.particles._ctx, *flow_args, C.byref(d), *view_args, C.byref(u) if view else None,
+                   C.byref(n), C.byref(vn))
         return int(n.value), int(vn.value)
-    world = dist.get_world_size()
-    texels = tendrils.flow.shape[0] * tendrils.flow.shape[1]
     _exchange_halos(dist, tendrils)
-    set_owners(tendrils, world)
-    if flow_fragment is not None:
-        keys, colors = emit_stage_fragments(tendrils, flow_shader, flow_fragment, _capi.TH_PASS_FLOW, uniforms)
-    elif flow_shader is not None:
-        keys, colors = emit_program_fragments(tendrils, flow_shader, _capi.TH_PASS_FLOW, uniforms)
-    else:
-        keys, colors = emit_fragments(tendrils)
-    fragments = int(keys.numel())
-    rkeys, rcolors = _exchange(dist, keys, colors, texels)
-    merge_fragments(tendrils, rkeys, rcolors)
-    _gather_owned(dist, flow_view(tendrils), texels)
-    if not view:
-        return fragments, 0
-    if view_fragment is not None:
-        keys, colors = emit_stage_fragments(tendrils, view_shader, view_fragment, _capi.TH_PASS_VIEW, uniforms)
-    elif view_shader is not None:
-        keys, colors = emit_program_fragments(tendrils, view_shader, _capi.TH_PASS_VIEW, uniforms)
-    else:
-        keys, colors = emit_view_fragments(tendrils)
-    view_fragments = int(keys.numel())
-    rkeys, rcolors = _exchange(dist, keys, colors, texels)
-    merge_view_fragments(tendrils, rkeys, rcolors)
-    _gather_owned(dist, view_view(tendrils), texels)
-    return fragments, view_fragments
+    set_owners(tendrils, dist.get_world_size())
+    return _draw_passes(dist, tendrils, view, stages, uniforms)
+
+
+def _draw_passes(dist, tendrils, view, stages, uniforms):
+    """the flow pass and - `view` - the view pass, each emitted with its `stages` and taken through the owners: (fragments,
+    view_fragments) of this band"""
+    from . import _capi
+    passes = ((_capi.TH_PASS_FLOW, merge_fragments, flow_view), (_capi.TH_PASS_VIEW, merge_view_fragments, view_view))
+    counts = [0, 0]
+    for which, merge, plane in passes[:2 if view else 1]:
+        keys, colors = _emit_pass(tendrils, which, stages[which], uniforms)
+        counts[which] = _through_owners(dist, tendrils, keys, colors, merge, (plane,))
+    return tuple(counts)
 
 
 def draw_sharded(dist, tendrils, view=False):
@@ -465,45 +449,30 @@ def draw_sharded(dist, tendrils, view=False):
     With tendrils.flowShader / renderShader set: draw_sharded_programs."""
     if _has_draw_program(tendrils):
         return draw_sharded_programs(dist, tendrils, view)[0]
-    world = dist.get_world_size()
-    fw, fh = tendrils.flow.shape
-    texels = fw * fh
     # edge rows of both state buffers to the neighbouring bands (the fp32 row lookup of the vertex stream can land
     # one row beside a line's own row for some texture heights)
     _exchange_halos(dist, tendrils)
-    set_owners(tendrils, world)
+    set_owners(tendrils, dist.get_world_size())
     if view and same_line_widths(tendrils):
         # both passes draw the same lines: one rasterisation, one exchange of fragments carrying both varyings, two all-gathers
         keys, colors = emit_draw_fragments(tendrils)
-        fragments = int(keys.numel())
-        rkeys, rcolors = _exchange(dist, keys, colors, texels)
-        merge_draw_fragments(tendrils, rkeys, rcolors)
-        _gather_owned(dist, flow_view(tendrils), texels)
-        _gather_owned(dist, view_view(tendrils), texels)
-        return fragments
-    keys, colors = emit_fragments(tendrils)
-    fragments = int(keys.numel())
-    rkeys, rcolors = _exchange(dist, keys, colors, texels)
-    merge_fragments(tendrils, rkeys, rcolors)
-    _gather_owned(dist, flow_view(tendrils), texels)
-    if view:
-        keys, colors = emit_view_fragments(tendrils)
-        rkeys, rcolors = _exchange(dist, keys, colors, texels)
-        merge_view_fragments(tendrils, rkeys, rcolors)
-        _gather_owned(dist, view_view(tendrils), texels)
-    return fragments
+        return _through_owners(dist, tendrils, keys, colors, merge_draw_fragments, (flow_view, view_view))
+    return _draw_passes(dist, tendrils, view, ((None, None), (None, None)), None)[0]
 
 
 def draw_sharded_native(tendrils, view=False):
     """The same draw() with the exchange issued by the LIBRARY over its own communicator (th_draw_sharded; needs
     sharding.comm_init): what a Node process per GPU calls as drawSharded - no torch.distributed in the data path.
     With tendrils.flowShader / renderShader set: th_draw_program_sharded (draw_sharded_programs)."""
-    from . import _capi
     if _has_draw_program(tendrils):
         return draw_sharded_programs(None, tendrils, view)[0]
-    d = _capi.DepositUniforms(time=float(tendrils.timer.time), speedLimit=float(tendrils.state["speedLimit"]))
-    d.viewSize[0], d.viewSize[1] = float(tendrils.viewSize[0]), float(tendrils.viewSize[1])
-    n = C.c_uint64(0)
+    return _draw_sharded_builtin(tendrils, view)
+
+
+def _draw_sharded_builtin(tendrils, view):
+    """th_draw_sharded: the library's own stages"""
+    from . import _capi
+    d, n = tendrils.deposit_uniforms(), C.c_uint64(0)
     u = tendrils.render_uniforms() if view else None
     _capi.call("th_draw_sharded", tendrils.particles._ctx, C.byref(d), C.byref(u) if view else None, C.byref(n))
     return int(n.value)

@@ -14,7 +14,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import LOGIC, DrawProgram, Particles, Program, ScreenProgram, StepProgram, draw_stages, run_pass, shader_stages
+from .particles import (LOGIC, Particles, Program, ScreenProgram, StepProgram, deposit_uniforms, draw_program_args, draw_stages, run_pass,
+                        shader_stages)
 from .timer import Timer
 
 
@@ -488,60 +489,71 @@ class Tendrils:
     def draw(self):                                            # src/index.js:278-340
         """The flow pass - particle lines into the flow texture, so that particles respond to each other's wake - and,
         with renderView, the view pass: the same lines into the RGBA8 view buffer (after the clear / fade the state
-        asks for).  Both passes draw the same lines: one call rasterises and sorts them once (th_draw) when they draw them
-        with the same width."""
+        asks for).  Each pass runs the stages of its shader - flowShader / renderShader: a fragment stage (th_draw_stages_run,
+        always stream-ordered), else a vertex program (th_draw_program_run), else the library's own stage; both passes with the
+        library's stages draw the same lines, and one call rasterises and sorts them once (th_draw) when they draw them with
+        the same width.  Programs get draw_program_uniforms(), packed into each program's uniform block by field name.  A
+        program pass takes the pipeline the library's own pass of this context would (Particles.draw_pipeline / TH_DRAW: binned
+        where the shape and the ring allow it, else stream-ordered - include/tendrils_hip.h "draw programs"); through the bins
+        a tile-sorted ring stays sorted, so step(); draw() keeps it."""
         self.line_widths()
-        if any(stage is not None for stage in shader_stages(self.flowShader) + shader_stages(self.renderShader)):
-            return self._draw_programs()
-        if self.dist is not None:          # row-band shard of a torch.distributed job: emit / exchange / merge, pass by pass
-            from .sharding import draw_sharded
-            if self.renderView:            # (every rank holds the whole view buffer: the clear / fade are the same everywhere)
-                self._bind_view(self.buffers[0] if self.buffers else None)
-                if self.state["autoClearView"]:
-                    self.clearView()
-                if self.state["autoFade"]:
-                    self.drawFade()
-            self.fragments = draw_sharded(self.dist, self, view=self.renderView)
-            self.view_fragments = self.fragments if self.renderView else 0
+        view = self.renderView
+        programs = any(stage is not None for stage in shader_stages(self.flowShader) + shader_stages(self.renderShader))
+        if self._sharded():
+            # a row band: the passes go through the owners' exchange - the host's, of a torch.distributed job, or the library's
+            # own over the communicator the ranks joined with sharding.comm_init() (th_draw_sharded / th_draw_program_sharded;
+            # what the Node host runs); every rank calls draw() together.  Every rank holds the whole view buffer: the bind, the
+            # clear and the fade are the same everywhere, and come first
+            from . import sharding
+            if view:
+                self._view_prologue()
+            if programs:
+                self.fragments, self.view_fragments = sharding.draw_sharded_programs(self.dist, self, view=view)
+                return self
+            self.fragments = sharding.draw_sharded(self.dist, self, view=view) if self.dist is not None else sharding.draw_sharded_native(self, view=view)
+            self.view_fragments = self.fragments if view else 0
             return self
-        row0, rows, gh = self._band
-        if rows and rows != (gh or self.state["rootNum"]):
-            # a row band without a torch.distributed host: the exchange is the library's, over the communicator the ranks
-            # joined with sharding.comm_init() (th_draw_sharded; what the Node host runs) - every rank calls draw() together
-            from .sharding import draw_sharded_native
-            if self.renderView:
-                self._bind_view(self.buffers[0] if self.buffers else None)
-                if self.state["autoClearView"]:
-                    self.clearView()
-                if self.state["autoFade"]:
-                    self.drawFade()
-            self.fragments = draw_sharded_native(self, view=self.renderView)
-            self.view_fragments = self.fragments if self.renderView else 0
+        if view and not programs:
+            # (the clear and the fade only touch the view buffer: it does not matter that the flow pass comes after them here)
+            self._view_prologue()
+            d, u, n = self.deposit_uniforms(), self.render_uniforms(), C.c_uint64(0)
+            call("th_draw", self.particles._ctx, C.byref(d), C.byref(u), C.byref(n))
+            self.fragments = self.view_fragments = int(n.value)
             return self
-        if not self.renderView:
-            self.fragments = self.particles.deposit_flow(self.viewSize, self.timer.time, self.state["speedLimit"])
-            return self
-        # (the clear and the fade only touch the view buffer: it does not matter that the flow pass comes after them here)
-        # The view goes to buffers[0] when there are buffers, else to the screen (src/index.js:318-325) - unless autoClearView
-        # comes in between: clearView() leaves the SCREEN bound (src/index.js:226), there as here.
+        uniforms = self.draw_program_uniforms() if programs else None
+        self.fragments = self._draw_pass(_capi.TH_PASS_FLOW, self.flowShader, uniforms)
+        if view:
+            self._view_prologue()
+            self.view_fragments = self._draw_pass(_capi.TH_PASS_VIEW, self.renderShader, uniforms)
+        return self
+
+    def _view_prologue(self):
+        """what comes in front of the view pass: the view goes to buffers[0] when there are buffers, else to the screen
+        (src/index.js:318-325) - unless autoClearView comes in between: clearView() leaves the SCREEN bound (src/index.js:226),
+        there as here - then the fade"""
         self._bind_view(self.buffers[0] if self.buffers else None)
         if self.state["autoClearView"]:
             self.clearView()
         if self.state["autoFade"]:
             self.drawFade()
-        d = _capi.DepositUniforms(time=float(self.timer.time), speedLimit=float(self.state["speedLimit"]))
-        d.viewSize[0], d.viewSize[1] = float(self.viewSize[0]), float(self.viewSize[1])
+
+    def _draw_pass(self, which, shader, uniforms):
+        """one pass of a whole texture with the stages of `shader`; returns its fragments"""
+        vertex, fragment = shader_stages(shader)
+        if fragment is not None:
+            return self._draw_stages(vertex, fragment, which, uniforms)
+        if vertex is not None:
+            return self._draw_program(vertex, which, uniforms)
+        if which == _capi.TH_PASS_FLOW:
+            return self.particles.deposit_flow(self.viewSize, self.timer.time, self.state["speedLimit"])
         u, n = self.render_uniforms(), C.c_uint64(0)
-        call("th_draw", self.particles._ctx, C.byref(d), C.byref(u), C.byref(n))
-        self.fragments = self.view_fragments = int(n.value)
-        return self
+        call("th_view_draw", self.particles._ctx, C.byref(u), C.byref(n))
+        return int(n.value)
 
     def _draw_program(self, program, which, uniforms):
-        if not isinstance(program, DrawProgram) or not program.handle:
-            raise TypeError("draw: %r is no compiled DrawProgram" % (program,))
-        block, n = program.pack(uniforms), C.c_uint64(0)
-        call("th_draw_program_run", self.particles._ctx, program.handle, None if block is None else C.byref(block),
-             0 if block is None else C.sizeof(block), which, C.byref(n))
+        args, _keep = draw_program_args(program, uniforms)
+        n = C.c_uint64(0)
+        call("th_draw_program_run", self.particles._ctx, *args, which, C.byref(n))
         return int(n.value)
 
     def _draw_stages(self, vertex, fragment, which, uniforms):
@@ -555,9 +567,7 @@ class Tendrils:
 
     def deposit_uniforms(self):
         """the library's flow stage's uniforms of this frame (th_deposit_uniforms)"""
-        d = _capi.DepositUniforms(time=float(self.timer.time), speedLimit=float(self.state["speedLimit"]))
-        d.viewSize[0], d.viewSize[1] = float(self.viewSize[0]), float(self.viewSize[1])
-        return d
+        return deposit_uniforms(self.viewSize, self.timer.time, self.state["speedLimit"])
 
     def _sharded(self):
         """this context is a row-band shard: of a torch.distributed job, or a band narrower than the texture"""
@@ -576,54 +586,6 @@ class Tendrils:
                         geomRes=[p.shape[0], 2 * height] if whole else p.geomShape, colorMapRes=self.colorMap.shape)
         uniforms.update(self.uniforms["render"])
         return uniforms
-
-    def _draw_programs(self):
-        """draw() with a caller's stages in one pass or both (src/index.js:278-340): the flow pass, then - with
-        renderView - the clear, the fade and the view pass; each pass runs its programs or, where there is none, the library's
-        own stage.  A pass with a fragment stage goes through th_draw_stages_run and is always stream-ordered.  Both programs get what the reference hands both shaders (src/index.js:284-293): the state, time, viewSize,
-        viewRes, colorMapRes - and dataRes, geomRes (src/particles.js:149-155) - with self.uniforms["render"] on top, packed
-        into each program's uniform block by field name.  A program pass takes the pipeline the library's own pass of this
-        context would (Particles.draw_pipeline / TH_DRAW: binned where the shape and the ring allow it, else stream-ordered -
-        include/tendrils_hip.h "draw programs"); through the bins a tile-sorted ring stays sorted, so step(); draw() keeps it."""
-        p = self.particles
-        uniforms = self.draw_program_uniforms()
-        if self._sharded():
-            # a row band: the passes go through the owners' exchange (sharding.draw_sharded_programs) - the host's, of a
-            # torch.distributed job, or the library's own (th_draw_program_sharded); every rank calls draw() together.  Every
-            # rank holds the whole view buffer: the bind, the clear and the fade are the same everywhere, and come first
-            from .sharding import draw_sharded_programs
-            if self.renderView:
-                self._bind_view(self.buffers[0] if self.buffers else None)
-                if self.state["autoClearView"]:
-                    self.clearView()
-                if self.state["autoFade"]:
-                    self.drawFade()
-            self.fragments, self.view_fragments = draw_sharded_programs(self.dist, self, view=self.renderView)
-            return self
-        vertex, fragment = shader_stages(self.flowShader)
-        if fragment is not None:
-            self.fragments = self._draw_stages(vertex, fragment, _capi.TH_PASS_FLOW, uniforms)
-        elif vertex is not None:
-            self.fragments = self._draw_program(vertex, _capi.TH_PASS_FLOW, uniforms)
-        else:
-            self.fragments = p.deposit_flow(self.viewSize, self.timer.time, self.state["speedLimit"])
-        if not self.renderView:
-            return self
-        self._bind_view(self.buffers[0] if self.buffers else None)
-        if self.state["autoClearView"]:
-            self.clearView()
-        if self.state["autoFade"]:
-            self.drawFade()
-        vertex, fragment = shader_stages(self.renderShader)
-        if fragment is not None:
-            self.view_fragments = self._draw_stages(vertex, fragment, _capi.TH_PASS_VIEW, uniforms)
-        elif vertex is not None:
-            self.view_fragments = self._draw_program(vertex, _capi.TH_PASS_VIEW, uniforms)
-        else:
-            u, n = self.render_uniforms(), C.c_uint64(0)
-            call("th_view_draw", p._ctx, C.byref(u), C.byref(n))
-            self.view_fragments = int(n.value)
-        return self
 
     def export_lines(self, view=False):
         """Trail export: the (previous -> current) line list this frame's draw() is made of (build-defined): [n, 12]

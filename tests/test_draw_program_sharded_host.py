@@ -74,16 +74,23 @@ def test_the_release_library_exports_both_calls(lib):
 
 def test_the_sharded_route_packs_uniforms_with_the_unsharded_function():
     """one function makes the dict a program's block is packed from - Tendrils.draw_program_uniforms - and both routes call it:
-    _draw_programs for the unsharded draw(), sharding.draw_sharded_programs for a band's"""
-    from tendrils_amd import sharding
+    Tendrils.draw for the unsharded passes, sharding.draw_sharded_programs for a band's.  Likewise th_deposit_uniforms: nothing in
+    tendrils.py or sharding.py constructs one but a deposit_uniforms() - Tendrils.deposit_uniforms hands the frame's scalars to
+    particles.deposit_uniforms, which Particles.deposit_flow and export_lines (they take scalars) build theirs with too"""
+    from tendrils_amd import particles, sharding, tendrils
     from tendrils_amd.tendrils import Tendrils
-    local, sharded = inspect.getsource(Tendrils._draw_programs), inspect.getsource(sharding.draw_sharded_programs)
+    local, sharded = inspect.getsource(Tendrils.draw), inspect.getsource(sharding.draw_sharded_programs)
     assert "self.draw_program_uniforms()" in local and "tendrils.draw_program_uniforms()" in sharded
     for source in (local, sharded):                # ... and neither builds a dict of its own
         assert "dict(" not in source and ".update(" not in source
     assert "draw_sharded_programs" in local
     for route in (sharding.draw_sharded, sharding.draw_sharded_native):
         assert "draw_sharded_programs" in inspect.getsource(route)
+    builder = inspect.getsource(particles.deposit_uniforms)
+    assert "DepositUniforms(" in builder and "deposit_uniforms(" in inspect.getsource(Tendrils.deposit_uniforms)
+    for module in (tendrils, sharding):
+        assert "DepositUniforms(" not in inspect.getsource(module), module.__name__
+    assert "DepositUniforms(" not in inspect.getsource(particles).replace(builder, "")
 
 
 class _Stub:

@@ -318,6 +318,59 @@ def test_emit_and_merge_equal_the_run(programs, owners):
             em.dispose()
 
 
+# ---- 5b. a stage is its pass's alone -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("policy", ["auto", "bins"])
+def test_builtin_passes_after_a_stage_pass_are_a_fresh_contexts(programs, policy):
+    """After passes with a fragment stage - run, and emitted as the band of all rows - the built-in flow pass and view pass of the
+    same context draw the bits, report the fragments and take the pipeline of a context that never saw a stage: nothing of a
+    stage outlives its pass (a stage pass itself is stream-ordered whatever the policy; reuses nothing, leaves nothing to reuse)"""
+    from tendrils_amd import sharding
+    n, view = 16, (64, 48)
+    cur, prev = deposit_hashed_inputs(n, 55, 1.05, 0.08, 3)
+    base, cmap = base_flow(view, 56), color_map()
+    staged, fresh = make(view, cur, prev, base, cmap), make(view, cur, prev, base, cmap)
+    for t in (staged, fresh):
+        t.particles.draw_pipeline(policy)
+    u = uniforms_of(staged)
+    pipeline = 1 if policy == "bins" else STREAM     # (TH_DRAW_BINS; auto: 256 particles are never tile-sorted)
+
+    def builtin_run(t):
+        t.flow.set_pixels(base)
+        t.clearView()
+        counts = []
+        for which in (FLOW_PASS, VIEW_PASS):         # (the view pass may reuse the flow pass's geometry: c->drawn)
+            counts.append(plain_run(t, which, None, u))
+            assert last_draw(t) == (pipeline, counts[-1])
+        return counts, t.flow.read(), t.read_view()
+
+    def builtin_emit(t):
+        t.flow.set_pixels(base)
+        t.clearView()
+        counts = []
+        for emit, merge in ((sharding.emit_fragments, sharding.merge_fragments), (sharding.emit_view_fragments, sharding.merge_view_fragments)):
+            keys, colors = emit(t)
+            counts.append(int(keys.numel()))
+            merge(t, keys, colors)
+        return counts, t.flow.read(), t.read_view()
+
+    want_run, want_emit = builtin_run(fresh), builtin_emit(fresh)
+    assert want_run[0][0] == want_run[0][1] == want_emit[0][0] == want_emit[0][1] > 50
+    for vertex_too in (False, True):
+        for which in (FLOW_PASS, VIEW_PASS):
+            assert stages_run(staged, which, vertex_of(programs, which, vertex_too), programs["vignette"], u) > 50
+            assert last_draw(staged)[0] == STREAM
+        got = builtin_run(staged)
+        assert got[0] == want_run[0] and bits_equal(got[1], want_run[1]).all() and (got[2] == want_run[2]).all(), vertex_too
+        for which in (FLOW_PASS, VIEW_PASS):
+            keys, _colors = sharding.emit_stage_fragments(staged, vertex_of(programs, which, vertex_too), programs["vignette"], which, u)
+            assert int(keys.numel()) > 50
+        got = builtin_emit(staged)
+        assert got[0] == want_emit[0] and bits_equal(got[1], want_emit[1]).all() and (got[2] == want_emit[2]).all(), vertex_too
+    assert not bits_equal(want_run[1], base).all() and want_run[2].any()
+    staged.dispose()
+    fresh.dispose()
+
+
 # ---- 6. packed rings and tile-sorted rings -------------------------------------------------------------------------------------------
 def sorted_buffers(t):
     from tendrils_amd import _capi
