@@ -829,7 +829,7 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
 
 /* Per-context switches between equivalent paths (build-defined; no switch changes a result - the parity suites rerun under
  * each, tests/conftest.py).  A context starts from the environment variables of the same names, read by th_create
- * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS, TH_HASH_WINDOW;
+ * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS, TH_HASH_WINDOW, TH_STAGE_BINS;
  * TH_DRAW=stream|bins sets what TH_DRAW_AUTO means).
  *   TH_OPT_BUCKET          tile-sorted slot order never (0) / always (1) / when it pays (-1, default)
  *   TH_OPT_RESORT_STEPS    re-sort period of single-step launches (default 64)
@@ -861,14 +861,19 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
  *   TH_OPT_HASH_WINDOW_LAUNCHES  (read-only) fused launches of this context that ran over the window so far
  *   TH_OPT_DENSE_SORTS     (read-only) plain re-sorts of this context (histogram pass + move: th_step_n's, a packed ring's, the one
  *                          beside a draw) whose two passes counted every sort class in LDS - flow fields of up to 2047 tiles,
- *                          1080p among them; larger fields count through a small table per workgroup */
+ *                          1080p among them; larger fields count through a small table per workgroup
+ *   TH_OPT_STAGE_BINS      (TH_STAGE_BINS) a pass of th_draw_stages_run with a caller's FRAGMENT stage takes the pipeline the same
+ *                          pass without the stage would take - through the bins the stage runs over the page store, in place, between
+ *                          the emitting pass and the blends (th_fragment_bins_kernel), and the ring keeps its slot order (1); such a
+ *                          pass is stream-ordered under every policy and pulls the ring to texel order (0, default) */
 enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH_OPT_FUSE = 3, TH_OPT_GRAPH = 4,
        TH_OPT_FORCE_GENERIC = 5, TH_OPT_DRAW_REUSE = 6, TH_OPT_BINS_POOL = 7,
 #ifdef TH_TESTING
        TH_OPT_INJECT_FAILURE = 8,
 #endif
        TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12,
-       TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14, TH_OPT_DENSE_SORTS = 15 };
+       TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14, TH_OPT_DENSE_SORTS = 15,
+       TH_OPT_STAGE_BINS = 16 };
 th_status th_option_set(th_context *ctx, int32_t option, int64_t value);
 th_status th_option_get(th_context *ctx, int32_t option, int64_t *value);
 

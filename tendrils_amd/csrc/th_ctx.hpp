@@ -75,6 +75,7 @@ struct th_options {
     int spawn_chunk_rows = 0;            // TH_SPAWN_CHUNK_ROWS: rows of a band that th_spawn_sample_sharded fetches at a time (0: by the scratch budget)
     bool async_sort = true;              // TH_ASYNC_SORT: a frame loop's re-sort runs beside its draw() instead of inside two of its steps (th_step.hip)
     bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
+    bool stage_bins = false;             // TH_STAGE_BINS: a pass with a caller's fragment stage takes the pipeline the pass without it would (th_draw.hip: deposit_prepare)
 };
 
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
@@ -98,7 +99,8 @@ struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel / th_fragment_kernel
-    hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order)
+    hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order); a fragment
+                                         // program's third: th_fragment_bins_kernel (the fragments of a binned pass, where they lie in the page store)
     hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines); a fragment
                                          // program's second: th_fragment_band_kernel (the fragments of an emit, under their 64-bit keys)
     hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
@@ -111,7 +113,7 @@ struct ProgramModule {
 }  // namespace thi
 
 // A caller's fragment stage as one pass carries it (th_fragprog.hip: th_draw_stages_run / _emit load the module): an argument from
-// the pass's entry point down to where its fragments lie (deposit_run, emit_parted), null when the pass has none - beside
+// the pass's entry point down to where its fragments lie (deposit_run, deposit_run_bins, emit_parted), null when the pass has none - beside
 // th::DepositParams, which is a kernel's argument and knows nothing of it.
 namespace thi {
 struct FragmentStage {
@@ -448,7 +450,7 @@ template <class Args> struct ProgramKernArgs {
 th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *record, size_t bytes);
 template <class Args> th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, ProgramKernArgs<Args> &k) { return program_launch(c, fn, lanes, &k, sizeof k); }
 // ... on a grid of the caller's (256-lane workgroups): a step program over tile-sorted slots takes the built-in fused launch's
-th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes);
+th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes, int grid_y = 1);
 // ---- th_drawprog.hip -------------------------------------------------------------------------------------------------
 // s.vertex over the lines of the (prepared) pass `p`, into the vertex buffer its raster stage draws from: a local pass's over the order its pipeline walks (bins: the slots), a band's by local row
 th_status vertex_stage_run(th_context *c, const PassSpec &s, th::DepositParams &p, bool bins);
@@ -457,6 +459,10 @@ th_status vertex_stage_band(th_context *c, const PassSpec &s, th::DepositParams 
 // `stage` over the `total` fragments (not 0) the scatter of the (prepared) pass `p` has just written: p.keys64 / p.keys and
 // p.colors, fragment i in place i of both - before anything sorts or parts them
 th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total);
+// ... and over the fragments an emitting attempt of the binned pass `p` (not mode 2) has just left in the page store: p.frag_keys /
+// p.colors at every place the bins' lists handed out - before anything blends, whether or not the host accepts the attempt
+// (crowded: the last draw put most of its fragments into crowded bins - a bin's places are dealt to more workgroups)
+th_status fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
 // an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format
@@ -500,15 +506,17 @@ int deposit_texel_bits(const th_context *c);
 float drawn_line_width(const th_context *c, int pass);
 // program: the pass of a caller's draw program (th_drawprog.hip) - its binned form walks the vertex records in texel order over
 // a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list); stage: the
-// pass's fragment stage, or null - with one the pass is stream-ordered, and no frame of the policy's count
+// pass's fragment stage, or null - with one the pass is stream-ordered, and no frame of the policy's count, unless
+// TH_OPT_STAGE_BINS is on: then it takes the pipeline the pass without the stage would
 th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false, const FragmentStage *stage = nullptr);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
 th_status deposit_temp(th_context *c, size_t need);
 // the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, `stage` (or null) over the fragments, sort by texel, blend
 th_status deposit_run(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *fragments);
-// ... and the binned one (program: p.vertices holds a draw program's records).  kRetryInStreamOrder: see below
-th_status deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program = false);
+// ... and the binned one (program: p.vertices holds a draw program's records; `stage`, or null, over the page store behind every
+// emitting attempt, before anything blends).  kRetryInStreamOrder: see below
+th_status deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program = false, const FragmentStage *stage = nullptr);
 th_status view_storage(th_context *c);
 void view_fields(th_context *c, const th_render_uniforms *u, th::DepositParams &p);
 th_status view_params(th_context *c, const th_render_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, const FragmentStage *stage = nullptr);
@@ -517,7 +525,7 @@ constexpr th_status kRetryInStreamOrder = -1;        // (internal) the binned pa
 th_status bins_store_for(th_context *c, th::DepositParams &p, uint32_t at_least);
 th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t pool);
 th_status bins_table_widen(th_context *c, th::DepositParams &p, bool keep);       // kRetryInStreamOrder: as wide as it goes (or no memory)
-th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program = false);
+th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program = false, const FragmentStage *stage = nullptr);
 void bins_pass_expect(th_context *c, th::DepositParams &p);          // before the plan's kernels are launched with p ...
 th_status bins_pass_totals(th_context *c, const th::DepositParams &p);  // ... their totals in c->bins_totals_host
 th_status bins_pass_finish(th_context *c, th::DepositParams &p, uint64_t *fragments, bool blended_early);
@@ -545,7 +553,8 @@ th_status texels_fit_keys(const th_context *c, const char *target);
 th_status emit_parted(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *count, void **keys_dev, void **colors_dev);
 
 // One pass of a local draw: prepare(p, first, &bins) readies `p` for an attempt - the first may take the bins - and says which
-// pipeline it takes (never the bins with `stage`); a binned pass that gives up before blending is repeated in stream order, and so are the other passes of its frame.
+// pipeline it takes (with `stage` the bins only under TH_OPT_STAGE_BINS); a binned pass that gives up before blending is repeated in stream order - its stage
+// with it, once - and so are the other passes of its frame.
 template <class Prepare>
 th_status draw_pass(th_context *c, uint64_t *fragments, bool program, const FragmentStage *stage, Prepare prepare)
 {
@@ -554,7 +563,7 @@ th_status draw_pass(th_context *c, uint64_t *fragments, bool program, const Frag
         bool bins = false;
         if (th_status s = prepare(p, attempt == 0, &bins)) return s;
         if (!bins) return deposit_run(c, p, stage, fragments);
-        const th_status s = deposit_run_bins(c, p, fragments, program);
+        const th_status s = deposit_run_bins(c, p, fragments, program, stage);
         if (s != kRetryInStreamOrder) return s;
         c->frame_bins = 0;                  // (the other passes of this frame as well)
     }

@@ -92,7 +92,9 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
     TH_REQUIRE(u, "null uniforms");
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
     if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
-    if (stage) want_bins = false;               // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count)
+    // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count - unless TH_OPT_STAGE_BINS is on:
+    // then it is the pass it would be without the stage, which runs over the bins' page store: deposit_run_bins)
+    if (stage && !c->opt.stage_bins) want_bins = false;
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -569,7 +571,7 @@ th_status bins_store_grow_keep(th_context *c, th::DepositParams &p, uint32_t poo
 // Part 1: rasterise + emit into the bins, the plan; repeated with a larger pool when the pool ran dry (nothing has been
 // blended).  blend_early: the ordinary bins' blend goes out right behind the pass and covers the totals' read-back.
 // Leaves the totals in c->bins_totals_host.  kRetryInStreamOrder: a bin outgrew its lists (or the store cannot be had).
-th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program)
+th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, bool program, const FragmentStage *stage)
 {
     c->drawn.valid = false;
     if (th_status s = bins_streams(c)) return s;
@@ -585,6 +587,11 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
         if (th_status s = bins_store_for(c, p, 0)) return s;
         bins_expect(c, p);
         th::launch_bins_fused(p, c->stream, program);
+        // A caller's fragment stage: over every place the attempt handed out, in place, before the fork - so before the early blend
+        // and both topologies of bins_pass_blend: every fragment has run before anything blends (th_flow inside a stage reads the
+        // field as it was before the pass).  On an attempt the host then turns down it is harmless: the kernel leaves a flagged
+        // pass alone, a repeated pass writes every varying again and an abandoned one is wiped.
+        if (stage) if (th_status s = fragment_stage_run_bins(c, *stage, p, !blend_early)) return s;
         // the totals come back over the side stream while the ordinary bins are already being blended (the kernel looks at the
         // pass's flags itself): the host's round trip - it sizes the crowded bins' launches - costs the GPU nothing
         TH_HIP(hipEventRecord(c->forked, c->stream));
@@ -718,14 +725,14 @@ th_status bins_pass_totals(th_context *c, const th::DepositParams &p)
 
 }  // namespace thi
 
-th_status thi::deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program)
+th_status thi::deposit_run_bins(th_context *c, th::DepositParams &p, uint64_t *fragments, bool program, const FragmentStage *stage)
 {
     if (th_status s = bins_streams(c)) return s;
     // Which comes first behind the emitting pass: the ordinary bins' blend - it needs nothing from the host and covers the
     // read-back - or, on a crowded target, the crowded bins' kernels: their long runs (walked by one thread each, on the
     // side stream) are then the longest chain of the draw and must start as early as they can.  Decided by the last draw.
     const bool early = !(c->last_draw.pipeline == TH_DRAW_BINS && (double)c->last_draw.crowded_fragments > kEarlyBlendShare * (double)c->last_draw.fragments);
-    if (th_status s = bins_pass_emit(c, p, early, program)) return s;
+    if (th_status s = bins_pass_emit(c, p, early, program, stage)) return s;
     return bins_pass_finish(c, p, fragments, early);
 }
 
@@ -742,7 +749,7 @@ static th_status pass_prepare(th_context *c, const PassSpec &s, th::DepositParam
 }
 
 // Through the pipeline the built-in pass of this context would take (deposit_prepare: the policy, the frame's one-pipeline rule, the
-// gate; a fragment stage: stream-ordered).  With a vertex program, binned: the ring stays in the order it is held in, the vertex
+// gate; a fragment stage: stream-ordered, or under TH_OPT_STAGE_BINS the same pipeline with the stage over the page store).  With a vertex program, binned: the ring stays in the order it is held in, the vertex
 // kernel fills the texel-indexed vertex buffer - over a sorted ring one lane per SLOT, the state read where it lies - and the bins
 // walk the records in texel order; stream: the ring goes to texel order (held for a while), one lane per vertex - every attempt runs the vertex kernel.  A caller's stage
 // made or coloured the lines: what a built-in pass left of its own (c->drawn) is not such a pass's, nor such a pass's a built-in's.

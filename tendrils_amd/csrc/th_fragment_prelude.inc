@@ -119,4 +119,92 @@ extern "C" __global__ __launch_bounds__(256) void th_fragment_band_kernel(const 
     for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
         th_fragment_lane(f, a, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
 }
+
+// ---- the same stage over the fragments of a BINNED pass (th_bins.hip), where they lie in its page store -----------------------
+// Between the emitting pass and the blends every fragment of a binned pass lies at a PLACE of the store: its key
+// (y << 44 | x << 32 | stream index of its line; all ones: a place handed out and not written) in frag_keys[place], its varying
+// in colors[place] - where the ordinary bins' blend, the crowd's regroup and the long and giant runs all fetch it later.  A bin
+// is TH_BIN_REPLICAS lists of pages of 2^TH_BIN_PAGE_SHIFT places; list l = bin * TH_BIN_REPLICAS + r has handed out the places
+// v < cursor(bin, r); place v lies in page v >> TH_BIN_PAGE_SHIFT of the list - page 0 is page l of the store, a further page n
+// is page_table[l * max_pages + n] (0: none was published, 0xffffffff: the pool was dry) - at v's low bits.  The lines below
+// restate th_bins.hip's arithmetic (list_cursor, page_of, place_of: this text cannot include the library's headers); the record
+// is th_fragprog.hip's FragmentBinsArgs, the same layout.
+#define TH_BIN_REPLICAS 16u
+#define TH_BIN_PAGE_SHIFT 8u
+#define TH_BINS_TOT_OOB 1
+#define TH_BINS_TOT_FLAGS 2
+struct th_fragment_bins_args {
+    th_fragment_args f;              // keys: the store's 64-bit keys; colors: its varyings; total, div_mul, div_shift: unused (0)
+    const unsigned *bin_cursor;      // the lists' cursors: list r of bin b at r * bin_stride + (b & 31) * ((nbins + 31) >> 5) + (b >> 5)
+    const unsigned *page_table;      // per list max_pages entries
+    const unsigned *totals;          // the pass's totals: [TH_BINS_TOT_OOB], [TH_BINS_TOT_FLAGS] not 0 - a pass nobody will blend
+    unsigned bin_stride, max_pages, nbins;
+    unsigned pages;                  // pages of the store: every page id is below it
+    unsigned replicas, page_shift;   // TH_BIN_REPLICAS, TH_BIN_PAGE_SHIFT as the library was built (anything else: the kernel does nothing)
+};
+static_assert(sizeof(th_fragment_bins_args) == 112, "th_fragment_bins_args: layout shared with th_fragprog.hip");
+
+// One fragment of a binned pass: x and y are the key's two 12-bit fields (no division), ONE 16-byte load of colors[at], the
+// program, ONE 16-byte store back - th_fragment_lane's body behind another split of the key.
+__device__ __forceinline__ void th_fragment_place(th_fragment_pass &f, const th_fragment_args &a, unsigned long long key, unsigned at)
+{
+    const unsigned x = (unsigned)(key >> 32) & 0xfffu, y = (unsigned)(key >> 44) & 0xfffu;
+    f.x = x; f.y = y;
+    f.coord = make_float2((float)x + 0.5f, (float)y + 0.5f);
+    th_float4_load *slot = reinterpret_cast<th_float4_load *>(a.colors + at);
+    const th_float4_load c = *slot;
+    f.color = make_float4(c.x, c.y, c.z, c.w);
+    const float4 o = th_fragment_main(f);
+    th_float4_load out;
+    out.x = o.x; out.y = o.y; out.z = o.z; out.w = o.w;
+    *slot = out;
+}
+
+// The harness: blockIdx.x is a bin, whose places - its lists walked one after the other, as bins_blend_kernel walks them - go to
+// the workgroup's 256 lanes in rounds; blockIdx.y deals the rounds of one bin to gridDim.y workgroups (a crowded target puts half
+// a million fragments into one bin).  The grid is sized by bins, not by fragments: the cursors are on the device.  Skipped: the
+// whole pass when it raised a flag or asked for a row nobody holds (it is repeated or abandoned, its table not to be trusted);
+// places at or beyond a list's cursor; pages the table does not hold (entry 0 or 0xffffffff, page number >= max_pages, an id
+// outside the store); places whose key is the empty key.  No LDS (a lane's list is found among sixteen running sums the wave
+// holds in scalar registers), no atomics; nothing is written but colors[place] of live places.
+extern "C" __global__ __launch_bounds__(256) void th_fragment_bins_kernel(const th_fragment_bins_args a, const th_program_uniform_block u)
+{
+    if (a.replicas != TH_BIN_REPLICAS || a.page_shift != TH_BIN_PAGE_SHIFT) return;
+    if (a.totals[TH_BINS_TOT_FLAGS] != 0u || a.totals[TH_BINS_TOT_OOB] != 0u) return;
+    const unsigned b = blockIdx.x;
+    if (b >= a.nbins) return;
+    // first place of every list in the walk; a list holds at most max_pages pages (a cursor beyond them: the pass was flagged)
+    const unsigned list_cap = a.max_pages << TH_BIN_PAGE_SHIFT;
+    const unsigned *cursor = a.bin_cursor + (size_t)(b & 31u) * ((a.nbins + 31u) >> 5) + (b >> 5);
+    unsigned first[TH_BIN_REPLICAS + 1u];
+    first[0] = 0u;
+#pragma unroll
+    for (unsigned r = 0; r < TH_BIN_REPLICAS; ++r) {
+        const unsigned n = cursor[(size_t)r * a.bin_stride];
+        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
+    }
+    const unsigned n = first[TH_BIN_REPLICAS], rounds = (n + 255u) >> 8;
+    if (blockIdx.y >= rounds) return;
+    th_fragment_pass f = th_fragment_pass_of(a.f, u);
+    const unsigned long long *keys = static_cast<const unsigned long long *>(a.f.keys);
+    for (unsigned round = blockIdx.y; round < rounds; round += gridDim.y) {
+        const unsigned w = (round << 8) + threadIdx.x;
+        if (w >= n) continue;
+        unsigned r = 0u, base = 0u;
+#pragma unroll
+        for (unsigned q = 1; q < TH_BIN_REPLICAS; ++q) if (w >= first[q]) { r = q; base = first[q]; }
+        const unsigned list = b * TH_BIN_REPLICAS + r, v = w - base, pn = v >> TH_BIN_PAGE_SHIFT;
+        unsigned id = list;
+        if (pn != 0u) {
+            if (pn >= a.max_pages) continue;
+            id = a.page_table[(size_t)list * a.max_pages + pn];
+            if (id == 0u) continue;
+        }
+        if (id >= a.pages) continue;                     // (0xffffffff among them)
+        const unsigned at = (id << TH_BIN_PAGE_SHIFT) | (v & ((1u << TH_BIN_PAGE_SHIFT) - 1u));
+        const unsigned long long key = keys[at];
+        if (key == ~0ull) continue;
+        th_fragment_place(f, a.f, key, at);
+    }
+}
 )TH_PRELUDE"

@@ -6,6 +6,8 @@
 // interpolated varying -, so nothing of the raster or blend kernels knows of it: the entry points here load the stage and describe
 // the pass with it (PassSpec::fragment) to the body every pass goes through (th_draw.hip: pass_run / pass_emit); it travels down as
 // an argument, and deposit_run (th_draw.hip) / emit_parted (th_shard.hip) call fragment_stage_run where the fragments lie.
+// Under TH_OPT_STAGE_BINS a local pass with a stage may go through the bins (th_bins.hip): its fragments then lie in the page
+// store, and bins_pass_emit (th_draw.hip) calls fragment_stage_run_bins between the emitting pass and the blends.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -35,6 +37,30 @@ struct FragmentArgs {
 using KernArgs = ProgramKernArgs<FragmentArgs>;
 static_assert(sizeof(FragmentArgs) == 64 && offsetof(FragmentArgs, total) == 32 && offsetof(FragmentArgs, div_mul) == 56 && offsetof(KernArgs, u) == 64 &&
               sizeof(KernArgs) == 64 + kUniformBytes, "launch record: layout shared with th_fragment_prelude.inc");
+
+// ... and the record of th_fragment_bins_kernel (th_fragment_bins_args): the first record, then where the bins' lists lie.  The
+// prelude restates th_bins.hip's constants; the kernel does nothing when `replicas` / `page_shift` are not its own.
+struct FragmentBinsArgs {
+    FragmentArgs f;
+    const uint32_t *bin_cursor, *page_table, *totals;
+    uint32_t bin_stride, max_pages, nbins, pages;
+    uint32_t replicas, page_shift;
+};
+using BinsKernArgs = ProgramKernArgs<FragmentBinsArgs>;
+constexpr uint32_t kPreludeReplicas = 16, kPreludePageShift = 8;      // (TH_BIN_REPLICAS, TH_BIN_PAGE_SHIFT)
+static_assert(sizeof(FragmentBinsArgs) == 112 && offsetof(FragmentBinsArgs, bin_cursor) == 64 && offsetof(FragmentBinsArgs, bin_stride) == 88 &&
+              offsetof(FragmentBinsArgs, replicas) == 104 && offsetof(BinsKernArgs, u) == 112 && sizeof(BinsKernArgs) == 112 + kUniformBytes,
+              "bins launch record: layout shared with th_fragment_prelude.inc");
+static_assert(th::kBinReplicas == kPreludeReplicas && th::kBinPage == 1u << kPreludePageShift && th::kTotOob == 1 && th::kTotFlags == 2 &&
+              th::kBinsMaxExtent == 1 << 12, "th_fragment_prelude.inc restates the bins' constants and the key's 12-bit fields");
+// A bin's rounds of 256 places are dealt to this many workgroups (gridDim.y).  Every workgroup reads its bin's sixteen cursors
+// before it knows whether a round is left for it, and on an ordinary target - 1 700 places a bin at 1080p, seven rounds - most
+// of a wide deal's workgroups find none: the kernel's time is then the time of starting them (8 160 bins x 128: 0.88 ms for a
+// pass whose bytes copy in 0.10).  A crowded target - most fragments in a few hundred bins of tens of thousands of places -
+// wants the wider deal: a workgroup walks its rounds one behind the other, a chain of three loads and a store each.  Which of
+// the two the target is was the last draw's to say, as for the early blend (deposit_run_bins).  Measured, ms a pass, ordinary /
+// crowded target: deal 2: 0.130 / 0.460, 8: 0.161 / 0.356, 32: 0.303 / 0.437, 128: 0.877 / 0.890 (profiles/fragment_program_bins.txt).
+constexpr int kBinsStageDeal = 2, kBinsStageDealCrowded = 8;
 
 // n / d for every 32-bit n by one multiplication (Granlund & Montgomery 1994, the round-up form): the multiplier and both shifts
 void divide_by(uint32_t d, uint32_t &mul, uint32_t &shifts)
@@ -103,6 +129,27 @@ th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, con
     return timer.end(c);
 }
 
+th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded)
+{
+    TH_REQUIRE(p.mode != 2 && p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: one varying a place, a store to run over");
+    BinsKernArgs k{};
+    FragmentBinsArgs &a = k.a;
+    a.f.keys = p.frag_keys; a.f.colors = p.colors;
+    a.f.flow = c->flow; a.f.fw = c->fw; a.f.fh = c->fh;
+    a.f.colormap = c->colormap; a.f.cw = c->cmap_w; a.f.ch = c->cmap_h;
+    a.f.pass = stage.pass;
+    a.bin_cursor = p.bin_cursor; a.bin_stride = p.bin_stride;
+    a.page_table = p.page_table; a.max_pages = p.max_pages;
+    a.totals = p.totals;
+    a.nbins = p.nbins; a.pages = p.nbins * th::kBinReplicas + p.pool_pages;
+    a.replicas = th::kBinReplicas; a.page_shift = kPreludePageShift;
+    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+    LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
+    if (th_status s = timer.begin(c)) return s;
+    if (th_status s = program_launch_grid(c, stage.module->fn_slots, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
+    return timer.end(c);
+}
+
 extern "C" {
 
 th_status th_fragment_program_compile(const char *source, const char *name, th_program **out)
@@ -112,7 +159,8 @@ th_status th_fragment_program_compile(const char *source, const char *name, th_p
 
 // One pass of draw() with the stages of `s`, through the body every local pass goes through (pass_run): with a fragment stage
 // deposit_prepare leaves the bins and the frame's pipeline count alone, deposit_run reuses nothing and calls the stage between
-// its scatter and its sort.  What such a pass leaves of its lines (c->drawn) is no other pass's to reuse.
+// its scatter and its sort - or, under TH_OPT_STAGE_BINS, the pass takes the pipeline it would take without the stage, and a
+// binned one runs the stage over its page store.  What such a pass leaves of its lines (c->drawn) is no other pass's to reuse.
 th_status th_draw_stages_run(th_context *c, const th_draw_stages *s, int32_t pass, uint64_t *fragments)
 {
     if (th_status st = stages_args(c, s, pass, "th_draw_stages_run", "th_flow_deposit / th_view_draw")) return st;

@@ -160,6 +160,7 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_draw_vertex_band_kernel"));
     if (prog->kind == kStepProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_step_packed_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_fragment_band_kernel"));
+    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_fragment_bins_kernel"));
     m->prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));
@@ -172,10 +173,10 @@ th_status program_launch(th_context *c, hipFunction_t fn, size_t lanes, void *re
     return program_launch_grid(c, fn, th::grid_for(lanes, 8), record, bytes);
 }
 
-th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes)
+th_status program_launch_grid(th_context *c, hipFunction_t fn, int grid, void *record, size_t bytes, int grid_y)
 {
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, record, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    TH_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
+    TH_HIP(hipModuleLaunchKernel(fn, (unsigned)grid, (unsigned)grid_y, 1, 256, 1, 1, 0, c->stream, nullptr, extra));
     return TH_OK;
 }
 

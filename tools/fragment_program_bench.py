@@ -17,7 +17,21 @@ Each pass figure is GPU ms per call between two events on the context's stream a
 alternate for --rounds rounds and the median round is reported with the spread.  th_program_query's registers / scratch / code
 size go out with the figures.
 
-Usage: python tools/fragment_program_bench.py [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
+--bins: the stage through the binned pipeline (TH_OPT_STAGE_BINS, th_fragment_bins_kernel) instead.  Five contexts in the same
+state run the frame loop - tick(); step(); draw() - side by side, policy auto:
+  loop(off)      flowShader = renderShader = (None, vignette), option off: both passes stream-ordered, the ring in texel order
+  loop(on)       the same shaders, option on: both passes through the bins, the ring in its tile-sorted slots
+  loop(identity, off) / loop(identity, on)  the same pair with `return f.color` in both passes: the stage changes nothing, so these
+                 loops draw what loop(builtin) draws, frame for frame (a vignette in the flow pass changes the field the particles
+                 follow: those loops go their own way, and within a few dozen frames nearly all their fragments lie in crowded bins)
+  loop(builtin)  no shaders: the library's own binned frame loop (one rasterisation for both passes), beside both
+Each figure is wall ms per frame around --reps frames that end in a synchronise, after --warmup-frames frames; the arms alternate
+for --rounds rounds (every context has then run the same number of frames) and the median round is reported.  Then, on the
+loop(on) context, the flow pass alone: th_draw_stages_run with `gain` and with the vignette through the bins - the pass between
+two events, and th_kernel_timing's pair around th_fragment_bins_kernel - against copy(40): a device-to-device copy that moves
+40 bytes a fragment in all, what the kernel moves (an 8-byte key and 16 bytes read, 16 bytes written).
+
+Usage: python tools/fragment_program_bench.py [--bins] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -60,7 +74,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bins", action="store_true", help="the stage through the binned pipeline: frame loops with the option off / on, the bins kernel alone")
+    ap.add_argument("--warmup-frames", type=int, default=12, help="--bins: frames every loop runs before anything is timed")
     args = ap.parse_args()
+    if args.bins:
+        return bins_main(args)
 
     import numpy as np
     import torch
@@ -186,6 +204,188 @@ def main():
     t.dispose()
     for prog in programs.values():
         prog.dispose()
+
+
+def bins_main(args):
+    import time
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("fragment_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import FragmentProgram
+    from tendrils_amd.tendrils import View
+    from test_fragment_program_build import IDENTITY, VIGNETTE, FragUniforms
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    identity = FragmentProgram.from_source(IDENTITY, name="identity")
+    vignette = FragmentProgram.from_source(VIGNETTE, FragUniforms, "vignette")
+    gain = FragmentProgram.from_source(GAIN, GainUniforms, "gain")
+    block = dict(gain=0.5, tint=[0.5, 0.25, 0.75, 0.875], invRes=[1.0 / w, 1.0 / h], edge=3.5 / (w * w + h * h))
+    state0 = workload.synth_state(0)
+    cmap = np.random.default_rng(7).uniform(0, 1, (64, 64, 4)).astype(np.float32)
+
+    def loop(stage, stage_bins):
+        opts = ta.defaults()
+        if stage is not None:
+            opts.update(flowShader=(None, stage), renderShader=(None, stage))
+        t = ta.Tendrils(View(w, h), opts)
+        t.resize()
+        t.setup(n)
+        t.particles.upload_texels(state0)
+        t.colorMap.set_pixels(cmap)
+        t.uniforms["render"].update(block)
+        t.particles.option("stage_bins", stage_bins)
+        t.timer.time = 1000.0
+        return t
+
+    loops = {"off": loop(vignette, 0), "on": loop(vignette, 1), "identity, off": loop(identity, 0), "identity, on": loop(identity, 1), "builtin": loop(None, 0)}
+
+    def frames(t, count):
+        """wall ms per frame"""
+        t.particles.sync()
+        t0 = time.perf_counter()
+        for _ in range(count):
+            t.timer.tick()
+            t.step()
+            t.draw()
+        t.particles.sync()
+        return (time.perf_counter() - t0) * 1e3 / count
+
+    def held(t):
+        info, order = _capi.DrawInfo(), _capi.SlotOrderInfo()
+        call("th_draw_query", t.particles._ctx, C.byref(info))
+        call("th_slot_order", t.particles._ctx, C.byref(order))
+        return dict(pipeline="bins" if info.pipeline == 1 else "stream", fragments=int(info.fragments), crowded_fragments=int(info.crowded_fragments),
+                    sorted_buffers=int(order.sorted_buffers))
+
+    for t in loops.values():
+        frames(t, args.warmup_frames)
+    rounds = {}
+    for _ in range(args.rounds):
+        for name, t in loops.items():
+            rounds.setdefault("loop(%s)" % name, []).append(frames(t, args.reps))
+    state = {name: held(t) for name, t in loops.items()}
+    assert state["on"]["fragments"] == state["off"]["fragments"], state      # (the same frames: the same lines)
+    assert state["identity, on"]["fragments"] == state["identity, off"]["fragments"] == state["builtin"]["fragments"], state
+
+    # the flow pass alone (no step in between: every call draws the same lines), on two states: a context three steps in - every
+    # line a texel or two long, no crowded bin: the state of the stream-ordered figures (without --bins) - and the loop(on)
+    # context as its frames left it
+    fresh = loop(None, 1)
+    for _ in range(3):
+        fresh.timer.tick()
+        fresh.step()
+    fresh.line_widths()
+    totals = {}
+    for label, t in (("3 steps in", fresh), ("after the loop", loops["on"])):
+        totals[label] = passes(args, t, label, dict(gain=gain, vignette=vignette), block, rounds)
+        assert held(t)["pipeline"] == "bins", held(t)
+        state[label] = held(t)
+
+    lines = ["fragment stage through the bins (TH_OPT_STAGE_BINS), %d^2 particles (C3 state) into %d x %d, policy auto; %d frames of warm-up a loop, then "
+             "%d rounds of %d frames / calls, arms alternating; loop: wall ms per frame (synchronised); pass, kernel, copy: GPU ms per call (events)"
+             % (n, w, h, args.warmup_frames, args.rounds, args.reps),
+             "device: %s" % torch.cuda.get_device_name(0)]
+    for name in state:
+        lines.append("%s: %s" % ("loop(%s) after its last frame" % name if name in loops else "the flow pass " + name, json.dumps(state[name])))
+    lines.append("%-36s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)"))
+    med = {}
+    for name, ms in rounds.items():
+        med[name] = statistics.median(ms)
+        label = name.split(" @ ")[-1]
+        gbps = "%.1f" % (40 * totals[label] / med[name] / 1e6) if name.startswith(("kernel(", "copy(")) else "-"
+        lines.append("%-36s %10.4f %10.4f %10.4f %14s" % (name, med[name], min(ms), max(ms), gbps))
+    lines.append("loop(on) / loop(off) = %.3f;  loop(identity, on) / loop(identity, off) = %.3f;  loop(identity, on) / loop(builtin) = %.3f;  loop(identity, off) / loop(builtin) = %.3f  (time ratios)"
+                 % (med["loop(on)"] / med["loop(off)"], med["loop(identity, on)"] / med["loop(identity, off)"], med["loop(identity, on)"] / med["loop(builtin)"],
+                    med["loop(identity, off)"] / med["loop(builtin)"]))
+    for label in totals:
+        m = lambda arm: med["%s @ %s" % (arm, label)]      # noqa: E731
+        lines.append("%s: pass(gain) / pass(plain) = %.3f;  pass(vignette) / pass(plain) = %.3f;  kernel(gain) / copy(40) = %.3f;  kernel(vignette) / copy(40) = %.3f  (time ratios)"
+                     % (label, m("pass(gain)") / m("pass(plain)"), m("pass(vignette)") / m("pass(plain)"), m("kernel(gain)") / m("copy(40)"), m("kernel(vignette)") / m("copy(40)")))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(dict(root=n, width=w, height=h, reps=args.reps, rounds=args.rounds, fragments=totals, state=state, median_ms=med)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    for t in list(loops.values()) + [fresh]:
+        t.dispose()
+    for prog in (identity, vignette, gain):
+        prog.dispose()
+
+
+def passes(args, t, label, programs, block, rounds):
+    """the flow pass of `t` without a stage and with each of `programs`, the bins kernel alone, the copy of its bytes: into
+    `rounds` under "<arm> @ <label>"; returns the pass's fragments"""
+    import torch
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import draw_stages
+    ctx, d = t.particles._ctx, t.deposit_uniforms()
+    uniforms = dict(t.state, **block)
+    stages = {name: draw_stages(None, prog, uniforms, d) for name, prog in programs.items()}
+    frags = {}
+
+    def plain():
+        count = C.c_uint64(0)
+        call("th_flow_deposit", ctx, C.byref(d), C.byref(count))
+        frags["plain"] = count.value
+
+    def staged(name):
+        def run():
+            count = C.c_uint64(0)
+            call("th_draw_stages_run", ctx, C.byref(stages[name][0]), 0, C.byref(count))
+            frags[name] = count.value
+        return run
+
+    arms = dict(plain=plain, **{name: staged(name) for name in programs})
+
+    def timed(name, fn, reps):
+        ms, kernel = C.c_float(0), None
+        if name != "plain":
+            call("th_kernel_timing", ctx, 1)
+        call("th_timer_start", ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", ctx, C.byref(ms))
+        if name != "plain":
+            mean, launches = C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+            call("th_kernel_timing", ctx, 0)
+            assert launches.value == reps, (launches.value, reps)          # (one attempt a pass: nothing was repeated)
+            kernel = mean.value
+        return ms.value / reps, kernel
+
+    for name, fn in arms.items():
+        timed(name, fn, args.warmup)
+    total = frags["plain"]
+    assert all(v == total for v in frags.values()), frags
+    src = torch.empty(total * 20, dtype=torch.uint8, device="cuda")          # (40 bytes a fragment in all: half read, half written)
+    dst = torch.empty_like(src)
+
+    def copy_ms(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    copy_ms(args.warmup)
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            ms, kernel = timed(name, fn, args.reps)
+            rounds.setdefault("pass(%s) @ %s" % (name, label), []).append(ms)
+            if kernel is not None:
+                rounds.setdefault("kernel(%s) @ %s" % (name, label), []).append(kernel)
+        rounds.setdefault("copy(40) @ %s" % label, []).append(copy_ms(args.reps))
+    return total
 
 
 if __name__ == "__main__":
