@@ -411,9 +411,25 @@ th_status th_draw_program_emit(th_context *ctx, th_program *program, const void 
  *   th_flow(f, u, v), th_flow_res(f)           texture2D(flow, (u, v)): NEAREST, CLAMP_TO_EDGE - the field as it was BEFORE this
  *                              pass, also in a pass that draws into it (every fragment runs before anything blends)
  *   th_colormap(f, u, v), th_colormap_res(f)   ... of the colour map; no map held: the 1 x 1 zero texture
+ *   th_line(f)         the line the fragment belongs to, a const th_fragment_line &:
+ *                        unsigned line   its stream index: column * H + row of the WHOLE particle texture (GL's primitive index; the
+ *                                        low word of the keys th_draw_stages_emit hands out)
+ *                        float along     the parameter the library mixed `color` with: 0 at the line's first vertex (the previous
+ *                                        state), 1 at its second, unclamped outside them; 0 when both endpoints snap to one point
+ *                        float across    signed distance of the texel centre from the line through the SNAPPED endpoints, in texels:
+ *                                        positive to the left of first -> second vertex, with y as the target's rows count
+ *                        float length    distance between the snapped endpoints, in texels
+ *                      fp32, no contraction, from the integers the varying is interpolated with (1/16 texel): ex = sx1 - sx0,
+ *                      ey = sy1 - sy0, qx = 16 x - sx0, qy = 16 y - sy0; along = (qx ex + qy ey) / (ex^2 + ey^2), len16 =
+ *                      sqrtf(ex^2 + ey^2), across = ((qy ex - qx ey) / len16) * 0.0625f, length = len16 * 0.0625f; all 0 when
+ *                      ex = ey = 0.  A program reads the line if its source names the identifier th_line (decided by
+ *                      th_fragment_program_compile; a mention in a comment counts): its passes run one more kernel behind the
+ *                      emit, which writes a 16-byte record per fragment, and are stream-ordered also under TH_OPT_STAGE_BINS
+ *                      (th_draw_query: TH_DRAW_STREAM; the bits of the option off).  Every other program launches what it
+ *                      always did.  In th_draw_stages_run and th_draw_stages_emit, behind either vertex stage.
  * Every accessor clamps: a program that reads through them alone cannot read out of bounds.  NOT offered: the destination
- * texel (GL has none either), `discard`, the identity or geometry of the fragment's line, th_particles - a source that names
- * an accessor it does not have fails to compile, on the caller's own line.  A fragment that wants to leave its texel alone
+ * texel (GL has none either), `discard`, th_particles - a source that names an accessor it does not have fails to compile,
+ * on the caller's own line.  A fragment that wants to leave its texel alone
  * returns alpha 0 WITH FINITE COLOUR: the blend is dst = src * a + dst * (1 - a), and 0 * inf is NaN.
  * The stage runs once per fragment, over the array the stream-ordered pipeline holds between its emit and its sort, in place;
  * everything before it (the vertex stage, the raster) and behind it (the sort, the blend in primitive order) is the code of a

@@ -91,6 +91,8 @@ struct th_program {
     bool destroyed = false;
     std::atomic<int> refs{1};
     uint32_t sgprs = 0, code_bytes = 0;  // of the kind's kernel, read from the code object
+    bool reads_line = false;             // a fragment program whose source names th_line (th_fragment_program_compile): its passes write the
+                                         // fragments' line records (th_fragline.hip) and launch the entry points that take them
 };
 // ... and as one context has loaded it (th_program.hip): the context owns the module - unloaded when the context goes - and
 // a reference to the program's record, so that th_program_destroy of a program a context has run is safe.
@@ -104,6 +106,8 @@ struct ProgramModule {
     hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines); a fragment
                                          // program's second: th_fragment_band_kernel (the fragments of an emit, under their 64-bit keys)
     hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
+    hipFunction_t fn_line = nullptr, fn_line_band = nullptr;      // a fragment program's fourth and fifth: th_fragment_line_kernel / th_fragment_line_band_kernel
+                                         // (fn / fn_band with the fragments' line records behind their record: a program that reads th_line)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -121,6 +125,8 @@ struct FragmentStage {
     const void *uniforms; uint32_t uniform_bytes;
     int32_t pass;
 };
+// the stage reads th_line(f): its pass is stream-ordered whatever TH_OPT_STAGE_BINS says, and holds a line record per fragment
+inline bool stage_reads_line(const FragmentStage *stage) { return stage && stage->module->prog->reads_line; }
 // One pass of draw() as its entry point describes it, for pass_run (a whole texture) and pass_emit (a row band; th_draw.hip); both passes in one (th_draw, th_draw_emit) prepare themselves
 struct PassSpec {
     int32_t pass = TH_PASS_FLOW;                                                         // TH_PASS_FLOW / TH_PASS_VIEW
@@ -267,6 +273,7 @@ struct th_context {
     size_t mrg_capacity = 0;
     DevBuf<float4> mrg_colors;           // the received varyings gathered into texel order
     DevBuf<float4> dep_colors;
+    DevBuf<th::FragmentLine> dep_fraglines;                          // per fragment: its line's record - only once a pass's fragment stage has read th_line (deposit_reserve)
     DevBuf<char> dep_temp;
     size_t dep_lines = 0, dep_capacity = 0;   // (set once all of their buffers are there: prepare_pass, deposit_reserve)
     uchar4 *view = nullptr;              // the BOUND view image (RGBA8, flow shape): what the view pass, fills, clears and read-backs touch
@@ -457,7 +464,8 @@ th_status vertex_stage_run(th_context *c, const PassSpec &s, th::DepositParams &
 th_status vertex_stage_band(th_context *c, const PassSpec &s, th::DepositParams &p);
 // ---- th_fragprog.hip -------------------------------------------------------------------------------------------------
 // `stage` over the `total` fragments (not 0) the scatter of the (prepared) pass `p` has just written: p.keys64 / p.keys and
-// p.colors, fragment i in place i of both - before anything sorts or parts them
+// p.colors, fragment i in place i of both - before anything sorts or parts them.  A stage that reads th_line: the line kernel
+// (th_fragline.hip) fills c->dep_fraglines first - reserved by the caller, deposit_reserve(..., lines) - and the stage's line entry points run
 th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total);
 // ... and over the fragments an emitting attempt of the binned pass `p` (not mode 2) has just left in the page store: p.frag_keys /
 // p.colors at every place the bins' lists handed out - before anything blends, whether or not the host accepts the attempt
@@ -507,10 +515,10 @@ float drawn_line_width(const th_context *c, int pass);
 // program: the pass of a caller's draw program (th_drawprog.hip) - its binned form walks the vertex records in texel order over
 // a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list); stage: the
 // pass's fragment stage, or null - with one the pass is stream-ordered, and no frame of the policy's count, unless
-// TH_OPT_STAGE_BINS is on: then it takes the pipeline the pass without the stage would
+// TH_OPT_STAGE_BINS is on and the stage does not read th_line: then it takes the pipeline the pass without the stage would
 th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false, const FragmentStage *stage = nullptr);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
-th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false);
+th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false, bool lines = false);      // lines: and a th::FragmentLine per fragment
 th_status deposit_temp(th_context *c, size_t need);
 // the stream-ordered pipeline over the (prepared) pass `p`: count, scan, emit, `stage` (or null) over the fragments, sort by texel, blend
 th_status deposit_run(th_context *c, th::DepositParams &p, const FragmentStage *stage, uint64_t *fragments);

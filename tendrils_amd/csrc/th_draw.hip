@@ -93,8 +93,9 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
     TH_REQUIRE(c->ring.size() >= 2, "draw needs at least 2 state buffers (have %zu)", c->ring.size());
     if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
     // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count - unless TH_OPT_STAGE_BINS is on:
-    // then it is the pass it would be without the stage, which runs over the bins' page store: deposit_run_bins)
-    if (stage && !c->opt.stage_bins) want_bins = false;
+    // then it is the pass it would be without the stage, which runs over the bins' page store: deposit_run_bins.  A stage that
+    // reads th_line stays stream-ordered under the option too: its line records lie beside the stream-ordered fragment array)
+    if (stage && (!c->opt.stage_bins || stage_reads_line(stage))) want_bins = false;
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -269,7 +270,7 @@ th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t
 }
 
 // per-fragment buffers for `total` fragments (grow-only)
-th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs)
+th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs, bool lines)
 {
     if (pairs && !c->dep_pairs) {                 // two varyings per fragment: the colour buffers at twice the size
         c->dep_colors.reset(); c->dep_colors_sorted.reset();
@@ -279,7 +280,7 @@ th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs)
     if (c->dep_capacity < total) {
         for (DevBuf<uint32_t> &q : c->dep_u32) q.reset();
         for (DevBuf<unsigned long long> &q : c->dep_u64) q.reset();
-        c->dep_colors.reset(); c->dep_colors_sorted.reset();
+        c->dep_colors.reset(); c->dep_colors_sorted.reset(); c->dep_fraglines.reset();
         c->dep_capacity = 0; c->dep_wide = false;
         const size_t cap = (size_t)total + (size_t)total / 4 + 1024;
         for (DevBuf<uint32_t> &q : c->dep_u32) if (th_status s = q.alloc(cap)) return s;
@@ -291,6 +292,7 @@ th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs)
         for (DevBuf<unsigned long long> &q : c->dep_u64) if (th_status s = q.alloc(c->dep_capacity)) return s;
         c->dep_wide = true;
     }
+    if (lines && !c->dep_fraglines) if (th_status s = c->dep_fraglines.alloc(c->dep_capacity)) return s;      // (a stage that reads th_line: fragment_stage_run)
     return TH_OK;
 }
 
@@ -414,7 +416,7 @@ th_status thi::deposit_run(th_context *c, th::DepositParams &p, const FragmentSt
     if (fragments) *fragments = total;
     draw_streamed(c, total);
     if (total == 0) return TH_OK;
-    if (!reuse) if (th_status s = deposit_reserve(c, total, false, p.mode == 2)) return s;
+    if (!reuse) if (th_status s = deposit_reserve(c, total, false, p.mode == 2, stage_reads_line(stage))) return s;
     p.keys = c->dep_u32[0]; p.slots = c->dep_u32[1]; p.keys_sorted = c->dep_u32[2]; p.slots_sorted = c->dep_u32[3];
     p.colors = c->dep_colors; p.colors_sorted = c->dep_colors_sorted;
     if (reuse) {

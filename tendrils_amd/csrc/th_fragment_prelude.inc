@@ -8,8 +8,8 @@ R"TH_PRELUDE(// th_fragment_prelude.inc - what th_fragment_program_compile puts 
 // main() of the fragment shader of one pass of draw() (the second of renderShader: [vert, frag] / flowShader: [vert, frag]): it
 // is called once per fragment the pass's lines cover and returns gl_FragColor, which the library blends into the target in
 // primitive order (SRC_ALPHA / ONE_MINUS_SRC_ALPHA) as it blends the varying of a pass without this stage.  There is no
-// destination texel to read (GL has none either), no `discard`, nothing of the line the fragment belongs to and nothing of the
-// particles: a source that names th_particles does not compile.  A fragment that wants to leave its texel alone returns
+// destination texel to read (GL has none either), no `discard` and nothing of the particles: a source that names th_particles
+// does not compile.  Of the line the fragment belongs to it sees th_line(f), below.  A fragment that wants to leave its texel alone returns
 // alpha 0 WITH FINITE COLOUR: the blend is dst = src * a + dst * (1 - a), and 0 * inf or 0 * NaN is NaN.
 //
 // th_fragment_args is the launch record th_fragprog.hip fills (same layout there; the static_asserts pin the sizes).
@@ -38,7 +38,23 @@ struct th_fragment_pass {
     int pass;                    // TH_PASS_FLOW | TH_PASS_VIEW
     const void *uniforms;        // the caller's uniform block (th_uniforms<T>(f))
     const th_fragment_args *args;
+    const struct th_fragment_line *line;      // th_line(f); null in the entry points of a program that does not read it
 };
+
+// The fragment's line, as the library's raster stage has it (th_fragline.hip writes one record per fragment for a pass whose
+// program names th_line; a program that does not pays nothing and launches what it always did):
+struct __attribute__((aligned(16))) th_fragment_line {
+    unsigned line;               // stream index of the fragment's line: column * H + row of the WHOLE particle texture (GL's
+                                 // primitive index; the low word of the band and bin keys)
+    float along;                 // the parameter the library mixed `color` with: 0 at the line's first vertex (the previous
+                                 // state), 1 at its second, unclamped outside them; 0 when both endpoints snap to one point
+    float across;                // signed distance of the texel centre from the line through the SNAPPED endpoints, in texels:
+                                 // positive to the left of first -> second vertex, with y as the target's rows count
+    float length;                // distance between the snapped endpoints, in texels
+};
+static_assert(sizeof(th_fragment_line) == 16, "th_fragment_line: layout shared with th_fragline.hip");
+static __device__ const th_fragment_line th_fragment_no_line = {0u, 0.0f, 0.0f, 0.0f};
+__device__ __forceinline__ const th_fragment_line &th_line(const th_fragment_pass &f) { return f.line ? *f.line : th_fragment_no_line; }
 
 __device__ float4 th_fragment_main(const th_fragment_pass &f);
 
@@ -95,6 +111,7 @@ __device__ __forceinline__ th_fragment_pass th_fragment_pass_of(const th_fragmen
     f.pass = a.pass;
     f.uniforms = u.bytes;
     f.args = &a;
+    f.line = nullptr;
     return f;
 }
 
@@ -118,6 +135,38 @@ extern "C" __global__ __launch_bounds__(256) void th_fragment_band_kernel(const 
     const unsigned long long *keys = static_cast<const unsigned long long *>(a.keys);
     for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
         th_fragment_lane(f, a, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
+}
+
+// ---- the two entry points of a program that reads the fragment's line (th_line) -------------------------------------------------
+// th_fragment_kernel and th_fragment_band_kernel with the pass's line records behind the record they take: lines[at] belongs to
+// the fragment at keys[at] / colors[at].  A record of its own (th_fragprog.hip: FragmentLineArgs, the same layout): the three
+// other entry points keep theirs.  A lane loads its 16-byte record once, beside its varying.
+struct th_fragment_line_args {
+    th_fragment_args f;
+    const th_fragment_line *lines;   // per fragment, in the keys' order
+};
+static_assert(sizeof(th_fragment_line_args) == 72, "th_fragment_line_args: layout shared with th_fragprog.hip");
+
+extern "C" __global__ __launch_bounds__(256) void th_fragment_line_kernel(const th_fragment_line_args a, const th_program_uniform_block u)
+{
+    th_fragment_pass f = th_fragment_pass_of(a.f, u);
+    const unsigned *keys = static_cast<const unsigned *>(a.f.keys);
+    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.f.total; at += gridDim.x * 256u) {
+        const th_fragment_line line = a.lines[at];
+        f.line = &line;
+        th_fragment_lane(f, a.f, keys[at], at);
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void th_fragment_line_band_kernel(const th_fragment_line_args a, const th_program_uniform_block u)
+{
+    th_fragment_pass f = th_fragment_pass_of(a.f, u);
+    const unsigned long long *keys = static_cast<const unsigned long long *>(a.f.keys);
+    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.f.total; at += gridDim.x * 256u) {
+        const th_fragment_line line = a.lines[at];
+        f.line = &line;
+        th_fragment_lane(f, a.f, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
+    }
 }
 
 // ---- the same stage over the fragments of a BINNED pass (th_bins.hip), where they lie in its page store -----------------------

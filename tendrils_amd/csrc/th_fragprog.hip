@@ -8,6 +8,8 @@
 // an argument, and deposit_run (th_draw.hip) / emit_parted (th_shard.hip) call fragment_stage_run where the fragments lie.
 // Under TH_OPT_STAGE_BINS a local pass with a stage may go through the bins (th_bins.hip): its fragments then lie in the page
 // store, and bins_pass_emit (th_draw.hip) calls fragment_stage_run_bins between the emitting pass and the blends.
+// A program whose source names th_line reads the fragment's line: its pass stays stream-ordered, fragment_stage_run has the line
+// kernel (th_fragline.hip) write a record per fragment beside key and varying, and launches the two entry points that take them.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -37,6 +39,16 @@ struct FragmentArgs {
 using KernArgs = ProgramKernArgs<FragmentArgs>;
 static_assert(sizeof(FragmentArgs) == 64 && offsetof(FragmentArgs, total) == 32 && offsetof(FragmentArgs, div_mul) == 56 && offsetof(KernArgs, u) == 64 &&
               sizeof(KernArgs) == 64 + kUniformBytes, "launch record: layout shared with th_fragment_prelude.inc");
+
+// ... the record of th_fragment_line_kernel / th_fragment_line_band_kernel (th_fragment_line_args): the first record, then the
+// fragments' line records (th_fragline.hip) - a program that reads th_line
+struct FragmentLineArgs {
+    FragmentArgs f;
+    const th::FragmentLine *lines;
+};
+using LineKernArgs = ProgramKernArgs<FragmentLineArgs>;
+static_assert(sizeof(FragmentLineArgs) == 72 && offsetof(FragmentLineArgs, lines) == 64 && offsetof(LineKernArgs, u) == 80 && sizeof(LineKernArgs) == 80 + kUniformBytes &&
+              sizeof(th::FragmentLine) == 16, "line launch record: layout shared with th_fragment_prelude.inc");
 
 // ... and the record of th_fragment_bins_kernel (th_fragment_bins_args): the first record, then where the bins' lists lie.  The
 // prelude restates th_bins.hip's constants; the kernel does nothing when `replicas` / `page_shift` are not its own.
@@ -109,12 +121,19 @@ th_status stages_pass(th_context *c, const th_draw_stages *s, int32_t pass, Frag
     return TH_OK;
 }
 
-}  // namespace
-
-th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total)
+// does `source` name the identifier `word`?  (anywhere: a comment counts - the pass then pays for records nobody reads)
+bool names_identifier(const char *source, const char *word)
 {
-    KernArgs k{};
-    FragmentArgs &a = k.a;
+    auto part = [](char ch) { return ch == '_' || (ch >= '0' && ch <= '9') || (ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z'); };
+    const size_t n = strlen(word);
+    for (const char *at = strstr(source, word); at; at = strstr(at + 1, word))
+        if ((at == source || !part(at[-1])) && !part(at[n])) return true;
+    return false;
+}
+
+// the record every stream-ordered entry point starts with
+void stage_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total, FragmentArgs &a)
+{
     a.keys = p.keys64 ? static_cast<const void *>(p.keys64) : static_cast<const void *>(p.keys);
     a.colors = p.colors;
     a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
@@ -122,8 +141,29 @@ th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, con
     a.total = total;
     a.pass = stage.pass;
     divide_by((uint32_t)c->fw, a.div_mul, a.div_shift);
-    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+}
+
+}  // namespace
+
+th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total)
+{
     LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
+    if (stage_reads_line(&stage)) {
+        // the fragments' line records first, beside the keys and varyings the scatter has just written (mode 2 has no stage)
+        TH_REQUIRE(c->dep_fraglines && c->dep_capacity >= total && (p.keys64 || p.keys), "a stage that reads the line: a record per fragment, keys to read the texels from");
+        th::launch_fragment_lines(p, c->dep_fraglines, c->stream);
+        TH_HIP(hipGetLastError());
+        LineKernArgs k{};
+        stage_record(c, stage, p, total, k.a.f);
+        k.a.lines = c->dep_fraglines;
+        k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+        if (th_status s = timer.begin(c)) return s;
+        if (th_status s = program_launch(c, p.keys64 ? stage.module->fn_line_band : stage.module->fn_line, total, k)) return s;
+        return timer.end(c);
+    }
+    KernArgs k{};
+    stage_record(c, stage, p, total, k.a);
+    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
     if (th_status s = timer.begin(c)) return s;
     if (th_status s = program_launch(c, p.keys64 ? stage.module->fn_band : stage.module->fn, total, k)) return s;
     return timer.end(c);
@@ -132,6 +172,7 @@ th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, con
 th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded)
 {
     TH_REQUIRE(p.mode != 2 && p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: one varying a place, a store to run over");
+    TH_REQUIRE(!stage_reads_line(&stage), "a fragment stage that reads the line is stream-ordered (deposit_prepare)");
     BinsKernArgs k{};
     FragmentBinsArgs &a = k.a;
     a.f.keys = p.frag_keys; a.f.colors = p.colors;
@@ -154,7 +195,10 @@ extern "C" {
 
 th_status th_fragment_program_compile(const char *source, const char *name, th_program **out)
 {
-    return program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out);
+    if (th_status s = program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out)) return s;
+    // who pays for the line records: decided here, once (the compiler has accepted the text; an identifier in a comment counts)
+    (*out)->reads_line = names_identifier(source, "th_line");
+    return TH_OK;
 }
 
 // One pass of draw() with the stages of `s`, through the body every local pass goes through (pass_run): with a fragment stage

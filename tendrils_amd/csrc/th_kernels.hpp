@@ -341,6 +341,10 @@ size_t deposit_list_words(uint32_t W, uint32_t rows, uint32_t *cap);
 void launch_deposit_count(const DepositParams &p, hipStream_t stream);
 void launch_deposit_scan(const DepositParams &p, uint32_t *scratch, uint32_t *total, hipStream_t stream);
 void launch_deposit_scatter(const DepositParams &p, hipStream_t stream);
+// the fragment's line (th_fragline.hip): per fragment of a stream-ordered pass, beside its key and varying, what a caller's fragment
+// stage reads through th_line(f) - th_fragment_line of th_fragment_prelude.inc, the same layout
+struct alignas(16) FragmentLine { uint32_t line; float along, across, length; };
+void launch_fragment_lines(const DepositParams &p, FragmentLine *lines, hipStream_t stream);      // behind launch_deposit_scatter(p)
 int deposit_key_bits(const DepositParams &p);
 void launch_export_mark(const DepositParams &p, hipStream_t stream);
 void launch_export_write(const DepositParams &p, float *out, hipStream_t stream);

@@ -22,7 +22,7 @@ th_status emit_parted(th_context *c, th::DepositParams &p, const FragmentStage *
     *count = total; *keys_dev = nullptr; *colors_dev = nullptr;
     if (total == 0) return TH_OK;
     const bool pairs = p.mode == 2;                  // th_draw_emit: two varyings per fragment, side by side
-    if (th_status s = deposit_reserve(c, total, true, pairs)) return s;
+    if (th_status s = deposit_reserve(c, total, true, pairs, stage_reads_line(stage))) return s;
     p.keys64 = c->dep_u64[0]; p.slots = c->dep_u32[1]; p.colors = c->dep_colors;
     p.owners = c->dep_owners;
     p.owner_chunk = (uint32_t)(((uint64_t)c->fw * c->fh + p.owners - 1u) / p.owners);

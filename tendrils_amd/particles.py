@@ -113,7 +113,9 @@ class FragmentProgram(Program):
     fragment with its window texel and the interpolated varying; what it returns is blended - and is otherwise
     Program.from_source: compiled once, for gfx950, no GPU needed; TendrilsHipError with the compiler's output; pack(), query()
     and dispose() as there.  Tendrils runs it as the second of a flowShader / renderShader pair (or alone: with the library's
-    vertex stage); such a pass is always stream-ordered."""
+    vertex stage); such a pass is stream-ordered unless Particles.option("stage_bins", 1) sends it through the bins.  A source
+    that names th_line reads the fragment's line (th_line(f): line, along, across, length): nothing to pass here - the library
+    sees it when it compiles, writes the records such a pass needs, and keeps the pass stream-ordered."""
     COMPILE, SOURCE_KIND = "th_fragment_program_compile", "fragment"
 
 

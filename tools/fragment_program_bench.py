@@ -31,7 +31,21 @@ loop(on) context, the flow pass alone: th_draw_stages_run with `gain` and with t
 two events, and th_kernel_timing's pair around th_fragment_bins_kernel - against copy(40): a device-to-device copy that moves
 40 bytes a fragment in all, what the kernel moves (an 8-byte key and 16 bytes read, 16 bytes written).
 
-Usage: python tools/fragment_program_bench.py [--bins] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
+--line: a stage that reads the fragment's line (th_line(f); th_fragline.hip, th_fragment_line_kernel).  One context in the state of
+the figures without --bins, the flow pass stream-ordered, reuse off; --line-width W draws it W texels wide (a GL that honours
+gl.lineWidth; 1: the reference's captured GL).  Arms:
+  plain       th_flow_deposit
+  vignette    th_draw_stages_run with the tests' VIGNETTE: it does not name th_line and launches what it always did
+  falloff     ... with alpha scaled by fmaxf(1 - fabsf(th_line(f).across) / half_width, 0) (the reference's @todo in src/flow/index.frag;
+              tests/test_fragment_program_line_build.py: FALLOFF): the line kernel behind the scatter, then th_fragment_line_kernel
+kernel(...) is th_kernel_timing's pair around the stage's kernel alone - the line kernel is not inside it.  copy(36) moves what the
+vignette kernel moves, copy(48) what th_fragment_line_kernel moves (a 16-byte record and the varying read, the varying written), and
+copy(lines) what the line kernel moves: 16 bytes written and one key read a fragment, two state texels, `count` and `offset` a line.
+The line kernel's own time is a kernel trace's to give (fragment_lines_kernel, fragment_lines_long_kernel beside deposit_emit_kernel):
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/fragment_program_bench.py --line --rounds 1 --reps 5
+pass(falloff) - pass(vignette) - (kernel(falloff) - kernel(vignette)) is the same figure from the events, and is printed.
+
+Usage: python tools/fragment_program_bench.py [--bins | --line [--line-width 1]] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -76,9 +90,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--bins", action="store_true", help="the stage through the binned pipeline: frame loops with the option off / on, the bins kernel alone")
     ap.add_argument("--warmup-frames", type=int, default=12, help="--bins: frames every loop runs before anything is timed")
+    ap.add_argument("--line", action="store_true", help="a stage that reads the fragment's line: the pass, the stage's kernel, the copies of what it and the line kernel move")
+    ap.add_argument("--line-width", type=float, default=1.0, help="--line: the width the flow pass is drawn with")
     args = ap.parse_args()
     if args.bins:
         return bins_main(args)
+    if args.line:
+        return line_main(args)
 
     import numpy as np
     import torch
@@ -198,6 +216,138 @@ def main():
     text = "\n".join(lines)
     print(text)
     print(json.dumps(dict(root=n, width=w, height=h, reps=args.reps, rounds=args.rounds, fragments=total, query=queries, median_ms=med)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    t.dispose()
+    for prog in programs.values():
+        prog.dispose()
+
+
+def line_main(args):
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("fragment_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import FragmentProgram, draw_stages
+    from tendrils_amd.tendrils import View
+    from test_fragment_program_build import VIGNETTE, FragUniforms
+    from test_fragment_program_line_build import FALLOFF
+
+    class Falloff(C.Structure):
+        _fields_ = [("halfWidth", C.c_float)]
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    programs = dict(vignette=FragmentProgram.from_source(VIGNETTE, FragUniforms, "vignette"),
+                    falloff=FragmentProgram.from_source(FALLOFF, Falloff, "falloff"))
+    opts = ta.defaults()
+    opts["lineWidthRange"] = (1, max(1.0, args.line_width))
+    opts["state"]["flowWidth"] = args.line_width
+    t = ta.Tendrils(View(w, h), opts)
+    t.resize()
+    t.setup(n)
+    p, ctx = t.particles, t.particles._ctx
+    p.upload_texels(workload.synth_state(0))
+    t.colorMap.set_pixels(np.random.default_rng(7).uniform(0, 1, (64, 64, 4)).astype(np.float32))
+    t.timer.time = 1000.0
+    for _ in range(3):
+        t.timer.tick()
+        t.step()
+    p.draw_pipeline("stream")
+    p.option("draw_reuse", 0)
+    t.line_widths()
+    uniforms = dict(t.state, halfWidth=0.5 * args.line_width + 0.5, tint=[0.5, 0.25, 0.75, 0.875], invRes=[1.0 / w, 1.0 / h], edge=3.5 / (w * w + h * h), gain=0.625)
+    d = t.deposit_uniforms()
+    held = {name: draw_stages(None, prog, uniforms, d) for name, prog in programs.items()}
+    frags = {}
+
+    def plain():
+        count = C.c_uint64(0)
+        call("th_flow_deposit", ctx, C.byref(d), C.byref(count))
+        frags["plain"] = count.value
+
+    def staged(name):
+        def run():
+            count = C.c_uint64(0)
+            call("th_draw_stages_run", ctx, C.byref(held[name][0]), 0, C.byref(count))
+            frags[name] = count.value
+        return run
+
+    arms = dict(plain=plain, vignette=staged("vignette"), falloff=staged("falloff"))
+
+    def timed(name, fn, reps):
+        ms, kernel = C.c_float(0), None
+        if name != "plain":
+            call("th_kernel_timing", ctx, 1)
+        call("th_timer_start", ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", ctx, C.byref(ms))
+        if name != "plain":
+            mean, launches = C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+            call("th_kernel_timing", ctx, 0)
+            assert launches.value == reps, (launches.value, reps)
+            kernel = mean.value
+        return ms.value / reps, kernel
+
+    for name, fn in arms.items():
+        timed(name, fn, args.warmup)
+    total = frags["plain"]
+    assert all(v == total for v in frags.values()), frags
+    moved = {"copy(36)": 36 * total, "copy(48)": 48 * total, "copy(lines)": 20 * total + 40 * n * n}
+    copies = {}
+    for name, size in moved.items():                 # half read, half written
+        src = torch.empty(size // 2, dtype=torch.uint8, device="cuda")
+        copies[name] = (src, torch.empty_like(src))
+
+    def copy_ms(name, reps):
+        src, dst = copies[name]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for name in copies:
+        copy_ms(name, args.warmup)
+    rounds = {}
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            ms, kernel = timed(name, fn, args.reps)
+            rounds.setdefault("pass(%s)" % name, []).append(ms)
+            if kernel is not None:
+                rounds.setdefault("kernel(%s)" % name, []).append(kernel)
+        for name in copies:
+            rounds.setdefault(name, []).append(copy_ms(name, args.reps))
+    queries = {name: prog.query(p) for name, prog in programs.items()}
+    moved.update({"kernel(vignette)": 36 * total, "kernel(falloff)": 48 * total})
+    lines = ["a stage that reads the fragment's line, the flow pass at width %g, %d^2 particles (C3 state, 3 steps in) into %d x %d, stream-ordered pipeline, reuse off; "
+             "%d rounds of %d calls, arms alternating; GPU ms per call (events on the stream)" % (args.line_width, n, w, h, args.rounds, args.reps),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "fragments per pass: %d; lines: %d" % (total, n * n),
+             "%-20s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)")]
+    med = {}
+    for name, ms in rounds.items():
+        med[name] = statistics.median(ms)
+        gbps = "%.1f" % (moved[name] / med[name] / 1e6) if name in moved else "-"
+        lines.append("%-20s %10.4f %10.4f %10.4f %14s" % (name, med[name], min(ms), max(ms), gbps))
+    line_kernels = med["pass(falloff)"] - med["pass(vignette)"] - (med["kernel(falloff)"] - med["kernel(vignette)"])
+    lines.append("pass(vignette) / pass(plain) = %.3f;  pass(falloff) / pass(plain) = %.3f;  pass(falloff) / pass(vignette) = %.3f  (time ratios)"
+                 % (med["pass(vignette)"] / med["pass(plain)"], med["pass(falloff)"] / med["pass(plain)"], med["pass(falloff)"] / med["pass(vignette)"]))
+    lines.append("the line kernels, from the events: pass(falloff) - pass(vignette) - (kernel(falloff) - kernel(vignette)) = %.4f ms;  / copy(lines) = %.3f;  kernel(falloff) / copy(48) = %.3f"
+                 % (line_kernels, line_kernels / med["copy(lines)"], med["kernel(falloff)"] / med["copy(48)"]))
+    for name, info in queries.items():
+        lines.append("th_program_query(%s): %s" % (name, json.dumps(info)))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(dict(root=n, width=w, height=h, line_width=args.line_width, reps=args.reps, rounds=args.rounds, fragments=total, query=queries, median_ms=med)))
     if args.out:
         with open(args.out, "w") as f:
             f.write(text + "\n")
