@@ -425,8 +425,11 @@ th_status th_draw_program_emit(th_context *ctx, th_program *program, const void 
  *                      ex = ey = 0.  A program reads the line if its source names the identifier th_line (decided by
  *                      th_fragment_program_compile; a mention in a comment counts): its passes run one more kernel behind the
  *                      emit, which writes a 16-byte record per fragment, and are stream-ordered also under TH_OPT_STAGE_BINS
- *                      (th_draw_query: TH_DRAW_STREAM; the bits of the option off).  Every other program launches what it
- *                      always did.  In th_draw_stages_run and th_draw_stages_emit, behind either vertex stage.
+ *                      (th_draw_query: TH_DRAW_STREAM; the bits of the option off) - unless TH_OPT_LINE_BINS is on as well: then
+ *                      such a pass goes through the bins like any other stage's, two kernels behind the emitting pass write the
+ *                      lines' snapped endpoints by stream index and a 16-byte record per place of the page store, and the stage
+ *                      runs there (th_fragment_line_bins_kernel; the same numbers, the same bits).  Every other program launches
+ *                      what it always did.  In th_draw_stages_run and th_draw_stages_emit, behind either vertex stage.
  * Every accessor clamps: a program that reads through them alone cannot read out of bounds.  NOT offered: the destination
  * texel (GL has none either), `discard`, th_particles - a source that names an accessor it does not have fails to compile,
  * on the caller's own line.  A fragment that wants to leave its texel alone
@@ -845,7 +848,7 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
 
 /* Per-context switches between equivalent paths (build-defined; no switch changes a result - the parity suites rerun under
  * each, tests/conftest.py).  A context starts from the environment variables of the same names, read by th_create
- * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS, TH_HASH_WINDOW, TH_STAGE_BINS;
+ * (TH_BUCKET, TH_RESORT_STEPS, TH_REBUCKET_STEPS, TH_FUSE, TH_GRAPH, TH_FORCE_GENERIC, TH_DRAW_REUSE, TH_BINS_POOL, TH_BINS_PAGES, TH_ASYNC_SORT, TH_SKIP_UNSEEN, TH_SPAWN_CHUNK_ROWS, TH_HASH_WINDOW, TH_STAGE_BINS, TH_LINE_BINS;
  * TH_DRAW=stream|bins sets what TH_DRAW_AUTO means).
  *   TH_OPT_BUCKET          tile-sorted slot order never (0) / always (1) / when it pays (-1, default)
  *   TH_OPT_RESORT_STEPS    re-sort period of single-step launches (default 64)
@@ -881,7 +884,12 @@ th_status th_flow_lines(th_context *ctx, const th_flow_line_uniforms *u, const f
  *   TH_OPT_STAGE_BINS      (TH_STAGE_BINS) a pass of th_draw_stages_run with a caller's FRAGMENT stage takes the pipeline the same
  *                          pass without the stage would take - through the bins the stage runs over the page store, in place, between
  *                          the emitting pass and the blends (th_fragment_bins_kernel), and the ring keeps its slot order (1); such a
- *                          pass is stream-ordered under every policy and pulls the ring to texel order (0, default) */
+ *                          pass is stream-ordered under every policy and pulls the ring to texel order (0, default)
+ *   TH_OPT_LINE_BINS       (TH_LINE_BINS) under TH_OPT_STAGE_BINS, a pass whose fragment stage reads th_line takes that pipeline too:
+ *                          through the bins the library keeps the lines' snapped endpoints by stream index (16 bytes a particle) and a
+ *                          line record per place of the page store (16 bytes a place), both reserved by the first such pass - a
+ *                          context that cannot have them draws the pass stream-ordered (1); such a pass is stream-ordered whatever
+ *                          TH_OPT_STAGE_BINS says (0, default).  Without TH_OPT_STAGE_BINS the switch changes nothing */
 enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH_OPT_FUSE = 3, TH_OPT_GRAPH = 4,
        TH_OPT_FORCE_GENERIC = 5, TH_OPT_DRAW_REUSE = 6, TH_OPT_BINS_POOL = 7,
 #ifdef TH_TESTING
@@ -889,7 +897,7 @@ enum { TH_OPT_BUCKET = 0, TH_OPT_RESORT_STEPS = 1, TH_OPT_REBUCKET_STEPS = 2, TH
 #endif
        TH_OPT_BINS_PAGES = 9, TH_OPT_ASYNC_SORT = 10, TH_OPT_SKIP_UNSEEN = 11, TH_OPT_SPAWN_CHUNK_ROWS = 12,
        TH_OPT_HASH_WINDOW = 13, TH_OPT_HASH_WINDOW_LAUNCHES = 14, TH_OPT_DENSE_SORTS = 15,
-       TH_OPT_STAGE_BINS = 16 };
+       TH_OPT_STAGE_BINS = 16, TH_OPT_LINE_BINS = 17 };
 th_status th_option_set(th_context *ctx, int32_t option, int64_t value);
 th_status th_option_get(th_context *ctx, int32_t option, int64_t *value);
 

@@ -47,6 +47,7 @@ void options_from_environment(th_options &o)
     o.skip_unseen = number("TH_SKIP_UNSEEN", 1) != 0;
     o.hash_window = number("TH_HASH_WINDOW", 1) != 0;
     o.stage_bins = number("TH_STAGE_BINS", 0) != 0;
+    o.line_bins = number("TH_LINE_BINS", 0) != 0;
     o.spawn_chunk_rows = (int)number("TH_SPAWN_CHUNK_ROWS", 0); if (o.spawn_chunk_rows < 0) o.spawn_chunk_rows = 0;
     o.bins_pool = (uint32_t)number("TH_BINS_POOL", 0);
     o.bins_pages = (int)number("TH_BINS_PAGES", 0); if (o.bins_pages > (int)th::kBinPagesLimit || o.bins_pages < -(int)th::kBinPagesLimit) o.bins_pages = 0;
@@ -596,6 +597,7 @@ th_status th_option_set(th_context *c, int32_t option, int64_t value)
     case TH_OPT_SKIP_UNSEEN: o.skip_unseen = value != 0; break;
     case TH_OPT_HASH_WINDOW: o.hash_window = value != 0; break;
     case TH_OPT_STAGE_BINS: o.stage_bins = value != 0; break;
+    case TH_OPT_LINE_BINS: o.line_bins = value != 0; break;
     case TH_OPT_HASH_WINDOW_LAUNCHES: return fail(TH_ERR_INVALID, "TH_OPT_HASH_WINDOW_LAUNCHES is read-only");
     case TH_OPT_DENSE_SORTS: return fail(TH_ERR_INVALID, "TH_OPT_DENSE_SORTS is read-only");
     case TH_OPT_ASYNC_SORT: o.async_sort = value != 0; if (!o.async_sort) { if (th_status s = asort_drop(c)) return s; } break;
@@ -634,6 +636,7 @@ th_status th_option_get(th_context *c, int32_t option, int64_t *value)
     case TH_OPT_SKIP_UNSEEN: *value = o.skip_unseen; break;
     case TH_OPT_HASH_WINDOW: *value = o.hash_window; break;
     case TH_OPT_STAGE_BINS: *value = o.stage_bins; break;
+    case TH_OPT_LINE_BINS: *value = o.line_bins; break;
     case TH_OPT_HASH_WINDOW_LAUNCHES: *value = c->hash_window_launches; break;
     case TH_OPT_DENSE_SORTS: *value = c->dense_sorts; break;
     case TH_OPT_BINS_POOL: *value = o.bins_pool; break;

@@ -76,6 +76,7 @@ struct th_options {
     bool async_sort = true;              // TH_ASYNC_SORT: a frame loop's re-sort runs beside its draw() instead of inside two of its steps (th_step.hip)
     bool hash_window = true;             // TH_HASH_WINDOW: fused launches hash over a window of the noise lattice where the host can bound it (th_step.hip: hash_window)
     bool stage_bins = false;             // TH_STAGE_BINS: a pass with a caller's fragment stage takes the pipeline the pass without it would (th_draw.hip: deposit_prepare)
+    bool line_bins = false;              // TH_LINE_BINS: ... also when the stage reads th_line: line records per place of the page store (th_fragline.hip); nothing without stage_bins
 };
 
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
@@ -108,6 +109,7 @@ struct ProgramModule {
     hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
     hipFunction_t fn_line = nullptr, fn_line_band = nullptr;      // a fragment program's fourth and fifth: th_fragment_line_kernel / th_fragment_line_band_kernel
                                          // (fn / fn_band with the fragments' line records behind their record: a program that reads th_line)
+    hipFunction_t fn_line_bins = nullptr;                         // ... and its sixth: th_fragment_line_bins_kernel (fn_slots with the places' line records behind its record)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -125,7 +127,8 @@ struct FragmentStage {
     const void *uniforms; uint32_t uniform_bytes;
     int32_t pass;
 };
-// the stage reads th_line(f): its pass is stream-ordered whatever TH_OPT_STAGE_BINS says, and holds a line record per fragment
+// the stage reads th_line(f): its pass holds a line record per fragment, and is stream-ordered whatever TH_OPT_STAGE_BINS says
+// unless TH_OPT_LINE_BINS is on as well
 inline bool stage_reads_line(const FragmentStage *stage) { return stage && stage->module->prog->reads_line; }
 // One pass of draw() as its entry point describes it, for pass_run (a whole texture) and pass_emit (a row band; th_draw.hip); both passes in one (th_draw, th_draw_emit) prepare themselves
 struct PassSpec {
@@ -230,6 +233,11 @@ struct th_context {
                                          // between the two): the next emitting pass wipes it first
     DevBuf<unsigned long long> bins_keys;      // the page store: (bins x kBinReplicas + bins_pool) pages of kBinPage places - keys (~0 = empty) ...
     DevBuf<float4> bins_colors;          // ... and varyings (two per place once a th_draw has run)
+    // TH_OPT_LINE_BINS, reserved by the first binned pass whose stage reads th_line (th_draw.hip: bins_line_store): the lines'
+    // snapped endpoints by stream index (W x H x 16 bytes), and a line record per place of the store (16 bytes a place: follows the store)
+    DevBuf<int4> bins_line_ends;
+    DevBuf<th::FragmentLine> bins_lines;
+    size_t bins_lines_places = 0;
     uint32_t bins_pool = 0, bins_store_bins = 0;
     bool bins_pairs = false;
     DevBuf<uint32_t> crowd_mem;          // per large bin: fragments per texel, first fragment of every texel, fill cursors, long runs
@@ -469,8 +477,10 @@ th_status vertex_stage_band(th_context *c, const PassSpec &s, th::DepositParams 
 th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total);
 // ... and over the fragments an emitting attempt of the binned pass `p` (not mode 2) has just left in the page store: p.frag_keys /
 // p.colors at every place the bins' lists handed out - before anything blends, whether or not the host accepts the attempt
-// (crowded: the last draw put most of its fragments into crowded bins - a bin's places are dealt to more workgroups)
-th_status fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded);
+// (crowded: the last draw put most of its fragments into crowded bins - a bin's places are dealt to more workgroups; program:
+// the pass's vertex stage was a caller's).  A stage that reads th_line: the two line kernels of th_fragline.hip fill
+// c->bins_line_ends and c->bins_lines first - reserved by the caller, bins_pass_emit - and the stage's sixth entry point runs
+th_status fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);
 // an image a pass taps, as the TH_VIEW_* names resolve: texels in a TH_TEX_* format
@@ -515,7 +525,8 @@ float drawn_line_width(const th_context *c, int pass);
 // program: the pass of a caller's draw program (th_drawprog.hip) - its binned form walks the vertex records in texel order over
 // a ring left in whatever order it is held in (no perm, no block_seen, no source table, the texel-order block list); stage: the
 // pass's fragment stage, or null - with one the pass is stream-ordered, and no frame of the policy's count, unless
-// TH_OPT_STAGE_BINS is on and the stage does not read th_line: then it takes the pipeline the pass without the stage would
+// TH_OPT_STAGE_BINS is on and the stage does not read th_line (or TH_OPT_LINE_BINS is on too): then it takes the pipeline the
+// pass without the stage would
 th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::DepositParams &p, bool want_bins = false, bool *bins = nullptr, bool program = false, const FragmentStage *stage = nullptr);
 th_status deposit_scan_total(th_context *c, const th::DepositParams &p, uint32_t *total);
 th_status deposit_reserve(th_context *c, uint32_t total, bool wide, bool pairs = false, bool lines = false);      // lines: and a th::FragmentLine per fragment

@@ -94,8 +94,9 @@ th_status deposit_prepare(th_context *c, const th_deposit_uniforms *u, th::Depos
     if (program && !kAutoBinsPrograms && draw_policy(c) != 1) want_bins = false;
     // (a pass with a caller's fragment stage is stream-ordered, and no frame of the policy's count - unless TH_OPT_STAGE_BINS is on:
     // then it is the pass it would be without the stage, which runs over the bins' page store: deposit_run_bins.  A stage that
-    // reads th_line stays stream-ordered under the option too: its line records lie beside the stream-ordered fragment array)
-    if (stage && (!c->opt.stage_bins || stage_reads_line(stage))) want_bins = false;
+    // reads th_line stays stream-ordered under the option too - its line records lie beside the stream-ordered fragment array -
+    // unless TH_OPT_LINE_BINS is on as well: then they lie beside the page store's places, bins_line_store)
+    if (stage && (!c->opt.stage_bins || (stage_reads_line(stage) && !c->opt.line_bins))) want_bins = false;
     // The auto policy counts FRAMES, and the passes of one frame - th_flow_deposit then th_view_draw, or two widths - take one
     // pipeline: a view pass that left the slot order its flow pass had drawn over would throw the order away in mid-frame.
     if (want_bins && c->draw_frame_step != c->total_steps) { ++c->draws; c->draw_frame_step = c->total_steps; c->frame_bins = -1; }
@@ -457,6 +458,7 @@ static th_status bins_store(th_context *c, uint32_t nbins, uint32_t pool, bool p
     if (c->bins_keys && c->bins_store_bins == nbins && c->bins_pool >= pool && (c->bins_pairs || !pairs)) return TH_OK;
     TH_HIP(hipStreamSynchronize(c->stream));
     c->bins_keys.reset(); c->bins_colors.reset();
+    c->bins_lines.reset(); c->bins_lines_places = 0;         // (the places' line records follow the store: bins_line_store)
     pool = pool > c->bins_pool ? pool : c->bins_pool;
     pairs = pairs || c->bins_pairs;
     c->bins_pool = 0; c->bins_store_bins = 0;
@@ -471,6 +473,28 @@ static th_status bins_store(th_context *c, uint32_t nbins, uint32_t pool, bool p
     }
     TH_HIP(hipMemsetAsync(c->bins_keys, 0xff, places * sizeof(unsigned long long), c->stream));
     c->bins_pool = pool; c->bins_store_bins = nbins; c->bins_pairs = pairs;
+    return TH_OK;
+}
+
+// What a binned pass whose fragment stage reads th_line holds beside the store (TH_OPT_LINE_BINS; th_fragline.hip): the lines'
+// snapped endpoints by stream index - 16 bytes a particle, 268 MB at 4096^2 - and a line record per place of the store - 16
+// bytes a place, the size of bins_colors with one varying a place -, reserved by the first pass that needs them;
+// the records are as long as the store and go when it is laid out anew (bins_store).  Memory that cannot be had is no error: the
+// pass goes stream-ordered, as for a store that cannot be had, and th_last_error() keeps what it said.
+static th_status bins_line_store(th_context *c)
+{
+    const size_t places = bins_places(c->bins_store_bins, c->bins_pool);
+    if (c->bins_line_ends && c->bins_lines && c->bins_lines_places >= places) return TH_OK;
+    TH_HIP(hipStreamSynchronize(c->stream));
+    const std::string said = last_error();
+    c->bins_lines.reset(); c->bins_lines_places = 0;
+    if ((!c->bins_line_ends && c->bins_line_ends.alloc((size_t)c->cfg.width * c->cfg.global_height) != TH_OK) || c->bins_lines.alloc(places) != TH_OK) {
+        (void)hipGetLastError();
+        last_error() = said;
+        c->bins_line_ends.reset(); c->bins_lines.reset();
+        return kRetryInStreamOrder;
+    }
+    c->bins_lines_places = places;
     return TH_OK;
 }
 
@@ -587,13 +611,17 @@ th_status bins_pass_emit(th_context *c, th::DepositParams &p, bool blend_early, 
     }
     for (int attempt = 0;; ++attempt) {
         if (th_status s = bins_store_for(c, p, 0)) return s;
+        // (a stage that reads th_line: room for this attempt's store's line records before anything is emitted - a pass that
+        // cannot have it has touched nothing)
+        if (stage_reads_line(stage)) if (th_status s = bins_line_store(c)) return s;
         bins_expect(c, p);
         th::launch_bins_fused(p, c->stream, program);
         // A caller's fragment stage: over every place the attempt handed out, in place, before the fork - so before the early blend
         // and both topologies of bins_pass_blend: every fragment has run before anything blends (th_flow inside a stage reads the
         // field as it was before the pass).  On an attempt the host then turns down it is harmless: the kernel leaves a flagged
         // pass alone, a repeated pass writes every varying again and an abandoned one is wiped.
-        if (stage) if (th_status s = fragment_stage_run_bins(c, *stage, p, !blend_early)) return s;
+        // (one that reads th_line: the two line kernels first, on this stream, then its sixth entry point - fragment_stage_run_bins)
+        if (stage) if (th_status s = fragment_stage_run_bins(c, *stage, p, !blend_early, program)) return s;
         // the totals come back over the side stream while the ordinary bins are already being blended (the kernel looks at the
         // pass's flags itself): the host's round trip - it sizes the crowded bins' launches - costs the GPU nothing
         TH_HIP(hipEventRecord(c->forked, c->stream));

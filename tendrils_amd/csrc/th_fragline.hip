@@ -15,8 +15,16 @@
 //   along  = dep_param's own result (num / den)
 //   len16  = sqrtf((float)den);  across = ((float)crs / len16) * 0.0625f;  length = len16 * 0.0625f
 //   den == 0: along = across = length = 0
+//
+// The binned pipeline (th_bins.hip) keeps no stream-ordered array: between its emit and its blends a fragment lies at a PLACE of
+// the page store, under a key that holds its texel and its line's stream index.  Under TH_OPT_LINE_BINS a stage that reads the
+// line runs there too, over records written by the two kernels at the end of this file: fragment_line_ends_kernel walks the slots
+// as the emit walked them and leaves every drawing line's four snapped integers in a table by stream index; fragment_lines_bins_kernel
+// walks the places as the stage's own kernel will, looks a place's line up by the key's low word and writes line_record()'s
+// result beside the key.  The numbers are line_record's from dep_setup's integers: the stream-ordered records, bit for bit.
 #include "th_kernels.hpp"
 #include "th_raster.hpp"
+#include "th_bins_places.hpp"
 
 namespace th {
 namespace {
@@ -97,6 +105,72 @@ __global__ __launch_bounds__(256) void fragment_lines_long_kernel(const DepositP
     });
 }
 
+// ---- the records of a BINNED pass ----------------------------------------------------------------------------------------------
+// Kernel A: the snapped endpoints of every line that draws, by stream index.  The walk is bins_fused_kernel's: a workgroup of 256
+// per listed block of slots, the blocks the step saw leave the view skipped, slot s's particle by slot_particle, its line by
+// dep_setup - the geometry alone (the built-in stage over `perm`, LineSources tables and packed texels; a vertex program's
+// records in texel order).  A line that does not draw has no fragment and its entry is never read: the table is not cleared.
+// Two 16-byte state loads (or the records) and one 16-byte store a lane; no LDS, no atomics; *p.oob only where the emit set it
+// (the same dep_fetch).
+template <bool PROGRAM>
+__global__ __launch_bounds__(256) void fragment_line_ends_kernel(const DepositParams p, int4 *ends)
+{
+    if (blockIdx.x >= p.draw_nblocks) return;
+    const uint32_t block = p.draw_blocks[blockIdx.x];
+    if (p.block_seen && p.block_seen[block] == 0u) return;
+    const uint32_t s = block * 256u + threadIdx.x;
+    uint32_t col = 0, row = 0;
+    if (!(s < p.W * p.rows && slot_particle<PROGRAM>(p, s, col, row))) return;
+    DepositLine L;
+    dep_setup<false, PROGRAM>(p, col, p.row0 + row, L, s, OwnTexels{}, false);
+    if (L.draws) ends[(size_t)col * p.H + p.row0 + row] = make_int4(L.sx[0], L.sy[0], L.sx[1], L.sy[1]);
+}
+
+// Kernel B: lines[place] for every live place of the store.  The walk is th_fragment_bins_kernel's (th_fragment_prelude.inc, which
+// restates it: that text cannot include this unit's headers): blockIdx.x is a bin, its sixteen lists' cursors are uniform loads
+// and their running sums stay in scalar registers, the places go to 256 lanes in rounds, blockIdx.y deals the rounds.  Skipped:
+// a flagged pass, places at or beyond a list's cursor, pages nobody published or outside the store, the empty key - and a key
+// whose low word is no line of this texture (none is written: the table's bound, checked where it is indexed).  Per lane: the
+// 8-byte key (x, y, line: its fields), the dependent 16-byte load of the line's endpoints, line_record, one 16-byte store.
+// Nothing is written but lines[place] of live places.
+__global__ __launch_bounds__(256) void fragment_lines_bins_kernel(const DepositParams p, const int4 *ends, FragmentLine *lines)
+{
+    if (p.totals[kTotFlags] != 0u || p.totals[kTotOob] != 0u) return;
+    const uint32_t b = blockIdx.x;
+    if (b >= p.nbins) return;
+    const uint32_t list_cap = p.max_pages << kPageShift;      // (a cursor beyond a list's pages: the pass was flagged)
+    uint32_t first[kBinReplicas + 1u];
+    first[0] = 0u;
+#pragma unroll
+    for (uint32_t r = 0; r < kBinReplicas; ++r) {
+        const uint32_t n = *list_cursor(p, b, r);
+        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
+    }
+    const uint32_t n = first[kBinReplicas], rounds = (n + 255u) >> 8;
+    const uint32_t pages = p.nbins * kBinReplicas + p.pool_pages, nlines = p.W * p.H;
+    for (uint32_t round = blockIdx.y; round < rounds; round += gridDim.y) {
+        const uint32_t w = (round << 8) + threadIdx.x;
+        if (w >= n) continue;
+        uint32_t r = 0u, base = 0u;
+#pragma unroll
+        for (uint32_t q = 1; q < kBinReplicas; ++q) if (w >= first[q]) { r = q; base = first[q]; }
+        const uint32_t list = b * kBinReplicas + r, v = w - base, pn = v >> kPageShift;
+        const uint32_t page = page_of<false>(p, list, pn);
+        if ((pn != 0u && page == 0u) || page >= pages) continue;          // (not published; kNoPlace among the rest)
+        const uint32_t at = (page << kPageShift) | (v & (kBinPage - 1u));
+        const unsigned long long key = p.frag_keys[at];
+        if (key == ~0ull) continue;
+        const uint32_t id = (uint32_t)key;
+        if (id >= nlines) continue;
+        const int4 e = ends[id];
+        DepositLine L;
+        L.sx[0] = e.x; L.sy[0] = e.y; L.sx[1] = e.z; L.sy[1] = e.w;
+        const int ex = L.sx[1] - L.sx[0], ey = L.sy[1] - L.sy[0];       // (dep_setup's own expression: either branch converts the exact integers)
+        L.short32 = ex > -(1 << 14) && ex < (1 << 14) && ey > -(1 << 14) && ey < (1 << 14);
+        lines[at] = line_record(L, id, (int)((uint32_t)(key >> 32) & 0xfffu), (int)((uint32_t)(key >> 44) & 0xfffu));
+    }
+}
+
 }  // namespace
 
 // behind launch_deposit_scatter(p), which left p.keys / p.keys64 (one of them: not a pass that reuses a sorted order); `lines`
@@ -112,6 +186,20 @@ void launch_fragment_lines(const DepositParams &p, FragmentLine *lines, hipStrea
     }
     hipLaunchKernelGGL(fragment_lines_kernel<false>, grid, dim3(kPatchCols * 64u), 0, s, p, lines);
     hipLaunchKernelGGL(fragment_lines_long_kernel<false>, dim3(kDepLists * 8u), dim3(256), 0, s, p, lines);
+}
+
+// behind launch_bins_fused(p, s, program) on the same stream: `ends` holds p.W * p.H entries
+void launch_fragment_line_ends(const DepositParams &p, int4 *ends, hipStream_t s, bool program)
+{
+    const dim3 grid(p.draw_nblocks ? p.draw_nblocks : 1u);
+    if (program) hipLaunchKernelGGL(fragment_line_ends_kernel<true>, grid, dim3(256), 0, s, p, ends);
+    else hipLaunchKernelGGL(fragment_line_ends_kernel<false>, grid, dim3(256), 0, s, p, ends);
+}
+
+// ... and behind that: `lines` holds a record for every place of the store p.frag_keys names
+void launch_fragment_lines_bins(const DepositParams &p, const int4 *ends, FragmentLine *lines, bool crowded, hipStream_t s)
+{
+    hipLaunchKernelGGL(fragment_lines_bins_kernel, dim3(p.nbins ? p.nbins : 1u, (uint32_t)(crowded ? kBinsStageDealCrowded : kBinsStageDeal)), dim3(256), 0, s, p, ends, lines);
 }
 
 }  // namespace th

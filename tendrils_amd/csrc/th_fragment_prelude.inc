@@ -256,4 +256,57 @@ extern "C" __global__ __launch_bounds__(256) void th_fragment_bins_kernel(const 
         th_fragment_place(f, a.f, key, at);
     }
 }
+
+// ---- ... and of a program that reads the fragment's line, over the same store (TH_OPT_LINE_BINS) -------------------------------
+// th_fragment_bins_kernel with the pass's line records behind the record it takes: lines[at] belongs to the fragment at place
+// `at` (th_fragline.hip writes it from the place's key and the line's snapped endpoints: line_record's numbers, as in a
+// stream-ordered pass).  A record of its own (th_fragprog.hip: FragmentLineBinsArgs, the same layout); the walk above, and a lane
+// loads its 16-byte record once, beside its varying - as th_fragment_line_kernel does.
+struct th_fragment_line_bins_args {
+    th_fragment_bins_args b;
+    const th_fragment_line *lines;   // per place of the store
+};
+static_assert(sizeof(th_fragment_line_bins_args) == 120, "th_fragment_line_bins_args: layout shared with th_fragprog.hip");
+
+extern "C" __global__ __launch_bounds__(256) void th_fragment_line_bins_kernel(const th_fragment_line_bins_args a, const th_program_uniform_block u)
+{
+    if (a.b.replicas != TH_BIN_REPLICAS || a.b.page_shift != TH_BIN_PAGE_SHIFT) return;
+    if (a.b.totals[TH_BINS_TOT_FLAGS] != 0u || a.b.totals[TH_BINS_TOT_OOB] != 0u) return;
+    const unsigned b = blockIdx.x;
+    if (b >= a.b.nbins) return;
+    const unsigned list_cap = a.b.max_pages << TH_BIN_PAGE_SHIFT;
+    const unsigned *cursor = a.b.bin_cursor + (size_t)(b & 31u) * ((a.b.nbins + 31u) >> 5) + (b >> 5);
+    unsigned first[TH_BIN_REPLICAS + 1u];
+    first[0] = 0u;
+#pragma unroll
+    for (unsigned r = 0; r < TH_BIN_REPLICAS; ++r) {
+        const unsigned n = cursor[(size_t)r * a.b.bin_stride];
+        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
+    }
+    const unsigned n = first[TH_BIN_REPLICAS], rounds = (n + 255u) >> 8;
+    if (blockIdx.y >= rounds) return;
+    th_fragment_pass f = th_fragment_pass_of(a.b.f, u);
+    const unsigned long long *keys = static_cast<const unsigned long long *>(a.b.f.keys);
+    for (unsigned round = blockIdx.y; round < rounds; round += gridDim.y) {
+        const unsigned w = (round << 8) + threadIdx.x;
+        if (w >= n) continue;
+        unsigned r = 0u, base = 0u;
+#pragma unroll
+        for (unsigned q = 1; q < TH_BIN_REPLICAS; ++q) if (w >= first[q]) { r = q; base = first[q]; }
+        const unsigned list = b * TH_BIN_REPLICAS + r, v = w - base, pn = v >> TH_BIN_PAGE_SHIFT;
+        unsigned id = list;
+        if (pn != 0u) {
+            if (pn >= a.b.max_pages) continue;
+            id = a.b.page_table[(size_t)list * a.b.max_pages + pn];
+            if (id == 0u) continue;
+        }
+        if (id >= a.b.pages) continue;                   // (0xffffffff among them)
+        const unsigned at = (id << TH_BIN_PAGE_SHIFT) | (v & ((1u << TH_BIN_PAGE_SHIFT) - 1u));
+        const unsigned long long key = keys[at];
+        if (key == ~0ull) continue;
+        const th_fragment_line line = a.lines[at];
+        f.line = &line;
+        th_fragment_place(f, a.b.f, key, at);
+    }
+}
 )TH_PRELUDE"

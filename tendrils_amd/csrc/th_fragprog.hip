@@ -10,6 +10,8 @@
 // store, and bins_pass_emit (th_draw.hip) calls fragment_stage_run_bins between the emitting pass and the blends.
 // A program whose source names th_line reads the fragment's line: its pass stays stream-ordered, fragment_stage_run has the line
 // kernel (th_fragline.hip) write a record per fragment beside key and varying, and launches the two entry points that take them.
+// Under TH_OPT_LINE_BINS as well such a pass goes through the bins like the others: fragment_stage_run_bins has th_fragline.hip's
+// two other kernels write a record per place of the store and launches the sixth entry point, which takes those.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -63,6 +65,15 @@ constexpr uint32_t kPreludeReplicas = 16, kPreludePageShift = 8;      // (TH_BIN
 static_assert(sizeof(FragmentBinsArgs) == 112 && offsetof(FragmentBinsArgs, bin_cursor) == 64 && offsetof(FragmentBinsArgs, bin_stride) == 88 &&
               offsetof(FragmentBinsArgs, replicas) == 104 && offsetof(BinsKernArgs, u) == 112 && sizeof(BinsKernArgs) == 112 + kUniformBytes,
               "bins launch record: layout shared with th_fragment_prelude.inc");
+// ... and of th_fragment_line_bins_kernel (th_fragment_line_bins_args): that record, then the places' line records
+// (th_fragline.hip) - a program that reads th_line, through the bins (TH_OPT_LINE_BINS)
+struct FragmentLineBinsArgs {
+    FragmentBinsArgs b;
+    const th::FragmentLine *lines;
+};
+using LineBinsKernArgs = ProgramKernArgs<FragmentLineBinsArgs>;
+static_assert(sizeof(FragmentLineBinsArgs) == 120 && offsetof(FragmentLineBinsArgs, lines) == 112 && offsetof(LineBinsKernArgs, u) == 128 &&
+              sizeof(LineBinsKernArgs) == 128 + kUniformBytes, "line bins launch record: layout shared with th_fragment_prelude.inc");
 static_assert(th::kBinReplicas == kPreludeReplicas && th::kBinPage == 1u << kPreludePageShift && th::kTotOob == 1 && th::kTotFlags == 2 &&
               th::kBinsMaxExtent == 1 << 12, "th_fragment_prelude.inc restates the bins' constants and the key's 12-bit fields");
 // A bin's rounds of 256 places are dealt to this many workgroups (gridDim.y).  Every workgroup reads its bin's sixteen cursors
@@ -72,7 +83,8 @@ static_assert(th::kBinReplicas == kPreludeReplicas && th::kBinPage == 1u << kPre
 // wants the wider deal: a workgroup walks its rounds one behind the other, a chain of three loads and a store each.  Which of
 // the two the target is was the last draw's to say, as for the early blend (deposit_run_bins).  Measured, ms a pass, ordinary /
 // crowded target: deal 2: 0.130 / 0.460, 8: 0.161 / 0.356, 32: 0.303 / 0.437, 128: 0.877 / 0.890 (profiles/fragment_program_bins.txt).
-constexpr int kBinsStageDeal = 2, kBinsStageDealCrowded = 8;
+using th::kBinsStageDeal;                  // (2; th_kernels.hpp: the line records of a binned pass are dealt alike)
+using th::kBinsStageDealCrowded;           // (8)
 
 // n / d for every 32-bit n by one multiplication (Granlund & Montgomery 1994, the round-up form): the multiplier and both shifts
 void divide_by(uint32_t d, uint32_t &mul, uint32_t &shifts)
@@ -169,12 +181,11 @@ th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, con
     return timer.end(c);
 }
 
-th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded)
+namespace {
+
+// the record every entry point over the page store starts with
+void bins_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, FragmentBinsArgs &a)
 {
-    TH_REQUIRE(p.mode != 2 && p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: one varying a place, a store to run over");
-    TH_REQUIRE(!stage_reads_line(&stage), "a fragment stage that reads the line is stream-ordered (deposit_prepare)");
-    BinsKernArgs k{};
-    FragmentBinsArgs &a = k.a;
     a.f.keys = p.frag_keys; a.f.colors = p.colors;
     a.f.flow = c->flow; a.f.fw = c->fw; a.f.fh = c->fh;
     a.f.colormap = c->colormap; a.f.cw = c->cmap_w; a.f.ch = c->cmap_h;
@@ -184,8 +195,33 @@ th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage
     a.totals = p.totals;
     a.nbins = p.nbins; a.pages = p.nbins * th::kBinReplicas + p.pool_pages;
     a.replicas = th::kBinReplicas; a.page_shift = kPreludePageShift;
-    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+}
+
+}  // namespace
+
+th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program)
+{
+    TH_REQUIRE(p.mode != 2 && p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: one varying a place, a store to run over");
     LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
+    if (stage_reads_line(&stage)) {
+        // the places' line records first, behind the emitting pass on this stream (bins_pass_emit reserved them for this store)
+        const size_t places = ((size_t)p.nbins * th::kBinReplicas + p.pool_pages) * th::kBinPage;
+        TH_REQUIRE(c->opt.line_bins && c->bins_line_ends && c->bins_lines && c->bins_lines_places >= places && p.frag_keys == c->bins_keys,
+                   "a stage that reads the line over the bins: the lines' endpoints and a record per place of the store");
+        th::launch_fragment_line_ends(p, c->bins_line_ends, c->stream, program);
+        th::launch_fragment_lines_bins(p, c->bins_line_ends, c->bins_lines, crowded, c->stream);
+        TH_HIP(hipGetLastError());
+        LineBinsKernArgs k{};
+        bins_record(c, stage, p, k.a.b);
+        k.a.lines = c->bins_lines;
+        k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+        if (th_status s = timer.begin(c)) return s;
+        if (th_status s = program_launch_grid(c, stage.module->fn_line_bins, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
+        return timer.end(c);
+    }
+    BinsKernArgs k{};
+    bins_record(c, stage, p, k.a);
+    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
     if (th_status s = timer.begin(c)) return s;
     if (th_status s = program_launch_grid(c, stage.module->fn_slots, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
     return timer.end(c);

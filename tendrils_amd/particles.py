@@ -115,7 +115,8 @@ class FragmentProgram(Program):
     and dispose() as there.  Tendrils runs it as the second of a flowShader / renderShader pair (or alone: with the library's
     vertex stage); such a pass is stream-ordered unless Particles.option("stage_bins", 1) sends it through the bins.  A source
     that names th_line reads the fragment's line (th_line(f): line, along, across, length): nothing to pass here - the library
-    sees it when it compiles, writes the records such a pass needs, and keeps the pass stream-ordered."""
+    sees it when it compiles, writes the records such a pass needs, and keeps the pass stream-ordered - unless
+    Particles.option("line_bins", 1) is on beside "stage_bins": then such a pass goes through the bins too."""
     COMPILE, SOURCE_KIND = "th_fragment_program_compile", "fragment"
 
 
@@ -373,14 +374,25 @@ class Particles:
     OPTIONS = dict(bucket=0, resort_steps=1, rebucket_steps=2, fuse=3, graph=4, force_generic=5, draw_reuse=6, bins_pool=7,
                    inject_failure=8, bins_pages=9, async_sort=10, skip_unseen=11, spawn_chunk_rows=12,
                    hash_window=13, hash_window_launches=14, dense_sorts=15, stage_bins=16)
+    # (OPTIONS is pinned as it stands - the numbers 0 .. 16, every one once: tests/test_fragment_program_bins_build.py - so the
+    # switches that came after it have a table of their own; option() looks a name up in both)
+    MORE_OPTIONS = dict(line_bins=17)
+
+    @classmethod
+    def option_number(cls, name):
+        """TH_OPT_* of the switch `name` (include/tendrils_hip.h)"""
+        return cls.OPTIONS[name] if name in cls.OPTIONS else cls.MORE_OPTIONS[name]
 
     def option(self, name, value=None):
         """A switch between equivalent paths of the library (th_option_set / _get; no switch changes a result): returns the
-        current value, sets `value` first if given."""
+        current value, sets `value` first if given.  "stage_bins": a draw() pass with a fragment program takes the pipeline the
+        pass without it would; "line_bins": beside it, so does a pass whose fragment program reads th_line(f) - alone it changes
+        nothing."""
+        number = self.option_number(name)
         if value is not None:
-            call("th_option_set", self._ctx, self.OPTIONS[name], int(value))
+            call("th_option_set", self._ctx, number, int(value))
         out = C.c_int64(0)
-        call("th_option_get", self._ctx, self.OPTIONS[name], C.byref(out))
+        call("th_option_get", self._ctx, number, C.byref(out))
         return out.value
 
     def fetches_taps(self, source):

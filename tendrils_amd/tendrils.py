@@ -490,7 +490,8 @@ class Tendrils:
         """The flow pass - particle lines into the flow texture, so that particles respond to each other's wake - and,
         with renderView, the view pass: the same lines into the RGBA8 view buffer (after the clear / fade the state
         asks for).  Each pass runs the stages of its shader - flowShader / renderShader: a fragment stage (th_draw_stages_run:
-        stream-ordered, or with particles.option("stage_bins", 1) the pipeline of the pass without it), else a vertex program (th_draw_program_run), else the library's own stage; both passes with the
+        stream-ordered, or with particles.option("stage_bins", 1) the pipeline of the pass without it - a stage that reads th_line(f) with
+        particles.option("line_bins", 1) beside it), else a vertex program (th_draw_program_run), else the library's own stage; both passes with the
         library's stages draw the same lines, and one call rasterises and sorts them once (th_draw) when they draw them with
         the same width.  Programs get draw_program_uniforms(), packed into each program's uniform block by field name.  A
         program pass takes the pipeline the library's own pass of this context would (Particles.draw_pipeline / TH_DRAW: binned
@@ -561,7 +562,9 @@ class Tendrils:
         th_draw_stages_run.  By default such a pass is stream-ordered under every policy and takes the ring to texel order;
         with particles.option("stage_bins", 1) (TH_STAGE_BINS) it takes the pipeline the same pass without the fragment stage
         would - through the bins the stage runs over the page store between the emit and the blends, and a tile-sorted ring
-        stays sorted.  The bits are the same either way."""
+        stays sorted.  A fragment program that reads th_line(f) stays stream-ordered under that switch unless
+        particles.option("line_bins", 1) (TH_LINE_BINS) is on beside it: then its line records lie beside the page store's places.
+        The bits are the same either way."""
         builtin = self.render_uniforms() if which == _capi.TH_PASS_VIEW else self.deposit_uniforms()
         stages, _keep = draw_stages(vertex, fragment, uniforms, builtin)
         n = C.c_uint64(0)

@@ -45,7 +45,25 @@ The line kernel's own time is a kernel trace's to give (fragment_lines_kernel, f
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/fragment_program_bench.py --line --rounds 1 --reps 5
 pass(falloff) - pass(vignette) - (kernel(falloff) - kernel(vignette)) is the same figure from the events, and is printed.
 
-Usage: python tools/fragment_program_bench.py [--bins | --line [--line-width 1]] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
+--line --bins: such a stage through the binned pipeline (TH_OPT_LINE_BINS beside TH_OPT_STAGE_BINS; th_fragline.hip:
+fragment_line_ends_kernel, fragment_lines_bins_kernel; th_fragment_line_bins_kernel).  Four contexts in the same state run the frame
+loop side by side, stage_bins = 1 in all of them, policy auto (--line-width above 2: policy bins - the auto policy leaves wide lines
+to the stream-ordered pipeline):
+  loop(falloff, off)  flowShader = (None, falloff), line_bins off: the flow pass stream-ordered, the ring pulled to texel order
+  loop(falloff, on)   the same shader, line_bins on: the flow pass through the bins, the ring in its tile-sorted slots
+  loop(identity)      flowShader = (None, `return f.color`): a stage that does not read the line, through the bins
+  loop(builtin)       no shaders
+(the falloff changes the field the particles follow: its two loops draw the same frames as each other, not as the other two.)
+Then, on a context three steps in with policy bins, the flow pass alone: th_flow_deposit, th_draw_stages_run with `gain` (the bins
+kernel, no line) and with the falloff (the two line kernels, then th_fragment_line_bins_kernel) - the pass between two events and
+th_kernel_timing's pair around the stage's kernel.  The two line kernels together, from the events:
+pass(falloff) - pass(gain) - (kernel(falloff) - kernel(gain)); each alone is a kernel trace's to give, in a run of its own:
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/fragment_program_bench.py --line --bins --rounds 1 --reps 5 --warmup-frames 2
+copy(ends) moves what fragment_line_ends_kernel moves (two 16-byte state texels read and 16 bytes written a line), copy(records)
+what fragment_lines_bins_kernel moves (an 8-byte key and 16 bytes of endpoints read, 16 bytes written a fragment), copy(56) what
+th_fragment_line_bins_kernel moves (key, record and varying read, the varying written).
+
+Usage: python tools/fragment_program_bench.py [--bins | --line [--bins] [--line-width 1]] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -93,6 +111,8 @@ def main():
     ap.add_argument("--line", action="store_true", help="a stage that reads the fragment's line: the pass, the stage's kernel, the copies of what it and the line kernel move")
     ap.add_argument("--line-width", type=float, default=1.0, help="--line: the width the flow pass is drawn with")
     args = ap.parse_args()
+    if args.bins and args.line:
+        return line_bins_main(args)
     if args.bins:
         return bins_main(args)
     if args.line:
@@ -467,6 +487,190 @@ def bins_main(args):
     for t in list(loops.values()) + [fresh]:
         t.dispose()
     for prog in (identity, vignette, gain):
+        prog.dispose()
+
+
+def line_bins_main(args):
+    import time
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("fragment_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import FragmentProgram, draw_stages
+    from tendrils_amd.tendrils import View
+    from test_fragment_program_build import IDENTITY
+    from test_fragment_program_line_build import FALLOFF
+
+    class Falloff(C.Structure):
+        _fields_ = [("halfWidth", C.c_float)]
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    identity = FragmentProgram.from_source(IDENTITY, name="identity")
+    falloff = FragmentProgram.from_source(FALLOFF, Falloff, "falloff")
+    gain = FragmentProgram.from_source(GAIN, GainUniforms, "gain")
+    block = dict(gain=0.5, halfWidth=0.5 * args.line_width + 0.5)
+    state0 = workload.synth_state(0)
+    cmap = np.random.default_rng(7).uniform(0, 1, (64, 64, 4)).astype(np.float32)
+    policy = "bins" if args.line_width > 2.0 else "auto"
+
+    def loop(stage, line_bins, pipeline=policy):
+        opts = ta.defaults()
+        opts["lineWidthRange"] = (1, max(1.0, args.line_width))
+        opts["state"]["flowWidth"] = args.line_width
+        if stage is not None:
+            opts.update(flowShader=(None, stage))
+        t = ta.Tendrils(View(w, h), opts)
+        t.resize()
+        t.setup(n)
+        t.particles.upload_texels(state0)
+        t.colorMap.set_pixels(cmap)
+        t.uniforms["render"].update(block)
+        t.particles.draw_pipeline(pipeline)
+        t.particles.option("stage_bins", 1)
+        t.particles.option("line_bins", line_bins)
+        t.timer.time = 1000.0
+        return t
+
+    loops = {"falloff, off": loop(falloff, 0), "falloff, on": loop(falloff, 1), "identity": loop(identity, 0), "builtin": loop(None, 0)}
+
+    def frames(t, count):
+        """wall ms per frame"""
+        t.particles.sync()
+        t0 = time.perf_counter()
+        for _ in range(count):
+            t.timer.tick()
+            t.step()
+            t.draw()
+        t.particles.sync()
+        return (time.perf_counter() - t0) * 1e3 / count
+
+    def held(t):
+        info, order = _capi.DrawInfo(), _capi.SlotOrderInfo()
+        call("th_draw_query", t.particles._ctx, C.byref(info))
+        call("th_slot_order", t.particles._ctx, C.byref(order))
+        return dict(pipeline="bins" if info.pipeline == 1 else "stream", fragments=int(info.fragments), crowded_fragments=int(info.crowded_fragments),
+                    sorted_buffers=int(order.sorted_buffers), flow_fragments=int(getattr(t, "fragments", 0)))
+
+    for t in loops.values():
+        frames(t, args.warmup_frames)
+    rounds = {}
+    for _ in range(args.rounds):
+        for name, t in loops.items():
+            rounds.setdefault("loop(%s)" % name, []).append(frames(t, args.reps))
+    state = {name: held(t) for name, t in loops.items()}
+    assert state["falloff, on"]["flow_fragments"] == state["falloff, off"]["flow_fragments"], state      # (the same frames: the same lines)
+    assert state["identity"]["flow_fragments"] == state["builtin"]["flow_fragments"], state
+
+    # the flow pass alone, three steps in (every call draws the same lines), policy bins
+    fresh = loop(None, 1, "bins")
+    for _ in range(3):
+        fresh.timer.tick()
+        fresh.step()
+    fresh.line_widths()
+    ctx, d = fresh.particles._ctx, fresh.deposit_uniforms()
+    uniforms = dict(fresh.state, **block)
+    stages = {name: draw_stages(None, prog, uniforms, d) for name, prog in (("gain", gain), ("falloff", falloff))}
+    frags = {}
+
+    def plain():
+        count = C.c_uint64(0)
+        call("th_flow_deposit", ctx, C.byref(d), C.byref(count))
+        frags["plain"] = count.value
+
+    def staged(name):
+        def run():
+            count = C.c_uint64(0)
+            call("th_draw_stages_run", ctx, C.byref(stages[name][0]), 0, C.byref(count))
+            frags[name] = count.value
+        return run
+
+    arms = dict(plain=plain, gain=staged("gain"), falloff=staged("falloff"))
+
+    def timed(name, fn, reps):
+        ms, kernel = C.c_float(0), None
+        if name != "plain":
+            call("th_kernel_timing", ctx, 1)
+        call("th_timer_start", ctx)
+        for _ in range(reps):
+            fn()
+        call("th_timer_stop", ctx, C.byref(ms))
+        if name != "plain":
+            mean, launches = C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+            call("th_kernel_timing", ctx, 0)
+            assert launches.value == reps, (launches.value, reps)          # (one attempt a pass: nothing was repeated)
+            kernel = mean.value
+        return ms.value / reps, kernel
+
+    for name, fn in arms.items():
+        timed(name, fn, args.warmup)
+        assert held(fresh)["pipeline"] == "bins", (name, held(fresh))
+    total = frags["plain"]
+    assert all(v == total for v in frags.values()), frags
+    moved = {"copy(ends)": 48 * n * n, "copy(records)": 40 * total, "copy(56)": 56 * total}
+    copies = {}
+    for name, size in moved.items():                 # half read, half written
+        src = torch.empty(size // 2, dtype=torch.uint8, device="cuda")
+        copies[name] = (src, torch.empty_like(src))
+
+    def copy_ms(name, reps):
+        src, dst = copies[name]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            dst.copy_(src)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    for name in copies:
+        copy_ms(name, args.warmup)
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            ms, kernel = timed(name, fn, args.reps)
+            rounds.setdefault("pass(%s)" % name, []).append(ms)
+            if kernel is not None:
+                rounds.setdefault("kernel(%s)" % name, []).append(kernel)
+        for name in copies:
+            rounds.setdefault(name, []).append(copy_ms(name, args.reps))
+    state["the flow pass, 3 steps in"] = held(fresh)
+    moved.update({"kernel(gain)": 40 * total, "kernel(falloff)": 56 * total})
+
+    lines = ["a stage that reads the fragment's line through the bins (TH_OPT_LINE_BINS), flow lines at width %g, %d^2 particles (C3 state) into %d x %d, "
+             "stage_bins = 1, policy %s; %d frames of warm-up a loop, then %d rounds of %d frames / calls, arms alternating; loop: wall ms per frame "
+             "(synchronised); pass, kernel, copy: GPU ms per call (events)" % (args.line_width, n, w, h, policy, args.warmup_frames, args.rounds, args.reps),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "fragments of the flow pass, 3 steps in: %d; lines: %d" % (total, n * n)]
+    for name in state:
+        lines.append("%s: %s" % ("loop(%s) after its last frame" % name if name in loops else name, json.dumps(state[name])))
+    lines.append("%-28s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)"))
+    med = {}
+    for name, ms in rounds.items():
+        med[name] = statistics.median(ms)
+        gbps = "%.1f" % (moved[name] / med[name] / 1e6) if name in moved else "-"
+        lines.append("%-28s %10.4f %10.4f %10.4f %14s" % (name, med[name], min(ms), max(ms), gbps))
+    both = med["pass(falloff)"] - med["pass(gain)"] - (med["kernel(falloff)"] - med["kernel(gain)"])
+    lines.append("loop(falloff, on) / loop(falloff, off) = %.3f;  loop(falloff, on) / loop(identity) = %.3f;  loop(identity) / loop(builtin) = %.3f  (time ratios)"
+                 % (med["loop(falloff, on)"] / med["loop(falloff, off)"], med["loop(falloff, on)"] / med["loop(identity)"], med["loop(identity)"] / med["loop(builtin)"]))
+    lines.append("pass(gain) / pass(plain) = %.3f;  pass(falloff) / pass(plain) = %.3f;  pass(falloff) / pass(gain) = %.3f;  kernel(falloff) / copy(56) = %.3f  (time ratios)"
+                 % (med["pass(gain)"] / med["pass(plain)"], med["pass(falloff)"] / med["pass(plain)"], med["pass(falloff)"] / med["pass(gain)"], med["kernel(falloff)"] / med["copy(56)"]))
+    lines.append("the two line kernels, from the events: pass(falloff) - pass(gain) - (kernel(falloff) - kernel(gain)) = %.4f ms;  / (copy(ends) + copy(records)) = %.3f"
+                 % (both, both / (med["copy(ends)"] + med["copy(records)"])))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(dict(root=n, width=w, height=h, line_width=args.line_width, reps=args.reps, rounds=args.rounds, fragments=total, state=state, median_ms=med)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    for t in list(loops.values()) + [fresh]:
+        t.dispose()
+    for prog in (identity, falloff, gain):
         prog.dispose()
 
 
