@@ -440,8 +440,9 @@ th_status th_draw_program_emit(th_context *ctx, th_program *program, const void 
  * the ring goes to texel order and is held there as after any stream-ordered pass (a packed ring is read as the library's own
  * stage reads it, through f32 copies under a vertex program), its content is untouched; the policy's frame count does not see the
  * pass; th_draw_query reports TH_DRAW_STREAM and the pass's fragments; nothing of the pass is reused by the next one, nor of
- * the one before by it.  Not built: the stage in the binned pipeline, in th_draw's one-rasterisation form, and in the
- * library-issued exchanges (th_draw_sharded, th_draw_program_sharded).
+ * the one before by it.  (TH_OPT_STAGE_BINS, below, lets such a pass through the bins; th_draw_stages_pair draws both passes'
+ * stages over th_draw's one rasterisation.)  Not built: the stage in the library-issued exchanges (th_draw_sharded,
+ * th_draw_program_sharded), and the pair of passes on row bands.
  *  th_fragment_program_compile    as th_program_compile (a source without th_fragment_main does not compile).  The handle is a
  *                      th_program of a fifth kind: th_program_destroy / _query / _log serve all five (_query: th_fragment_kernel);
  *                      th_program_run, th_screen_run, th_draw_program_run / _emit / _sharded and th_step_program_run refuse it, and
@@ -461,6 +462,30 @@ th_status th_draw_program_emit(th_context *ctx, th_program *program, const void 
  *                      hands them out; th_deposit_merge (TH_PASS_FLOW) / th_view_merge (TH_PASS_VIEW) blend them: for the owned
  *                      texels th_draw_stages_run of the unsharded state bit for bit.  A whole-texture context is the band of all
  *                      rows.  Errors of the call it stands for, and: null outputs.
+ *  th_draw_stages_pair BOTH passes of draw() with a caller's fragment stage in either or both: the results - both targets,
+ *                      the ring, every counter - are bit for bit those of th_draw_stages_run(flow, TH_PASS_FLOW) followed by
+ *                      th_draw_stages_run(view, TH_PASS_VIEW), a slot whose `fragment` is NULL running as the call it stands for
+ *                      (th_flow_deposit / th_view_draw, th_draw_program_run).  The lines are rasterised ONCE for both passes, as
+ *                      th_draw rasterises them - every fragment carries both passes' varyings side by side, each stage runs over
+ *                      its pass's half (th_fragment_pair_kernel / th_fragment_pair_bins_kernel,
+ *                      tendrils_amd/csrc/th_fragment_pair_prelude.inc), the flow pass's first, before anything blends - exactly when
+ *                        1. both `vertex` slots are NULL (draw programs in one rasterisation are not built),
+ *                        2. both passes draw their lines equally wide (th_line_width),
+ *                        3. neither fragment program reads th_line, and
+ *                        4. the VIEW pass's fragment program does not name the identifier th_flow (decided by
+ *                           th_fragment_program_compile like th_line: a mention in a comment counts, th_flow_res does not).
+ *                      4. is a rule of correctness: run in sequence, the view pass's th_flow reads the field AFTER the flow pass
+ *                      has blended into it; in one rasterisation every stage runs before anything blends.  (The flow pass's stage
+ *                      may tap th_flow: it reads the field as it was before the call either way.)  In every other case the call
+ *                      runs the two passes one after the other.  *rasterisations (optional): 1 or 2.  *fragments (optional): the
+ *                      fragments of the one rasterisation, or of the flow pass of two (as th_draw reports two widths; th_draw_query
+ *                      then holds the view pass's).  The pipeline is the one th_draw would take under the rule of the single
+ *                      stage pass: stream-ordered by default; with TH_OPT_STAGE_BINS whatever the policy, the frame's one-pipeline
+ *                      rule and the gates give th_draw - through the bins a tile-sorted ring stays sorted.  th_kernel_timing: an
+ *                      event pair around each stage's launch - two for two stages, none without fragments.  Errors, nothing
+ *                      launched: null `flow` or `view`; both `fragment` slots NULL (th_draw is the call); what th_draw_stages_run
+ *                      refuses of a slot; with both vertex slots NULL, viewSize / time / speedLimit that differ between the two
+ *                      `builtin` blocks (as th_draw); on a row-band shard TH_ERR_UNSUPPORTED.
  *  TH_ERR_INVALID from both, nothing launched: both stages NULL (th_flow_deposit / th_view_draw, th_deposit_emit / th_view_emit
  *                      are the calls), a program of another kind in either slot, more than 1024 uniform bytes in either block,
  *                      null uniforms with a size, a size without a program, vertex NULL without `builtin`, an unknown pass, null
@@ -473,6 +498,10 @@ typedef struct th_draw_stages {
 th_status th_fragment_program_compile(const char *source, const char *name, th_program **out);
 th_status th_draw_stages_run(th_context *ctx, const th_draw_stages *stages, int32_t pass /* TH_PASS_FLOW | TH_PASS_VIEW */, uint64_t *fragments);
 th_status th_draw_stages_emit(th_context *ctx, const th_draw_stages *stages, int32_t pass, uint64_t *count, void **keys_dev, void **colors_dev);
+/* Both passes of Tendrils.draw() with a caller's fragment stage in either or both, over ONE rasterisation where that gives the
+ * bits of the two passes run one after the other; else as those two passes.  *rasterisations (may be null): 1 or 2. */
+th_status th_draw_stages_pair(th_context *ctx, const th_draw_stages *flow, const th_draw_stages *view,
+                              uint64_t *fragments, int32_t *rasterisations);
 
 /* -- step programs: n steps of an integrator the CALLER wrote, fused in one launch -----------------------------------
  * new Tendrils(gl, { logicShader }) takes a caller's integrator (src/index.js:70, 107-113).  As a state program (above) it

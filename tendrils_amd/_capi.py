@@ -251,6 +251,7 @@ PROTOTYPES = {
     "th_draw_stages_run": (C.c_int32, [_ctx, C.POINTER(DrawStages), C.c_int32, C.POINTER(C.c_uint64)]),
     "th_draw_stages_emit": (C.c_int32, [_ctx, C.POINTER(DrawStages), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p)]),
+    "th_draw_stages_pair": (C.c_int32, [_ctx, C.POINTER(DrawStages), C.POINTER(DrawStages), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
     "th_step_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_step_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32]),
     "th_step_program_view_size": (C.c_int32, [_ctx, C.POINTER(C.c_float)]),

@@ -94,6 +94,8 @@ struct th_program {
     uint32_t sgprs = 0, code_bytes = 0;  // of the kind's kernel, read from the code object
     bool reads_line = false;             // a fragment program whose source names th_line (th_fragment_program_compile): its passes write the
                                          // fragments' line records (th_fragline.hip) and launch the entry points that take them
+    bool names_flow = false;             // a fragment program whose source names th_flow (th_fragment_program_compile): as the VIEW pass's stage it
+                                         // keeps th_draw_stages_pair to two passes - run in sequence it sees the field the flow pass has blended into
 };
 // ... and as one context has loaded it (th_program.hip): the context owns the module - unloaded when the context goes - and
 // a reference to the program's record, so that th_program_destroy of a program a context has run is safe.
@@ -110,6 +112,8 @@ struct ProgramModule {
     hipFunction_t fn_line = nullptr, fn_line_band = nullptr;      // a fragment program's fourth and fifth: th_fragment_line_kernel / th_fragment_line_band_kernel
                                          // (fn / fn_band with the fragments' line records behind their record: a program that reads th_line)
     hipFunction_t fn_line_bins = nullptr;                         // ... and its sixth: th_fragment_line_bins_kernel (fn_slots with the places' line records behind its record)
+    hipFunction_t fn_pair = nullptr, fn_pair_bins = nullptr;      // ... its seventh and eighth: th_fragment_pair_kernel / th_fragment_pair_bins_kernel (fn / fn_slots
+                                         // over one half of the two varyings a fragment of th_draw_stages_pair's one rasterisation carries)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -120,7 +124,9 @@ struct ProgramModule {
 
 // A caller's fragment stage as one pass carries it (th_fragprog.hip: th_draw_stages_run / _emit load the module): an argument from
 // the pass's entry point down to where its fragments lie (deposit_run, deposit_run_bins, emit_parted), null when the pass has none - beside
-// th::DepositParams, which is a kernel's argument and knows nothing of it.
+// th::DepositParams, which is a kernel's argument and knows nothing of it.  Beside a pass that draws BOTH passes from one
+// rasterisation (p.mode == 2: th_draw_stages_pair) the same argument points at TWO of these - [0] the flow pass's stage, [1] the
+// view pass's, `module` null where that pass has none -, and fragment_stage_run / fragment_stage_run_bins run each over its half.
 namespace thi {
 struct FragmentStage {
     ProgramModule *module;
@@ -129,7 +135,8 @@ struct FragmentStage {
 };
 // the stage reads th_line(f): its pass holds a line record per fragment, and is stream-ordered whatever TH_OPT_STAGE_BINS says
 // unless TH_OPT_LINE_BINS is on as well
-inline bool stage_reads_line(const FragmentStage *stage) { return stage && stage->module->prog->reads_line; }
+// (the two stages of a mode 2 pass never do: th_draw_stages_pair runs such a program's pass on its own)
+inline bool stage_reads_line(const FragmentStage *stage) { return stage && stage->module && stage->module->prog->reads_line; }
 // One pass of draw() as its entry point describes it, for pass_run (a whole texture) and pass_emit (a row band; th_draw.hip); both passes in one (th_draw, th_draw_emit) prepare themselves
 struct PassSpec {
     int32_t pass = TH_PASS_FLOW;                                                         // TH_PASS_FLOW / TH_PASS_VIEW
@@ -479,7 +486,8 @@ th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th
 // p.colors at every place the bins' lists handed out - before anything blends, whether or not the host accepts the attempt
 // (crowded: the last draw put most of its fragments into crowded bins - a bin's places are dealt to more workgroups; program:
 // the pass's vertex stage was a caller's).  A stage that reads th_line: the two line kernels of th_fragline.hip fill
-// c->bins_line_ends and c->bins_lines first - reserved by the caller, bins_pass_emit - and the stage's sixth entry point runs
+// c->bins_line_ends and c->bins_lines first - reserved by the caller, bins_pass_emit - and the stage's sixth entry point runs.
+// p.mode == 2: the pair of both passes' stages, as above, over the two varyings a place of the store then holds
 th_status fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------
 th_status colormap_storage(th_context *c);

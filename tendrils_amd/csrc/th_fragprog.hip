@@ -12,6 +12,9 @@
 // kernel (th_fragline.hip) write a record per fragment beside key and varying, and launches the two entry points that take them.
 // Under TH_OPT_LINE_BINS as well such a pass goes through the bins like the others: fragment_stage_run_bins has th_fragline.hip's
 // two other kernels write a record per place of the store and launches the sixth entry point, which takes those.
+// th_draw_stages_pair draws both passes with their stages from ONE rasterisation where that gives the two passes' bits (th_draw's
+// mode 2: two varyings a fragment): both stages then travel down in the one argument, and fragment_stage_run / _run_bins launch
+// the seventh or eighth entry point (th_fragment_pair_prelude.inc) once per stage, each over its half of the pairs.
 #include "th_ctx.hpp"
 
 using namespace thi;
@@ -26,6 +29,10 @@ const char kTaps[] =
 #undef TH_TAPS
 const char kPrelude[] =
 #include "th_fragment_prelude.inc"
+    ;
+// ... and behind it the two entry points of th_draw_stages_pair's one rasterisation
+const char kPairPrelude[] =
+#include "th_fragment_pair_prelude.inc"
     ;
 
 // the launch record (th_fragment_prelude.inc: th_fragment_args, th_program_uniform_block - the same layout)
@@ -74,6 +81,23 @@ struct FragmentLineBinsArgs {
 using LineBinsKernArgs = ProgramKernArgs<FragmentLineBinsArgs>;
 static_assert(sizeof(FragmentLineBinsArgs) == 120 && offsetof(FragmentLineBinsArgs, lines) == 112 && offsetof(LineBinsKernArgs, u) == 128 &&
               sizeof(LineBinsKernArgs) == 128 + kUniformBytes, "line bins launch record: layout shared with th_fragment_prelude.inc");
+// ... and of th_fragment_pair_kernel / th_fragment_pair_bins_kernel (th_fragment_pair_prelude.inc: th_fragment_pair_args,
+// th_fragment_pair_bins_args): the first record, respectively the bins' record, then which of a fragment's two varyings the
+// stage runs over - both passes from one rasterisation (p.mode == 2: th_draw_stages_pair)
+struct FragmentPairArgs {
+    FragmentArgs f;
+    uint32_t half;
+};
+using PairKernArgs = ProgramKernArgs<FragmentPairArgs>;
+static_assert(sizeof(FragmentPairArgs) == 72 && offsetof(FragmentPairArgs, half) == 64 && offsetof(PairKernArgs, u) == 80 && sizeof(PairKernArgs) == 80 + kUniformBytes,
+              "pair launch record: layout shared with th_fragment_pair_prelude.inc");
+struct FragmentPairBinsArgs {
+    FragmentBinsArgs b;
+    uint32_t half;
+};
+using PairBinsKernArgs = ProgramKernArgs<FragmentPairBinsArgs>;
+static_assert(sizeof(FragmentPairBinsArgs) == 120 && offsetof(FragmentPairBinsArgs, half) == 112 && offsetof(PairBinsKernArgs, u) == 128 &&
+              sizeof(PairBinsKernArgs) == 128 + kUniformBytes, "pair bins launch record: layout shared with th_fragment_pair_prelude.inc");
 static_assert(th::kBinReplicas == kPreludeReplicas && th::kBinPage == 1u << kPreludePageShift && th::kTotOob == 1 && th::kTotFlags == 2 &&
               th::kBinsMaxExtent == 1 << 12, "th_fragment_prelude.inc restates the bins' constants and the key's 12-bit fields");
 // A bin's rounds of 256 places are dealt to this many workgroups (gridDim.y).  Every workgroup reads its bin's sixteen cursors
@@ -159,9 +183,27 @@ void stage_record(const th_context *c, const FragmentStage &stage, const th::Dep
 
 th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total)
 {
+    if (p.mode == 2) {
+        // both passes from one rasterisation: two varyings a fragment, and `stage` the first of two - the flow pass's stage over
+        // the first of every two, then the view pass's over the second; each launch in an event pair of its own
+        TH_REQUIRE(p.keys && !p.keys64 && p.colors, "the stages of both passes over one rasterisation: 32-bit texel keys, two varyings a fragment");
+        const FragmentStage *pair = &stage;
+        for (uint32_t half = 0; half < 2; ++half) {
+            if (!pair[half].module) continue;
+            PairKernArgs k{};
+            stage_record(c, pair[half], p, total, k.a.f);
+            k.a.half = half;
+            k.set_uniforms(pair[half].uniforms, pair[half].uniform_bytes);
+            LaunchTimer timer;
+            if (th_status s = timer.begin(c)) return s;
+            if (th_status s = program_launch(c, pair[half].module->fn_pair, total, k)) return s;
+            if (th_status s = timer.end(c)) return s;
+        }
+        return TH_OK;
+    }
     LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
     if (stage_reads_line(&stage)) {
-        // the fragments' line records first, beside the keys and varyings the scatter has just written (mode 2 has no stage)
+        // the fragments' line records first, beside the keys and varyings the scatter has just written (mode 2: no stage reads them)
         TH_REQUIRE(c->dep_fraglines && c->dep_capacity >= total && (p.keys64 || p.keys), "a stage that reads the line: a record per fragment, keys to read the texels from");
         th::launch_fragment_lines(p, c->dep_fraglines, c->stream);
         TH_HIP(hipGetLastError());
@@ -201,7 +243,24 @@ void bins_record(const th_context *c, const FragmentStage &stage, const th::Depo
 
 th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program)
 {
-    TH_REQUIRE(p.mode != 2 && p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: one varying a place, a store to run over");
+    TH_REQUIRE(p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: a store to run over");
+    if (p.mode == 2) {
+        // both passes from one rasterisation: two varyings a place, `stage` the first of two (fragment_stage_run, above)
+        TH_REQUIRE(c->bins_pairs && p.colors == c->bins_colors, "the stages of both passes over the bins: a store of two varyings a place");
+        const FragmentStage *pair = &stage;
+        for (uint32_t half = 0; half < 2; ++half) {
+            if (!pair[half].module) continue;
+            PairBinsKernArgs k{};
+            bins_record(c, pair[half], p, k.a.b);
+            k.a.half = half;
+            k.set_uniforms(pair[half].uniforms, pair[half].uniform_bytes);
+            LaunchTimer timer;
+            if (th_status s = timer.begin(c)) return s;
+            if (th_status s = program_launch_grid(c, pair[half].module->fn_pair_bins, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
+            if (th_status s = timer.end(c)) return s;
+        }
+        return TH_OK;
+    }
     LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
     if (stage_reads_line(&stage)) {
         // the places' line records first, behind the emitting pass on this stream (bins_pass_emit reserved them for this store)
@@ -231,9 +290,11 @@ extern "C" {
 
 th_status th_fragment_program_compile(const char *source, const char *name, th_program **out)
 {
-    if (th_status s = program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude, source, name, out)) return s;
+    if (th_status s = program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude + "\n" + kPairPrelude, source, name, out)) return s;
     // who pays for the line records: decided here, once (the compiler has accepted the text; an identifier in a comment counts)
     (*out)->reads_line = names_identifier(source, "th_line");
+    // ... and whether, as the view pass's stage, it keeps th_draw_stages_pair to two passes (th_flow_res is another identifier)
+    (*out)->names_flow = names_identifier(source, "th_flow");
     return TH_OK;
 }
 
@@ -250,6 +311,66 @@ th_status th_draw_stages_run(th_context *c, const th_draw_stages *s, int32_t pas
     if (th_status st = stages_pass(c, s, pass, stage, spec)) return st;
     draw_moves_nothing(c);
     return pass_run(c, spec, fragments);
+}
+
+// Both passes of draw() with a caller's fragment stage in either or both.  Where one rasterisation gives the bits of the two
+// passes run one after the other it is th_draw's pass (p.mode == 2: every fragment carries both passes' varyings side by side)
+// with both stages handed down as one argument - deposit_run / bins_pass_emit call fragment_stage_run / _run_bins where the
+// fragments lie, and those launch each stage over its half, the flow pass's first, before anything blends.  That is so when
+// the lines are the library's own in both passes (no vertex program: a draw program in mode 2 is not built), both passes draw
+// them equally wide, no stage reads th_line (the line records lie beside one varying a fragment) and the VIEW pass's stage does
+// not name th_flow: run in sequence it would see the field after the flow pass has blended into it, here every stage runs
+// before anything blends.  Every other pair of slots is the two passes through pass_run, one after the other.
+th_status th_draw_stages_pair(th_context *c, const th_draw_stages *flow, const th_draw_stages *view, uint64_t *fragments, int32_t *rasterisations)
+{
+    const char *const entry = "th_draw_stages_pair";
+    TH_REQUIRE(c, "null context");
+    TH_REQUIRE(flow && view, "null stages");
+    TH_REQUIRE(flow->fragment || view->fragment, "%s with no fragment program in either pass: both passes with the library's fragment stage are th_draw, or th_draw_stages_run pass by pass", entry);
+    const th_draw_stages *const slots[2] = {flow, view};
+    for (int32_t pass = 0; pass < 2; ++pass) {
+        const th_draw_stages *s = slots[pass];
+        if (th_status st = stage_args(s->vertex, kDrawProgram, entry, "vertex", s->vertex_uniforms, s->vertex_uniform_bytes)) return st;
+        if (th_status st = stage_args(s->fragment, kFragmentProgram, entry, "fragment", s->fragment_uniforms, s->fragment_uniform_bytes)) return st;
+        TH_REQUIRE(s->vertex || s->builtin, "%s: the %s pass without a vertex program needs `builtin`: the %s of the library's vertex stage", entry,
+                   pass == TH_PASS_VIEW ? "view" : "flow", pass == TH_PASS_VIEW ? "th_render_uniforms" : "th_deposit_uniforms");
+    }
+    const th_deposit_uniforms *du = static_cast<const th_deposit_uniforms *>(flow->builtin);
+    const th_render_uniforms *ru = static_cast<const th_render_uniforms *>(view->builtin);
+    if (!flow->vertex && !view->vertex) if (th_status st = shared_uniforms(du, ru)) return st;
+    if (th_status st = use(c)) return st;
+    if (th_status st = refuse_band(c, "the draw stages of both passes", "a band's passes go through th_draw_stages_emit and the owners' exchange, pass by pass")) return st;
+    const bool one = !flow->vertex && !view->vertex && drawn_line_width(c, TH_PASS_FLOW) == drawn_line_width(c, TH_PASS_VIEW) &&
+                     !(flow->fragment && flow->fragment->reads_line) && !(view->fragment && (view->fragment->reads_line || view->fragment->names_flow));
+    if (rasterisations) *rasterisations = one ? 1 : 2;
+    draw_moves_nothing(c);
+    if (!one) {
+        // (*fragments: the flow pass's, as th_draw reports them of two widths; th_draw_query has the view pass's afterwards)
+        for (int32_t pass = 0; pass < 2; ++pass) {
+            FragmentStage stage{}; PassSpec spec;
+            if (th_status st = stages_pass(c, slots[pass], pass, stage, spec)) return st;
+            if (th_status st = pass_run(c, spec, pass == TH_PASS_FLOW ? fragments : nullptr)) return st;
+        }
+        return TH_OK;
+    }
+    FragmentStage pair[2] = {};
+    for (int32_t pass = 0; pass < 2; ++pass) {
+        const th_draw_stages *s = slots[pass];
+        pair[pass].pass = pass;
+        if (!s->fragment) continue;                      // (module null: this half is blended as the library interpolated it)
+        if (th_status st = program_loaded(c, s->fragment, &pair[pass].module)) return st;
+        pair[pass].uniforms = s->fragment_uniforms; pair[pass].uniform_bytes = s->fragment_uniform_bytes;
+    }
+    if (th_status st = view_storage(c)) return st;
+    const th_status ran = draw_pass(c, fragments, false, pair, [&](th::DepositParams &p, bool first, bool *bins) -> th_status {
+        if (th_status st = deposit_prepare(c, du, p, first, bins, false, pair)) return st;
+        p.mode = 2;
+        view_fields(c, ru, p);
+        p.view = c->view;
+        return TH_OK;
+    });
+    c->drawn.valid = false;          // (deposit_run has said what it left: no built-in pass reuses the lines of a pass with a caller's stage)
+    return ran;
 }
 
 // ... and of a row band (a whole-texture context: the band of all rows), through pass_emit: emit_parted calls the stage behind its

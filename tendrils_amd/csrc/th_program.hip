@@ -128,7 +128,7 @@ void ProgramModule::reset()
 {
     if (module) (void)hipModuleUnload(module);
     program_release(prog);
-    module = nullptr; fn = nullptr; fn_slots = nullptr; fn_band = nullptr; fn_packed = nullptr; fn_line = nullptr; fn_line_band = nullptr; fn_line_bins = nullptr; prog = nullptr;
+    module = nullptr; fn = nullptr; fn_slots = nullptr; fn_band = nullptr; fn_packed = nullptr; fn_line = nullptr; fn_line_band = nullptr; fn_line_bins = nullptr; fn_pair = nullptr; fn_pair_bins = nullptr; prog = nullptr;
 }
 
 const char *program_kind_name(ProgramKind kind)
@@ -164,6 +164,8 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line, m->module, "th_fragment_line_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line_band, m->module, "th_fragment_line_band_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line_bins, m->module, "th_fragment_line_bins_kernel"));
+    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_pair, m->module, "th_fragment_pair_kernel"));
+    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_pair_bins, m->module, "th_fragment_pair_bins_kernel"));
     m->prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));

@@ -230,6 +230,12 @@ class Tendrils:
         # FragmentProgram (the fragment stage; the library's vertex stage) or the pair (vertex or None, fragment or None).
         self.flowShader = params.get("flowShader")
         self.renderShader = params.get("renderShader")
+        # draw() with a fragment stage in either shader and renderView: both passes in ONE call (th_draw_stages_pair), over one
+        # rasterisation of the lines where that gives the bits of the two passes run one after the other - else as those two.
+        # Off (the default): a call per pass, as ever.  Assignable.  `rasterisations`: what the last such call ran, 1 or 2
+        # (None: draw() has made no such call yet).
+        self.pairedStages = bool(params.get("pairedStages", False))
+        self.rasterisations = None
         self.uniforms = dict(render={}, update={})
         self.viewRes = [0, 0]
         self.viewSize = [0, 0]
@@ -493,7 +499,8 @@ class Tendrils:
         stream-ordered, or with particles.option("stage_bins", 1) the pipeline of the pass without it - a stage that reads th_line(f) with
         particles.option("line_bins", 1) beside it), else a vertex program (th_draw_program_run), else the library's own stage; both passes with the
         library's stages draw the same lines, and one call rasterises and sorts them once (th_draw) when they draw them with
-        the same width.  Programs get draw_program_uniforms(), packed into each program's uniform block by field name.  A
+        the same width - and so does, with self.pairedStages on, a draw() with a fragment stage in either shader
+        (th_draw_stages_pair: _draw_stages_pair has the conditions).  Programs get draw_program_uniforms(), packed into each program's uniform block by field name.  A
         program pass takes the pipeline the library's own pass of this context would (Particles.draw_pipeline / TH_DRAW: binned
         where the shape and the ring allow it, else stream-ordered - include/tendrils_hip.h "draw programs"); through the bins
         a tile-sorted ring stays sorted, so step(); draw() keeps it."""
@@ -522,6 +529,11 @@ class Tendrils:
             self.fragments = self.view_fragments = int(n.value)
             return self
         uniforms = self.draw_program_uniforms() if programs else None
+        if view and self.pairedStages and (shader_stages(self.flowShader)[1] is not None or shader_stages(self.renderShader)[1] is not None):
+            # (the clear and the fade only touch the view buffer, and no stage reads it: in front of both passes, as for th_draw)
+            self._view_prologue()
+            self.fragments, self.view_fragments = self._draw_stages_pair(uniforms)
+            return self
         self.fragments = self._draw_pass(_capi.TH_PASS_FLOW, self.flowShader, uniforms)
         if view:
             self._view_prologue()
@@ -570,6 +582,23 @@ class Tendrils:
         n = C.c_uint64(0)
         call("th_draw_stages_run", self.particles._ctx, C.byref(stages), which, C.byref(n))
         return int(n.value)
+
+    def _draw_stages_pair(self, uniforms):
+        """both passes with the stages of flowShader and renderShader in one call, th_draw_stages_pair (pairedStages): the bits of
+        the two passes one after the other; ONE rasterisation when neither shader has a vertex program, both passes draw equally
+        wide lines, no fragment program reads th_line(f) and renderShader's does not name th_flow - run in sequence the view
+        pass's th_flow would see the field after the flow pass has blended into it, in one rasterisation every stage runs before
+        anything blends.  self.rasterisations says which it was.  Returns (fragments, view_fragments)."""
+        flow, _keep_flow = draw_stages(*shader_stages(self.flowShader), uniforms, self.deposit_uniforms())
+        view, _keep_view = draw_stages(*shader_stages(self.renderShader), uniforms, self.render_uniforms())
+        n, ran = C.c_uint64(0), C.c_int32(0)
+        call("th_draw_stages_pair", self.particles._ctx, C.byref(flow), C.byref(view), C.byref(n), C.byref(ran))
+        self.rasterisations = int(ran.value)
+        if self.rasterisations == 1:
+            return int(n.value), int(n.value)
+        info = _capi.DrawInfo()                     # (two passes: the call reports the flow pass's fragments, the query the view pass's)
+        call("th_draw_query", self.particles._ctx, C.byref(info))
+        return int(n.value), int(info.fragments)
 
     def deposit_uniforms(self):
         """the library's flow stage's uniforms of this frame (th_deposit_uniforms)"""

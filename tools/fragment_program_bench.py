@@ -63,7 +63,21 @@ copy(ends) moves what fragment_line_ends_kernel moves (two 16-byte state texels 
 what fragment_lines_bins_kernel moves (an 8-byte key and 16 bytes of endpoints read, 16 bytes written a fragment), copy(56) what
 th_fragment_line_bins_kernel moves (key, record and varying read, the varying written).
 
-Usage: python tools/fragment_program_bench.py [--bins | --line [--bins] [--line-width 1]] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
+--pair [--bins]: both passes' stages over ONE rasterisation (th_draw_stages_pair, Tendrils.pairedStages; th_fragment_pair_kernel /
+th_fragment_pair_bins_kernel).  Seven contexts in the same state run the frame loop side by side, policy auto, stage_bins off
+(--bins: on) in all of them:
+  loop(identity, off) / loop(identity, on)   flowShader = renderShader = (None, `return f.color`), pairedStages off / on
+  loop(vignette, off) / loop(vignette, on)   ... the tests' VIGNETTE in both passes
+  loop(vignette, flow alone, off) / (.., on) flowShader = (None, vignette) and no renderShader
+  loop(builtin)                              no shaders: th_draw's one rasterisation
+An off arm issues the calls draw() has always issued - two stage passes, two rasterisations - through code this call does not touch:
+it is what the parent commit runs (--arms off,builtin runs on a commit without the call).  After the last frame the flow field and
+the view of every on / off pair are compared bit for bit.  Then, on a context three steps in, each pair kernel alone -
+th_kernel_timing's pair around the one launch of a th_draw_stages_pair with the program in the view slot - against copy(36) (--bins:
+copy(40)): a device-to-device copy of the bytes the kernel moves a fragment - the key (4 bytes; 8 in the page store), 16 bytes read,
+16 written.
+
+Usage: python tools/fragment_program_bench.py [--bins | --line [--bins] [--line-width 1] | --pair [--bins] [--arms off,on,builtin]] [--root 4096] [--width 1920] [--height 1080] [--reps 10] [--warmup 2] [--rounds 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -110,7 +124,11 @@ def main():
     ap.add_argument("--warmup-frames", type=int, default=12, help="--bins: frames every loop runs before anything is timed")
     ap.add_argument("--line", action="store_true", help="a stage that reads the fragment's line: the pass, the stage's kernel, the copies of what it and the line kernel move")
     ap.add_argument("--line-width", type=float, default=1.0, help="--line: the width the flow pass is drawn with")
+    ap.add_argument("--pair", action="store_true", help="both passes' stages over one rasterisation: frame loops with Tendrils.pairedStages off / on, each pair kernel alone (--bins: stage_bins on)")
+    ap.add_argument("--arms", default="off,on,builtin", help="--pair: the loops to run (off,builtin: what a commit without the call can run)")
     args = ap.parse_args()
+    if args.pair:
+        return pair_main(args)
     if args.bins and args.line:
         return line_bins_main(args)
     if args.bins:
@@ -740,6 +758,185 @@ def passes(args, t, label, programs, block, rounds):
                 rounds.setdefault("kernel(%s) @ %s" % (name, label), []).append(kernel)
         rounds.setdefault("copy(40) @ %s" % label, []).append(copy_ms(args.reps))
     return total
+
+
+def pair_main(args):
+    import time
+
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("fragment_program_bench: no GPU - nothing is measured without one")
+    import tendrils_amd as ta
+    from benchlib import workload
+    from tendrils_amd import _capi
+    from tendrils_amd._capi import call
+    from tendrils_amd.particles import FragmentProgram, draw_stages
+    from tendrils_amd.tendrils import View
+    from test_fragment_program_build import IDENTITY, VIGNETTE, FragUniforms
+
+    n, w, h = args.root, args.width, args.height
+    workload.N = n
+    identity = FragmentProgram.from_source(IDENTITY, name="identity")
+    vignette = FragmentProgram.from_source(VIGNETTE, FragUniforms, "vignette")
+    gain = FragmentProgram.from_source(GAIN, GainUniforms, "gain")
+    block = dict(gain=0.5, tint=[0.5, 0.25, 0.75, 0.875], invRes=[1.0 / w, 1.0 / h], edge=3.5 / (w * w + h * h))
+    state0 = workload.synth_state(0)
+    cmap = np.random.default_rng(7).uniform(0, 1, (64, 64, 4)).astype(np.float32)
+    stage_bins = 1 if args.bins else 0
+    wanted = set(args.arms.split(","))
+
+    def loop(flow_stage, view_stage, paired):
+        opts = ta.defaults()
+        if flow_stage is not None:
+            opts.update(flowShader=(None, flow_stage))
+        if view_stage is not None:
+            opts.update(renderShader=(None, view_stage))
+        if paired:
+            opts.update(pairedStages=True)
+        t = ta.Tendrils(View(w, h), opts)
+        t.resize()
+        t.setup(n)
+        t.particles.upload_texels(state0)
+        t.colorMap.set_pixels(cmap)
+        t.uniforms["render"].update(block)
+        t.particles.option("stage_bins", stage_bins)
+        t.timer.time = 1000.0
+        return t
+
+    shaders = {"identity": (identity, identity), "vignette": (vignette, vignette), "vignette, flow alone": (vignette, None)}
+    loops = {}
+    for name, (flow_stage, view_stage) in shaders.items():
+        for arm in ("off", "on"):
+            if arm in wanted:
+                loops["%s, %s" % (name, arm)] = loop(flow_stage, view_stage, arm == "on")
+    if "builtin" in wanted:
+        loops["builtin"] = loop(None, None, False)
+
+    def frames(t, count):
+        """wall ms per frame"""
+        t.particles.sync()
+        t0 = time.perf_counter()
+        for _ in range(count):
+            t.timer.tick()
+            t.step()
+            t.draw()
+        t.particles.sync()
+        return (time.perf_counter() - t0) * 1e3 / count
+
+    def held(t):
+        info, order = _capi.DrawInfo(), _capi.SlotOrderInfo()
+        call("th_draw_query", t.particles._ctx, C.byref(info))
+        call("th_slot_order", t.particles._ctx, C.byref(order))
+        return dict(pipeline="bins" if info.pipeline == 1 else "stream", fragments=int(info.fragments), crowded_fragments=int(info.crowded_fragments),
+                    sorted_buffers=int(order.sorted_buffers), rasterisations=getattr(t, "rasterisations", None))
+
+    for t in loops.values():
+        frames(t, args.warmup_frames)
+    rounds = {}
+    for _ in range(args.rounds):
+        for name, t in loops.items():
+            rounds.setdefault("loop(%s)" % name, []).append(frames(t, args.reps))
+    state = {name: held(t) for name, t in loops.items()}
+    same = {}
+    if "on" in wanted and "off" in wanted:
+        # the same frames, the same bits: the flow field and the view of each on / off pair after the last frame
+        for name in shaders:
+            on, off = loops[name + ", on"], loops[name + ", off"]
+            assert state[name + ", on"]["fragments"] == state[name + ", off"]["fragments"] and on.rasterisations == 1, (name, state)
+            same[name] = bool((on.flow.read().view(np.uint32) == off.flow.read().view(np.uint32)).all() and (on.read_view() == off.read_view()).all())
+            assert same[name], "loop(%s): the paired frames are not the unpaired frames" % name
+
+    # each pair kernel alone, on a context three steps in (every line a texel or two long, no crowded bin): one th_draw_stages_pair
+    # with the program in the VIEW slot - one launch, th_kernel_timing's pair around it - against a device-to-device copy of the
+    # bytes the kernel moves a fragment: the key (4 bytes stream-ordered, 8 in the page store), 16 bytes read, 16 written
+    kernels, total = {}, 0
+    if "on" in wanted:
+        fresh = loop(None, None, False)
+        if args.bins:
+            fresh.particles.draw_pipeline("bins")
+        for _ in range(3):
+            fresh.timer.tick()
+            fresh.step()
+        fresh.line_widths()
+        ctx = fresh.particles._ctx
+        uniforms = dict(fresh.state, **block)
+        d, r = fresh.deposit_uniforms(), fresh.render_uniforms()
+        flow_slot = draw_stages(None, None, uniforms, d)
+
+        def kernel_ms(prog, reps):
+            view_slot = draw_stages(None, prog, uniforms, r)
+            count, ran, mean, launches = C.c_uint64(0), C.c_int32(0), C.c_float(0), C.c_int32(0)
+            call("th_kernel_timing", ctx, 1)
+            for _ in range(reps):
+                call("th_draw_stages_pair", ctx, C.byref(flow_slot[0]), C.byref(view_slot[0]), C.byref(count), C.byref(ran))
+            call("th_kernel_timing_read", ctx, C.byref(mean), C.byref(launches))
+            call("th_kernel_timing", ctx, 0)
+            assert ran.value == 1 and launches.value == reps, (ran.value, launches.value, reps)
+            return mean.value, int(count.value)
+
+        per_fragment = 40 if args.bins else 36
+        for name, prog in (("gain", gain), ("vignette", vignette)):
+            _, total = kernel_ms(prog, args.warmup)
+        src = torch.empty(total * (per_fragment // 2), dtype=torch.uint8, device="cuda")          # (half read, half written)
+        dst = torch.empty_like(src)
+
+        def copy_ms(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / reps
+
+        copy_ms(args.warmup)
+        for _ in range(args.rounds):
+            for name, prog in (("gain", gain), ("vignette", vignette)):
+                kernels.setdefault("kernel(%s)" % name, []).append(kernel_ms(prog, args.reps)[0])
+            kernels.setdefault("copy(%d)" % per_fragment, []).append(copy_ms(args.reps))
+        state["the pair call, 3 steps in"] = held(fresh)
+        assert state["the pair call, 3 steps in"]["pipeline"] == ("bins" if args.bins else "stream"), state
+        fresh.dispose()
+
+    kernel_name = "th_fragment_pair_bins_kernel" if args.bins else "th_fragment_pair_kernel"
+    lines = ["both passes' fragment stages over one rasterisation (th_draw_stages_pair; Tendrils.pairedStages), stage_bins %d: %d^2 particles (C3 state) "
+             "into %d x %d, policy auto; %d frames of warm-up a loop, then %d rounds of %d frames / calls, arms alternating; loop: wall ms per "
+             "frame of step(); draw() (synchronised); kernel (%s alone, th_kernel_timing), copy: GPU ms per call (events)"
+             % (stage_bins, n, w, h, args.warmup_frames, args.rounds, args.reps, kernel_name),
+             "device: %s" % torch.cuda.get_device_name(0), "arms: %s" % args.arms,
+             "on / off pairs after their last frame, flow field and view bit for bit: %s" % json.dumps(same)]
+    for name in state:
+        lines.append("%s: %s" % ("loop(%s) after its last frame" % name if name in loops else name, json.dumps(state[name])))
+    lines.append("%-36s %10s %10s %10s %14s" % ("arm", "median ms", "min ms", "max ms", "GB/s (median)"))
+    med = {}
+    for name, ms in list(rounds.items()) + list(kernels.items()):
+        med[name] = statistics.median(ms)
+        gbps = "%.1f" % ((40 if args.bins else 36) * total / med[name] / 1e6) if name in kernels else "-"
+        lines.append("%-36s %10.4f %10.4f %10.4f %14s" % (name, med[name], min(ms), max(ms), gbps))
+    if "on" in wanted and "off" in wanted:
+        for name in shaders:
+            on, off = rounds["loop(%s, on)" % name], rounds["loop(%s, off)" % name]
+            lines.append("loop(%s): on / off = %.3f (time ratio of the medians); on %.4f .. %.4f, off %.4f .. %.4f: the on arm's range %s below the off arm's"
+                         % (name, med["loop(%s, on)" % name] / med["loop(%s, off)" % name], min(on), max(on), min(off), max(off),
+                            "lies" if max(on) < min(off) else "does NOT lie"))
+        if "builtin" in wanted:
+            lines.append("loop(identity, on) / loop(builtin) = %.3f;  loop(identity, off) / loop(builtin) = %.3f  (time ratios)"
+                         % (med["loop(identity, on)"] / med["loop(builtin)"], med["loop(identity, off)"] / med["loop(builtin)"]))
+    if kernels:
+        copy = "copy(%d)" % (40 if args.bins else 36)
+        lines.append("kernel(gain) / %s = %.3f;  kernel(vignette) / %s = %.3f  (time ratios; %d fragments)"
+                     % (copy, med["kernel(gain)"] / med[copy], copy, med["kernel(vignette)"] / med[copy], total))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(dict(root=n, width=w, height=h, reps=args.reps, rounds=args.rounds, stage_bins=stage_bins, fragments=total, state=state, median_ms=med)))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    for t in loops.values():
+        t.dispose()
+    for prog in (identity, vignette, gain):
+        prog.dispose()
 
 
 if __name__ == "__main__":
