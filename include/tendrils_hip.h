@@ -558,6 +558,8 @@ th_status th_step_program_run(th_context *ctx, th_program *program, const void *
 th_status th_step_program_view_size(th_context *ctx, const float viewSize[2]);
 
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
+/* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
+ * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */
 th_status th_frames_resize(th_context *ctx, int32_t w, int32_t h);     /* OpticalFlow.resize */
 th_status th_frames_upload(th_context *ctx, const uint8_t *rgba8);     /* setPixels -> buffers[0] */
 th_status th_frames_rotate(th_context *ctx);                           /* OpticalFlow.step */

@@ -362,12 +362,13 @@ def gen_loop(r, only):
 
 def gen_optical_flow(r, only):
     """One blended pass of the reference's optical-flow shader (docs/js/demo.js:73) per case.
-    Frames are regenerated from seeds by tests/helpers.py:synth_frame; only parameters and the
-    reference output (whole texture, or row bands for the 1080p case) are stored."""
+    Frames are regenerated from seeds by tests/helpers.py:synth_frame (or noise_frame: the cases of kind "noise"); only
+    parameters and the reference output (whole texture, or row bands for the 1080p case) are stored.  The out sizes are
+    ones at which the reference rasteriser's interpolation gradient is fl(2 / size) (oracle/tendrils_oracle.c)."""
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
     from helpers import of_inputs
     cases = [
-        # name, frame (w,h), out (w,h), uniforms, bands
+        # name, frame (w,h), out (w,h), uniforms, bands[, frame kind]
         ("of_default_64", (64, 48), (64, 48), dict(viewSize=[1, 1], scaleUV=[1, -1], offset=1.0 / 64, speed=1,
                                                    speedLimit=1, time=1234.5), None),
         # demo settings src/demo.main.js:526-530 (speed .08, offset .1, scaleUV [-1,-1]) + tendrils speedLimit
@@ -382,8 +383,23 @@ def gen_optical_flow(r, only):
         ("of_c3_1080p", (1920, 1080), (1920, 1080), dict(viewSize=[1, 1920 / 1080], scaleUV=[-1, -1], offset=0.1,
                                                          speed=0.08, speedLimit=0.01, time=1000.0),
          [(0, 8), (536, 544), (1072, 1080)]),
+        # the shapes at which optical_flow_kernel's two tap paths part (tests/optical_flow_cases.py), on frames without any
+        # smoothness: frames larger than the field (every workgroup's taps are global loads) ...
+        ("of_downscale_64x32", (512, 288), (64, 32), dict(viewSize=[1, 2], scaleUV=[-1, -1], offset=1.0 / 512, speed=1,
+                                                          speedLimit=1, time=1234.5), None, "noise"),
+        ("of_small_direct_32x16", (160, 90), (32, 16), dict(viewSize=[1, 1], scaleUV=[-1, -1], offset=0.1, speed=1,
+                                                            speedLimit=1, time=1234.5), None, "noise"),
+        # ... |scaleUV| = 2.5: most taps clamped to a frame edge, the middle workgroup's box exactly the kernel's LDS budget ...
+        ("of_clamped_96x64", (96, 64), (96, 64), dict(viewSize=[1, 1], scaleUV=[-2.5, 2.5], offset=0.1, speed=1,
+                                                      speedLimit=1, time=1234.5), None, "noise"),
+        # ... a frame far smaller than the field (neighbouring lanes tap the same texel) ...
+        ("of_upscale_96x64", (16, 9), (96, 64), dict(viewSize=[1, 1.5], scaleUV=[-1, -1], offset=0.1, speed=0.08,
+                                                     speedLimit=0.01, time=777.0), None, "smooth"),
+        # ... and staged and direct workgroups in one launch
+        ("of_mixed_256x128", (256, 128), (256, 128), dict(viewSize=[1, 1], scaleUV=[1, -1], offset=0.12, speed=1,
+                                                          speedLimit=1, time=1234.5), None, "noise"),
     ]
-    for name, fr, out, un, bands in cases:
+    for name, fr, out, un, bands, *kind in cases:
         if only and only not in name:
             continue
         un = dict(un)
@@ -391,6 +407,8 @@ def gen_optical_flow(r, only):
         seed = sum(map(ord, name))
         meta = dict(kind="optical_flow", frame=list(fr), out=list(out), uniforms=un, seed=seed,
                     shift8=[12, 6], bands=bands)          # frame1 = frame0 translated by (1.5, 0.75) px
+        if kind and kind[0] != "smooth":
+            meta["frameKind"] = kind[0]                   # (noise: frame1 is another seed's noise)
         f0, f1, dst = of_inputs(meta)
         ow, oh = out
         ref = r.shader("optical_flow", (ow, oh), textures={"view": f1, "last": f0}, uniforms=un, blend=True, dst=dst)

@@ -433,6 +433,8 @@ th_status th_frames_resize(th_context *c, int32_t w, int32_t h)
 {
     if (th_status s = use(c)) return s;
     TH_REQUIRE(w > 0 && h > 0 && (uint64_t)w * h < (1ull << 28), "bad frame shape %dx%d", w, h);
+    // the taps of an RGBA8 image (th_tap_fx16: a 16-bit coordinate times the size, in 32 bits) hold up to 65536 texels a side
+    TH_REQUIRE(w <= 65536 && h <= 65536, "bad frame shape %dx%d (frames are RGBA8 images: at most 65536 a side)", w, h);
     if (w == c->frw && h == c->frh) return TH_OK;
     TH_HIP(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k) {

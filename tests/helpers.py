@@ -56,14 +56,33 @@ def synth_frame(w, h, seed, shift8=(0, 0)):
     return out
 
 
+def noise_frame(w, h, seed):
+    """Deterministic RGBA8 frame with no smoothness at all: an independent uniform byte per texel and channel
+    (the top byte of a 32-bit integer hash of the channel's index - integer arithmetic only), alpha 255.  A tap
+    one texel off reads an unrelated value."""
+    k = np.arange(w * h * 3, dtype=np.uint64) + np.uint64((int(seed) * 0x9e3779b1) & 0xffffffff)
+    out = np.empty((h, w, 4), np.uint8)
+    out[..., :3] = (_mix32(k) >> np.uint64(24)).astype(np.uint8).reshape(h, w, 3)
+    out[..., 3] = 255
+    return out
+
+
 def of_inputs(meta):
     """Inputs of an optical-flow fixture, regenerated from its seeds: (last frame, view frame,
-    destination flow contents before the blended pass)."""
+    destination flow contents before the blended pass).  meta["frameKind"]: "smooth" (synth_frame, the
+    default: the view frame is the last one translated by shift8) or "noise" (noise_frame, two seeds - one seed, the same
+    frame twice, where shift8 is (0, 0))."""
     fw, fh = meta["frame"]
     ow, oh = meta["out"]
     seed = meta["seed"]
-    f0 = synth_frame(fw, fh, seed)
-    f1 = synth_frame(fw, fh, seed, shift8=tuple(meta["shift8"]))
+    kind = meta.get("frameKind", "smooth")
+    if kind == "noise":
+        f0 = noise_frame(fw, fh, seed)
+        f1 = noise_frame(fw, fh, seed + (1 if any(meta["shift8"]) else 0))
+    else:
+        assert kind == "smooth", kind
+        f0 = synth_frame(fw, fh, seed)
+        f1 = synth_frame(fw, fh, seed, shift8=tuple(meta["shift8"]))
     rng = np.random.default_rng(seed)
     dst = np.zeros((oh, ow, 4), np.float32)
     dst[..., :2] = rng.uniform(-.01, .01, (oh, ow, 2))

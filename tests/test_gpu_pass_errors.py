@@ -2,8 +2,8 @@
 th_program_run, th_draw_program_run), and what a pass is handed as `spawnData` whichever entry point resolves the name.  The
 entry points share the host code that turns a TH_SOURCE_* / TH_VIEW_* name into memory (tendrils_amd/csrc/th_spawn.hip,
 th_blend.hip, th_program.hip): every rejection is pinned by its status and its WHOLE th_last_error() text, and after every one
-a valid call of the same entry point goes through.  An RGBA8 texture of more than 65536 texels a side cannot be uploaded
-(th_texture_upload refuses it, pinned below): the frames are the RGBA8 image that reaches the tap-size rule of the passes."""
+a valid call of the same entry point goes through.  An RGBA8 image of more than 65536 texels a side reaches no pass: th_texture_upload
+refuses such a texture and th_frames_resize such frames (both pinned below), so the passes' own tap-size rule has nothing left to refuse."""
 import ctypes as C
 
 import numpy as np
@@ -25,6 +25,7 @@ TO_VIEW, TO_MAP, TO_TEX = _capi.SCREEN_TARGET_VIEW, _capi.SCREEN_TARGET_COLORMAP
 NONE, FROM_FLOW, FROM_IMAGE = _capi.TH_SOURCE_NONE, _capi.TH_SOURCE_FLOW, _capi.TH_SOURCE_IMAGE
 RGBA32F_SLOT, L32F_SLOT, RGBA8_SLOT, EMPTY_SLOT = 0, 1, 2, 5
 OWN_TARGET = " is the memory this pass renders into: a pass cannot sample its own target"
+BIG_FRAMES = "bad frame shape %dx%d (frames are RGBA8 images: at most 65536 a side)"
 BAND_GATHER = ("sampling the particle texture on a row-band shard (4 of 8 rows) reads every band: gather buffer 0 first "
                "(th_state_gather / th_state_gather_ptr)")
 
@@ -137,12 +138,13 @@ def test_colormap_blend_refusals(world):
     check([good] * 9, "a blend takes 1..8 views (got 9)")
     refused("th_colormap_blend", (ctx, None, 1, 1, 1), INVALID, "a blend takes 1..8 views (got 1)")
     call("th_colormap_blend", *blend_args(ctx, [good]))
-    # the tap-size rule: frames of 65537 texels a side (an RGBA8 texture of that size is refused where it is uploaded)
+    # the tap-size rule: an RGBA8 image of 65537 texels a side is refused where it is made, texture and frames alike
     refused("th_texture_upload", (ctx, EMPTY_SLOT, _capi.TEX_RGBA8, np.zeros(4, np.uint8).ctypes.data_as(C.c_void_p), 65537, 1),
             INVALID, "bad texture 65537x1 (an RGBA8 texture: at most 65536 a side) or null texels")
-    call("th_frames_resize", ctx, 65537, 1)
-    check([(FRAMES, 0)], "view 0: 65537x1 frames are beyond what a blend samples (65536 a side)")
+    refused("th_frames_resize", (ctx, 65537, 1), INVALID, BIG_FRAMES % (65537, 1))
+    check([(FRAMES, 0)], "view 0: no frame buffers (call th_frames_resize)")          # (the refused resize made none)
     call("th_frames_resize", ctx, 4, 2)
+    refused("th_frames_resize", (ctx, 1, 65537), INVALID, BIG_FRAMES % (1, 65537))
     call("th_colormap_blend", *blend_args(ctx, [(FRAMES, 0), (FRAMES, 1)]))
 
 
@@ -164,8 +166,8 @@ def test_screen_run_refusals(world):
     check("unit 1: no view buffer -1 (there are 2)", [(BUFFER, 0), (BUFFER, -1)])
     check("unit 0: unknown source 7", [(7, 0)])
     check("a screen pass takes 0..8 units (got 9) - or null units", [(FLOW, 0)] * 9)
-    call("th_frames_resize", ctx, 65537, 1)
-    check("unit 0: a 65537x1 RGBA8 texture is beyond what a tap samples (65536 a side)", [(FRAMES, 0)])
+    refused("th_frames_resize", (ctx, 65537, 1), INVALID, BIG_FRAMES % (65537, 1))
+    check("unit 0: no frame buffers (call th_frames_resize)", [(FRAMES, 0)])         # (the refused resize made none)
     call("th_frames_resize", ctx, 4, 2)
     call("th_screen_run", *screen_args(ctx, paint, [(FRAMES, 0), (FRAMES, 1)]))
     # a unit that is the pass's own target
