@@ -557,6 +557,61 @@ th_status th_step_program_run(th_context *ctx, th_program *program, const void *
  * non-positive component is refused (TH_ERR_INVALID, the value named) and the key in force stays. */
 th_status th_step_program_view_size(th_context *ctx, const float viewSize[2]);
 
+/* -- measure programs: a reduction over the state ring whose per-particle sample the CALLER wrote ----------------------
+ * The five kinds of program above write: the ring, a view image, a vertex record, a varying.  What a host could learn of its
+ * particles was th_stats' seven fixed fields, or the whole ring through th_download_state.  A measure program returns numbers:
+ * HIP source defining one device function,
+ *     __device__ th_sample th_measure_main(const th_measure_pass &m);   - once per particle: up to `channels` floats, or nothing
+ * compiled exactly as a user program is (same hiprtc, same flags, same `#line 1 "<name>"`, same th_program_log()) behind a
+ * prelude of its own (tendrils_amd/csrc/th_measure_prelude.inc), with TH_MEASURE_CHANNELS = `channels`, that declares:
+ *   th_sample          { float v[TH_MEASURE_CHANNELS]; int take; } - th_sample_zero(): take = 1, every channel 0.0f, to be filled
+ *                      in; th_no_sample(): this particle contributes nothing, to no channel and not to `taken`
+ *   th_measure_pass    x, y, index (in the WHOLE texture: a row band adds row0), dataRes, uv - as th_pass has them, the same fp32
+ *                      expressions -, self (the particle's texel as f32; of a TH_STATE_F16 ring what the texel decodes to - what a
+ *                      step program sees), uniforms
+ *   th_uniforms<T>(m), th_flow(m, u, v), th_flow_res(m)   as for a step program (clamped NEAREST taps)
+ * There is NO th_particles(), no spawn data and no `targets`: a source that names th_particles does not compile.
+ * The library reduces the samples per channel - sum in double (every float converted exactly), min and max in float (v < min,
+ * v > max: a NaN sample enters neither and makes its channel's sum NaN) - and counts the samples taken:
+ *   th_measure_result  taken; particles (the texels measured); sum[8], min[8], max[8] - channels at and beyond `channels`, and
+ *                      every channel when nothing was taken: 0.0, +inf, -inf.  144 bytes.
+ * How: the caller's kernel (th_measure_kernel; th_measure_packed_kernel on a TH_STATE_F16 ring, on the 8-byte texels in place)
+ * reads ring buffer `buffer` where it lies, one 16-byte (8-byte) load a particle - tile-sorted slots through their perm table:
+ * x, y, index are the particle's whatever slot holds it -, keeps its accumulators in registers, reduces each wave by shuffles and
+ * the four waves of a workgroup through LDS, and stores one partial per workgroup; one workgroup of the library then folds the
+ * partials in a fixed assignment.  No atomics: the same ring in the same slot order gives the same bits on every run.  Sums whose
+ * partial sums are all exact in double (counts, integers) do not depend on the order at all, and neither do taken, min, max; the
+ * last bits of any other sum may differ between a tile-sorted ring and the same ring in texel order.
+ * A measure is READ-ONLY: it moves no buffer to texel order, rotates nothing, and leaves the slot orders, the geometry a view
+ * pass reuses, the draw policy's frame count and the `respawned` counter alone - step(); measure(); draw() leaves the bits of
+ * step(); draw().  A context that never measures allocates nothing for it (the first measure reserves 2048 partials and a few
+ * result blocks).  th_kernel_timing puts an event pair around the caller's kernel.
+ *  th_measure_program_compile  channels: 1 .. 8 (else TH_ERR_INVALID).  The handle is a th_program of a sixth kind:
+ *                      th_program_destroy / _query / _log serve it; every run call refuses the other kinds' programs, and
+ *                      th_measure_* theirs (TH_ERR_INVALID, both kinds named, nothing launched).
+ *  th_measure_run      the measure of ring buffer `buffer` (an index into the ring as th_slot_order_read takes it: 0 = buffers[0]),
+ *                      downloaded; synchronises.
+ *  th_measure_async    enqueues only (th_stats_async's pattern): the result lands at *device_result, a th_measure_result in
+ *                      device memory owned by the context, valid until the context's next measure.
+ *  th_measure_global   over every rank's band of a row-band job: the local measure, ONE all-gather of the ranks' 144-byte blocks
+ *                      over the context's communicator, and the same fold over them in rank order - every rank returns the same
+ *                      bits; `particles` is the whole texture's.  Collective: every rank calls it.  A context without a
+ *                      communicator, or a world of one, is th_measure_run (no collective).
+ *  TH_ERR_INVALID, before anything is launched: another kind's program, a null program, `buffer` outside the ring, more than 1024
+ *  uniform bytes, null uniforms with a size, a null `out`. */
+typedef struct th_measure_result {
+    uint64_t taken, particles;
+    double sum[8];
+    float min[8], max[8];
+} th_measure_result;      /* 144 bytes */
+th_status th_measure_program_compile(const char *source, const char *name, int32_t channels, th_program **out);
+th_status th_measure_run(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes, int32_t buffer,
+                         th_measure_result *out);
+th_status th_measure_async(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes, int32_t buffer,
+                           void **device_result);
+th_status th_measure_global(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes, int32_t buffer,
+                            th_measure_result *out);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 /* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
  * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */

@@ -10,10 +10,10 @@ from ._capi import (INERT, TH_MODE_EXACT, TH_MODE_FAST, TH_SOURCE_FLOW, TH_STATE
                     TH_TARGET_RING, TH_TARGET_TARGETS, TendrilsHipError)
 from .blend import AudioTexture, Blend
 from .flow_line import FlowLine, FlowLines
-from .particles import DrawProgram, FragmentProgram, Particles, Program, ScreenProgram, StepProgram, defaults as particles_defaults
+from .particles import DrawProgram, FragmentProgram, MeasureProgram, Particles, Program, ScreenProgram, StepProgram, defaults as particles_defaults
 from .tendrils import Tendrils, defaults, gl_settings
 from .timer import Timer
 
-__all__ = ["AudioTexture", "Blend", "Particles", "Program", "ScreenProgram", "DrawProgram", "FragmentProgram", "StepProgram", "FlowLine", "FlowLines", "Tendrils", "Timer", "defaults", "particles_defaults", "gl_settings",
+__all__ = ["AudioTexture", "Blend", "Particles", "Program", "ScreenProgram", "DrawProgram", "FragmentProgram", "StepProgram", "MeasureProgram", "FlowLine", "FlowLines", "Tendrils", "Timer", "defaults", "particles_defaults", "gl_settings",
            "TendrilsHipError", "INERT", "TH_MODE_EXACT", "TH_MODE_FAST", "TH_STATE_F32", "TH_STATE_F16", "TH_TARGET_RING",
            "TH_TARGET_TARGETS", "TH_SOURCE_FLOW"]

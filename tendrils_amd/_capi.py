@@ -109,6 +109,12 @@ class ProgramInfo(C.Structure):
                 ("code_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MeasureResult(C.Structure):
+    """th_measure_result: what a measure program's reduction returns (144 bytes)"""
+    _fields_ = [("taken", C.c_uint64), ("particles", C.c_uint64), ("sum", C.c_double * 8), ("min", C.c_float * 8),
+                ("max", C.c_float * 8)]
+
+
 class DrawStages(C.Structure):
     """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
     _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
@@ -255,6 +261,10 @@ PROTOTYPES = {
     "th_step_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "th_step_program_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_int32]),
     "th_step_program_view_size": (C.c_int32, [_ctx, C.POINTER(C.c_float)]),
+    "th_measure_program_compile": (C.c_int32, [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "th_measure_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(MeasureResult)]),
+    "th_measure_async": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "th_measure_global": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(MeasureResult)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

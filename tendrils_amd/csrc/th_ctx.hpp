@@ -12,6 +12,7 @@
 //   th_screen.hip  screen programs: a caller's HIP pass over a view image, the colour map or a texture (th_screen_program_compile / th_screen_run)
 //   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
 //   th_stepprog.hip step programs: n steps of a caller's integrator in one launch (th_step_program_compile / th_step_program_run)
+//   th_measure.hip measure programs: a caller's reduction over a ring buffer (th_measure_program_compile / th_measure_run / _async / _global)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -82,7 +83,7 @@ struct th_options {
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
 // anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
 namespace thi {
-enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3, kFragmentProgram = 4 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile / th_fragment_program_compile
+enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3, kFragmentProgram = 4, kMeasureProgram = 5 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile / th_fragment_program_compile / th_measure_program_compile
 }
 struct th_program {
     thi::ProgramKind kind = thi::kStateProgram;
@@ -103,12 +104,13 @@ namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel / th_fragment_kernel
+    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel / th_fragment_kernel / th_measure_kernel
     hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order); a fragment
                                          // program's third: th_fragment_bins_kernel (the fragments of a binned pass, where they lie in the page store)
     hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines); a fragment
                                          // program's second: th_fragment_band_kernel (the fragments of an emit, under their 64-bit keys)
-    hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels)
+    hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels);
+                                         // a measure program's second: th_measure_packed_kernel (the same reduction over those texels)
     hipFunction_t fn_line = nullptr, fn_line_band = nullptr;      // a fragment program's fourth and fifth: th_fragment_line_kernel / th_fragment_line_band_kernel
                                          // (fn / fn_band with the fragments' line records behind their record: a program that reads th_line)
     hipFunction_t fn_line_bins = nullptr;                         // ... and its sixth: th_fragment_line_bins_kernel (fn_slots with the places' line records behind its record)
@@ -364,6 +366,10 @@ struct th_context {
 
     std::vector<std::unique_ptr<thi::ProgramModule>> programs;     // th_program_run / th_screen_run / th_draw_program_run: the programs this context has loaded
     DevBuf<unsigned> prog_flag;                   // ... and the word a pass on a row band raises (th_particles outside the band)
+
+    // th_measure_run / _async / _global (th_measure.hip), reserved by the first measure of the context: a partial per workgroup of
+    // the caller's kernel (2048), and the result blocks - this context's | the ranks', gathered | the job's
+    DevBuf<th_measure_result> measure_parts, measure_blocks;
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
     // (grows and stays, like the flow lines' scratch)

@@ -9,7 +9,7 @@
 // else by soname; TH_HIPRTC_LIB names another.  Nothing here is linked against it: a host that never compiles a program never
 // loads it, and compiling needs no device.
 //
-// What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs; th_stepprog.hip: step programs; th_fragprog.hip: fragment programs) is here too: the hiprtc binding, the compile, the log,
+// What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs; th_stepprog.hip: step programs; th_fragprog.hip: fragment programs; th_measure.hip: measure programs) is here too: the hiprtc binding, the compile, the log,
 // what is read out of the code object, the per-context modules (thi::program_*).
 #include <dlfcn.h>
 #include <elf.h>
@@ -24,8 +24,8 @@ namespace {
 const char kPrelude[] =
 #include "th_program_prelude.inc"
     ;
-const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel", "th_step_kernel", "th_fragment_kernel"};      // by ProgramKind
-const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude", "th_step_prelude", "th_fragment_prelude"};
+const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel", "th_step_kernel", "th_fragment_kernel", "th_measure_kernel"};      // by ProgramKind
+const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude", "th_step_prelude", "th_fragment_prelude", "th_measure_prelude"};
 
 // the launch record (th_program_prelude.inc: th_program_args, th_program_uniform_block - the same layout)
 struct ProgramArgs {
@@ -136,7 +136,8 @@ const char *program_kind_name(ProgramKind kind)
     return kind == kScreenProgram ? "screen program (th_screen_program_compile)"
          : kind == kDrawProgram   ? "draw program (th_draw_program_compile)"
          : kind == kStepProgram   ? "step program (th_step_program_compile)"
-         : kind == kFragmentProgram ? "fragment program (th_fragment_program_compile)" : "state program (th_program_compile)";
+         : kind == kFragmentProgram ? "fragment program (th_fragment_program_compile)"
+         : kind == kMeasureProgram ? "measure program (th_measure_program_compile)" : "state program (th_program_compile)";
 }
 
 th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes)
@@ -159,6 +160,7 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_draw_vertex_slots_kernel"));
     if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_draw_vertex_band_kernel"));
     if (prog->kind == kStepProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_step_packed_kernel"));
+    if (prog->kind == kMeasureProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_measure_packed_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_fragment_band_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_fragment_bins_kernel"));
     if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line, m->module, "th_fragment_line_kernel"));

@@ -190,6 +190,49 @@ class StepProgram(Program):
     COMPILE, SOURCE_KIND = "th_step_program_compile", "step"
 
 
+class MeasureProgram(Program):
+    """A measure program (include/tendrils_hip.h "measure programs"): from_source() takes HIP source defining
+    `__device__ th_sample th_measure_main(const th_measure_pass &m)` - what one particle contributes to up to `channels`
+    (1 .. 8) numbers, or th_no_sample() - and is otherwise Program.from_source: compiled once, for gfx950, no GPU needed;
+    TendrilsHipError with the compiler's output; pack(), query() and dispose() as there.  Particles.measure() reduces it over a
+    ring buffer - per channel the sum, the minimum and the maximum, and the count of samples taken - and reads nothing back but
+    the 144-byte result; nothing of the context changes."""
+    COMPILE, SOURCE_KIND = "th_measure_program_compile", "measure"
+
+    @classmethod
+    def from_source(cls, source, uniforms_struct=None, channels=1, name="measure_program"):
+        if uniforms_struct is not None and C.sizeof(uniforms_struct) > 1024:
+            raise ValueError("a uniform block holds at most 1024 bytes (%d)" % C.sizeof(uniforms_struct))
+        lib = _capi.load()
+        handle = C.c_void_p()
+        status = lib.th_measure_program_compile(source.encode(), name.encode(), int(channels), C.byref(handle))
+        if status != _capi.TH_OK:
+            raise _capi.TendrilsHipError(status, lib.th_last_error().decode(errors="replace") + "\n" +
+                                         lib.th_program_log().decode(errors="replace"))
+        prog = cls(cls.SOURCE_KIND, name=name, channels=int(channels))
+        prog.handle, prog.uniforms_struct = handle, uniforms_struct
+        return prog
+
+    @property
+    def channels(self):
+        return self.fixed["channels"]
+
+
+class Measure:
+    """What Particles.measure returns: taken (samples), particles (texels measured), and per channel sum (float64), min, max
+    (float32) - numpy arrays of the program's `channels`"""
+
+    def __init__(self, result, channels):
+        self.taken, self.particles = int(result.taken), int(result.particles)
+        self.sum = np.array(result.sum[:channels], np.float64)
+        self.min = np.array(result.min[:channels], np.float32)
+        self.max = np.array(result.max[:channels], np.float32)
+        self.raw = bytes(result)
+
+    def __repr__(self):
+        return "Measure(taken=%d, particles=%d, sum=%r, min=%r, max=%r)" % (self.taken, self.particles, self.sum, self.min, self.max)
+
+
 LOGIC = "logic"
 
 
@@ -427,6 +470,31 @@ class Particles:
         c = _capi.Counters()
         call("th_stats", self._ctx, C.c_float(speed_limit), C.byref(c))
         return {k: getattr(c, k) for k, _ in _capi.Counters._fields_}
+
+    def _measure_args(self, program, uniforms, buffer):
+        if not isinstance(program, MeasureProgram) or not program.handle:
+            raise TypeError("measure: %r is no compiled MeasureProgram" % (program,))
+        handle, block, size = program_block(program, uniforms or {})
+        index = buffer.index if isinstance(buffer, StateBuffer) else int(buffer)
+        return (self._ctx, handle, None if block is None else C.byref(block), size, index), block
+
+    def measure(self, program, uniforms=None, buffer=0, everywhere=False):
+        """The reduction of a MeasureProgram over ring buffer `buffer` (th_measure_run): a Measure - taken, particles, and sum,
+        min, max per channel.  Read-only: the ring stays in the slot order it is held in and nothing else of the context
+        changes.  everywhere: over every rank's band of a row-band job (th_measure_global - every rank calls it, all get the
+        same bits); without a communicator the same as the local measure."""
+        args, _block = self._measure_args(program, uniforms, buffer)
+        out = _capi.MeasureResult()
+        call("th_measure_global" if everywhere else "th_measure_run", *args, C.byref(out))
+        return Measure(out, program.channels)
+
+    def measure_async(self, program, uniforms=None, buffer=0):
+        """... enqueued only (th_measure_async): the device address the 144-byte th_measure_result lands at once the context's
+        stream gets there (sync()), valid until this context's next measure"""
+        args, _block = self._measure_args(program, uniforms, buffer)      # (the block is copied when the launch is enqueued)
+        out = C.c_void_p()
+        call("th_measure_async", *args, C.byref(out))
+        return out.value
 
     @staticmethod
     def generateLUT(shape):                          # src/particles.js:171-190

@@ -663,5 +663,12 @@ class Tendrils:
         self.blending = True                                    # src/index.js:453-454
         return self
 
+    def measure(self, program, uniforms=None):
+        """A MeasureProgram's reduction over the particles' current state (Particles.measure of buffers[0]): its uniform block
+        is filled from tendrils.state, time, viewSize and viewRes under `uniforms`, as spawnShader fills a pass's.  Read-only:
+        no tick, no step - the next draw() is the one it would have been."""
+        base = dict(self.state, time=self.timer.time, viewSize=self.viewSize, viewRes=self.viewRes)
+        return self.particles.measure(program, Particles.applyUpdate(base, uniforms))
+
 
 default = Tendrils
