@@ -44,10 +44,17 @@ __device__ __forceinline__ uint2 pack_state(float4 s)
     __builtin_memcpy(&ux, &hx, 2); __builtin_memcpy(&uy, &hy, 2);
     return make_uint2(px, (unsigned)ux | ((unsigned)uy << 16));
 }
-// unpack_state(pack_state(s)) without the 8 bytes in between: what a packed ring holds of a state, as the next fused step reads it.
-// The quantised position is an integer-valued float in [-32767, 32767]: the stored short converts back to exactly that float, and
-// never to the sentinel -32768; the velocity goes through fp16 and back; inert and NaN positions come back as unpack_state gives
-// them.  (Sixteen instructions fewer per fused step than the words packed, stored in registers and unpacked: round 6.)
+// unpack_state(pack_state(s)) without the 8 bytes in between: what a packed ring holds of a state, as the next fused step reads it,
+// bit for bit for EVERY input (tests/test_gpu_packed_codec.py: every rounding boundary of both formats, planted inside a fused
+// launch and read back by a program that tells all 32 bits).  The quantised position is an integer-valued float in
+// [-32767, 32767]: the stored short converts back to exactly that float, and never to the sentinel -32768 - but for one value: a
+// negative position of magnitude up to half a quantum rounds to -0.0, whose short is 0 and decodes to +0.0.  Hence the scaling
+// back as fma(q, 2^-14, +0.0f) and not as a product: the sum takes -0.0 to +0.0 (round to nearest) and leaves every other float
+// as it is - q * 2^-14 is exact - and the compiler must keep it (no -fno-signed-zeros in the product's flags).  One v_fma_f32
+// where a v_mul_f32 stood: no instruction more per step (q + 0.0f before the product costs two; profiles/packed_codec.txt has
+// both, counted and timed).  The velocity goes through fp16 and back, which keeps a zero's sign on both paths; inert and NaN
+// positions come back as unpack_state gives them.  (Sixteen instructions fewer per fused step than the words packed, stored in
+// registers and unpacked: round 6.)
 __device__ __forceinline__ float4 quantize_state(float4 s)
 {
     float4 r;
@@ -55,8 +62,8 @@ __device__ __forceinline__ float4 quantize_state(float4 s)
     if (!(s.x != -1000000.0f || s.y != -1000000.0f)) { r.x = -1000000.0f; r.y = -1000000.0f; }
     else if (s.x != s.x || s.y != s.y) { r.x = __builtin_nanf(""); r.y = __builtin_nanf(""); }
     else {
-        r.x = __builtin_rintf(__builtin_amdgcn_fmed3f(s.x * 16384.0f, -32767.0f, 32767.0f)) * 6.103515625e-05f;
-        r.y = __builtin_rintf(__builtin_amdgcn_fmed3f(s.y * 16384.0f, -32767.0f, 32767.0f)) * 6.103515625e-05f;
+        r.x = __builtin_fmaf(__builtin_rintf(__builtin_amdgcn_fmed3f(s.x * 16384.0f, -32767.0f, 32767.0f)), 6.103515625e-05f, 0.0f);
+        r.y = __builtin_fmaf(__builtin_rintf(__builtin_amdgcn_fmed3f(s.y * 16384.0f, -32767.0f, 32767.0f)), 6.103515625e-05f, 0.0f);
     }
     return r;
 }

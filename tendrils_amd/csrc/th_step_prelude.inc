@@ -134,7 +134,7 @@ extern "C" __global__ __launch_bounds__(256) void th_step_kernel(const th_step_a
 // as namespace th): `in`, `out` and `out_prev` point at uint2 texels behind the record's float4 * fields, the record itself is
 // th_step_kernel's.  The slot's state comes in as one 8-byte non-temporal load and is decoded as every kernel of the library
 // decodes it; after EVERY step the result is replaced by what a packed ring would hold of it (quantize_state =
-// unpack_state(pack_state(.)) bit for bit), so a launch of n steps leaves the bits of n single passes; states nsteps and
+// unpack_state(pack_state(.)) bit for bit, a zero's sign included: tests/test_gpu_packed_codec.py), so a launch of n steps leaves the bits of n single passes; states nsteps and
 // nsteps - 1 leave as one 8-byte non-temporal store each (the codec is idempotent on quantised values: packing the carried
 // `prev` is exact).  A lane touches its own slot alone, so `out` or `out_prev` may be `in`.
 __device__ __forceinline__ void th_step_packed_slot(const th_step_args &a, th_step_pass &s, unsigned idx, unsigned pid)
