@@ -34,6 +34,7 @@
 
 #include "th_kernels.hpp"
 #include "th_math.hpp"
+#include "th_program_kinds.hpp"
 
 namespace thi {
 struct FlowLineScratch;                   // th_flowline.hip
@@ -82,9 +83,6 @@ struct th_options {
 
 // A compiled program of any kind: the gfx950 code object, until th_program_destroy; the record itself lives as long as
 // anything names it - the caller (until th_program_destroy) and every context that loaded it (until th_destroy).
-namespace thi {
-enum ProgramKind { kStateProgram = 0, kScreenProgram = 1, kDrawProgram = 2, kStepProgram = 3, kFragmentProgram = 4, kMeasureProgram = 5 };      // th_program_compile / th_screen_program_compile / th_draw_program_compile / th_step_program_compile / th_fragment_program_compile / th_measure_program_compile
-}
 struct th_program {
     thi::ProgramKind kind = thi::kStateProgram;
     std::string name;
@@ -104,18 +102,7 @@ namespace thi {
 struct ProgramModule {
     th_program *prog = nullptr;
     hipModule_t module = nullptr;
-    hipFunction_t fn = nullptr;          // th_program_kernel / th_screen_kernel / th_draw_vertex_kernel / th_step_kernel / th_fragment_kernel / th_measure_kernel
-    hipFunction_t fn_slots = nullptr;    // a draw program's second kernel: th_draw_vertex_slots_kernel (the vertex stage over a slot order); a fragment
-                                         // program's third: th_fragment_bins_kernel (the fragments of a binned pass, where they lie in the page store)
-    hipFunction_t fn_band = nullptr;     // ... and its third: th_draw_vertex_band_kernel (the vertex stage of a row band's lines); a fragment
-                                         // program's second: th_fragment_band_kernel (the fragments of an emit, under their 64-bit keys)
-    hipFunction_t fn_packed = nullptr;   // a step program's second kernel: th_step_packed_kernel (the fused steps on a packed ring's 8-byte texels);
-                                         // a measure program's second: th_measure_packed_kernel (the same reduction over those texels)
-    hipFunction_t fn_line = nullptr, fn_line_band = nullptr;      // a fragment program's fourth and fifth: th_fragment_line_kernel / th_fragment_line_band_kernel
-                                         // (fn / fn_band with the fragments' line records behind their record: a program that reads th_line)
-    hipFunction_t fn_line_bins = nullptr;                         // ... and its sixth: th_fragment_line_bins_kernel (fn_slots with the places' line records behind its record)
-    hipFunction_t fn_pair = nullptr, fn_pair_bins = nullptr;      // ... its seventh and eighth: th_fragment_pair_kernel / th_fragment_pair_bins_kernel (fn / fn_slots
-                                         // over one half of the two varyings a fragment of th_draw_stages_pair's one rasterisation carries)
+    hipFunction_t entry[kMaxProgramEntries] = {};      // the kind's entry points, by its enumerators (th_program_kinds.hpp: DrawEntry, FragmentEntry, ...)
     ProgramModule() = default;
     ProgramModule(const ProgramModule &) = delete;             // (the context holds each behind a pointer: nothing moves one)
     ProgramModule &operator=(const ProgramModule &) = delete;
@@ -460,7 +447,7 @@ void fused_routed(th_context *c, int32_t m);
 
 // ---- th_program.hip --------------------------------------------------------------------------------------------------
 constexpr uint32_t kUniformBytes = 1024;        // a program's uniform block (th_program_uniform_block in the preludes)
-const char *program_kind_name(ProgramKind kind);
+inline const char *program_kind_name(ProgramKind kind) { return kProgramKindTable[kind].what; }
 // `prelude` + `#line 1 "<name>"` + `source` through hiprtc into a program of `kind`; th_program_log() holds the compiler's output
 th_status program_compile(ProgramKind kind, const std::string &prelude, const char *source, const char *name, th_program **out);
 // the checks every run of a program starts with: the handle, its kind (`entry`: the entry point asked), the uniform block
@@ -492,7 +479,7 @@ th_status fragment_stage_run(th_context *c, const FragmentStage &stage, const th
 // p.colors at every place the bins' lists handed out - before anything blends, whether or not the host accepts the attempt
 // (crowded: the last draw put most of its fragments into crowded bins - a bin's places are dealt to more workgroups; program:
 // the pass's vertex stage was a caller's).  A stage that reads th_line: the two line kernels of th_fragline.hip fill
-// c->bins_line_ends and c->bins_lines first - reserved by the caller, bins_pass_emit - and the stage's sixth entry point runs.
+// c->bins_line_ends and c->bins_lines first - reserved by the caller, bins_pass_emit - and the stage's kFragmentLineBins entry point runs.
 // p.mode == 2: the pair of both passes' stages, as above, over the two varyings a place of the store then holds
 th_status fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program);
 // ---- th_blend.hip ----------------------------------------------------------------------------------------------------

@@ -99,13 +99,13 @@ th_status thi::vertex_stage_run(th_context *c, const PassSpec &s, th::DepositPar
     if (th_status st = vertex_buffer(c, s, p, lines, &m)) return st;
     KernArgs k{};
     DrawArgs &a = k.a;
-    hipFunction_t fn = m->fn;
+    hipFunction_t fn = m->entry[kDrawVertex];
     size_t lanes = 2 * lines;                           // (one per stream vertex)
     const int order = bins ? order_of(c, c->ring[0]) : -1;
     if (order >= 0) {
         // over sorted slots (f32 texels, both buffers in ONE order: the gate, align_slot_orders): one lane per slot
         a.cur = c->ring[0]; a.prev = c->ring[1]; a.perm = c->orders[(size_t)order].perm;
-        fn = m->fn_slots; lanes = lines;
+        fn = m->entry[kDrawSlots]; lanes = lines;
     } else {
         float4 *cur = nullptr, *prev = nullptr;             // (a packed ring: f32 copies, as th_program_run sees it)
         if (th_status st = unpacked_view(c, c->ring[0], 0, &cur)) return st;
@@ -134,7 +134,7 @@ th_status thi::vertex_stage_band(th_context *c, const PassSpec &s, th::DepositPa
     k.a.halo_lo = p.halo_lo; k.a.halo_hi = p.halo_hi; k.a.oob = p.oob;
     k.a.row0 = p.row0; k.a.rows = p.rows;
     k.set_uniforms(s.uniforms, s.uniform_bytes);
-    return vertex_launch(c, m->fn_band, 2 * lines, k);
+    return vertex_launch(c, m->entry[kDrawBand], 2 * lines, k);
 }
 
 extern "C" {

@@ -20,7 +20,7 @@
 // the page store, under a key that holds its texel and its line's stream index.  Under TH_OPT_LINE_BINS a stage that reads the
 // line runs there too, over records written by the two kernels at the end of this file: fragment_line_ends_kernel walks the slots
 // as the emit walked them and leaves every drawing line's four snapped integers in a table by stream index; fragment_lines_bins_kernel
-// walks the places as the stage's own kernel will, looks a place's line up by the key's low word and writes line_record()'s
+// walks the places by the walk the stage's own kernel is compiled from (th_bins_walk.inc), looks a place's line up by the key's low word and writes line_record()'s
 // result beside the key.  The numbers are line_record's from dep_setup's integers: the stream-ordered records, bit for bit.
 #include "th_kernels.hpp"
 #include "th_raster.hpp"
@@ -28,6 +28,13 @@
 
 namespace th {
 namespace {
+
+// the walk over a binned pass's page store: the text th_fragprog.hip hands to hiprtc in front of a fragment program, here as code
+#define TH_BINS_WALK(...) __VA_ARGS__
+#include "th_bins_walk.inc"
+#undef TH_BINS_WALK
+static_assert(th_bins_replicas == kBinReplicas && th_bins_page_shift == kPageShift && th_bins_tot_oob == kTotOob && th_bins_tot_flags == kTotFlags &&
+              kBinsMaxExtent == 1 << 12, "th_bins_walk.inc holds the bins' constants, and a key's x and y are 12-bit fields");
 
 static_assert(sizeof(FragmentLine) == 16, "FragmentLine: th_fragment_line of th_fragment_prelude.inc, one 16-byte store a fragment");
 
@@ -126,49 +133,24 @@ __global__ __launch_bounds__(256) void fragment_line_ends_kernel(const DepositPa
     if (L.draws) ends[(size_t)col * p.H + p.row0 + row] = make_int4(L.sx[0], L.sy[0], L.sx[1], L.sy[1]);
 }
 
-// Kernel B: lines[place] for every live place of the store.  The walk is th_fragment_bins_kernel's (th_fragment_prelude.inc, which
-// restates it: that text cannot include this unit's headers): blockIdx.x is a bin, its sixteen lists' cursors are uniform loads
-// and their running sums stay in scalar registers, the places go to 256 lanes in rounds, blockIdx.y deals the rounds.  Skipped:
-// a flagged pass, places at or beyond a list's cursor, pages nobody published or outside the store, the empty key - and a key
-// whose low word is no line of this texture (none is written: the table's bound, checked where it is indexed).  Per lane: the
+// Kernel B: lines[place] for every live place of the store, by th_bins_walk - the places the stage's kernel will visit - less a
+// key whose low word is no line of this texture (none is written: the table's bound, checked where it is indexed).  Per lane: the
 // 8-byte key (x, y, line: its fields), the dependent 16-byte load of the line's endpoints, line_record, one 16-byte store.
 // Nothing is written but lines[place] of live places.
 __global__ __launch_bounds__(256) void fragment_lines_bins_kernel(const DepositParams p, const int4 *ends, FragmentLine *lines)
 {
-    if (p.totals[kTotFlags] != 0u || p.totals[kTotOob] != 0u) return;
-    const uint32_t b = blockIdx.x;
-    if (b >= p.nbins) return;
-    const uint32_t list_cap = p.max_pages << kPageShift;      // (a cursor beyond a list's pages: the pass was flagged)
-    uint32_t first[kBinReplicas + 1u];
-    first[0] = 0u;
-#pragma unroll
-    for (uint32_t r = 0; r < kBinReplicas; ++r) {
-        const uint32_t n = *list_cursor(p, b, r);
-        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
-    }
-    const uint32_t n = first[kBinReplicas], rounds = (n + 255u) >> 8;
-    const uint32_t pages = p.nbins * kBinReplicas + p.pool_pages, nlines = p.W * p.H;
-    for (uint32_t round = blockIdx.y; round < rounds; round += gridDim.y) {
-        const uint32_t w = (round << 8) + threadIdx.x;
-        if (w >= n) continue;
-        uint32_t r = 0u, base = 0u;
-#pragma unroll
-        for (uint32_t q = 1; q < kBinReplicas; ++q) if (w >= first[q]) { r = q; base = first[q]; }
-        const uint32_t list = b * kBinReplicas + r, v = w - base, pn = v >> kPageShift;
-        const uint32_t page = page_of<false>(p, list, pn);
-        if ((pn != 0u && page == 0u) || page >= pages) continue;          // (not published; kNoPlace among the rest)
-        const uint32_t at = (page << kPageShift) | (v & (kBinPage - 1u));
-        const unsigned long long key = p.frag_keys[at];
-        if (key == ~0ull) continue;
+    const th_bins_store store{p.frag_keys, p.bin_cursor, p.page_table, p.totals, p.bin_stride, p.max_pages, p.nbins, p.nbins * kBinReplicas + p.pool_pages};
+    const uint32_t nlines = p.W * p.H;
+    th_bins_walk(store, [&](unsigned long long key, uint32_t at) {
         const uint32_t id = (uint32_t)key;
-        if (id >= nlines) continue;
+        if (id >= nlines) return;
         const int4 e = ends[id];
         DepositLine L;
         L.sx[0] = e.x; L.sy[0] = e.y; L.sx[1] = e.z; L.sy[1] = e.w;
         const int ex = L.sx[1] - L.sx[0], ey = L.sy[1] - L.sy[0];       // (dep_setup's own expression: either branch converts the exact integers)
         L.short32 = ex > -(1 << 14) && ex < (1 << 14) && ey > -(1 << 14) && ey < (1 << 14);
         lines[at] = line_record(L, id, (int)((uint32_t)(key >> 32) & 0xfffu), (int)((uint32_t)(key >> 44) & 0xfffu));
-    }
+    });
 }
 
 }  // namespace
@@ -197,9 +179,9 @@ void launch_fragment_line_ends(const DepositParams &p, int4 *ends, hipStream_t s
 }
 
 // ... and behind that: `lines` holds a record for every place of the store p.frag_keys names
-void launch_fragment_lines_bins(const DepositParams &p, const int4 *ends, FragmentLine *lines, bool crowded, hipStream_t s)
+void launch_fragment_lines_bins(const DepositParams &p, const int4 *ends, FragmentLine *lines, int deal, hipStream_t s)
 {
-    hipLaunchKernelGGL(fragment_lines_bins_kernel, dim3(p.nbins ? p.nbins : 1u, (uint32_t)(crowded ? kBinsStageDealCrowded : kBinsStageDeal)), dim3(256), 0, s, p, ends, lines);
+    hipLaunchKernelGGL(fragment_lines_bins_kernel, dim3(p.nbins ? p.nbins : 1u, (uint32_t)deal), dim3(256), 0, s, p, ends, lines);
 }
 
 }  // namespace th

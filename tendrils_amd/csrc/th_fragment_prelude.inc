@@ -1,5 +1,5 @@
 R"TH_PRELUDE(// th_fragment_prelude.inc - what th_fragment_program_compile puts in front of a fragment program, after the text of
-// th_taps.inc (th_fragprog.hip embeds this file as text: the first and the last line make it one raw string literal).
+// th_taps.inc and th_bins_walk.inc (th_fragprog.hip embeds this file as text: the first and the last line make it one raw string literal).
 // Self-contained: no project header, only what hiprtc's built-in headers give.  Compiled with the product's arithmetic flags
 // (-ffp-contract=off: a*b+c stays two rounded fp32 operations, as in the reference's shaders).
 //
@@ -86,23 +86,31 @@ __device__ __forceinline__ float2 th_colormap_res(const th_fragment_pass &f)
     return a.colormap ? make_float2((float)a.cw, (float)a.ch) : make_float2(1.0f, 1.0f);
 }
 
-// One fragment: its texel split into (x, y) with the record's multiplier (five integer operations, no division), ONE 16-byte
-// load of colors[at], the program, ONE 16-byte store back.
+// One fragment at window texel (x, y): ONE 16-byte load of *color, the program, ONE 16-byte store back.
 typedef float th_float4_load __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void th_fragment_lane(th_fragment_pass &f, const th_fragment_args &a, unsigned texel, unsigned at)
+__device__ __forceinline__ void th_fragment_shade(th_fragment_pass &f, unsigned x, unsigned y, float4 *color)
 {
-    const unsigned t = __umulhi(a.div_mul, texel);
-    const unsigned y = (t + ((texel - t) >> (a.div_shift & 0xffu))) >> (a.div_shift >> 8);
-    const unsigned x = texel - y * (unsigned)a.fw;
     f.x = x; f.y = y;
     f.coord = make_float2((float)x + 0.5f, (float)y + 0.5f);
-    th_float4_load *slot = reinterpret_cast<th_float4_load *>(a.colors + at);
+    th_float4_load *slot = reinterpret_cast<th_float4_load *>(color);
     const th_float4_load c = *slot;
     f.color = make_float4(c.x, c.y, c.z, c.w);
     const float4 o = th_fragment_main(f);
     th_float4_load out;
     out.x = o.x; out.y = o.y; out.z = o.z; out.w = o.w;
     *slot = out;
+}
+// ... under a texel key: split into (x, y) with the record's multiplier (five integer operations, no division)
+__device__ __forceinline__ void th_fragment_lane(th_fragment_pass &f, const th_fragment_args &a, unsigned texel, float4 *color)
+{
+    const unsigned t = __umulhi(a.div_mul, texel);
+    const unsigned y = (t + ((texel - t) >> (a.div_shift & 0xffu))) >> (a.div_shift >> 8);
+    th_fragment_shade(f, texel - y * (unsigned)a.fw, y, color);
+}
+// ... under a key of the page store: x and y are its two 12-bit fields
+__device__ __forceinline__ void th_fragment_place(th_fragment_pass &f, unsigned long long key, float4 *color)
+{
+    th_fragment_shade(f, (unsigned)(key >> 32) & 0xfffu, (unsigned)(key >> 44) & 0xfffu, color);
 }
 __device__ __forceinline__ th_fragment_pass th_fragment_pass_of(const th_fragment_args &a, const th_program_uniform_block &u)
 {
@@ -115,32 +123,42 @@ __device__ __forceinline__ th_fragment_pass th_fragment_pass_of(const th_fragmen
     return f;
 }
 
-// The harness: one lane per fragment of the pass, 256-thread workgroups, grid-stride (total < 2^31).  A wave reads 256 bytes of
-// keys and 1 KiB of varyings, contiguous, and writes that KiB back where it read it; the record is the kernel's argument (scalar
-// loads).  No LDS, no atomics; nothing is written but colors[at], at < total.
-extern "C" __global__ __launch_bounds__(256) void th_fragment_kernel(const th_fragment_args a, const th_program_uniform_block u)
+// The harness of the stream-ordered entry points: one lane per fragment of the pass, 256-thread workgroups, grid-stride
+// (total < 2^31).  Key: 32-bit texel keys, or the 64-bit keys of an emit (th_draw_stages_emit) - owner << 56 | texel << 32 | stream
+// index, the texel of the WHOLE target whatever rows of the particle texture the context holds.  LINES: lines[at] belongs to the
+// fragment at keys[at]; a lane loads its 16-byte record once, beside its varying.  PAIR: two varyings a fragment
+// (th_fragment_pair_prelude.inc), this stage's at colors[2 * at + half]; otherwise colors[at].  A wave reads its keys and its
+// varyings, contiguous, and writes the varyings back where it read them; the record is the kernel's argument (scalar loads).
+// No LDS, no atomics; nothing is written but the lane's varying.
+template <class Key, bool LINES, bool PAIR>
+__device__ __forceinline__ void th_fragment_stream(const th_fragment_args &a, const th_program_uniform_block &u, const th_fragment_line *lines, unsigned half)
 {
     th_fragment_pass f = th_fragment_pass_of(a, u);
-    const unsigned *keys = static_cast<const unsigned *>(a.keys);
-    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
-        th_fragment_lane(f, a, keys[at], at);
+    const Key *keys = static_cast<const Key *>(a.keys);
+    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u) {
+        th_fragment_line line;
+        if constexpr (LINES) { line = lines[at]; f.line = &line; }
+        unsigned texel;
+        if constexpr (sizeof(Key) == 8) texel = (unsigned)(keys[at] >> 32) & 0xffffffu;
+        else texel = keys[at];
+        th_fragment_lane(f, a, texel, a.colors + (PAIR ? 2u * at + half : at));
+    }
 }
 
-// The same stage over the fragments of an emit (th_draw_stages_emit), under their 64-bit keys: the texel is bits 32 .. 55 - of
-// the WHOLE target, whatever rows of the particle texture the context holds.  An entry point of its own and no switch in one
-// kernel: each loop loads keys of one width, and neither carries the other's registers.
+// An entry point per key width and no switch in one kernel: each loop loads keys of one width, and neither carries the other's
+// registers.
+extern "C" __global__ __launch_bounds__(256) void th_fragment_kernel(const th_fragment_args a, const th_program_uniform_block u)
+{
+    th_fragment_stream<unsigned, false, false>(a, u, nullptr, 0u);
+}
+
 extern "C" __global__ __launch_bounds__(256) void th_fragment_band_kernel(const th_fragment_args a, const th_program_uniform_block u)
 {
-    th_fragment_pass f = th_fragment_pass_of(a, u);
-    const unsigned long long *keys = static_cast<const unsigned long long *>(a.keys);
-    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.total; at += gridDim.x * 256u)
-        th_fragment_lane(f, a, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
+    th_fragment_stream<unsigned long long, false, false>(a, u, nullptr, 0u);
 }
 
 // ---- the two entry points of a program that reads the fragment's line (th_line) -------------------------------------------------
-// th_fragment_kernel and th_fragment_band_kernel with the pass's line records behind the record they take: lines[at] belongs to
-// the fragment at keys[at] / colors[at].  A record of its own (th_fragprog.hip: FragmentLineArgs, the same layout): the three
-// other entry points keep theirs.  A lane loads its 16-byte record once, beside its varying.
+// A record of its own (th_fragprog.hip: the same layout): the other entry points keep theirs.
 struct th_fragment_line_args {
     th_fragment_args f;
     const th_fragment_line *lines;   // per fragment, in the keys' order
@@ -149,118 +167,42 @@ static_assert(sizeof(th_fragment_line_args) == 72, "th_fragment_line_args: layou
 
 extern "C" __global__ __launch_bounds__(256) void th_fragment_line_kernel(const th_fragment_line_args a, const th_program_uniform_block u)
 {
-    th_fragment_pass f = th_fragment_pass_of(a.f, u);
-    const unsigned *keys = static_cast<const unsigned *>(a.f.keys);
-    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.f.total; at += gridDim.x * 256u) {
-        const th_fragment_line line = a.lines[at];
-        f.line = &line;
-        th_fragment_lane(f, a.f, keys[at], at);
-    }
+    th_fragment_stream<unsigned, true, false>(a.f, u, a.lines, 0u);
 }
 
 extern "C" __global__ __launch_bounds__(256) void th_fragment_line_band_kernel(const th_fragment_line_args a, const th_program_uniform_block u)
 {
-    th_fragment_pass f = th_fragment_pass_of(a.f, u);
-    const unsigned long long *keys = static_cast<const unsigned long long *>(a.f.keys);
-    for (unsigned at = blockIdx.x * 256u + threadIdx.x; at < a.f.total; at += gridDim.x * 256u) {
-        const th_fragment_line line = a.lines[at];
-        f.line = &line;
-        th_fragment_lane(f, a.f, (unsigned)(keys[at] >> 32) & 0xffffffu, at);
-    }
+    th_fragment_stream<unsigned long long, true, false>(a.f, u, a.lines, 0u);
 }
 
 // ---- the same stage over the fragments of a BINNED pass (th_bins.hip), where they lie in its page store -----------------------
-// Between the emitting pass and the blends every fragment of a binned pass lies at a PLACE of the store: its key
-// (y << 44 | x << 32 | stream index of its line; all ones: a place handed out and not written) in frag_keys[place], its varying
-// in colors[place] - where the ordinary bins' blend, the crowd's regroup and the long and giant runs all fetch it later.  A bin
-// is TH_BIN_REPLICAS lists of pages of 2^TH_BIN_PAGE_SHIFT places; list l = bin * TH_BIN_REPLICAS + r has handed out the places
-// v < cursor(bin, r); place v lies in page v >> TH_BIN_PAGE_SHIFT of the list - page 0 is page l of the store, a further page n
-// is page_table[l * max_pages + n] (0: none was published, 0xffffffff: the pool was dry) - at v's low bits.  The lines below
-// restate th_bins.hip's arithmetic (list_cursor, page_of, place_of: this text cannot include the library's headers); the record
-// is th_fragprog.hip's FragmentBinsArgs, the same layout.
-#define TH_BIN_REPLICAS 16u
-#define TH_BIN_PAGE_SHIFT 8u
-#define TH_BINS_TOT_OOB 1
-#define TH_BINS_TOT_FLAGS 2
+// The walk is th_bins_walk (th_bins_walk.inc, whose text stands in front of this one): a place's key in keys[place], its varying
+// in colors[place] - where the ordinary bins' blend, the crowd's regroup and the long and giant runs all fetch it later.  Nothing
+// is written but colors[place] of live places.  The record is th_fragprog.hip's, the same layout.
 struct th_fragment_bins_args {
     th_fragment_args f;              // keys: the store's 64-bit keys; colors: its varyings; total, div_mul, div_shift: unused (0)
-    const unsigned *bin_cursor;      // the lists' cursors: list r of bin b at r * bin_stride + (b & 31) * ((nbins + 31) >> 5) + (b >> 5)
+    const unsigned *bin_cursor;      // the lists' cursors
     const unsigned *page_table;      // per list max_pages entries
-    const unsigned *totals;          // the pass's totals: [TH_BINS_TOT_OOB], [TH_BINS_TOT_FLAGS] not 0 - a pass nobody will blend
+    const unsigned *totals;          // the pass's totals
     unsigned bin_stride, max_pages, nbins;
     unsigned pages;                  // pages of the store: every page id is below it
-    unsigned replicas, page_shift;   // TH_BIN_REPLICAS, TH_BIN_PAGE_SHIFT as the library was built (anything else: the kernel does nothing)
+    unsigned replicas, page_shift;   // th_bins_replicas, th_bins_page_shift (the library fills them from the constants this text was built with)
 };
 static_assert(sizeof(th_fragment_bins_args) == 112, "th_fragment_bins_args: layout shared with th_fragprog.hip");
-
-// One fragment of a binned pass: x and y are the key's two 12-bit fields (no division), ONE 16-byte load of colors[at], the
-// program, ONE 16-byte store back - th_fragment_lane's body behind another split of the key.
-__device__ __forceinline__ void th_fragment_place(th_fragment_pass &f, const th_fragment_args &a, unsigned long long key, unsigned at)
+__device__ __forceinline__ th_bins_store th_fragment_store_of(const th_fragment_bins_args &a)
 {
-    const unsigned x = (unsigned)(key >> 32) & 0xfffu, y = (unsigned)(key >> 44) & 0xfffu;
-    f.x = x; f.y = y;
-    f.coord = make_float2((float)x + 0.5f, (float)y + 0.5f);
-    th_float4_load *slot = reinterpret_cast<th_float4_load *>(a.colors + at);
-    const th_float4_load c = *slot;
-    f.color = make_float4(c.x, c.y, c.z, c.w);
-    const float4 o = th_fragment_main(f);
-    th_float4_load out;
-    out.x = o.x; out.y = o.y; out.z = o.z; out.w = o.w;
-    *slot = out;
+    return th_bins_store{static_cast<const unsigned long long *>(a.f.keys), a.bin_cursor, a.page_table, a.totals, a.bin_stride, a.max_pages, a.nbins, a.pages};
 }
 
-// The harness: blockIdx.x is a bin, whose places - its lists walked one after the other, as bins_blend_kernel walks them - go to
-// the workgroup's 256 lanes in rounds; blockIdx.y deals the rounds of one bin to gridDim.y workgroups (a crowded target puts half
-// a million fragments into one bin).  The grid is sized by bins, not by fragments: the cursors are on the device.  Skipped: the
-// whole pass when it raised a flag or asked for a row nobody holds (it is repeated or abandoned, its table not to be trusted);
-// places at or beyond a list's cursor; pages the table does not hold (entry 0 or 0xffffffff, page number >= max_pages, an id
-// outside the store); places whose key is the empty key.  No LDS (a lane's list is found among sixteen running sums the wave
-// holds in scalar registers), no atomics; nothing is written but colors[place] of live places.
 extern "C" __global__ __launch_bounds__(256) void th_fragment_bins_kernel(const th_fragment_bins_args a, const th_program_uniform_block u)
 {
-    if (a.replicas != TH_BIN_REPLICAS || a.page_shift != TH_BIN_PAGE_SHIFT) return;
-    if (a.totals[TH_BINS_TOT_FLAGS] != 0u || a.totals[TH_BINS_TOT_OOB] != 0u) return;
-    const unsigned b = blockIdx.x;
-    if (b >= a.nbins) return;
-    // first place of every list in the walk; a list holds at most max_pages pages (a cursor beyond them: the pass was flagged)
-    const unsigned list_cap = a.max_pages << TH_BIN_PAGE_SHIFT;
-    const unsigned *cursor = a.bin_cursor + (size_t)(b & 31u) * ((a.nbins + 31u) >> 5) + (b >> 5);
-    unsigned first[TH_BIN_REPLICAS + 1u];
-    first[0] = 0u;
-#pragma unroll
-    for (unsigned r = 0; r < TH_BIN_REPLICAS; ++r) {
-        const unsigned n = cursor[(size_t)r * a.bin_stride];
-        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
-    }
-    const unsigned n = first[TH_BIN_REPLICAS], rounds = (n + 255u) >> 8;
-    if (blockIdx.y >= rounds) return;
     th_fragment_pass f = th_fragment_pass_of(a.f, u);
-    const unsigned long long *keys = static_cast<const unsigned long long *>(a.f.keys);
-    for (unsigned round = blockIdx.y; round < rounds; round += gridDim.y) {
-        const unsigned w = (round << 8) + threadIdx.x;
-        if (w >= n) continue;
-        unsigned r = 0u, base = 0u;
-#pragma unroll
-        for (unsigned q = 1; q < TH_BIN_REPLICAS; ++q) if (w >= first[q]) { r = q; base = first[q]; }
-        const unsigned list = b * TH_BIN_REPLICAS + r, v = w - base, pn = v >> TH_BIN_PAGE_SHIFT;
-        unsigned id = list;
-        if (pn != 0u) {
-            if (pn >= a.max_pages) continue;
-            id = a.page_table[(size_t)list * a.max_pages + pn];
-            if (id == 0u) continue;
-        }
-        if (id >= a.pages) continue;                     // (0xffffffff among them)
-        const unsigned at = (id << TH_BIN_PAGE_SHIFT) | (v & ((1u << TH_BIN_PAGE_SHIFT) - 1u));
-        const unsigned long long key = keys[at];
-        if (key == ~0ull) continue;
-        th_fragment_place(f, a.f, key, at);
-    }
+    th_bins_walk(th_fragment_store_of(a), [&](unsigned long long key, unsigned at) { th_fragment_place(f, key, a.f.colors + at); });
 }
 
 // ---- ... and of a program that reads the fragment's line, over the same store (TH_OPT_LINE_BINS) -------------------------------
-// th_fragment_bins_kernel with the pass's line records behind the record it takes: lines[at] belongs to the fragment at place
-// `at` (th_fragline.hip writes it from the place's key and the line's snapped endpoints: line_record's numbers, as in a
-// stream-ordered pass).  A record of its own (th_fragprog.hip: FragmentLineBinsArgs, the same layout); the walk above, and a lane
+// lines[at] belongs to the fragment at place `at` (th_fragline.hip writes it from the place's key and the line's snapped
+// endpoints: line_record's numbers, as in a stream-ordered pass).  A record of its own (th_fragprog.hip: the same layout); a lane
 // loads its 16-byte record once, beside its varying - as th_fragment_line_kernel does.
 struct th_fragment_line_bins_args {
     th_fragment_bins_args b;
@@ -270,43 +212,11 @@ static_assert(sizeof(th_fragment_line_bins_args) == 120, "th_fragment_line_bins_
 
 extern "C" __global__ __launch_bounds__(256) void th_fragment_line_bins_kernel(const th_fragment_line_bins_args a, const th_program_uniform_block u)
 {
-    if (a.b.replicas != TH_BIN_REPLICAS || a.b.page_shift != TH_BIN_PAGE_SHIFT) return;
-    if (a.b.totals[TH_BINS_TOT_FLAGS] != 0u || a.b.totals[TH_BINS_TOT_OOB] != 0u) return;
-    const unsigned b = blockIdx.x;
-    if (b >= a.b.nbins) return;
-    const unsigned list_cap = a.b.max_pages << TH_BIN_PAGE_SHIFT;
-    const unsigned *cursor = a.b.bin_cursor + (size_t)(b & 31u) * ((a.b.nbins + 31u) >> 5) + (b >> 5);
-    unsigned first[TH_BIN_REPLICAS + 1u];
-    first[0] = 0u;
-#pragma unroll
-    for (unsigned r = 0; r < TH_BIN_REPLICAS; ++r) {
-        const unsigned n = cursor[(size_t)r * a.b.bin_stride];
-        first[r + 1u] = first[r] + (n < list_cap ? n : list_cap);
-    }
-    const unsigned n = first[TH_BIN_REPLICAS], rounds = (n + 255u) >> 8;
-    if (blockIdx.y >= rounds) return;
     th_fragment_pass f = th_fragment_pass_of(a.b.f, u);
-    const unsigned long long *keys = static_cast<const unsigned long long *>(a.b.f.keys);
-    for (unsigned round = blockIdx.y; round < rounds; round += gridDim.y) {
-        const unsigned w = (round << 8) + threadIdx.x;
-        if (w >= n) continue;
-        unsigned r = 0u, base = 0u;
-#pragma unroll
-        for (unsigned q = 1; q < TH_BIN_REPLICAS; ++q) if (w >= first[q]) { r = q; base = first[q]; }
-        const unsigned list = b * TH_BIN_REPLICAS + r, v = w - base, pn = v >> TH_BIN_PAGE_SHIFT;
-        unsigned id = list;
-        if (pn != 0u) {
-            if (pn >= a.b.max_pages) continue;
-            id = a.b.page_table[(size_t)list * a.b.max_pages + pn];
-            if (id == 0u) continue;
-        }
-        if (id >= a.b.pages) continue;                   // (0xffffffff among them)
-        const unsigned at = (id << TH_BIN_PAGE_SHIFT) | (v & ((1u << TH_BIN_PAGE_SHIFT) - 1u));
-        const unsigned long long key = keys[at];
-        if (key == ~0ull) continue;
+    th_bins_walk(th_fragment_store_of(a.b), [&](unsigned long long key, unsigned at) {
         const th_fragment_line line = a.lines[at];
         f.line = &line;
-        th_fragment_place(f, a.b.f, key, at);
-    }
+        th_fragment_place(f, key, a.b.f.colors + at);
+    });
 }
 )TH_PRELUDE"

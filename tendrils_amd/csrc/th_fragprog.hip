@@ -11,22 +11,30 @@
 // A program whose source names th_line reads the fragment's line: its pass stays stream-ordered, fragment_stage_run has the line
 // kernel (th_fragline.hip) write a record per fragment beside key and varying, and launches the two entry points that take them.
 // Under TH_OPT_LINE_BINS as well such a pass goes through the bins like the others: fragment_stage_run_bins has th_fragline.hip's
-// two other kernels write a record per place of the store and launches the sixth entry point, which takes those.
+// two other kernels write a record per place of the store and launches the entry point that takes those.
 // th_draw_stages_pair draws both passes with their stages from ONE rasterisation where that gives the two passes' bits (th_draw's
 // mode 2: two varyings a fragment): both stages then travel down in the one argument, and fragment_stage_run / _run_bins launch
-// the seventh or eighth entry point (th_fragment_pair_prelude.inc) once per stage, each over its half of the pairs.
+// a pair entry point (th_fragment_pair_prelude.inc) once per stage, each over its half of the pairs.
+// Eight entry points (th_ctx.hpp: FragmentEntry), one way to launch them: a record - the context's part, where the fragments lie,
+// what the entry point takes behind that - and stage_launch.
 #include "th_ctx.hpp"
 
 using namespace thi;
 
 namespace {
 
-// the tap rules as text (th_taps.inc: the library's kernels compile the same lines), then the prelude
+// the tap rules as text (th_taps.inc: the library's kernels compile the same lines), the walk over a binned pass's page store as
+// text (th_bins_walk.inc: th_fragline.hip compiles the same lines, and ties their constants to th_bins.hip's), then the prelude
 #define TH_TAPS(...) #__VA_ARGS__
 const char kTaps[] =
 #include "th_taps.inc"
     ;
 #undef TH_TAPS
+#define TH_BINS_WALK(...) #__VA_ARGS__
+const char kBinsWalk[] =
+#include "th_bins_walk.inc"
+    ;
+#undef TH_BINS_WALK
 const char kPrelude[] =
 #include "th_fragment_prelude.inc"
     ;
@@ -45,61 +53,42 @@ struct FragmentArgs {
     int32_t pass;
     uint32_t div_mul, div_shift;
 };
-using KernArgs = ProgramKernArgs<FragmentArgs>;
-static_assert(sizeof(FragmentArgs) == 64 && offsetof(FragmentArgs, total) == 32 && offsetof(FragmentArgs, div_mul) == 56 && offsetof(KernArgs, u) == 64 &&
-              sizeof(KernArgs) == 64 + kUniformBytes, "launch record: layout shared with th_fragment_prelude.inc");
-
-// ... the record of th_fragment_line_kernel / th_fragment_line_band_kernel (th_fragment_line_args): the first record, then the
-// fragments' line records (th_fragline.hip) - a program that reads th_line
-struct FragmentLineArgs {
-    FragmentArgs f;
-    const th::FragmentLine *lines;
-};
-using LineKernArgs = ProgramKernArgs<FragmentLineArgs>;
-static_assert(sizeof(FragmentLineArgs) == 72 && offsetof(FragmentLineArgs, lines) == 64 && offsetof(LineKernArgs, u) == 80 && sizeof(LineKernArgs) == 80 + kUniformBytes &&
-              sizeof(th::FragmentLine) == 16, "line launch record: layout shared with th_fragment_prelude.inc");
-
-// ... and the record of th_fragment_bins_kernel (th_fragment_bins_args): the first record, then where the bins' lists lie.  The
-// prelude restates th_bins.hip's constants; the kernel does nothing when `replicas` / `page_shift` are not its own.
+// ... of the entry points over the page store (th_fragment_bins_args): the first record, then where the bins' lists lie.
+// `replicas` / `page_shift` keep their place in the layout; the kernels' constants are th_bins_walk.inc's own, which
+// th_fragline.hip's static_assert holds to the library's
 struct FragmentBinsArgs {
     FragmentArgs f;
     const uint32_t *bin_cursor, *page_table, *totals;
     uint32_t bin_stride, max_pages, nbins, pages;
     uint32_t replicas, page_shift;
 };
-using BinsKernArgs = ProgramKernArgs<FragmentBinsArgs>;
-constexpr uint32_t kPreludeReplicas = 16, kPreludePageShift = 8;      // (TH_BIN_REPLICAS, TH_BIN_PAGE_SHIFT)
-static_assert(sizeof(FragmentBinsArgs) == 112 && offsetof(FragmentBinsArgs, bin_cursor) == 64 && offsetof(FragmentBinsArgs, bin_stride) == 88 &&
-              offsetof(FragmentBinsArgs, replicas) == 104 && offsetof(BinsKernArgs, u) == 112 && sizeof(BinsKernArgs) == 112 + kUniformBytes,
-              "bins launch record: layout shared with th_fragment_prelude.inc");
-// ... and of th_fragment_line_bins_kernel (th_fragment_line_bins_args): that record, then the places' line records
-// (th_fragline.hip) - a program that reads th_line, through the bins (TH_OPT_LINE_BINS)
-struct FragmentLineBinsArgs {
-    FragmentBinsArgs b;
+// ... of the entry points of a program that reads th_line (th_fragment_line_args, th_fragment_line_bins_args): either record,
+// then the line records of the fragments / of the places (th_fragline.hip)
+template <class First> struct WithLines {
+    First first;
     const th::FragmentLine *lines;
 };
-using LineBinsKernArgs = ProgramKernArgs<FragmentLineBinsArgs>;
-static_assert(sizeof(FragmentLineBinsArgs) == 120 && offsetof(FragmentLineBinsArgs, lines) == 112 && offsetof(LineBinsKernArgs, u) == 128 &&
-              sizeof(LineBinsKernArgs) == 128 + kUniformBytes, "line bins launch record: layout shared with th_fragment_prelude.inc");
 // ... and of th_fragment_pair_kernel / th_fragment_pair_bins_kernel (th_fragment_pair_prelude.inc: th_fragment_pair_args,
-// th_fragment_pair_bins_args): the first record, respectively the bins' record, then which of a fragment's two varyings the
-// stage runs over - both passes from one rasterisation (p.mode == 2: th_draw_stages_pair)
-struct FragmentPairArgs {
-    FragmentArgs f;
+// th_fragment_pair_bins_args): either record, then which of a fragment's two varyings the stage runs over - both passes from
+// one rasterisation (p.mode == 2: th_draw_stages_pair)
+template <class First> struct WithHalf {
+    First first;
     uint32_t half;
 };
-using PairKernArgs = ProgramKernArgs<FragmentPairArgs>;
-static_assert(sizeof(FragmentPairArgs) == 72 && offsetof(FragmentPairArgs, half) == 64 && offsetof(PairKernArgs, u) == 80 && sizeof(PairKernArgs) == 80 + kUniformBytes,
-              "pair launch record: layout shared with th_fragment_pair_prelude.inc");
-struct FragmentPairBinsArgs {
-    FragmentBinsArgs b;
-    uint32_t half;
-};
-using PairBinsKernArgs = ProgramKernArgs<FragmentPairBinsArgs>;
-static_assert(sizeof(FragmentPairBinsArgs) == 120 && offsetof(FragmentPairBinsArgs, half) == 112 && offsetof(PairBinsKernArgs, u) == 128 &&
-              sizeof(PairBinsKernArgs) == 128 + kUniformBytes, "pair bins launch record: layout shared with th_fragment_pair_prelude.inc");
-static_assert(th::kBinReplicas == kPreludeReplicas && th::kBinPage == 1u << kPreludePageShift && th::kTotOob == 1 && th::kTotFlags == 2 &&
-              th::kBinsMaxExtent == 1 << 12, "th_fragment_prelude.inc restates the bins' constants and the key's 12-bit fields");
+template <class Args, size_t Bytes, size_t Last> constexpr bool record_is()      // sizeof, the offset of what stands behind `first`, the uniform block behind both
+{
+    using K = ProgramKernArgs<Args>;
+    return sizeof(Args) == Bytes && offsetof(Args, first) == 0 && sizeof(Args::first) == Last && offsetof(K, u) == (Bytes + 15) / 16 * 16 && sizeof(K) == (Bytes + 15) / 16 * 16 + kUniformBytes;
+}
+static_assert(sizeof(FragmentArgs) == 64 && offsetof(FragmentArgs, total) == 32 && offsetof(FragmentArgs, div_mul) == 56 && offsetof(ProgramKernArgs<FragmentArgs>, u) == 64 &&
+              sizeof(ProgramKernArgs<FragmentArgs>) == 64 + kUniformBytes, "launch record: layout shared with th_fragment_prelude.inc");
+static_assert(sizeof(FragmentBinsArgs) == 112 && offsetof(FragmentBinsArgs, bin_cursor) == 64 && offsetof(FragmentBinsArgs, bin_stride) == 88 &&
+              offsetof(FragmentBinsArgs, replicas) == 104 && offsetof(ProgramKernArgs<FragmentBinsArgs>, u) == 112 && sizeof(ProgramKernArgs<FragmentBinsArgs>) == 112 + kUniformBytes,
+              "bins launch record: layout shared with th_fragment_prelude.inc");
+static_assert(record_is<WithLines<FragmentArgs>, 72, 64>() && offsetof(WithLines<FragmentArgs>, lines) == 64 && record_is<WithLines<FragmentBinsArgs>, 120, 112>() &&
+              offsetof(WithLines<FragmentBinsArgs>, lines) == 112 && sizeof(th::FragmentLine) == 16, "line launch records: layout shared with th_fragment_prelude.inc");
+static_assert(record_is<WithHalf<FragmentArgs>, 72, 64>() && offsetof(WithHalf<FragmentArgs>, half) == 64 && record_is<WithHalf<FragmentBinsArgs>, 120, 112>() &&
+              offsetof(WithHalf<FragmentBinsArgs>, half) == 112, "pair launch records: layout shared with th_fragment_pair_prelude.inc");
 // A bin's rounds of 256 places are dealt to this many workgroups (gridDim.y).  Every workgroup reads its bin's sixteen cursors
 // before it knows whether a round is left for it, and on an ordinary target - 1 700 places a bin at 1080p, seven rounds - most
 // of a wide deal's workgroups find none: the kernel's time is then the time of starting them (8 160 bins x 128: 0.88 ms for a
@@ -167,130 +156,120 @@ bool names_identifier(const char *source, const char *word)
     return false;
 }
 
-// the record every stream-ordered entry point starts with
-void stage_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total, FragmentArgs &a)
+// the context's part of a record: the pass, and the textures as they were before it
+void stage_context(const th_context *c, const FragmentStage &stage, FragmentArgs &a)
 {
-    a.keys = p.keys64 ? static_cast<const void *>(p.keys64) : static_cast<const void *>(p.keys);
-    a.colors = p.colors;
     a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
     a.colormap = c->colormap; a.cw = c->cmap_w; a.ch = c->cmap_h;
-    a.total = total;
     a.pass = stage.pass;
+}
+// the record every stream-ordered entry point starts with ...
+void stage_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total, FragmentArgs &a)
+{
+    stage_context(c, stage, a);
+    a.keys = p.keys64 ? static_cast<const void *>(p.keys64) : static_cast<const void *>(p.keys);
+    a.colors = p.colors;
+    a.total = total;
     divide_by((uint32_t)c->fw, a.div_mul, a.div_shift);
+}
+// ... and every entry point over the page store (total: none - the cursors are on the device)
+void stage_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t, FragmentBinsArgs &a)
+{
+    stage_context(c, stage, a.f);
+    a.f.keys = p.frag_keys; a.f.colors = p.colors;
+    a.bin_cursor = p.bin_cursor; a.bin_stride = p.bin_stride;
+    a.page_table = p.page_table; a.max_pages = p.max_pages;
+    a.totals = p.totals;
+    a.nbins = p.nbins; a.pages = p.nbins * th::kBinReplicas + p.pool_pages;
+    a.replicas = th::kBinReplicas; a.page_shift = (uint32_t)__builtin_ctz(th::kBinPage);
+}
+
+// where a stage's workgroups go: over `lanes` fragments on the grid of the streaming passes, or (lanes 0) a bin of the page
+// store a workgroup column, its rounds dealt to `deal` workgroups
+struct StageGrid { size_t lanes; int bins, deal; };
+
+// the filled record with the stage's uniforms behind it, to the stage's entry point `entry`; th_kernel_timing: this launch alone
+template <class Args> th_status stage_launch(th_context *c, const FragmentStage &stage, FragmentEntry entry, ProgramKernArgs<Args> &k, const StageGrid &g)
+{
+    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
+    const hipFunction_t fn = stage.module->entry[entry];
+    LaunchTimer timer;
+    if (th_status s = timer.begin(c)) return s;
+    if (th_status s = g.lanes ? program_launch(c, fn, g.lanes, k) : program_launch_grid(c, fn, g.bins, &k, sizeof k, g.deal)) return s;
+    return timer.end(c);
+}
+
+// both passes from one rasterisation: two varyings a fragment (a place), and `pair` the two stages - the flow pass's over the
+// first of every two, then the view pass's over the second (module null: that half stays as the library interpolated it); each
+// launch in an event pair of its own
+template <class First> th_status stage_launch_pair(th_context *c, const FragmentStage *pair, const th::DepositParams &p, uint32_t total, FragmentEntry entry, const StageGrid &g)
+{
+    for (uint32_t half = 0; half < 2; ++half) {
+        if (!pair[half].module) continue;
+        ProgramKernArgs<WithHalf<First>> k{};
+        stage_record(c, pair[half], p, total, k.a.first);
+        k.a.half = half;
+        if (th_status s = stage_launch(c, pair[half], entry, k, g)) return s;
+    }
+    return TH_OK;
+}
+
+// `stage` alone: its record, with the line records behind it for a program that reads th_line
+template <class First> th_status stage_launch_one(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total, FragmentEntry entry,
+                                                  const th::FragmentLine *lines, const StageGrid &g)
+{
+    if (lines) {
+        ProgramKernArgs<WithLines<First>> k{};
+        stage_record(c, stage, p, total, k.a.first);
+        k.a.lines = lines;
+        return stage_launch(c, stage, entry, k, g);
+    }
+    ProgramKernArgs<First> k{};
+    stage_record(c, stage, p, total, k.a);
+    return stage_launch(c, stage, entry, k, g);
 }
 
 }  // namespace
 
 th_status thi::fragment_stage_run(th_context *c, const FragmentStage &stage, const th::DepositParams &p, uint32_t total)
 {
+    const StageGrid grid{total, 0, 0};
     if (p.mode == 2) {
-        // both passes from one rasterisation: two varyings a fragment, and `stage` the first of two - the flow pass's stage over
-        // the first of every two, then the view pass's over the second; each launch in an event pair of its own
         TH_REQUIRE(p.keys && !p.keys64 && p.colors, "the stages of both passes over one rasterisation: 32-bit texel keys, two varyings a fragment");
-        const FragmentStage *pair = &stage;
-        for (uint32_t half = 0; half < 2; ++half) {
-            if (!pair[half].module) continue;
-            PairKernArgs k{};
-            stage_record(c, pair[half], p, total, k.a.f);
-            k.a.half = half;
-            k.set_uniforms(pair[half].uniforms, pair[half].uniform_bytes);
-            LaunchTimer timer;
-            if (th_status s = timer.begin(c)) return s;
-            if (th_status s = program_launch(c, pair[half].module->fn_pair, total, k)) return s;
-            if (th_status s = timer.end(c)) return s;
-        }
-        return TH_OK;
+        return stage_launch_pair<FragmentArgs>(c, &stage, p, total, kFragmentPair, grid);
     }
-    LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
-    if (stage_reads_line(&stage)) {
-        // the fragments' line records first, beside the keys and varyings the scatter has just written (mode 2: no stage reads them)
-        TH_REQUIRE(c->dep_fraglines && c->dep_capacity >= total && (p.keys64 || p.keys), "a stage that reads the line: a record per fragment, keys to read the texels from");
-        th::launch_fragment_lines(p, c->dep_fraglines, c->stream);
-        TH_HIP(hipGetLastError());
-        LineKernArgs k{};
-        stage_record(c, stage, p, total, k.a.f);
-        k.a.lines = c->dep_fraglines;
-        k.set_uniforms(stage.uniforms, stage.uniform_bytes);
-        if (th_status s = timer.begin(c)) return s;
-        if (th_status s = program_launch(c, p.keys64 ? stage.module->fn_line_band : stage.module->fn_line, total, k)) return s;
-        return timer.end(c);
-    }
-    KernArgs k{};
-    stage_record(c, stage, p, total, k.a);
-    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
-    if (th_status s = timer.begin(c)) return s;
-    if (th_status s = program_launch(c, p.keys64 ? stage.module->fn_band : stage.module->fn, total, k)) return s;
-    return timer.end(c);
+    if (!stage_reads_line(&stage)) return stage_launch_one<FragmentArgs>(c, stage, p, total, p.keys64 ? kFragmentBand : kFragmentStream, nullptr, grid);
+    // the fragments' line records first, beside the keys and varyings the scatter has just written (mode 2: no stage reads them)
+    TH_REQUIRE(c->dep_fraglines && c->dep_capacity >= total && (p.keys64 || p.keys), "a stage that reads the line: a record per fragment, keys to read the texels from");
+    th::launch_fragment_lines(p, c->dep_fraglines, c->stream);
+    TH_HIP(hipGetLastError());
+    return stage_launch_one<FragmentArgs>(c, stage, p, total, p.keys64 ? kFragmentLineBand : kFragmentLine, c->dep_fraglines, grid);
 }
-
-namespace {
-
-// the record every entry point over the page store starts with
-void bins_record(const th_context *c, const FragmentStage &stage, const th::DepositParams &p, FragmentBinsArgs &a)
-{
-    a.f.keys = p.frag_keys; a.f.colors = p.colors;
-    a.f.flow = c->flow; a.f.fw = c->fw; a.f.fh = c->fh;
-    a.f.colormap = c->colormap; a.f.cw = c->cmap_w; a.f.ch = c->cmap_h;
-    a.f.pass = stage.pass;
-    a.bin_cursor = p.bin_cursor; a.bin_stride = p.bin_stride;
-    a.page_table = p.page_table; a.max_pages = p.max_pages;
-    a.totals = p.totals;
-    a.nbins = p.nbins; a.pages = p.nbins * th::kBinReplicas + p.pool_pages;
-    a.replicas = th::kBinReplicas; a.page_shift = kPreludePageShift;
-}
-
-}  // namespace
 
 th_status thi::fragment_stage_run_bins(th_context *c, const FragmentStage &stage, const th::DepositParams &p, bool crowded, bool program)
 {
     TH_REQUIRE(p.frag_keys && p.colors && p.nbins, "a fragment stage over the bins: a store to run over");
+    const StageGrid grid{0, (int)p.nbins, crowded ? kBinsStageDealCrowded : kBinsStageDeal};
     if (p.mode == 2) {
-        // both passes from one rasterisation: two varyings a place, `stage` the first of two (fragment_stage_run, above)
         TH_REQUIRE(c->bins_pairs && p.colors == c->bins_colors, "the stages of both passes over the bins: a store of two varyings a place");
-        const FragmentStage *pair = &stage;
-        for (uint32_t half = 0; half < 2; ++half) {
-            if (!pair[half].module) continue;
-            PairBinsKernArgs k{};
-            bins_record(c, pair[half], p, k.a.b);
-            k.a.half = half;
-            k.set_uniforms(pair[half].uniforms, pair[half].uniform_bytes);
-            LaunchTimer timer;
-            if (th_status s = timer.begin(c)) return s;
-            if (th_status s = program_launch_grid(c, pair[half].module->fn_pair_bins, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
-            if (th_status s = timer.end(c)) return s;
-        }
-        return TH_OK;
+        return stage_launch_pair<FragmentBinsArgs>(c, &stage, p, 0, kFragmentPairBins, grid);
     }
-    LaunchTimer timer;                                  // (th_kernel_timing: the fragment kernel alone)
-    if (stage_reads_line(&stage)) {
-        // the places' line records first, behind the emitting pass on this stream (bins_pass_emit reserved them for this store)
-        const size_t places = ((size_t)p.nbins * th::kBinReplicas + p.pool_pages) * th::kBinPage;
-        TH_REQUIRE(c->opt.line_bins && c->bins_line_ends && c->bins_lines && c->bins_lines_places >= places && p.frag_keys == c->bins_keys,
-                   "a stage that reads the line over the bins: the lines' endpoints and a record per place of the store");
-        th::launch_fragment_line_ends(p, c->bins_line_ends, c->stream, program);
-        th::launch_fragment_lines_bins(p, c->bins_line_ends, c->bins_lines, crowded, c->stream);
-        TH_HIP(hipGetLastError());
-        LineBinsKernArgs k{};
-        bins_record(c, stage, p, k.a.b);
-        k.a.lines = c->bins_lines;
-        k.set_uniforms(stage.uniforms, stage.uniform_bytes);
-        if (th_status s = timer.begin(c)) return s;
-        if (th_status s = program_launch_grid(c, stage.module->fn_line_bins, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
-        return timer.end(c);
-    }
-    BinsKernArgs k{};
-    bins_record(c, stage, p, k.a);
-    k.set_uniforms(stage.uniforms, stage.uniform_bytes);
-    if (th_status s = timer.begin(c)) return s;
-    if (th_status s = program_launch_grid(c, stage.module->fn_slots, (int)p.nbins, &k, sizeof k, crowded ? kBinsStageDealCrowded : kBinsStageDeal)) return s;
-    return timer.end(c);
+    if (!stage_reads_line(&stage)) return stage_launch_one<FragmentBinsArgs>(c, stage, p, 0, kFragmentBins, nullptr, grid);
+    // the places' line records first, behind the emitting pass on this stream (bins_pass_emit reserved them for this store)
+    const size_t places = ((size_t)p.nbins * th::kBinReplicas + p.pool_pages) * th::kBinPage;
+    TH_REQUIRE(c->opt.line_bins && c->bins_line_ends && c->bins_lines && c->bins_lines_places >= places && p.frag_keys == c->bins_keys,
+               "a stage that reads the line over the bins: the lines' endpoints and a record per place of the store");
+    th::launch_fragment_line_ends(p, c->bins_line_ends, c->stream, program);
+    th::launch_fragment_lines_bins(p, c->bins_line_ends, c->bins_lines, grid.deal, c->stream);
+    TH_HIP(hipGetLastError());
+    return stage_launch_one<FragmentBinsArgs>(c, stage, p, 0, kFragmentLineBins, c->bins_lines, grid);
 }
 
 extern "C" {
 
 th_status th_fragment_program_compile(const char *source, const char *name, th_program **out)
 {
-    if (th_status s = program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kPrelude + "\n" + kPairPrelude, source, name, out)) return s;
+    if (th_status s = program_compile(kFragmentProgram, std::string(kTaps) + "\n" + kBinsWalk + "\n" + kPrelude + "\n" + kPairPrelude, source, name, out)) return s;
     // who pays for the line records: decided here, once (the compiler has accepted the text; an identifier in a comment counts)
     (*out)->reads_line = names_identifier(source, "th_line");
     // ... and whether, as the view pass's stage, it keeps th_draw_stages_pair to two passes (th_flow_res is another identifier)

@@ -348,9 +348,9 @@ void launch_fragment_lines(const DepositParams &p, FragmentLine *lines, hipStrea
 // ... and per PLACE of a binned pass's page store (TH_OPT_LINE_BINS), behind launch_bins_fused(p, stream, program): first every
 // drawing line's snapped endpoints {sx0, sy0, sx1, sy1} into `ends` (W x H entries, by stream index - the low word of a place's
 // key), then lines[place] beside p.frag_keys[place] / p.colors[place] for every live place (`lines`: as many as the store has
-// places; crowded: the deal of the fragment stage's own walk)
+// places; deal: workgroups a bin - the deal of the fragment stage's own walk)
 void launch_fragment_line_ends(const DepositParams &p, int4 *ends, hipStream_t stream, bool program);
-void launch_fragment_lines_bins(const DepositParams &p, const int4 *ends, FragmentLine *lines, bool crowded, hipStream_t stream);
+void launch_fragment_lines_bins(const DepositParams &p, const int4 *ends, FragmentLine *lines, int deal, hipStream_t stream);
 constexpr int kBinsStageDeal = 2, kBinsStageDealCrowded = 8;      // workgroups a bin's rounds of 256 places are dealt to (th_fragprog.hip has the measurement)
 int deposit_key_bits(const DepositParams &p);
 void launch_export_mark(const DepositParams &p, hipStream_t stream);

@@ -148,7 +148,7 @@ th_status measure_enqueue(th_context *c, th_program *prog, const char *entry, co
     const int grid = th::grid_for(c->texels(), 8);
     LaunchTimer timer;
     if (th_status s = timer.begin(c)) return s;
-    if (th_status s = program_launch(c, c->packed ? m->fn_packed : m->fn, c->texels(), k)) return s;
+    if (th_status s = program_launch(c, m->entry[c->packed ? kMeasurePacked : kMeasureF32], c->texels(), k)) return s;
     if (th_status s = timer.end(c)) return s;
     hipLaunchKernelGGL(measure_fold_kernel, dim3(1), dim3(256), 0, c->stream, c->measure_parts.get(), (uint32_t)grid,
                        (unsigned long long)c->texels(), c->measure_blocks.get());

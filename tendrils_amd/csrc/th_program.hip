@@ -10,7 +10,8 @@
 // loads it, and compiling needs no device.
 //
 // What the kinds of program share (th_screen.hip: screen programs; th_drawprog.hip: draw programs; th_stepprog.hip: step programs; th_fragprog.hip: fragment programs; th_measure.hip: measure programs) is here too: the hiprtc binding, the compile, the log,
-// what is read out of the code object, the per-context modules (thi::program_*).
+// what is read out of the code object, the per-context modules (thi::program_*).  What a kind is called and which kernels its
+// module holds stands in one table (th_program_kinds.hpp).
 #include <dlfcn.h>
 #include <elf.h>
 #include <hip/hiprtc.h>
@@ -24,8 +25,6 @@ namespace {
 const char kPrelude[] =
 #include "th_program_prelude.inc"
     ;
-const char *const kKernelNames[] = {"th_program_kernel", "th_screen_kernel", "th_draw_vertex_kernel", "th_step_kernel", "th_fragment_kernel", "th_measure_kernel"};      // by ProgramKind
-const char *const kPreludeNames[] = {"th_program_prelude", "th_screen_prelude", "th_draw_prelude", "th_step_prelude", "th_fragment_prelude", "th_measure_prelude"};
 
 // the launch record (th_program_prelude.inc: th_program_args, th_program_uniform_block - the same layout)
 struct ProgramArgs {
@@ -104,7 +103,8 @@ void inspect_code_object(th_program *p)
             }
         }
     }
-    const std::string name = std::string(1, (char)(0xa0 + strlen(kKernelNames[p->kind]))) + kKernelNames[p->kind], key = "\xab.sgpr_count";
+    const char *const kernel = kProgramKindTable[p->kind].entry[0];
+    const std::string name = std::string(1, (char)(0xa0 + strlen(kernel))) + kernel, key = "\xab.sgpr_count";
     auto at = std::search(b.begin(), b.end(), name.begin(), name.end());
     if (at != b.end()) at = std::search(at, b.end(), key.begin(), key.end());
     if (at == b.end() || (size_t)(b.end() - at) < key.size() + 5) return;
@@ -128,16 +128,8 @@ void ProgramModule::reset()
 {
     if (module) (void)hipModuleUnload(module);
     program_release(prog);
-    module = nullptr; fn = nullptr; fn_slots = nullptr; fn_band = nullptr; fn_packed = nullptr; fn_line = nullptr; fn_line_band = nullptr; fn_line_bins = nullptr; fn_pair = nullptr; fn_pair_bins = nullptr; prog = nullptr;
-}
-
-const char *program_kind_name(ProgramKind kind)
-{
-    return kind == kScreenProgram ? "screen program (th_screen_program_compile)"
-         : kind == kDrawProgram   ? "draw program (th_draw_program_compile)"
-         : kind == kStepProgram   ? "step program (th_step_program_compile)"
-         : kind == kFragmentProgram ? "fragment program (th_fragment_program_compile)"
-         : kind == kMeasureProgram ? "measure program (th_measure_program_compile)" : "state program (th_program_compile)";
+    module = nullptr; prog = nullptr;
+    for (hipFunction_t &fn : entry) fn = nullptr;
 }
 
 th_status program_run_args(const th_program *prog, ProgramKind kind, const char *entry, const void *uniforms, uint32_t uniform_bytes)
@@ -156,18 +148,8 @@ th_status program_loaded(th_context *c, th_program *prog, ProgramModule **out)
     TH_REQUIRE(!prog->destroyed, "program '%s' was destroyed before this context had loaded it", prog->name.c_str());
     std::unique_ptr<ProgramModule> m(new ProgramModule);
     TH_HIP(hipModuleLoadData(&m->module, prog->code.data()));
-    TH_HIP(hipModuleGetFunction(&m->fn, m->module, kKernelNames[prog->kind]));
-    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_draw_vertex_slots_kernel"));
-    if (prog->kind == kDrawProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_draw_vertex_band_kernel"));
-    if (prog->kind == kStepProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_step_packed_kernel"));
-    if (prog->kind == kMeasureProgram) TH_HIP(hipModuleGetFunction(&m->fn_packed, m->module, "th_measure_packed_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_band, m->module, "th_fragment_band_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_slots, m->module, "th_fragment_bins_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line, m->module, "th_fragment_line_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line_band, m->module, "th_fragment_line_band_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_line_bins, m->module, "th_fragment_line_bins_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_pair, m->module, "th_fragment_pair_kernel"));
-    if (prog->kind == kFragmentProgram) TH_HIP(hipModuleGetFunction(&m->fn_pair_bins, m->module, "th_fragment_pair_bins_kernel"));
+    const ProgramKindInfo &kind = kProgramKindTable[prog->kind];
+    for (int e = 0; e < kind.entries; ++e) TH_HIP(hipModuleGetFunction(&m->entry[e], m->module, kind.entry[e]));
     m->prog = prog;
     prog->refs.fetch_add(1);
     c->programs.push_back(std::move(m));
@@ -198,7 +180,7 @@ th_status program_compile(ProgramKind kind, const std::string &prelude, const ch
     // the user's text begins at line 1 of a file called `label`: a diagnostic names the line the user wrote
     const std::string text = prelude + "\n#line 1 \"" + label + "\"\n" + source + "\n";
     hiprtcProgram hp = nullptr;
-    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), kPreludeNames[kind], 0, nullptr, nullptr);
+    hiprtcResult r = R.CreateProgram(&hp, text.c_str(), kProgramKindTable[kind].prelude, 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) return fail(TH_ERR_INVALID, "hiprtcCreateProgram: %s", R.GetErrorString(r));
     // the product's arithmetic flags (csrc/Makefile: HIPFLAGS)
     const char *opts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950"};
@@ -281,7 +263,7 @@ th_status th_program_run(th_context *c, th_program *prog, const void *uniforms, 
     k.a.count = (uint32_t)c->texels(); k.a.width = (uint32_t)c->cfg.width; k.a.rows = (uint32_t)c->cfg.height;
     k.a.row0 = (uint32_t)c->cfg.row0; k.a.global_height = (uint32_t)c->cfg.global_height;
     k.set_uniforms(uniforms, uniform_bytes);
-    if (th_status s = program_launch(c, m->fn, c->texels(), k)) return s;
+    if (th_status s = program_launch(c, m->entry[kStateRun], c->texels(), k)) return s;
     if (th_status s = pass.commit(c)) return s;
     if (band) {
         // only a row band can be asked for rows it does not hold: checked like the sharded spawn's out-of-band flag
@@ -303,9 +285,10 @@ th_status th_program_query(th_context *c, th_program *prog, th_program_info *inf
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     int vgprs = 0, lds = 0, scratch = 0;
-    TH_HIP(hipFuncGetAttribute(&vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, m->fn));
-    TH_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, m->fn));
-    TH_HIP(hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, m->fn));
+    const hipFunction_t first = m->entry[0];          // (the kind's first kernel, whose SGPRs and code size the compile read)
+    TH_HIP(hipFuncGetAttribute(&vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, first));
+    TH_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, first));
+    TH_HIP(hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, first));
     info->vgprs = (uint32_t)vgprs; info->sgprs = m->prog->sgprs;
     info->lds_bytes = (uint32_t)lds; info->scratch_bytes = (uint32_t)scratch; info->code_bytes = m->prog->code_bytes;
     return TH_OK;

@@ -93,7 +93,7 @@ th_status th_screen_run(th_context *c, th_program *prog, const void *uniforms, u
     if (!a.count) return TH_OK;
     // the record and the uniform block travel in the kernel's argument segment; a memory-bound pass (program_launch)
     k.set_uniforms(uniforms, uniform_bytes);
-    return program_launch(c, m->fn, a.count, k);
+    return program_launch(c, m->entry[kScreenRun], a.count, k);
 }
 
 }  // extern "C"

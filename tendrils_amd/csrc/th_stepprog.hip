@@ -134,7 +134,7 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
             a.out_prev = steps == 1 ? nullptr : r.out_prev;
             a.nsteps = (uint32_t)steps; a.step0 = (uint32_t)done;
             for (int32_t j = 0; j < steps; ++j) a.times[j] = times[(size_t)(done + j)];
-            if (th_status s = step_launch(c, c->packed ? m->fn_packed : m->fn, k)) return s;
+            if (th_status s = step_launch(c, m->entry[c->packed ? kStepPacked : kStepF32], k)) return s;
             set_order(c, r.other, order);                            // both outputs sit at the input's slots (a single step's input stays)
             fused_routed(c, steps);
             done += steps;
@@ -146,7 +146,7 @@ th_status th_step_program_run(th_context *c, th_program *prog, const void *unifo
             if (th_status s = pass.begin(c, TH_TARGET_RING)) return s;
             a.in = pass.particles; a.out = pass.rt;
             a.step0 = (uint32_t)done; a.times[0] = times[(size_t)done];
-            if (th_status s = step_launch(c, m->fn, k)) return s;
+            if (th_status s = step_launch(c, m->entry[kStepF32], k)) return s;
             if (th_status s = pass.commit(c)) return s;
             ++c->steps_since_sort; ++c->total_steps;
         }
