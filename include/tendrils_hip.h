@@ -612,6 +612,47 @@ th_status th_measure_async(th_context *ctx, th_program *program, const void *uni
 th_status th_measure_global(th_context *ctx, th_program *program, const void *uniforms, uint32_t uniform_bytes, int32_t buffer,
                             th_measure_result *out);
 
+/* -- density map: the particles' count and summed velocity on a grid over the view -------------------------------------
+ * th_stats and the measure programs return numbers ABOUT the particles; this says WHERE they are, in an image that never leaves
+ * the device: a TH_TEX_RGBA32F image of w x h - a caller texture slot (dest = TH_VIEW_TEXTURE, left as th_texture_upload would
+ * leave it: the slot's memory is kept when shape and format are unchanged) or the spawner's image (dest = TH_VIEW_SPAWN_IMAGE, as
+ * th_spawn_image_upload would leave it) - that th_colormap_blend, a screen program's texture units and the best-sample spawn
+ * (TH_SOURCE_IMAGE) take as they take any other.  Row 0 is the row of uv.y nearest 0, as in the flow texture.  A built-in
+ * pass (tendrils_amd/csrc/th_density.hip): fixed kernels, no hiprtc, not a program kind.
+ * Per particle, with s its state (of a TH_STATE_F16 ring: what the texel decodes to), in fp32, no contraction:
+ *   inert     s.x == -1e6f && s.y == -1e6f: counts in `particles` only.  Every other particle is `live`.
+ *   cell      fx = floorf((((s.x * viewSize[0]) + 1.0f) * 0.5f) * (float)w), fy likewise with viewSize[1] and h: the flow texel
+ *             the integrator would tap were w x h the flow's shape.  `inside` iff 0 <= fx <= w - 1 and 0 <= fy <= h - 1, compared
+ *             as floats (a NaN or infinite position fails); every other live particle is `outside` and touches no cell - no clamp
+ *             to the edge: the off-screen particles do not pile up on the border.
+ *   inside    adds 1 to its cell's count (uint32) and, per velocity component v of s.z, s.w,
+ *             q = (int64) rint(clamp(v, -4, 4) * 2^32), ties to even, to the cell's int64 sum of that component; a non-finite
+ *             v adds nothing, and the particle counts once in `nonfinite_velocity`.
+ *   texel     (float)count, (float)((double)sumx * 2^-32), (float)((double)sumy * 2^-32), count ? 1.0f : 0.0f - every conversion
+ *             to nearest; the alpha of 1 on occupied cells makes the image a blend view (weight c.a * alpha).
+ * Every accumulation is an integer addition: the bits depend on neither the slot order nor the order of arrival - the ring in
+ * texel order, tile-sorted, and run after run give the same image.  The ring buffer is read where it lies (tile-sorted slots
+ * without their perm table, packed texels in place); the call is READ-ONLY towards the context exactly as a measure is:
+ * step(); density(); draw() leaves the bits of step(); draw().  A context that never calls allocates nothing for it (the first
+ * call reserves 20 bytes a cell and a 40-byte info block; the accumulators grow with the largest grid asked).
+ * On a row-band shard the call tallies this context's rows; summing the ranks' grids is the host's.
+ *  th_density        synchronises and fills *out.
+ *  th_density_async  enqueues only (th_stats_async's pattern): *device_info (may be null) receives the address of a
+ *                    th_density_info in device memory owned by the context, valid until the context's next density call.
+ *  `buffer` is an index into the ring, as th_measure_run takes it.
+ *  TH_ERR_INVALID, nothing launched, the destination untouched: a null context, uniforms or `out`; w or h below 1 or
+ *  w * h above 1 << 22; `dest` neither of the two; `slot` outside 0 .. TH_MAX_TEXTURES - 1 (dest = TH_VIEW_TEXTURE); `buffer`
+ *  outside the ring; a viewSize component that is not finite. */
+typedef struct th_density_uniforms {
+    float viewSize[2];     /* as th_logic_uniforms.viewSize */
+    int32_t w, h;          /* the grid: 1 <= w, h and w * h <= 1 << 22 */
+    int32_t dest;          /* TH_VIEW_TEXTURE: caller texture slot `slot`; TH_VIEW_SPAWN_IMAGE: the spawner's image (slot ignored) */
+    int32_t slot;          /* 0 .. TH_MAX_TEXTURES - 1 */
+} th_density_uniforms;     /* 24 bytes */
+typedef struct th_density_info { uint64_t particles, live, inside, outside, nonfinite_velocity; } th_density_info;   /* 40 bytes */
+th_status th_density(th_context *ctx, const th_density_uniforms *u, int32_t buffer, th_density_info *out);
+th_status th_density_async(th_context *ctx, const th_density_uniforms *u, int32_t buffer, void **device_info);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 /* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
  * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */

@@ -115,6 +115,17 @@ class MeasureResult(C.Structure):
                 ("max", C.c_float * 8)]
 
 
+class DensityUniforms(C.Structure):
+    """th_density_uniforms: the view size, the grid and where the image goes (24 bytes)"""
+    _fields_ = [("viewSize", C.c_float * 2), ("w", C.c_int32), ("h", C.c_int32), ("dest", C.c_int32), ("slot", C.c_int32)]
+
+
+class DensityInfo(C.Structure):
+    """th_density_info: what a density call says of the particles it went over (40 bytes)"""
+    _fields_ = [("particles", C.c_uint64), ("live", C.c_uint64), ("inside", C.c_uint64), ("outside", C.c_uint64),
+                ("nonfinite_velocity", C.c_uint64)]
+
+
 class DrawStages(C.Structure):
     """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
     _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
@@ -265,6 +276,8 @@ PROTOTYPES = {
     "th_measure_run": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(MeasureResult)]),
     "th_measure_async": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     "th_measure_global": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(MeasureResult)]),
+    "th_density": (C.c_int32, [_ctx, C.POINTER(DensityUniforms), C.c_int32, C.POINTER(DensityInfo)]),
+    "th_density_async": (C.c_int32, [_ctx, C.POINTER(DensityUniforms), C.c_int32, C.POINTER(C.c_void_p)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
+from .particles import Density
 from .spawn.pixels import ImageBuffer, PixelSpawner
 
 
@@ -88,7 +89,8 @@ class FrameView:
 class Blend:
     """src/screen/blend/index.js: `views` summed into a target, each with its alpha of `alphas`.  A view is an AudioTexture
     (or its .texture), an OpticalFlow frame (optical_flow.frame(k)), or the image spawner's buffer (a PixelSpawner, its
-    .buffer - an ImageBuffer - or .buffer.color[0]).  The only target is a Tendrils' colorMap."""
+    .buffer - an ImageBuffer - or .buffer.color[0]), or a Density (what Particles.density returned: the texture slot or the
+    spawn image it filled; the audio textures of the draw then travel in the other slots).  The only target is a Tendrils' colorMap."""
 
     def __init__(self, gl=None, options=None, views=None, alphas=None, resolution=None):
         params = dict(views=[], alphas=[], resolution=[1, 1])
@@ -119,8 +121,10 @@ class Blend:
             raise ValueError("Blend.draw: 1..%d views (got %d)" % (_capi.MAX_BLEND_VIEWS, n))
         table = (_capi.BlendView * n)()
         slots = []                                # the distinct audio textures of this draw, in order of appearance
+        taken = {v.slot for v in self.views if isinstance(v, Density) and v.into == "texture"}
+        free = [k for k in range(_capi.MAX_TEXTURES) if k not in taken]
         for i, view in enumerate(self.views):
-            found = resolve_view(particles, view, slots)
+            found = resolve_view(particles, view, slots, free)
             if found is None:
                 raise TypeError("Blend.draw: view %d (%r) is no AudioTexture, OpticalFlow frame or image buffer" % (i, view))
             table[i].source, table[i].index = found
@@ -137,6 +141,8 @@ def resolve_view(particles, view, slots, free=range(_capi.MAX_TEXTURES)):
     an OpticalFlow frame, the image spawner's buffer (a PixelSpawner, its .buffer or .buffer.color[0]) - or None for anything
     else.  `slots`: the distinct audio textures of this pass so far, in order of appearance; the k-th of them travels in
     texture slot free[k]."""
+    if isinstance(view, Density):
+        return (_capi.VIEW_TEXTURE, view.slot) if view.into == "texture" else (_capi.VIEW_SPAWN_IMAGE, 0)
     view = getattr(view, "texture", view)
     if isinstance(view, PixelSpawner):
         view = view.buffer

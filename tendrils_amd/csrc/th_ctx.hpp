@@ -13,6 +13,7 @@
 //   th_drawprog.hip draw programs: a caller's vertex stage in one pass of draw() (th_draw_program_compile / th_draw_program_run)
 //   th_stepprog.hip step programs: n steps of a caller's integrator in one launch (th_step_program_compile / th_step_program_run)
 //   th_measure.hip measure programs: a caller's reduction over a ring buffer (th_measure_program_compile / th_measure_run / _async / _global)
+//   th_density.hip the density map: the particles' count and summed velocity on a grid, into a texture slot or the spawn image (th_density / _async)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -357,6 +358,11 @@ struct th_context {
     // th_measure_run / _async / _global (th_measure.hip), reserved by the first measure of the context: a partial per workgroup of
     // the caller's kernel (2048), and the result blocks - this context's | the ranks', gathered | the job's
     DevBuf<th_measure_result> measure_parts, measure_blocks;
+
+    // th_density / _async (th_density.hip), reserved by the first density of the context: the cells' accumulators - 20 bytes a
+    // cell, in 16-byte words, grow-only - and the info block the call leaves (a th_density_info)
+    DevBuf<uint4> density_acc;
+    DevBuf<unsigned long long> density_info;
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
     // (grows and stays, like the flow lines' scratch)

@@ -233,6 +233,28 @@ class Measure:
         return "Measure(taken=%d, particles=%d, sum=%r, min=%r, max=%r)" % (self.taken, self.particles, self.sum, self.min, self.max)
 
 
+class Density:
+    """What Particles.density returns: particles, live, inside, outside, nonfinite_velocity (th_density_info), and where the
+    image lies - read() downloads its h x w x 4 float texels (count, summed velocity x, y, occupied)"""
+
+    def __init__(self, particles, info, w, h, into, slot):
+        for k, _ in _capi.DensityInfo._fields_:
+            setattr(self, k, int(getattr(info, k)))
+        self.shape, self.into, self.slot = (int(w), int(h)), into, int(slot)
+        self._p = particles
+
+    def read(self):
+        out = np.empty((self.shape[1], self.shape[0], 4), np.float32)
+        if self.into == "texture":
+            call("th_texture_download", self._p._ctx, self.slot, out.ctypes.data_as(C.c_void_p))
+        else:
+            call("th_spawn_image_download", self._p._ctx, out.ctypes.data_as(_capi._fp))
+        return out
+
+    def __repr__(self):
+        return "Density(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.DensityInfo._fields_)
+
+
 LOGIC = "logic"
 
 
@@ -494,6 +516,37 @@ class Particles:
         args, _block = self._measure_args(program, uniforms, buffer)      # (the block is copied when the launch is enqueued)
         out = C.c_void_p()
         call("th_measure_async", *args, C.byref(out))
+        return out.value
+
+    def _density_args(self, w, h, view_size, slot, buffer, into):
+        if into not in ("texture", "spawn_image"):
+            raise ValueError("density: into=%r (\"texture\" or \"spawn_image\")" % (into,))
+        u = _capi.DensityUniforms()
+        u.viewSize[0], u.viewSize[1] = float(view_size[0]), float(view_size[1])
+        u.w, u.h, u.slot = int(w), int(h), int(slot)
+        u.dest = _capi.VIEW_TEXTURE if into == "texture" else _capi.VIEW_SPAWN_IMAGE
+        return u, (buffer.index if isinstance(buffer, StateBuffer) else int(buffer))
+
+    def density(self, w, h, view_size, slot=0, buffer=0, into="texture"):
+        """The particles of ring buffer `buffer` counted, and their velocities summed, on a w x h grid over the view
+        (th_density): the image goes into caller texture `slot` (into="texture": a Blend view, a screen program's unit) or
+        becomes the spawner's image (into="spawn_image").  Returns a Density: the five counts, read() for the texels.
+        Read-only towards the ring, as measure()."""
+        u, index = self._density_args(w, h, view_size, slot, buffer, into)
+        info = _capi.DensityInfo()
+        call("th_density", self._ctx, C.byref(u), index, C.byref(info))
+        if into == "texture":
+            self.textures[int(slot)] = None          # (blend.py: whoever uploaded into the slot before no longer holds it)
+        return Density(self, info, w, h, into, slot)
+
+    def density_async(self, w, h, view_size, slot=0, buffer=0, into="texture"):
+        """... enqueued only (th_density_async): the device address the 40-byte th_density_info lands at once the context's
+        stream gets there (sync()), valid until this context's next density"""
+        u, index = self._density_args(w, h, view_size, slot, buffer, into)
+        out = C.c_void_p()
+        call("th_density_async", self._ctx, C.byref(u), index, C.byref(out))
+        if into == "texture":
+            self.textures[int(slot)] = None
         return out.value
 
     @staticmethod

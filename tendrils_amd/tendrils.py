@@ -670,5 +670,12 @@ class Tendrils:
         base = dict(self.state, time=self.timer.time, viewSize=self.viewSize, viewRes=self.viewRes)
         return self.particles.measure(program, Particles.applyUpdate(base, uniforms))
 
+    def density(self, shape=None, slot=0, into="texture"):
+        """The particles' count and summed velocity on a grid over the view (Particles.density of buffers[0]) under the view size
+        step() hands the integrator; shape: (w, h) of the grid, the flow's by default - a cell is then the flow texel the
+        particle taps.  Read-only, as measure()."""
+        w, h = self.flow.shape if shape is None else shape
+        return self.particles.density(w, h, self.viewSize, slot=slot, into=into)
+
 
 default = Tendrils
