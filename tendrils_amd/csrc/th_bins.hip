@@ -689,7 +689,8 @@ struct BinShared {
     TH_D uint32_t *osrc() { return pool; }
     TH_D unsigned long long *skey() { return reinterpret_cast<unsigned long long *>(pool); }     // kCrowdCap keys = 4096 words
     TH_D uint16_t *order() { return reinterpret_cast<uint16_t *>(pool + 2u * kCrowdCap); }         // kCrowdCap indices = 1024 words
-    TH_D uint32_t *hist() { return pool + 2u * kCrowdCap + kCrowdCap; }                             // 1024 buckets
+    TH_D uint32_t *hist() { return pool + 2u * kCrowdCap + kCrowdCap / 2u; }                        // 1024 buckets: the pool's last 1024 words
+    static_assert(2u * kCrowdCap + kCrowdCap / 2u + 1024u <= 3u * kCrowdCap, "skey | order | hist side by side inside the pool");
 };
 
 // all threads: exclusive scan of s.cnt into s.first (first[256] = total); returns the longest run
