@@ -653,6 +653,59 @@ typedef struct th_density_info { uint64_t particles, live, inside, outside, nonf
 th_status th_density(th_context *ctx, const th_density_uniforms *u, int32_t buffer, th_density_info *out);
 th_status th_density_async(th_context *ctx, const th_density_uniforms *u, int32_t buffer, void **device_info);
 
+/* -- select: the particles that match a fixed predicate, as records in texel order, the ring left on the device ----------
+ * A measure says numbers ABOUT the particles, the density map WHERE they are; this says WHICH ones: those inside a rectangle,
+ * the fast ones, a 1 : n thinning - for an overlay, an export, an inspector - without th_download_state's 16 bytes a particle
+ * and without the return to texel order a download of tile-sorted slots costs.  Stream compaction by a built-in pass
+ * (tendrils_amd/csrc/th_select.hip): fixed kernels, no hiprtc, not a program kind.
+ * Per particle, with s its state (of a TH_STATE_F16 ring: what the texel decodes to), in fp32, no contraction; every clause
+ * must hold, a clause whose flag is clear is not evaluated:
+ *   live      !(s.x == -1e6f && s.y == -1e6f).  A particle passes if it is live, or if TH_SELECT_INERT is set.
+ *   box       (TH_SELECT_BOX) s.x >= x0 && s.x < x1 && s.y >= y0 && s.y < y1, compared as floats: half-open, a NaN position fails.
+ *   speed     (TH_SELECT_SPEED) q = (s.z * s.z) + (s.w * s.w); q >= lo && q <= hi: closed, on the SQUARED speed.  A NaN q fails;
+ *             an infinite q passes only under an infinite hi.
+ *   stride    index % stride == phase, `index` the particle's texel in the WHOLE texture as th_measure_pass.index has it (a row
+ *             band adds row0 * width); x and y of a record likewise.
+ *   matched   the particles passing all clauses; live: the live particles of the buffer, whatever the predicate; particles: the
+ *             texels of this context.
+ * The records come in increasing `index`; `state` holds the four floats as decoded, bit for bit what th_download_state of that
+ * buffer gives; reserved = 0.  written = min(matched, capacity), and the records are the FIRST `written` in that order:
+ * truncation is TH_OK, not an error.  Records beyond `written` are unspecified.  Everything that decides is an integer or a
+ * float compare: the result depends on neither the slot order, nor the order of arrival, nor the run.
+ * The ring buffer is read where it lies - tile-sorted slots through their perm table, packed texels in place - twice: once for
+ * the predicate, which leaves a bit per texel, and once, behind a scan of the bits' counts, for the records.  The call is
+ * READ-ONLY towards the context exactly as a measure is: no buffer moves to texel order, nothing rotates, the slot orders, the
+ * geometry a view pass reuses, the draw policy's frame count and the `respawned` counter stay - step(); select(); draw() leaves
+ * the bits of step(); draw().  A context that never selects allocates nothing for it (the first call reserves a bit and a
+ * sixteenth of a byte of counts a texel and a 32-byte info block; the records grow with the largest capacity asked).
+ * On a row-band shard the call selects among this context's rows; a gather over the bands is the host's.
+ *  th_select        out == NULL counts only: no gather pass, written = 0, `capacity` ignored.  Otherwise it synchronises once
+ *                   behind the scan to learn `matched` (as th_flow_deposit sizes its lists), reserves min(matched, capacity)
+ *                   records, gathers them and copies them to `out`.  *info is always filled.
+ *  th_select_async  enqueues only (th_stats_async's pattern): `capacity` is clipped to the context's texels and that many records
+ *                   are reserved in a grow-only buffer of the context; capacity == 0 counts only (*device_records = NULL).
+ *                   *device_records and *device_info (either may be null) receive the addresses of the th_selected records and
+ *                   the th_select_info in device memory owned by the context, valid until the context's next select.
+ *  `buffer` is an index into the ring, as th_measure_run takes it.
+ *  TH_ERR_INVALID, before anything is launched or reserved: a null context or uniforms; a null `info` (th_select); `buffer`
+ *  outside the ring; stride == 0 or phase >= stride; unknown flag bits; reserved != 0; a NaN among the bounds of a clause whose
+ *  flag is set (infinities are allowed); more than 1 << 28 texels. */
+#define TH_SELECT_BOX    1u   /* test position against box */
+#define TH_SELECT_SPEED  2u   /* test squared speed against speed2 */
+#define TH_SELECT_INERT  4u   /* inert particles may match too (default: live only) */
+typedef struct th_select_uniforms {
+    float    box[4];        /* x0, y0, x1, y1 in state coordinates (s.x, s.y): half-open */
+    float    speed2[2];     /* lo, hi of the SQUARED speed: closed */
+    uint32_t stride, phase; /* index % stride == phase; stride >= 1, phase < stride */
+    uint32_t flags, reserved;   /* reserved must be 0 */
+} th_select_uniforms;       /* 40 bytes */
+typedef struct th_selected { float state[4]; uint32_t index, x, y, reserved; } th_selected;   /* 32 bytes, reserved = 0 */
+typedef struct th_select_info { uint64_t particles, live, matched, written; } th_select_info; /* 32 bytes */
+th_status th_select(th_context *ctx, const th_select_uniforms *u, int32_t buffer,
+                    th_selected *out, uint64_t capacity, th_select_info *info);
+th_status th_select_async(th_context *ctx, const th_select_uniforms *u, int32_t buffer, uint64_t capacity,
+                          void **device_records, void **device_info);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 /* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
  * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */

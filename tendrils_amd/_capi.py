@@ -126,6 +126,25 @@ class DensityInfo(C.Structure):
                 ("nonfinite_velocity", C.c_uint64)]
 
 
+SELECT_BOX, SELECT_SPEED, SELECT_INERT = 1, 2, 4           # TH_SELECT_*
+
+
+class SelectUniforms(C.Structure):
+    """th_select_uniforms: the box, the squared speeds, the thinning and which clauses count (40 bytes)"""
+    _fields_ = [("box", C.c_float * 4), ("speed2", C.c_float * 2), ("stride", C.c_uint32), ("phase", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Selected(C.Structure):
+    """th_selected: one matching particle - its state as decoded, its texel in the whole texture (32 bytes)"""
+    _fields_ = [("state", C.c_float * 4), ("index", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SelectInfo(C.Structure):
+    """th_select_info: what a select says of the particles it went over (32 bytes)"""
+    _fields_ = [("particles", C.c_uint64), ("live", C.c_uint64), ("matched", C.c_uint64), ("written", C.c_uint64)]
+
+
 class DrawStages(C.Structure):
     """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
     _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
@@ -278,6 +297,8 @@ PROTOTYPES = {
     "th_measure_global": (C.c_int32, [_ctx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(MeasureResult)]),
     "th_density": (C.c_int32, [_ctx, C.POINTER(DensityUniforms), C.c_int32, C.POINTER(DensityInfo)]),
     "th_density_async": (C.c_int32, [_ctx, C.POINTER(DensityUniforms), C.c_int32, C.POINTER(C.c_void_p)]),
+    "th_select": (C.c_int32, [_ctx, C.POINTER(SelectUniforms), C.c_int32, C.POINTER(Selected), C.c_uint64, C.POINTER(SelectInfo)]),
+    "th_select_async": (C.c_int32, [_ctx, C.POINTER(SelectUniforms), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

@@ -14,6 +14,7 @@
 //   th_stepprog.hip step programs: n steps of a caller's integrator in one launch (th_step_program_compile / th_step_program_run)
 //   th_measure.hip measure programs: a caller's reduction over a ring buffer (th_measure_program_compile / th_measure_run / _async / _global)
 //   th_density.hip the density map: the particles' count and summed velocity on a grid, into a texture slot or the spawn image (th_density / _async)
+//   th_select.hip  select: the particles of a ring buffer that match a fixed predicate, as records in texel order (th_select / _async)
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -363,6 +364,13 @@ struct th_context {
     // cell, in 16-byte words, grow-only - and the info block the call leaves (a th_density_info)
     DevBuf<uint4> density_acc;
     DevBuf<unsigned long long> density_info;
+
+    // th_select / _async (th_select.hip), reserved by the first select of the context: a bit per texel (64-bit words, indexed by
+    // LOCAL TEXEL), the words' popcounts - scanned in place - with the scan's block sums, the info block the call leaves (a
+    // th_select_info), and the records (grow-only: the largest capacity asked)
+    DevBuf<unsigned long long> select_mask, select_info;
+    DevBuf<uint32_t> select_counts, select_sums;
+    DevBuf<th_selected> select_records;
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
     // (grows and stays, like the flow lines' scratch)

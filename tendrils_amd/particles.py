@@ -255,6 +255,28 @@ class Density:
         return "Density(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.DensityInfo._fields_)
 
 
+SELECTED = np.dtype([("state", np.float32, 4), ("index", np.uint32), ("x", np.uint32), ("y", np.uint32), ("reserved", np.uint32)])
+assert SELECTED.itemsize == C.sizeof(_capi.Selected)
+
+
+class Selection:
+    """What Particles.select returns: the matching particles in increasing texel - index, x, y (uint32 arrays, in the whole
+    texture) and state ([written, 4] float32, as decoded) - and particles, live, matched, written (th_select_info)"""
+
+    def __init__(self, info, records):
+        for k, _ in _capi.SelectInfo._fields_:
+            setattr(self, k, int(getattr(info, k)))
+        records = records[:self.written]
+        self.index, self.x, self.y = (np.ascontiguousarray(records[k]) for k in ("index", "x", "y"))
+        self.state = np.ascontiguousarray(records["state"]).reshape(-1, 4)
+
+    def __len__(self):
+        return self.written
+
+    def __repr__(self):
+        return "Selection(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.SelectInfo._fields_)
+
+
 LOGIC = "logic"
 
 
@@ -548,6 +570,46 @@ class Particles:
         if into == "texture":
             self.textures[int(slot)] = None
         return out.value
+
+    @staticmethod
+    def _select_args(box, speed, stride, phase, inert, buffer):
+        u = _capi.SelectUniforms()
+        u.stride, u.phase = int(stride), int(phase)
+        if box is not None:
+            u.flags |= _capi.SELECT_BOX
+            u.box[:] = [float(v) for v in box]
+        if speed is not None:                        # (lo, hi) in speed units: the library compares the SQUARED speed
+            u.flags |= _capi.SELECT_SPEED
+            lo, hi = np.float32(speed[0]), np.float32(speed[1])
+            with np.errstate(over="ignore"):
+                u.speed2[0], u.speed2[1] = float(lo * lo), float(hi * hi)
+        if inert:
+            u.flags |= _capi.SELECT_INERT
+        return u, (buffer.index if isinstance(buffer, StateBuffer) else int(buffer))
+
+    def select(self, box=None, speed=None, stride=1, phase=0, inert=False, buffer=0, capacity=None):
+        """The particles of ring buffer `buffer` that match (th_select): inside box = (x0, y0, x1, y1) (half-open, state
+        coordinates), with a speed in speed = (lo, hi) (closed; each bound squared in float32), whose texel index % stride ==
+        phase; live ones only unless inert.  Returns a Selection, its records in increasing texel: all `matched` of them
+        (capacity=None: counted first, then fetched), or the first min(matched, capacity).  Read-only towards the ring, as
+        measure()."""
+        u, index = self._select_args(box, speed, stride, phase, inert, buffer)
+        info = _capi.SelectInfo()
+        if capacity is None:
+            call("th_select", self._ctx, C.byref(u), index, None, 0, C.byref(info))
+            capacity = int(info.matched)
+        records = np.zeros(max(int(capacity), 1), SELECTED)
+        call("th_select", self._ctx, C.byref(u), index, records.ctypes.data_as(C.POINTER(_capi.Selected)), int(capacity), C.byref(info))
+        return Selection(info, records)
+
+    def select_async(self, capacity, box=None, speed=None, stride=1, phase=0, inert=False, buffer=0):
+        """... enqueued only (th_select_async): the device addresses (records, info) that up to `capacity` 32-byte th_selected
+        records and the 32-byte th_select_info land at once the context's stream gets there (sync()), valid until this
+        context's next select; capacity=0 counts only (records: None)"""
+        u, index = self._select_args(box, speed, stride, phase, inert, buffer)
+        records, info = C.c_void_p(), C.c_void_p()
+        call("th_select_async", self._ctx, C.byref(u), index, int(capacity), C.byref(records), C.byref(info))
+        return records.value, info.value
 
     @staticmethod
     def generateLUT(shape):                          # src/particles.js:171-190

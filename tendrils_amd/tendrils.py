@@ -677,5 +677,10 @@ class Tendrils:
         w, h = self.flow.shape if shape is None else shape
         return self.particles.density(w, h, self.viewSize, slot=slot, into=into)
 
+    def select(self, **kw):
+        """The particles that match a box, a band of speeds, a thinning (Particles.select, its arguments; buffers[0] by
+        default): a Selection, its records in texel order.  Read-only, as measure()."""
+        return self.particles.select(**kw)
+
 
 default = Tendrils
