@@ -706,6 +706,66 @@ th_status th_select(th_context *ctx, const th_select_uniforms *u, int32_t buffer
 th_status th_select_async(th_context *ctx, const th_select_uniforms *u, int32_t buffer, uint64_t capacity,
                           void **device_records, void **device_info);
 
+/* -- histogram: how one scalar of the state is DISTRIBUTED over the matching particles, the ring left on the device -----
+ * A measure says numbers ABOUT the particles, the density map WHERE they are, select WHICH ones; this says how a quantity is
+ * spread: the count of the particles that pass a select predicate, per bin of one scalar - and, through the key mode, the
+ * exact k-th order statistic by radix select (three passes of 11, 11 and 10 key bits: Particles.quantiles).  A built-in pass
+ * (tendrils_amd/csrc/th_histogram.hip): fixed kernels, no hiprtc, not a program kind.
+ * Per particle, with s its state (of a TH_STATE_F16 ring: what th_packed.inc decodes), in fp32, no contraction:
+ *   particles, live, matched   exactly th_select_info's: `matched` counts the particles passing `select`'s clauses.
+ *   v         the channel's value of a matched particle: TH_HIST_X s.x, _Y s.y, _VX s.z, _VY s.w, _SPEED2
+ *             q = (s.z * s.z) + (s.w * s.w), _SPEED __builtin_sqrtf(q), the correctly rounded root.
+ *   nan       v is NaN: nan += 1 and no bin is touched.
+ *  TH_HIST_LINEAR  scale = (float)bins / (hi - lo), computed once on the host in fp32.  v < lo goes to `below`, v >= hi to
+ *             `above` - float compares, so -inf and +inf fall there.  Otherwise b = (int)floorf((v - lo) * scale) and the bin
+ *             is min(b, bins - 1): the min is live code - the last float below hi can give b == bins (lo = -1, hi = 1,
+ *             bins = 4096).  A subtract followed by a multiply: nothing can be contracted.
+ *  TH_HIST_KEY     u is the bits of v, key = (u >> 31) ? ~u : (u | 0x80000000u): the order of the keys is the order of the
+ *             floats, with -0.0 just below +0.0.  d = log2(bins), top = key_shift + d (at most 32); compared in 64 bits,
+ *             ((uint64)key >> top) < ((uint64)key_prefix >> top) goes to `below`, > to `above`, equal to bin
+ *             (key >> key_shift) & (bins - 1).  A value counted in `nan` takes no part in any order statistic.
+ * Always below + sum(counts) + above + nan == matched.  Every accumulation is an integer addition: the bits depend on
+ * neither the slot order, nor the order of arrival, nor the run.
+ * The ring buffer is read where it lies - tile-sorted slots (their perm table only when the stride clause needs the index: a
+ * bin does not depend on who the particle is), packed texels in place - once.  The call is READ-ONLY towards the context
+ * exactly as a select is: no buffer moves to texel order, nothing rotates, the slot orders, the geometry a view pass reuses,
+ * the draw policy's frame count and the `respawned` counter stay - step(); histogram(); draw() leaves the bits of step();
+ * draw().  A context that never calls allocates nothing for it (the first call reserves 4096 counts and a 48-byte info block).
+ * On a row-band shard the call counts this context's rows (the stride clause sees whole-texture indices, as in select);
+ * summing the ranks' counts is the host's.
+ *  th_histogram        synchronises once and copies `bins` words to `counts` and the info block to *info; counts == NULL: the
+ *                      info alone.
+ *  th_histogram_async  enqueues only (th_stats_async's pattern): *device_counts and *device_info (either may be null) receive
+ *                      the addresses of the `bins` uint32 counts and the th_histogram_info in device memory owned by the
+ *                      context, valid until the context's next histogram call.
+ *  `buffer` is an index into the ring, as th_measure_run takes it.
+ *  TH_ERR_INVALID, nothing launched, `counts` untouched: a null context, uniforms or `info` (th_histogram); anything th_select
+ *  refuses about `select`; a channel or mode outside the lists; bins == 0 or bins > 4096; TH_HIST_LINEAR: a NaN or infinite
+ *  lo or hi, lo >= hi, an infinite hi - lo or scale; TH_HIST_KEY: bins not a power of two, key_shift + d > 32;
+ *  reserved != 0; more than 1 << 28 texels. */
+#define TH_HIST_X 0      /* s.x */
+#define TH_HIST_Y 1      /* s.y */
+#define TH_HIST_VX 2     /* s.z */
+#define TH_HIST_VY 3     /* s.w */
+#define TH_HIST_SPEED2 4 /* q = (s.z * s.z) + (s.w * s.w) */
+#define TH_HIST_SPEED 5  /* __builtin_sqrtf(q): the correctly rounded root the exact kernels already rely on */
+#define TH_HIST_LINEAR 0
+#define TH_HIST_KEY 1
+#define TH_HIST_MAX_BINS 4096
+typedef struct th_histogram_uniforms {
+    th_select_uniforms select;   /* WHICH particles: th_select's clauses, its semantics and its checks, unchanged */
+    int32_t  channel, mode;
+    uint32_t bins;               /* 1 .. 4096; TH_HIST_KEY: a power of two */
+    float    lo, hi;             /* TH_HIST_LINEAR */
+    uint32_t key_prefix, key_shift; /* TH_HIST_KEY */
+    uint32_t reserved;           /* 0 */
+} th_histogram_uniforms;         /* 72 bytes */
+typedef struct th_histogram_info { uint64_t particles, live, matched, below, above, nan; } th_histogram_info;  /* 48 bytes */
+th_status th_histogram(th_context *ctx, const th_histogram_uniforms *u, int32_t buffer, uint32_t *counts /* [bins] */,
+                       th_histogram_info *info);
+th_status th_histogram_async(th_context *ctx, const th_histogram_uniforms *u, int32_t buffer, void **device_counts,
+                             void **device_info);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 /* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
  * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */

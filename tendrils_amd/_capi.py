@@ -145,6 +145,23 @@ class SelectInfo(C.Structure):
     _fields_ = [("particles", C.c_uint64), ("live", C.c_uint64), ("matched", C.c_uint64), ("written", C.c_uint64)]
 
 
+HIST_X, HIST_Y, HIST_VX, HIST_VY, HIST_SPEED2, HIST_SPEED = range(6)      # TH_HIST_*: the channel
+HIST_LINEAR, HIST_KEY = 0, 1                               # ... the mode
+HIST_MAX_BINS = 4096
+
+
+class HistogramUniforms(C.Structure):
+    """th_histogram_uniforms: which particles (a th_select_uniforms), which scalar, how it is binned (72 bytes)"""
+    _fields_ = [("select", SelectUniforms), ("channel", C.c_int32), ("mode", C.c_int32), ("bins", C.c_uint32),
+                ("lo", C.c_float), ("hi", C.c_float), ("key_prefix", C.c_uint32), ("key_shift", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HistogramInfo(C.Structure):
+    """th_histogram_info: what a histogram says of the particles it went over (48 bytes)"""
+    _fields_ = [("particles", C.c_uint64), ("live", C.c_uint64), ("matched", C.c_uint64), ("below", C.c_uint64),
+                ("above", C.c_uint64), ("nan", C.c_uint64)]
+
+
 class DrawStages(C.Structure):
     """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
     _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
@@ -299,6 +316,8 @@ PROTOTYPES = {
     "th_density_async": (C.c_int32, [_ctx, C.POINTER(DensityUniforms), C.c_int32, C.POINTER(C.c_void_p)]),
     "th_select": (C.c_int32, [_ctx, C.POINTER(SelectUniforms), C.c_int32, C.POINTER(Selected), C.c_uint64, C.POINTER(SelectInfo)]),
     "th_select_async": (C.c_int32, [_ctx, C.POINTER(SelectUniforms), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "th_histogram": (C.c_int32, [_ctx, C.POINTER(HistogramUniforms), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(HistogramInfo)]),
+    "th_histogram_async": (C.c_int32, [_ctx, C.POINTER(HistogramUniforms), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

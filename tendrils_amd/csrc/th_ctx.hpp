@@ -15,6 +15,8 @@
 //   th_measure.hip measure programs: a caller's reduction over a ring buffer (th_measure_program_compile / th_measure_run / _async / _global)
 //   th_density.hip the density map: the particles' count and summed velocity on a grid, into a texture slot or the spawn image (th_density / _async)
 //   th_select.hip  select: the particles of a ring buffer that match a fixed predicate, as records in texel order (th_select / _async)
+//   th_histogram.hip the histogram: the matching particles counted per bin of one scalar of the state (th_histogram / _async);
+//                  th_select_match.hpp is what the two units share - the slot loader, the predicate, the checks of its block
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -371,6 +373,11 @@ struct th_context {
     DevBuf<unsigned long long> select_mask, select_info;
     DevBuf<uint32_t> select_counts, select_sums;
     DevBuf<th_selected> select_records;
+
+    // th_histogram / _async (th_histogram.hip), reserved by the first histogram of the context: TH_HIST_MAX_BINS counts and the
+    // info block the call leaves (a th_histogram_info)
+    DevBuf<uint32_t> hist_counts;
+    DevBuf<unsigned long long> hist_info;
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
     // (grows and stays, like the flow lines' scratch)

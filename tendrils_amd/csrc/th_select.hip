@@ -21,18 +21,12 @@
 // whatever slot holds it.  The price is the second walk over the slots (and, tile-sorted, the atomics).
 // No lane leaves the mark kernel before its wave-wide operations: the loop's bound is the workgroup's, a lane past the last
 // slot carries "no match, not live".  Every index that addresses memory comes from a value compared in range first.
-#include "th_ctx.hpp"
-#include "th_logic.hpp"          // th::unpack_state (th_packed.inc)
+#include "th_select_match.hpp"   // Slot, SelectClauses, select_match, select_checks: shared with th_histogram.hip
 
 using namespace thi;
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kSelectFlags = TH_SELECT_BOX | TH_SELECT_SPEED | TH_SELECT_INERT;
 constexpr int kInfoWords = 4;             // th_select_info
 enum { kParticles, kLive, kMatched, kWritten };
 static_assert(sizeof(th_select_uniforms) == 40 && sizeof(th_selected) == 32 && sizeof(th_select_info) == kInfoWords * 8, "th_select_*: the header's layout");
@@ -43,8 +37,7 @@ struct SelectParams {
     const uint32_t *perm;             // slot -> local texel (tile-sorted slots), or null: texel order
     uint32_t count, width, row0;      // this context's texels; the texture's width; the band's first row
     uint32_t nwords;                  // mask words: (count + 63) / 64
-    float x0, y0, x1, y1, lo, hi;
-    uint32_t stride, phase, flags;
+    SelectClauses q;                  // the predicate's clauses
     uint32_t capacity;                // records the gather may write
     unsigned long long *mask;         // [nwords]: bit t & 63 of word t >> 6 is local texel t
     uint32_t *counts;                 // [nwords]: the words' popcounts, then (scanned in place) the matches before each word
@@ -52,33 +45,7 @@ struct SelectParams {
     th_selected *records;
 };
 
-// a slot as it lies in memory - 16 bytes, or the 8 of a packed ring - and the state it holds
-template <bool PACKED> struct Slot;
-template <> struct Slot<false> {
-    using Raw = v4f;
-    TH_D static Raw load(const void *in, uint32_t idx) { return __builtin_nontemporal_load(static_cast<const Raw *>(in) + idx); }
-    TH_D static v4f state(Raw t) { return t; }
-};
-template <> struct Slot<true> {
-    using Raw = v2u;
-    TH_D static Raw load(const void *in, uint32_t idx) { return __builtin_nontemporal_load(static_cast<const Raw *>(in) + idx); }
-    TH_D static v4f state(Raw t) { const float4 s = th::unpack_state(make_uint2(t.x, t.y)); return v4f{s.x, s.y, s.z, s.w}; }
-};
-
 TH_D uint32_t wave_sum(uint32_t v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
-
-// the clauses of the header, in its words: local texel t of a live-or-admitted particle with state s
-TH_D bool select_match(const SelectParams &p, v4f s, bool live, uint32_t t)
-{
-    bool m = live || (p.flags & TH_SELECT_INERT);
-    if (p.flags & TH_SELECT_BOX) m = m && s.x >= p.x0 && s.x < p.x1 && s.y >= p.y0 && s.y < p.y1;      // (a NaN position fails)
-    if (p.flags & TH_SELECT_SPEED) {
-        const float q = (s.z * s.z) + (s.w * s.w);
-        m = m && q >= p.lo && q <= p.hi;                        // (a NaN q fails)
-    }
-    if (p.stride > 1u) m = m && (t + p.row0 * p.width) % p.stride == p.phase;
-    return m;
-}
 
 // {0, 0, 0, 0} into the info block and, over tile-sorted slots, zero into the mask
 __global__ __launch_bounds__(256) void select_clear_kernel(unsigned long long *mask, uint32_t nwords, unsigned long long *info)
@@ -102,8 +69,8 @@ __global__ __launch_bounds__(256) void select_mark_kernel(const SelectParams p)
         if (idx < p.count) {
             const v4f s = Slot<PACKED>::state(Slot<PACKED>::load(p.in, idx));
             if (p.perm) t = __builtin_nontemporal_load(p.perm + idx);          // (wave-uniform test: the argument segment)
-            live = !(s.x == th::kInert && s.y == th::kInert);
-            match = t < p.count && select_match(p, s, live, t);
+            live = slot_live(s);
+            match = t < p.count && select_match(p.q, s, live, t);
         }
         live_n += live ? 1u : 0u;
         if (!p.perm) {
@@ -157,21 +124,6 @@ __global__ __launch_bounds__(256) void select_gather_kernel(const SelectParams p
     }
 }
 
-th_status select_checks(th_context *c, const th_select_uniforms *u, int32_t buffer, const char *entry)
-{
-    TH_REQUIRE(c, "%s: null context", entry);
-    TH_REQUIRE(u, "%s: null uniforms", entry);
-    TH_REQUIRE(buffer >= 0 && (size_t)buffer < c->ring.size(), "%s: buffer %d out of range (the ring has %zu)", entry, buffer, c->ring.size());
-    TH_REQUIRE(u->stride >= 1u && u->phase < u->stride, "%s: stride %u, phase %u (stride >= 1, phase < stride)", entry, u->stride, u->phase);
-    TH_REQUIRE(!(u->flags & ~kSelectFlags), "%s: flags 0x%x (TH_SELECT_BOX | _SPEED | _INERT)", entry, u->flags);
-    TH_REQUIRE(u->reserved == 0u, "%s: reserved is %u, not 0", entry, u->reserved);
-    if (u->flags & TH_SELECT_BOX)
-        TH_REQUIRE(!(std::isnan(u->box[0]) || std::isnan(u->box[1]) || std::isnan(u->box[2]) || std::isnan(u->box[3])), "%s: a NaN in the box", entry);
-    if (u->flags & TH_SELECT_SPEED) TH_REQUIRE(!(std::isnan(u->speed2[0]) || std::isnan(u->speed2[1])), "%s: a NaN in speed2", entry);
-    TH_REQUIRE(c->texels() > 0 && c->texels() <= (1ull << 28), "%s: %zu particles", entry, c->texels());
-    return TH_OK;
-}
-
 // the context's scratch, reserved by its first select (the texture's shape is the context's: only the records ever grow)
 th_status select_storage(th_context *c, uint32_t nwords)
 {
@@ -200,9 +152,7 @@ SelectParams select_params(th_context *c, const th_select_uniforms *u, int32_t b
     p.perm = order >= 0 ? c->orders[(size_t)order].perm.get() : nullptr;
     p.count = (uint32_t)c->texels(); p.width = (uint32_t)c->cfg.width; p.row0 = (uint32_t)c->cfg.row0;
     p.nwords = (p.count + 63u) / 64u;
-    p.x0 = u->box[0]; p.y0 = u->box[1]; p.x1 = u->box[2]; p.y1 = u->box[3];
-    p.lo = u->speed2[0]; p.hi = u->speed2[1];
-    p.stride = u->stride; p.phase = u->phase; p.flags = u->flags;
+    p.q = select_clauses(c, u);
     p.capacity = capacity;
     p.mask = c->select_mask; p.counts = c->select_counts; p.info = c->select_info;
     p.records = c->select_records;

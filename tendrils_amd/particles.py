@@ -277,6 +277,37 @@ class Selection:
         return "Selection(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.SelectInfo._fields_)
 
 
+HIST_CHANNELS = dict(x=_capi.HIST_X, y=_capi.HIST_Y, vx=_capi.HIST_VX, vy=_capi.HIST_VY, speed2=_capi.HIST_SPEED2, speed=_capi.HIST_SPEED)
+QUANTILE_PASSES = ((2048, 21), (2048, 10), (1024, 0))      # (bins, key_shift): 11, 11 and 10 bits of the key, from the top
+
+
+class Histogram:
+    """What Particles.histogram returns: counts (uint32, one per bin), edges (bins + 1 float64 values, for plotting only: the
+    library bins in float32 by its own expression), and below, above, nan, matched, live, particles (th_histogram_info):
+    below + counts.sum() + above + nan == matched"""
+
+    def __init__(self, info, counts, lo, hi):
+        for k, _ in _capi.HistogramInfo._fields_:
+            setattr(self, k, int(getattr(info, k)))
+        self.counts = counts
+        self.edges = np.linspace(float(lo), float(hi), len(counts) + 1)
+
+    def __repr__(self):
+        return "Histogram(bins=%d, %s)" % (len(self.counts), ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.HistogramInfo._fields_))
+
+
+def float_key(values):
+    """the monotone integer key of float32 values (th_histogram's TH_HIST_KEY): its order is the floats', -0.0 just below +0.0"""
+    u = np.ascontiguousarray(values, np.float32).view(np.uint32)
+    return np.where(u >> 31, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def key_float(key):
+    """... and the float32 a key stands for"""
+    key = np.asarray(key, np.uint32)
+    return np.where(key >> 31, key ^ np.uint32(0x80000000), ~key).astype(np.uint32).view(np.float32)
+
+
 LOGIC = "logic"
 
 
@@ -610,6 +641,80 @@ class Particles:
         records, info = C.c_void_p(), C.c_void_p()
         call("th_select_async", self._ctx, C.byref(u), index, int(capacity), C.byref(records), C.byref(info))
         return records.value, info.value
+
+    def _histogram_args(self, channel, mode, bins, clauses):
+        if isinstance(channel, str):
+            if channel not in HIST_CHANNELS:
+                raise ValueError("histogram: channel %r (one of %s)" % (channel, ", ".join(HIST_CHANNELS)))
+            channel = HIST_CHANNELS[channel]
+        buffer = clauses.pop("buffer", 0)
+        unknown = set(clauses) - {"box", "speed", "stride", "phase", "inert"}
+        if unknown:
+            raise TypeError("histogram: unexpected clause(s) %s" % ", ".join(sorted(unknown)))
+        select, index = self._select_args(clauses.get("box"), clauses.get("speed"), clauses.get("stride", 1), clauses.get("phase", 0),
+                                          clauses.get("inert", False), buffer)
+        u = _capi.HistogramUniforms()
+        u.select = select
+        u.channel, u.mode, u.bins = int(channel), int(mode), int(bins)
+        return u, index
+
+    def histogram(self, channel, bins, range, box=None, speed=None, stride=1, phase=0, inert=False, buffer=0):
+        """How one scalar of the state is distributed (th_histogram): the particles of ring buffer `buffer` that match select()'s
+        clauses, counted per bin of `channel` - "x", "y", "vx", "vy", "speed2", "speed" or a TH_HIST_* number - over `bins`
+        (1 .. 4096) equal bins of range = (lo, hi), lo inclusive, hi exclusive, binned in float32.  Returns a Histogram.
+        Read-only towards the ring, as select()."""
+        u, index = self._histogram_args(channel, _capi.HIST_LINEAR, bins, dict(box=box, speed=speed, stride=stride, phase=phase, inert=inert, buffer=buffer))
+        u.lo, u.hi = float(range[0]), float(range[1])
+        counts, info = np.zeros(max(int(bins), 0), np.uint32), _capi.HistogramInfo()
+        call("th_histogram", self._ctx, C.byref(u), index, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info))
+        return Histogram(info, counts, u.lo, u.hi)
+
+    def histogram_async(self, channel, bins, range, box=None, speed=None, stride=1, phase=0, inert=False, buffer=0):
+        """... enqueued only (th_histogram_async): the device addresses (counts, info) that the `bins` uint32 counts and the
+        48-byte th_histogram_info land at once the context's stream gets there (sync()), valid until this context's next
+        histogram"""
+        u, index = self._histogram_args(channel, _capi.HIST_LINEAR, bins, dict(box=box, speed=speed, stride=stride, phase=phase, inert=inert, buffer=buffer))
+        u.lo, u.hi = float(range[0]), float(range[1])
+        counts, info = C.c_void_p(), C.c_void_p()
+        call("th_histogram_async", self._ctx, C.byref(u), index, C.byref(counts), C.byref(info))
+        return counts.value, info.value
+
+    def _key_pass(self, channel, bins, shift, prefix, clauses):
+        """one TH_HIST_KEY pass: (the counts as int64, th_histogram_info)"""
+        u, index = self._histogram_args(channel, _capi.HIST_KEY, bins, dict(clauses))
+        u.key_prefix, u.key_shift = int(prefix), int(shift)
+        counts, info = np.zeros(bins, np.uint32), _capi.HistogramInfo()
+        call("th_histogram", self._ctx, C.byref(u), index, counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info))
+        return counts.astype(np.int64), info
+
+    def quantiles(self, channel, q, **clauses):
+        """Exact order statistics of `channel` over the particles that match (select()'s clauses, `buffer` among them): for each
+        q in [0, 1] the element of rank k = min(floor(q * n), n - 1) of the n = matched - nan values in ascending order (-0.0
+        below +0.0), as float32 - bit for bit what sorting them gives.  Radix select over the monotone key of the float: three
+        TH_HIST_KEY passes of 11, 11 and 10 bits, the prefix narrowed from `below` and the cumulative counts; ranks whose
+        prefixes coincide share their passes.  q a float: a float32, a sequence: a float32 array; None when n == 0."""
+        scalar = np.ndim(q) == 0
+        qs = [float(v) for v in np.atleast_1d(q)]
+        if not all(0.0 <= v <= 1.0 for v in qs):
+            raise ValueError("quantiles: q outside [0, 1]")
+        (bins, shift), rest = QUANTILE_PASSES[0], QUANTILE_PASSES[1:]
+        counts, info = self._key_pass(channel, bins, shift, 0, clauses)
+        n = int(info.matched) - int(info.nan)
+        if n <= 0:
+            return None
+        ranks = [min(int(np.floor(v * n)), n - 1) for v in qs]
+        # (the first pass has no prefix: nothing is below it)
+        reached = int(info.below) + np.cumsum(counts)
+        prefixes = {k: int(np.searchsorted(reached, k, side="right")) << shift for k in set(ranks)}
+        for bins, shift in rest:
+            passes = {}
+            for k, prefix in prefixes.items():
+                if prefix not in passes:
+                    counts, info = self._key_pass(channel, bins, shift, prefix, clauses)
+                    passes[prefix] = int(info.below) + np.cumsum(counts)
+                prefixes[k] = prefix | (int(np.searchsorted(passes[prefix], k, side="right")) << shift)
+        out = key_float(np.array([prefixes[k] for k in ranks], np.uint32))
+        return out[0] if scalar else out
 
     @staticmethod
     def generateLUT(shape):                          # src/particles.js:171-190

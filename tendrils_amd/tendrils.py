@@ -682,5 +682,15 @@ class Tendrils:
         default): a Selection, its records in texel order.  Read-only, as measure()."""
         return self.particles.select(**kw)
 
+    def histogram(self, channel, bins, range, **kw):
+        """How a scalar of the state is distributed over the matching particles (Particles.histogram, its arguments;
+        buffers[0] by default): a Histogram.  Read-only, as select()."""
+        return self.particles.histogram(channel, bins, range, **kw)
+
+    def quantiles(self, channel, q, **kw):
+        """Exact order statistics of a scalar of the state over the matching particles (Particles.quantiles, its arguments):
+        the median speed, the 95th percentile to normalise a ramp to.  Read-only, as select()."""
+        return self.particles.quantiles(channel, q, **kw)
+
 
 default = Tendrils
