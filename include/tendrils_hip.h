@@ -766,6 +766,64 @@ th_status th_histogram(th_context *ctx, const th_histogram_uniforms *u, int32_t 
 th_status th_histogram_async(th_context *ctx, const th_histogram_uniforms *u, int32_t buffer, void **device_counts,
                              void **device_info);
 
+/* -- follow: the paths of a chosen set of particles, sample by sample, in a history kept on the device -------------------
+ * A measure says numbers ABOUT the particles, the density map WHERE they are, select WHICH ones, the histogram how a quantity
+ * is spread - each of one instant.  This says OVER TIME: the states of the SAME particles from sample to sample, for an
+ * inspector, a plotter export, a trail overlay of a few thousand picked particles - a set a predicate no longer describes
+ * (a box at time t0) can be asked for again by its indices alone.  A built-in pass (tendrils_amd/csrc/th_follow.hip): fixed
+ * kernels, no hiprtc, not a program kind.
+ *   the set     `indices` are texel indices in the WHOLE texture, as th_selected.index has them (a row band adds row0 * width),
+ *               strictly increasing, each inside this context's rows.  1 <= n <= 1 << 20, 1 <= depth <= 1 << 16,
+ *               n * depth <= 1 << 24: the history is 16 bytes a particle and sample, 256 MiB at most.  n == 0 (`indices` may
+ *               then be null) ends following and releases the history.  A new set replaces the old one; samples, held and
+ *               locates start at 0.  One set per context.  A context that never follows allocates nothing for it.
+ *   a sample    for every followed index, in set order, the four floats of that particle in ring buffer `buffer` go into row
+ *               samples % depth of the history, and `samples` grows by one.  The floats are AS DECODED: bit for bit what
+ *               th_download_state of that buffer gives at that texel - inert particles, NaNs and signed zeros included; of a
+ *               TH_STATE_F16 ring what th_packed.inc decodes.  Only integer arithmetic and copies: the result depends on
+ *               neither the slot order nor the run.  `time` is the caller's and is kept on the host.
+ *   the slots   a buffer in texel order holds texel t in slot t.  For a buffer in tile-sorted slots the call keeps a table of
+ *               the slots of the followed texels ONLY, found by one walk over the order's perm table - no state is loaded -
+ *               when, and only when, the sampled buffer's slot order is another than the one the table was built for
+ *               (`locates` counts these walks); a sample itself costs n gathered texels, not a walk over the ring.
+ * Nothing samples by itself: th_step, th_step_n and th_draw behave exactly as before.  th_step_n(20) followed by
+ * th_follow_sample records the state after the 20th step - the states between are not seen.
+ * The calls are READ-ONLY towards the context exactly as a select is: no buffer moves to texel order, nothing rotates, the
+ * slot orders, the geometry a view pass reuses, the draw policy's frame count and the `respawned` counter stay - step();
+ * sample(); draw() leaves the bits of step(); draw().  Select's scratch is not touched: its device addresses stay valid.
+ * On a row-band shard a context follows particles of its own rows; a gather over the bands is the host's.
+ *  th_follow_set     synchronises (the set's indices are uploaded, an earlier history may still be written).
+ *  th_follow_sample  enqueues only (th_stats_async's pattern).  `buffer` is an index into the ring, as th_measure_run takes it.
+ *  th_follow_read    synchronises and copies samples [first, first + count), oldest first, sample-major ([count][n][4]
+ *                    floats; at most two device copies where the history wraps), the callers' times to `times` (may be null)
+ *                    and fills *info.  The range must lie inside [samples - held, samples); count == 0 with null `states` is
+ *                    the info alone.
+ *  th_follow_query   never launches anything: *info (may be null) from host state, *device_history (may be null) the address
+ *                    of the history - float4[depth][n], row k % depth holding sample k - and *device_slots (may be null) that
+ *                    of the current slot table (uint32[n], in set order; null while none has been built: no sample of this set
+ *                    has read tile-sorted slots yet), both valid until the next th_follow_set.
+ *  TH_ERR_INVALID, named by the entry point, before anything is launched, reserved or changed - a refused th_follow_set
+ *  leaves the previous set followed: a null context; null `indices` with n > 0; n, depth or n * depth outside the limits; an
+ *  index that is not above its predecessor or lies outside this context's rows (its position is named); `buffer` outside the
+ *  ring; a sample or a read without a set; a read range outside what is held; null `states` with count > 0; a null `info`
+ *  (th_follow_read); more than 1 << 28 texels. */
+#define TH_FOLLOW_MAX_PARTICLES (1u << 20)
+#define TH_FOLLOW_MAX_DEPTH     (1u << 16)
+#define TH_FOLLOW_MAX_ENTRIES   (1u << 24)   /* n * depth */
+typedef struct th_follow_info {
+    uint64_t particles;   /* texels of this context */
+    uint64_t followed;    /* n of the current set (0: none) */
+    uint64_t depth;       /* samples the history holds */
+    uint64_t samples;     /* samples taken since th_follow_set */
+    uint64_t held;        /* min(samples, depth): samples [samples - held, samples) can be read */
+    uint64_t locates;     /* times the slot table was rebuilt since th_follow_set */
+} th_follow_info;         /* 48 bytes */
+th_status th_follow_set(th_context *ctx, const uint32_t *indices, uint64_t n, uint32_t depth);
+th_status th_follow_sample(th_context *ctx, int32_t buffer, double time);
+th_status th_follow_read(th_context *ctx, uint64_t first, uint64_t count, float *states /* [count][n][4] */,
+                         double *times /* [count], may be null */, th_follow_info *info);
+th_status th_follow_query(th_context *ctx, th_follow_info *info, void **device_history, void **device_slots);
+
 /* -- optical flow producer: OpticalFlow (src/optical-flow/index.js:32-71) ---- */
 /* The frames are RGBA8 images, tapped with a 16-bit fixed-point coordinate: 1..65536 texels a side and fewer than 2^28
  * texels in all.  Any other shape: TH_ERR_INVALID, and the frames the context has (or has not) stay as they are. */

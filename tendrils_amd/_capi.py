@@ -162,6 +162,15 @@ class HistogramInfo(C.Structure):
                 ("above", C.c_uint64), ("nan", C.c_uint64)]
 
 
+FOLLOW_MAX_PARTICLES, FOLLOW_MAX_DEPTH, FOLLOW_MAX_ENTRIES = 1 << 20, 1 << 16, 1 << 24      # TH_FOLLOW_MAX_*
+
+
+class FollowInfo(C.Structure):
+    """th_follow_info: the followed set, its history and how often its slots were found again (48 bytes)"""
+    _fields_ = [("particles", C.c_uint64), ("followed", C.c_uint64), ("depth", C.c_uint64), ("samples", C.c_uint64),
+                ("held", C.c_uint64), ("locates", C.c_uint64)]
+
+
 class DrawStages(C.Structure):
     """th_draw_stages: a draw program or None (the library's vertex stage, with `builtin` its uniforms), a fragment program or None"""
     _fields_ = [("vertex", C.c_void_p), ("vertex_uniforms", C.c_void_p), ("vertex_uniform_bytes", C.c_uint32),
@@ -318,6 +327,10 @@ PROTOTYPES = {
     "th_select_async": (C.c_int32, [_ctx, C.POINTER(SelectUniforms), C.c_int32, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "th_histogram": (C.c_int32, [_ctx, C.POINTER(HistogramUniforms), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(HistogramInfo)]),
     "th_histogram_async": (C.c_int32, [_ctx, C.POINTER(HistogramUniforms), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "th_follow_set": (C.c_int32, [_ctx, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32]),
+    "th_follow_sample": (C.c_int32, [_ctx, C.c_int32, C.c_double]),
+    "th_follow_read": (C.c_int32, [_ctx, C.c_uint64, C.c_uint64, _fp, C.POINTER(C.c_double), C.POINTER(FollowInfo)]),
+    "th_follow_query": (C.c_int32, [_ctx, C.POINTER(FollowInfo), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "th_flow_line_attributes": (C.c_int32, [_fp, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                             _fp, _fp, _fp, _fp, _fp, _fp]),
     "th_flow_lines": (C.c_int32, [_ctx, C.POINTER(FlowLineUniforms), _fp, C.POINTER(C.c_double), C.POINTER(C.c_int32),

@@ -17,6 +17,8 @@
 //   th_select.hip  select: the particles of a ring buffer that match a fixed predicate, as records in texel order (th_select / _async)
 //   th_histogram.hip the histogram: the matching particles counted per bin of one scalar of the state (th_histogram / _async);
 //                  th_select_match.hpp is what the two units share - the slot loader, the predicate, the checks of its block
+//   th_follow.hip  follow: the states of a chosen set of particles, sample by sample, in a history kept on the device
+//                  (th_follow_set / _sample / _read / _query); the slots of the set in a tile-sorted order, found when the order changes
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -378,6 +380,21 @@ struct th_context {
     // info block the call leaves (a th_histogram_info)
     DevBuf<uint32_t> hist_counts;
     DevBuf<unsigned long long> hist_info;
+
+    // th_follow_set / _sample / _read / _query (th_follow.hip), reserved by the first th_follow_set of the context: the set as a
+    // bit per LOCAL TEXEL (64-bit words) with the set's members before each word - scanned in place, the scan's block sums
+    // beside them - and as its local texels in set order; the slot of every member in the order `follow.order` / `.stamp`
+    // names (-1: texel order, where the texel is the slot; -2: nothing yet); the history, float4[depth][n], row k % depth
+    // holding sample k; the callers' times of the samples, by the same row
+    DevBuf<unsigned long long> follow_mask;
+    DevBuf<uint32_t> follow_counts, follow_sums, follow_set, follow_slots;
+    DevBuf<float4> follow_history;
+    struct {
+        uint64_t n = 0, depth = 0, samples = 0, locates = 0;
+        int order = -2;
+        unsigned long long stamp = 0;
+        std::vector<double> times;
+    } follow;
 
     // th_draw_program_run: what the caller's vertex stage leaves for the pass - two float4 per stream vertex, 64 B per particle
     // (grows and stays, like the flow lines' scratch)

@@ -308,6 +308,89 @@ def key_float(key):
     return np.where(key >> 31, key ^ np.uint32(0x80000000), ~key).astype(np.uint32).view(np.float32)
 
 
+class FollowCounts:
+    """th_follow_info as plain integers: particles, followed, depth, samples, held, locates"""
+
+    def __init__(self, info):
+        for k, _ in _capi.FollowInfo._fields_:
+            setattr(self, k, int(getattr(info, k)))
+
+    def __repr__(self):
+        return "FollowCounts(%s)" % ", ".join("%s=%d" % (k, getattr(self, k)) for k, _ in _capi.FollowInfo._fields_)
+
+
+class Follow:
+    """What Particles.follow returns: a set of particles - `index`, their texels in the whole texture, strictly increasing - whose
+    states sample() appends to a history of `depth` samples kept on the device, and paths() reads back.  Nothing samples by
+    itself: step_n(20); sample() records the state after the 20th step.  One set per Particles: a later follow() that succeeds
+    replaces this one, and stop() ends it; from then on this object's sample(), read(), paths() and info raise RuntimeError -
+    the context's history is another set's, of another size - and its stop() does nothing."""
+
+    def __init__(self, particles, indices, depth):
+        self._p = particles
+        self.index = np.ascontiguousarray(np.asarray(indices, np.uint32).reshape(-1))
+        self.depth = int(depth)
+        if not len(self.index):
+            raise ValueError("follow: an empty set (stop() ends following)")
+        call("th_follow_set", particles._ctx, self.index.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.index), self.depth)
+        particles._following = self                 # (a refused set raised above: the set of before is still the followed one)
+
+    def __len__(self):
+        return len(self.index)
+
+    @property
+    def followed(self):
+        """this object's set is the one its Particles follows"""
+        return self._p._following is self
+
+    def _current(self, what):
+        if not self.followed:
+            raise RuntimeError("follow: %s of a set that is no longer followed (replaced by a later follow(), or stopped)" % what)
+
+    def sample(self, time=0.0, buffer=0):
+        """the set's states in ring buffer `buffer`, as decoded, into the next row of the history (th_follow_sample: enqueued
+        only); `time` is kept beside it on the host"""
+        self._current("sample()")
+        call("th_follow_sample", self._p._ctx, buffer.index if isinstance(buffer, StateBuffer) else int(buffer), float(time))
+
+    def _counts(self, what):
+        """th_follow_info of the context, once it is sure to be of THIS set (th_follow_query: nothing is launched)"""
+        self._current(what)
+        info = _capi.FollowInfo()
+        call("th_follow_query", self._p._ctx, C.byref(info), None, None)
+        if int(info.followed) != len(self.index):   # (th_follow_set called beside this object: a row is not len(self) states wide)
+            raise RuntimeError("follow: %s of a set of %d, the context follows %d" % (what, len(self.index), int(info.followed)))
+        return FollowCounts(info)
+
+    @property
+    def info(self):
+        """particles, followed, depth, samples, held, locates (th_follow_info)"""
+        return self._counts("info")
+
+    def read(self, first, count):
+        """samples [first, first + count), oldest first (th_follow_read): ([count, n, 4] float32, [count] float64)"""
+        self._counts("read()")                      # (the buffer below is sized by this set: the context's must be the same)
+        n, count = len(self.index), max(int(count), 0)
+        states, times, info = np.zeros((count, n, 4), np.float32), np.zeros(count, np.float64), _capi.FollowInfo()
+        call("th_follow_read", self._p._ctx, int(first), count, states.ctypes.data_as(C.POINTER(C.c_float)) if count else None,
+             times.ctypes.data_as(C.POINTER(C.c_double)), C.byref(info))
+        return states, times
+
+    def paths(self, last=None):
+        """(states, times) of the last `last` samples held (None: all that are held): states a [n, k, 4] float32 view - particle
+        r of the set, sample by sample, oldest first - and times their k times"""
+        info = self.info
+        k = info.held if last is None else min(max(int(last), 0), info.held)
+        states, times = self.read(info.samples - k, k)
+        return states.transpose(1, 0, 2), times
+
+    def stop(self):
+        """ends following and releases the history (th_follow_set with n = 0); nothing when this set is followed no longer"""
+        if self.followed:
+            call("th_follow_set", self._p._ctx, None, 0, 1)
+            self._p._following = None
+
+
 LOGIC = "logic"
 
 
@@ -357,6 +440,7 @@ class Particles:
         self._row0 = int(params.get("row0", 0))
         self._global_height = int(params.get("globalHeight", 0))
         self._next_id = 0
+        self._following = None                      # the Follow whose set the context follows (Particles.follow), or None
         # best-sample spawning from the particle texture on a row-band shard (PixelSpawner): "auto" - through
         # th_spawn_sample_sharded when the context holds the job's communicator, else the gathered path; True / False force one
         self.sharded_spawn = "auto"
@@ -715,6 +799,13 @@ class Particles:
                 prefixes[k] = prefix | (int(np.searchsorted(passes[prefix], k, side="right")) << shift)
         out = key_float(np.array([prefixes[k] for k in ranks], np.uint32))
         return out[0] if scalar else out
+
+    def follow(self, indices, depth=64):
+        """Follow the particles at texels `indices` - anything np.asarray(..., np.uint32) takes, Selection.index in particular:
+        whole-texture indices, strictly increasing, inside this context's rows - in a history of `depth` samples on the device
+        (th_follow_set).  Returns a Follow: .sample(time=0.0, buffer=0), .paths(last=None), .info, .stop().  Read-only towards
+        the ring, as select(); replaces the set followed before, whose Follow raises from then on."""
+        return Follow(self, indices, depth)
 
     @staticmethod
     def generateLUT(shape):                          # src/particles.js:171-190

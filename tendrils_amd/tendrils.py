@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import call
-from .particles import (LOGIC, Particles, Program, ScreenProgram, StepProgram, deposit_uniforms, draw_program_args, draw_stages, run_pass,
+from .particles import (LOGIC, Follow, Particles, Program, ScreenProgram, StepProgram, deposit_uniforms, draw_program_args, draw_stages, run_pass,
                         shader_stages)
 from .timer import Timer
 
@@ -691,6 +691,23 @@ class Tendrils:
         """Exact order statistics of a scalar of the state over the matching particles (Particles.quantiles, its arguments):
         the median speed, the 95th percentile to normalise a ramp to.  Read-only, as select()."""
         return self.particles.quantiles(channel, q, **kw)
+
+    def follow(self, indices, depth=64):
+        """Follow the particles at texels `indices` - a Selection's .index, say - from sample to sample in a history on the
+        device (Particles.follow): a TimedFollow, whose sample() takes its time from tendrils.timer unless told one.  Nothing samples
+        by itself - step(); follow.sample(); draw() - and sampling is read-only, as select()."""
+        return TimedFollow(self.particles, indices, depth, self.timer)
+
+
+class TimedFollow(Follow):
+    """What Tendrils.follow returns: a Follow whose sample() takes `time` from the tendrils' timer when it is given none"""
+
+    def __init__(self, particles, indices, depth, timer):
+        self.timer = timer
+        super().__init__(particles, indices, depth)
+
+    def sample(self, time=None, buffer=0):
+        super().sample(self.timer.time if time is None else time, buffer)
 
 
 default = Tendrils
