@@ -16,9 +16,10 @@
 //   th_density.hip the density map: the particles' count and summed velocity on a grid, into a texture slot or the spawn image (th_density / _async)
 //   th_select.hip  select: the particles of a ring buffer that match a fixed predicate, as records in texel order (th_select / _async)
 //   th_histogram.hip the histogram: the matching particles counted per bin of one scalar of the state (th_histogram / _async);
-//                  th_select_match.hpp is what the two units share - the slot loader, the predicate, the checks of its block
+//                  th_select_match.hpp is what the two units share - the predicate and the checks of its block
 //   th_follow.hip  follow: the states of a chosen set of particles, sample by sample, in a history kept on the device
 //                  (th_follow_set / _sample / _read / _query); the slots of the set in a tile-sorted order, found when the order changes
+//   th_ring.hpp    what the last five units - the passes that read a ring buffer where it lies - share, on the device and on the host
 //   th_blend.hip  the demo's colour-map blend and the caller's textures it reads (th_colormap_blend, th_texture_upload); the TH_VIEW_*
 //                 names as images (view_image)
 #pragma once
@@ -63,6 +64,23 @@ std::string &last_error();
 #include "th_mem.hpp"                     // thi::DevBuf / thi::HostBuf: every device and pinned buffer below is one of these
 using thi::DevBuf;
 using thi::HostBuf;
+
+// A set of LOCAL TEXELS on the device: a bit per texel in 64-bit words, and the members before each word - the words' popcounts,
+// scanned in place (th_sort.hip: launch_texel_set_rank), with the scan's block sums.  A member's rank is th_ring.hpp's texel_rank.
+namespace thi {
+struct TexelSetView { const unsigned long long *mask; const uint32_t *counts; };      // ... as a kernel reads it
+struct TexelSet {
+    DevBuf<unsigned long long> mask;
+    DevBuf<uint32_t> counts, sums;
+    th_status reserve(uint32_t nwords)   // grow-only
+    {
+        if (th_status s = mask.reserve(nwords, nwords)) return s;
+        if (th_status s = counts.reserve(nwords, nwords)) return s;
+        return sums.reserve(th::exclusive_scan_sum_words(nwords), th::exclusive_scan_sum_words(nwords));
+    }
+    TexelSetView view() const { return TexelSetView{mask.get(), counts.get()}; }
+};
+}  // namespace thi
 
 // Per-context switches (th_option_set / th_option_get).  A context starts from the environment variables of the same
 // names, read when it is created - not once per process - so one process can hold contexts on different paths.
@@ -369,11 +387,10 @@ struct th_context {
     DevBuf<uint4> density_acc;
     DevBuf<unsigned long long> density_info;
 
-    // th_select / _async (th_select.hip), reserved by the first select of the context: a bit per texel (64-bit words, indexed by
-    // LOCAL TEXEL), the words' popcounts - scanned in place - with the scan's block sums, the info block the call leaves (a
+    // th_select / _async (th_select.hip), reserved by the first select of the context: the matching texels, the info block the call leaves (a
     // th_select_info), and the records (grow-only: the largest capacity asked)
-    DevBuf<unsigned long long> select_mask, select_info;
-    DevBuf<uint32_t> select_counts, select_sums;
+    thi::TexelSet select_set;
+    DevBuf<unsigned long long> select_info;
     DevBuf<th_selected> select_records;
 
     // th_histogram / _async (th_histogram.hip), reserved by the first histogram of the context: TH_HIST_MAX_BINS counts and the
@@ -382,12 +399,12 @@ struct th_context {
     DevBuf<unsigned long long> hist_info;
 
     // th_follow_set / _sample / _read / _query (th_follow.hip), reserved by the first th_follow_set of the context: the set as a
-    // bit per LOCAL TEXEL (64-bit words) with the set's members before each word - scanned in place, the scan's block sums
-    // beside them - and as its local texels in set order; the slot of every member in the order `follow.order` / `.stamp`
+    // TexelSet of its own - select's device addresses stay valid until the next select
+    // - and as its local texels in set order; the slot of every member in the order `follow.order` / `.stamp`
     // names (-1: texel order, where the texel is the slot; -2: nothing yet); the history, float4[depth][n], row k % depth
     // holding sample k; the callers' times of the samples, by the same row
-    DevBuf<unsigned long long> follow_mask;
-    DevBuf<uint32_t> follow_counts, follow_sums, follow_set, follow_slots;
+    thi::TexelSet follow_texels;
+    DevBuf<uint32_t> follow_set, follow_slots;
     DevBuf<float4> follow_history;
     struct {
         uint64_t n = 0, depth = 0, samples = 0, locates = 0;

@@ -19,16 +19,11 @@
 //                           and is not in the product: profiles/density_map.txt.)
 //   density_convert_kernel  accumulators -> RGBA32F texels, and the sum of the counts = `inside`
 // No float atomics, no inline assembly; every index that addresses LDS or memory comes from a value compared in range first.
-#include "th_ctx.hpp"
-#include "th_logic.hpp"          // th::unpack_state (th_packed.inc)
+#include "th_ring.hpp"           // Slot, wave_sum, fold_counters, RingView: what the passes that read the ring where it lies share
 
 using namespace thi;
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int kWinHalo = 8, kWinSide = 32 + 2 * kWinHalo, kWinCells = kWinSide * kWinSide;      // the window: a 32 x 32 tile and a halo around it
 constexpr uint32_t kLaneSlots = 8, kBlockSlots = 256u * kLaneSlots;   // slots a lane / a workgroup takes at a time
@@ -57,19 +52,6 @@ __global__ __launch_bounds__(256) void density_clear_kernel(v4u *acc, uint32_t w
     if (blockIdx.x == 0 && threadIdx.x < (unsigned)kInfoWords) info[threadIdx.x] = threadIdx.x == kParticles ? particles : 0ull;
 }
 
-// a slot as it lies in memory - 16 bytes, or the 8 of a packed ring - and what it holds; none(): what stands for a slot past the end - an inert particle
-template <bool PACKED> struct Slot;
-template <> struct Slot<false> {
-    using Raw = v4f;
-    TH_D static Raw none() { return Raw{th::kInert, th::kInert, 0.0f, 0.0f}; }
-    TH_D static float4 state(Raw t) { return make_float4(t.x, t.y, t.z, t.w); }
-};
-template <> struct Slot<true> {
-    using Raw = v2u;
-    TH_D static Raw none() { return Raw{0x80008000u, 0u}; }
-    TH_D static float4 state(Raw t) { return th::unpack_state(make_uint2(t.x, t.y)); }
-};
-
 // a velocity component in 2^-32 units, round-half-even; false: not finite, adds nothing
 TH_D bool density_quantum(float v, long long &q)
 {
@@ -79,8 +61,6 @@ TH_D bool density_quantum(float v, long long &q)
     return true;
 }
 
-TH_D uint32_t wave_sum(uint32_t v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
-
 template <bool PACKED>
 __global__ __launch_bounds__(256) void density_tally_kernel(const DensityParams p, uint32_t run)
 {
@@ -88,10 +68,10 @@ __global__ __launch_bounds__(256) void density_tally_kernel(const DensityParams 
     __shared__ unsigned long long win_sum[kWinCells * 2];
     __shared__ int cand[4][2];                  // per wave: the cell of its first inside particle of the block (x < 0: none)
     __shared__ uint32_t votes[2][3];            // by the block's parity: its inside particles | those in the window | ... in the window proposed
-    __shared__ uint32_t tally[3];               // live, outside, nonfinite of the workgroup
+    __shared__ uint32_t tally[4 * 3];           // live, outside, nonfinite of the four waves (fold_counters)
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < (uint32_t)kWinCells; i += 256u) { win_cnt[i] = 0u; win_sum[2 * i] = 0ull; win_sum[2 * i + 1] = 0ull; }
-    if (tid < 3u) { tally[tid] = 0u; votes[0][tid] = 0u; votes[1][tid] = 0u; }
+    if (tid < 3u) { votes[0][tid] = 0u; votes[1][tid] = 0u; }
     __syncthreads();
     const float wf = (float)p.w, hf = (float)p.h, wm1 = (float)(p.w - 1), hm1 = (float)(p.h - 1);
     uint32_t live = 0u, outside = 0u, nonfinite = 0u;
@@ -121,9 +101,9 @@ __global__ __launch_bounds__(256) void density_tally_kernel(const DensityParams 
 #pragma unroll
         for (uint32_t k = 0; k < kLaneSlots; ++k) {
             const uint32_t idx = base + k * 256u;
-            raw[k] = idx < p.count ? __builtin_nontemporal_load(static_cast<const typename Slot<PACKED>::Raw *>(p.in) + idx) : Slot<PACKED>::none();
+            raw[k] = idx < p.count ? Slot<PACKED>::load(p.in, idx) : Slot<PACKED>::none();
         }
-        float4 s[kLaneSlots];
+        v4f s[kLaneSlots];
 #pragma unroll
         for (uint32_t k = 0; k < kLaneSlots; ++k) s[k] = Slot<PACKED>::state(raw[k]);
         int cx[kLaneSlots], cy[kLaneSlots];     // the cell; cx < 0: none (inert, outside, past the end)
@@ -132,7 +112,7 @@ __global__ __launch_bounds__(256) void density_tally_kernel(const DensityParams 
 #pragma unroll
         for (uint32_t k = 0; k < kLaneSlots; ++k) {
             cx[k] = cy[k] = -1;
-            if (s[k].x == th::kInert && s[k].y == th::kInert) continue;       // (a slot past the end was loaded as inert)
+            if (!slot_live(s[k])) continue;                  // (a slot past the end was loaded as inert)
             ++live;
             const float fx = __builtin_floorf((((s[k].x * p.view_x) + 1.0f) * 0.5f) * wf);
             const float fy = __builtin_floorf((((s[k].y * p.view_y) + 1.0f) * 0.5f) * hf);
@@ -198,19 +178,13 @@ __global__ __launch_bounds__(256) void density_tally_kernel(const DensityParams 
         __syncthreads();                                  // (the block's LDS atomics before a flush; cand and votes before the next block writes them)
     }
     if (open) flush();
-    // the counters: per lane, a butterfly per wave, the four waves through LDS, one atomic per counter and workgroup
-    live = wave_sum(live); outside = wave_sum(outside); nonfinite = wave_sum(nonfinite);
-    if ((tid & 63u) == 0u) { atomicAdd(&tally[0], live); atomicAdd(&tally[1], outside); atomicAdd(&tally[2], nonfinite); }
-    __syncthreads();
-    if (tid == 0u && tally[0]) atomicAdd(&p.info[kLive], (unsigned long long)tally[0]);
-    if (tid == 1u && tally[1]) atomicAdd(&p.info[kOutside], (unsigned long long)tally[1]);
-    if (tid == 2u && tally[2]) atomicAdd(&p.info[kNonfinite], (unsigned long long)tally[2]);
+    fold_counters<kLive, kOutside, kNonfinite>(tally, p.info, {live, outside, nonfinite});      // every lane of the workgroup is here
 }
 
 // one lane per cell: (count, sumx * 2^-32, sumy * 2^-32, count ? 1 : 0), every conversion to nearest; the counts' sum is `inside`
 __global__ __launch_bounds__(256) void density_convert_kernel(const DensityParams p)
 {
-    __shared__ unsigned long long part[4];
+    __shared__ unsigned long long part[4];      // (fold_counters)
     const uint32_t cells = (uint32_t)p.w * (uint32_t)p.h;
     unsigned long long inside = 0ull;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < cells; i += gridDim.x * 256u) {
@@ -219,13 +193,7 @@ __global__ __launch_bounds__(256) void density_convert_kernel(const DensityParam
         inside += n;
         p.dst[i] = make_float4((float)n, (float)((double)sx * 0x1p-32), (float)((double)sy * 0x1p-32), n ? 1.0f : 0.0f);
     }
-    for (int o = 32; o > 0; o >>= 1) inside += __shfl_xor(inside, o);      // (every lane arrives: the loop above returns nobody)
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = inside;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(&p.info[kInside], t);
-    }
+    fold_counters<kInside>(part, p.info, {inside});      // (every lane arrives: the loop above returns nobody)
 }
 
 size_t acc_words(int64_t cells) { return (size_t)((cells * 20 + 15) / 16); }      // 16 B of sums and 4 B of count a cell, in 16-byte words
@@ -239,8 +207,8 @@ th_status density_enqueue(th_context *c, const th_density_uniforms *u, int32_t b
     TH_REQUIRE(std::isfinite(u->viewSize[0]) && std::isfinite(u->viewSize[1]), "%s: viewSize is not finite", entry);
     TH_REQUIRE(u->dest == TH_VIEW_TEXTURE || u->dest == TH_VIEW_SPAWN_IMAGE, "%s: dest %d (TH_VIEW_TEXTURE or TH_VIEW_SPAWN_IMAGE)", entry, u->dest);
     TH_REQUIRE(u->dest != TH_VIEW_TEXTURE || (u->slot >= 0 && u->slot < TH_MAX_TEXTURES), "%s: texture slot %d outside 0..%d", entry, u->slot, TH_MAX_TEXTURES - 1);
-    TH_REQUIRE(buffer >= 0 && (size_t)buffer < c->ring.size(), "%s: buffer %d out of range (the ring has %zu)", entry, buffer, c->ring.size());
-    TH_REQUIRE(c->texels() > 0 && c->texels() <= (1ull << 28), "%s: %zu particles", entry, c->texels());
+    TH_RING_BUFFER_OK(c, buffer, entry);
+    TH_RING_TEXELS_OK(c, entry);
     const int64_t cells = (int64_t)u->w * u->h;
     if (!c->density_info) if (th_status s = c->density_info.alloc(kInfoWords)) return s;
     if (c->density_acc.size() < acc_words(cells)) {
@@ -259,8 +227,8 @@ th_status density_enqueue(th_context *c, const th_density_uniforms *u, int32_t b
         if (u->w != c->iw || u->h != c->ih) if (th_status s = image_reshape(c, c->image, c->iw, c->ih, u->w, u->h)) return s;
         p.dst = c->image;
     }
-    p.in = c->ring[(size_t)buffer];                        // where it lies: whatever slot order it is held in (order_of), packed texels in place
-    p.count = (uint32_t)c->texels();
+    const RingView ring = ring_read(c, buffer);            // where it lies, in whatever slot order (a cell does not depend on who the particle is: ring.perm is not read)
+    p.in = ring.in; p.count = ring.count;
     p.view_x = u->viewSize[0]; p.view_y = u->viewSize[1];
     p.w = u->w; p.h = u->h;
     p.sum = reinterpret_cast<unsigned long long *>(c->density_acc.get());
@@ -273,8 +241,7 @@ th_status density_enqueue(th_context *c, const th_density_uniforms *u, int32_t b
     // CU (the LDS), twelve waves with eight loads a lane in flight
     const uint32_t nblocks = (p.count + kBlockSlots - 1u) / kBlockSlots;
     const uint32_t run = (nblocks + 256u * kTallyPerCu - 1u) / (256u * kTallyPerCu), grid = (nblocks + run - 1u) / run;
-    if (c->packed) hipLaunchKernelGGL(density_tally_kernel<true>, dim3(grid), dim3(256), 0, c->stream, p, run);
-    else hipLaunchKernelGGL(density_tally_kernel<false>, dim3(grid), dim3(256), 0, c->stream, p, run);
+    dispatch_packed(c, [&](auto packed) { hipLaunchKernelGGL(density_tally_kernel<decltype(packed)::value>, dim3(grid), dim3(256), 0, c->stream, p, run); });
     hipLaunchKernelGGL(density_convert_kernel, dim3(th::grid_for((size_t)cells, 8)), dim3(256), 0, c->stream, p);
     TH_HIP(hipGetLastError());
     return TH_OK;

@@ -6,11 +6,11 @@
 // Fetching by index is free in texel order: slot = texel.  The frame loop lives in tile-sorted slots, and there is no inverse
 // of perm; this unit keeps the small inverse that following a set needs - the slots of the followed texels only - and
 // rebuilds it when, and only when, the sampled buffer's (order, SlotOrder::stamp) is another than the table's:
-//   follow_clear / _mark / _count_kernel   once per th_follow_set: the set as a bit per LOCAL TEXEL (lane r ORs the bit of
-//                          indices[r] - row0 * width: an integer atomic), the words' popcounts, and th_sort.hip's exclusive scan
-//                          over them as it is.  The set is strictly increasing, so the rank of texel t in it is
-//                          counts[t >> 6] + popcount(word below its bit): select's ranking, no search.  The context's own
-//                          scratch, not select's - select's device addresses stay valid until the next select.
+//   follow_mark_kernel     once per th_follow_set, between th_sort.hip's launch_texel_set_clear and launch_texel_set_rank: the
+//                          set as a bit per LOCAL TEXEL (lane r ORs the bit of indices[r] - row0 * width: an integer atomic),
+//                          then the words' popcounts and the exclusive scan over them.  The set is strictly increasing, so
+//                          the rank of texel t in it is th_ring.hpp's texel_rank: select's ranking, no search.  A TexelSet
+//                          of the context's own, not select's - select's device addresses stay valid until the next select.
 //   follow_fill_kernel     0xFFFFFFFF into the slot table, then
 //   follow_locate_kernel   one walk over perm on the streaming passes' grid, one non-temporal load a slot: t = perm[i] is
 //                          compared against the texel count BEFORE it addresses the mask; a set bit gives slots[rank] = i.  No
@@ -22,7 +22,7 @@
 //                          cannot happen - stores four 0x7FC00000 rather than reading anywhere.
 // Only integer arithmetic and copies: the history's bits depend on neither the slot order nor the run.  No wave-wide
 // operation anywhere: a lane past the end leaves.  Every index that addresses memory comes from a value compared in range first.
-#include "th_select_match.hpp"   // Slot<PACKED>, v4f, v4u: a slot as it lies in memory and the state it holds
+#include "th_ring.hpp"           // Slot<PACKED>, v4f, v4u, texel_rank, RingView: what the passes that read the ring where it lies share
 
 using namespace thi;
 
@@ -31,11 +31,6 @@ namespace {
 static_assert(sizeof(th_follow_info) == 48 && offsetof(th_follow_info, locates) == 40, "th_follow_info: the header's layout");
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr uint32_t kQuietNan = 0x7FC00000u;
-
-__global__ __launch_bounds__(256) void follow_clear_kernel(unsigned long long *mask, uint32_t nwords)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nwords; i += gridDim.x * 256u) mask[i] = 0ull;
-}
 
 // indices: whole-texture texels; base = row0 * width; count: this context's texels
 __global__ __launch_bounds__(256) void follow_mark_kernel(const uint32_t *indices, uint32_t n, uint32_t base, uint32_t count, unsigned long long *mask)
@@ -46,27 +41,19 @@ __global__ __launch_bounds__(256) void follow_mark_kernel(const uint32_t *indice
     }
 }
 
-__global__ __launch_bounds__(256) void follow_count_kernel(const unsigned long long *mask, uint32_t *counts, uint32_t nwords)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nwords; i += gridDim.x * 256u) counts[i] = (uint32_t)__popcll(mask[i]);
-}
-
 __global__ __launch_bounds__(256) void follow_fill_kernel(uint32_t *slots, uint32_t n)
 {
     for (uint32_t r = blockIdx.x * 256u + threadIdx.x; r < n; r += gridDim.x * 256u) slots[r] = kNoSlot;
 }
 
-// behind the scan: counts[] holds the members of the set before each word
-__global__ __launch_bounds__(256) void follow_locate_kernel(const uint32_t *perm, uint32_t count, const unsigned long long *mask, const uint32_t *counts,
-                                                            uint32_t *slots, uint32_t n)
+// behind the rank: set.counts[] holds the members of the set before each word
+__global__ __launch_bounds__(256) void follow_locate_kernel(const uint32_t *perm, uint32_t count, const TexelSetView set, uint32_t *slots, uint32_t n)
 {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < count; i += gridDim.x * 256u) {
         const uint32_t t = __builtin_nontemporal_load(perm + i);
         if (t >= count) continue;
-        const unsigned long long word = mask[t >> 6], bit = 1ull << (t & 63u);
-        if (!(word & bit)) continue;
-        const uint32_t rank = counts[t >> 6] + (uint32_t)__popcll(word & (bit - 1ull));
-        if (rank < n) slots[rank] = i;
+        const uint32_t rank = texel_rank(set, t);
+        if (rank < n) slots[rank] = i;                    // (kNoRank: not followed)
     }
 }
 
@@ -98,8 +85,7 @@ void follow_info(const th_context *c, th_follow_info *info)
 th_status follow_release(th_context *c)
 {
     TH_HIP(hipStreamSynchronize(c->stream));
-    c->follow_mask.reset(); c->follow_counts.reset(); c->follow_sums.reset();
-    c->follow_set.reset(); c->follow_slots.reset(); c->follow_history.reset();
+    c->follow_texels = {}; c->follow_set.reset(); c->follow_slots.reset(); c->follow_history.reset();
     c->follow = {};
     return TH_OK;
 }
@@ -113,7 +99,7 @@ th_status follow_locate(th_context *c, int order)
     const uint32_t count = (uint32_t)c->texels(), n = (uint32_t)f.n;
     hipLaunchKernelGGL(follow_fill_kernel, dim3(th::grid_for(n, 8)), dim3(256), 0, c->stream, c->follow_slots.get(), n);
     hipLaunchKernelGGL(follow_locate_kernel, dim3(th::grid_for(count, 8)), dim3(256), 0, c->stream, (const uint32_t *)o.perm.get(), count,
-                       (const unsigned long long *)c->follow_mask.get(), (const uint32_t *)c->follow_counts.get(), c->follow_slots.get(), n);
+                       c->follow_texels.view(), c->follow_slots.get(), n);
     TH_HIP(hipGetLastError());
     f.order = order; f.stamp = o.stamp;
     ++f.locates;
@@ -127,7 +113,7 @@ extern "C" {
 th_status th_follow_set(th_context *c, const uint32_t *indices, uint64_t n, uint32_t depth)
 {
     TH_REQUIRE(c, "th_follow_set: null context");
-    TH_REQUIRE(c->texels() > 0 && c->texels() <= (1ull << 28), "th_follow_set: %zu particles", c->texels());
+    TH_RING_TEXELS_OK(c, "th_follow_set");
     if (n == 0) {
         if (th_status s = use(c, true)) return s;
         return follow_release(c);
@@ -147,14 +133,7 @@ th_status th_follow_set(th_context *c, const uint32_t *indices, uint64_t n, uint
     TH_HIP(hipStreamSynchronize(c->stream));              // (a sample of the old set may still write the old history)
     const uint32_t count = (uint32_t)c->texels(), nwords = (count + 63u) / 64u, members = (uint32_t)n;
     // the new set's storage first: a failure leaves the old set as it was
-    if (!c->follow_mask) {
-        DevBuf<unsigned long long> mask;
-        DevBuf<uint32_t> counts, sums;
-        if (th_status s = mask.alloc(nwords)) return s;
-        if (th_status s = counts.alloc(nwords)) return s;
-        if (th_status s = sums.alloc(th::exclusive_scan_sum_words(nwords))) return s;
-        c->follow_mask = std::move(mask); c->follow_counts = std::move(counts); c->follow_sums = std::move(sums);
-    }
+    if (th_status s = c->follow_texels.reserve(nwords)) return s;      // (grow-only, and the texture's shape is the context's: an old set's is left as it is)
     DevBuf<uint32_t> set, slots;
     DevBuf<float4> history;
     if (th_status s = set.alloc(members)) return s;
@@ -166,12 +145,10 @@ th_status th_follow_set(th_context *c, const uint32_t *indices, uint64_t n, uint
     c->follow.n = n; c->follow.depth = depth;
     c->follow.times.assign(depth, 0.0);
     TH_HIP(hipMemsetAsync(c->follow_history, 0, c->follow_history.bytes(), c->stream));
-    hipLaunchKernelGGL(follow_clear_kernel, dim3(th::grid_for(nwords, 8)), dim3(256), 0, c->stream, c->follow_mask.get(), nwords);
+    th::launch_texel_set_clear(c->follow_texels.mask, nwords, c->stream);
     hipLaunchKernelGGL(follow_mark_kernel, dim3(th::grid_for(members, 8)), dim3(256), 0, c->stream, (const uint32_t *)c->follow_set.get(), members,
-                       follow_base(c), count, c->follow_mask.get());
-    hipLaunchKernelGGL(follow_count_kernel, dim3(th::grid_for(nwords, 8)), dim3(256), 0, c->stream, (const unsigned long long *)c->follow_mask.get(),
-                       c->follow_counts.get(), nwords);
-    th::launch_exclusive_scan_u32(c->follow_counts, c->follow_sums, nwords, c->stream);
+                       follow_base(c), count, c->follow_texels.mask.get());
+    th::launch_texel_set_rank(c->follow_texels.mask, c->follow_texels.counts, c->follow_texels.sums, nwords, false, c->stream);
     TH_HIP(hipGetLastError());
     return TH_OK;
 }
@@ -179,21 +156,21 @@ th_status th_follow_set(th_context *c, const uint32_t *indices, uint64_t n, uint
 th_status th_follow_sample(th_context *c, int32_t buffer, double time)
 {
     TH_REQUIRE(c, "th_follow_sample: null context");
-    TH_REQUIRE(buffer >= 0 && (size_t)buffer < c->ring.size(), "th_follow_sample: buffer %d out of range (the ring has %zu)", buffer, c->ring.size());
+    TH_RING_BUFFER_OK(c, buffer, "th_follow_sample");
     TH_REQUIRE(c->follow.n > 0, "th_follow_sample: no set is followed (th_follow_set)");
     if (th_status s = use(c, true)) return s;
     auto &f = c->follow;
-    const float4 *buf = c->ring[(size_t)buffer];
-    const int order = order_of(c, buf);                   // (the slot order stays: slot i holds texel perm[i])
+    int order;
+    const RingView ring = ring_read(c, buffer, &order);   // (the slot order stays: slot i holds texel perm[i])
     if (order >= 0) if (th_status s = follow_locate(c, order)) return s;
     const uint32_t *table = order >= 0 ? c->follow_slots.get() : c->follow_set.get();
     const uint32_t base = order >= 0 ? 0u : follow_base(c);
-    const uint32_t count = (uint32_t)c->texels(), n = (uint32_t)f.n;
+    const uint32_t n = (uint32_t)f.n;
     const size_t at = (size_t)(f.samples % f.depth);
     v4f *row = reinterpret_cast<v4f *>(c->follow_history.get() + at * (size_t)n);
-    const dim3 grid((n + 255u) / 256u);
-    if (c->packed) hipLaunchKernelGGL(follow_gather_kernel<true>, grid, dim3(256), 0, c->stream, (const void *)buf, table, base, count, n, row);
-    else hipLaunchKernelGGL(follow_gather_kernel<false>, grid, dim3(256), 0, c->stream, (const void *)buf, table, base, count, n, row);
+    dispatch_packed(c, [&](auto packed) {
+        hipLaunchKernelGGL(follow_gather_kernel<decltype(packed)::value>, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, ring.in, table, base, ring.count, n, row);
+    });
     TH_HIP(hipGetLastError());
     f.times[at] = time;
     ++f.samples;

@@ -13,11 +13,11 @@
 //                       predicate is th_select's own (th_select_match.hpp).  A workgroup-private histogram in LDS (4 bytes a
 //                       bin, sized by the call) takes the adds as LDS integer atomics; at the end the workgroup flushes its
 //                       non-zero bins with global integer atomics, neighbouring lanes neighbouring bins.  live, matched, below,
-//                       above and nan are per-lane integers: a butterfly per wave, one LDS add per wave, one global atomic per
-//                       counter and workgroup.
+//                       above and nan are per-lane integers: th_ring.hpp's fold of a workgroup's counters - a butterfly per
+//                       wave, one global atomic per counter and workgroup.
 // No lane leaves before the wave-wide operations: the loop's bounds are the workgroup's, a lane past the last slot carries "not
 // live, no match".  Every index that addresses LDS or memory comes from a value compared in range first.  No float atomics.
-#include "th_select_match.hpp"   // Slot, SelectClauses, select_match, select_checks: shared with th_select.hip
+#include "th_select_match.hpp"   // SelectClauses, select_match, select_checks: shared with th_select.hip; th_ring.hpp behind it
 
 using namespace thi;
 
@@ -28,15 +28,13 @@ constexpr uint32_t kMaxGroups = 1024;     // four workgroups a CU: sixteen waves
 constexpr uint32_t kNone = 0xffffffffu;   // "no bin": not matched, below, above, NaN
 constexpr int kInfoWords = 6;             // th_histogram_info
 enum { kParticles, kLive, kMatched, kBelow, kAbove, kNan };
-constexpr uint32_t kTallyWords = 8;       // LDS: the workgroup's five counters (kLive - 1 ...), then its histogram
+constexpr uint32_t kTallyWords = 4 * 5;   // LDS: the four waves' five counters (fold_counters), then the workgroup's histogram
 static_assert(sizeof(th_histogram_uniforms) == 72 && sizeof(th_histogram_info) == kInfoWords * 8, "th_histogram_*: the header's layout");
 static_assert(offsetof(th_histogram_uniforms, channel) == 40 && offsetof(th_histogram_uniforms, reserved) == 68, "th_histogram_uniforms: select, then the rest");
 static_assert(TH_HIST_MAX_BINS == 4096, "th_histogram: the scratch and the LDS are sized for 4096 bins");
 
 struct HistParams {
-    const void *in;                   // the ring buffer: float4 or, packed, uint2 per slot
-    const uint32_t *perm;             // slot -> local texel, or null: texel order, or nobody asks (stride 1)
-    uint32_t count;                   // this context's texels
+    RingView ring;                    // the buffer where it lies; ring.perm is read only when the stride clause asks who a particle is
     SelectClauses q;                  // the predicate's clauses
     int32_t channel;
     uint32_t bins;
@@ -51,8 +49,6 @@ __global__ __launch_bounds__(256) void hist_clear_kernel(uint32_t *counts, uint3
     for (uint32_t i = threadIdx.x; i < bins; i += 256u) counts[i] = 0u;
     if (threadIdx.x < (unsigned)kInfoWords) info[threadIdx.x] = threadIdx.x == kParticles ? particles : 0ull;
 }
-
-TH_D uint32_t wave_sum(uint32_t v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
 
 // the channel's value, in the header's words (the test is wave-uniform: the argument segment)
 TH_D float hist_value(int32_t channel, v4f s)
@@ -90,11 +86,10 @@ __global__ __launch_bounds__(256) void hist_tally_kernel(const HistParams p)
     uint32_t *tally = lds, *hist = lds + kTallyWords;
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < p.bins; i += 256u) hist[i] = 0u;
-    if (tid < kTallyWords) tally[tid] = 0u;
     __syncthreads();
     uint32_t live = 0u, matched = 0u, below = 0u, above = 0u, nan = 0u;
-    const bool indexed = p.perm && p.q.stride > 1u;       // (wave-uniform: the argument segment)
-    const uint32_t nblocks = (p.count + kBlockSlots - 1u) / kBlockSlots;
+    const bool indexed = p.ring.perm && p.q.stride > 1u;       // (wave-uniform: the argument segment)
+    const uint32_t nblocks = (p.ring.count + kBlockSlots - 1u) / kBlockSlots;
     // `b` is the workgroup's: every lane of the workgroup takes the same turns
     for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
         const uint32_t base = b * kBlockSlots + tid;
@@ -105,20 +100,20 @@ __global__ __launch_bounds__(256) void hist_tally_kernel(const HistParams p)
             const uint32_t idx = base + k * 256u;
             raw[k] = typename Slot<PACKED>::Raw{};
             t[k] = idx;
-            if (idx < p.count) {
-                raw[k] = Slot<PACKED>::load(p.in, idx);
-                if (indexed) t[k] = __builtin_nontemporal_load(p.perm + idx);
+            if (idx < p.ring.count) {
+                raw[k] = Slot<PACKED>::load(p.ring.in, idx);
+                if (indexed) t[k] = __builtin_nontemporal_load(p.ring.perm + idx);
             }
         }
 #pragma unroll
         for (uint32_t k = 0; k < kLaneSlots; ++k) {
             const uint32_t idx = base + k * 256u;
             uint32_t bin = kNone;
-            if (idx < p.count) {
+            if (idx < p.ring.count) {
                 const v4f s = Slot<PACKED>::state(raw[k]);
                 const bool is_live = slot_live(s);
                 live += is_live ? 1u : 0u;
-                if (t[k] < p.count && select_match(p.q, s, is_live, t[k])) {
+                if (t[k] < p.ring.count && select_match(p.q, s, is_live, t[k])) {
                     ++matched;
                     bin = hist_bin<MODE>(p, hist_value(p.channel, s), below, above, nan);
                 }
@@ -131,14 +126,7 @@ __global__ __launch_bounds__(256) void hist_tally_kernel(const HistParams p)
         const uint32_t n = hist[i];
         if (n) atomicAdd(&p.counts[i], n);
     }
-    // the counters: per lane, a butterfly per wave, the four waves through LDS, one atomic per counter and workgroup
-    live = wave_sum(live); matched = wave_sum(matched); below = wave_sum(below); above = wave_sum(above); nan = wave_sum(nan);
-    if ((tid & 63u) == 0u) {
-        atomicAdd(&tally[kLive - 1], live); atomicAdd(&tally[kMatched - 1], matched); atomicAdd(&tally[kBelow - 1], below);
-        atomicAdd(&tally[kAbove - 1], above); atomicAdd(&tally[kNan - 1], nan);
-    }
-    __syncthreads();
-    if (tid < (uint32_t)(kInfoWords - 1) && tally[tid]) atomicAdd(&p.info[tid + 1u], (unsigned long long)tally[tid]);
+    fold_counters<kLive, kMatched, kBelow, kAbove, kNan>(tally, p.info, {live, matched, below, above, nan});      // every lane of the workgroup is here
 }
 
 th_status hist_checks(th_context *c, const th_histogram_uniforms *u, int32_t buffer, const char *entry)
@@ -161,12 +149,6 @@ th_status hist_checks(th_context *c, const th_histogram_uniforms *u, int32_t buf
     return TH_OK;
 }
 
-template <bool PACKED, int MODE>
-void hist_launch(th_context *c, const HistParams &p, uint32_t grid)
-{
-    hipLaunchKernelGGL((hist_tally_kernel<PACKED, MODE>), dim3(grid), dim3(256), (kTallyWords + p.bins) * sizeof(uint32_t), c->stream, p);
-}
-
 // the checks, the scratch, the two kernels: enqueued, nothing more
 th_status hist_enqueue(th_context *c, const th_histogram_uniforms *u, int32_t buffer, const char *entry)
 {
@@ -175,11 +157,7 @@ th_status hist_enqueue(th_context *c, const th_histogram_uniforms *u, int32_t bu
     if (!c->hist_info) if (th_status s = c->hist_info.alloc(kInfoWords)) return s;
     if (!c->hist_counts) if (th_status s = c->hist_counts.alloc(TH_HIST_MAX_BINS)) return s;
     HistParams p{};
-    const float4 *buf = c->ring[(size_t)buffer];
-    const int order = order_of(c, buf);                   // (the slot order stays: slot i holds texel perm[i])
-    p.in = buf;
-    p.perm = order >= 0 ? c->orders[(size_t)order].perm.get() : nullptr;
-    p.count = (uint32_t)c->texels();
+    p.ring = ring_read(c, buffer);
     p.q = select_clauses(c, &u->select);
     p.channel = u->channel; p.bins = u->bins;
     if (u->mode == TH_HIST_LINEAR) {
@@ -191,9 +169,12 @@ th_status hist_enqueue(th_context *c, const th_histogram_uniforms *u, int32_t bu
     }
     p.counts = c->hist_counts; p.info = c->hist_info;
     hipLaunchKernelGGL(hist_clear_kernel, dim3(1), dim3(256), 0, c->stream, p.counts, p.bins, p.info, (unsigned long long)c->texels());
-    const uint32_t nblocks = (p.count + kBlockSlots - 1u) / kBlockSlots, grid = std::min(nblocks, kMaxGroups);
-    if (c->packed) { if (u->mode == TH_HIST_LINEAR) hist_launch<true, TH_HIST_LINEAR>(c, p, grid); else hist_launch<true, TH_HIST_KEY>(c, p, grid); }
-    else { if (u->mode == TH_HIST_LINEAR) hist_launch<false, TH_HIST_LINEAR>(c, p, grid); else hist_launch<false, TH_HIST_KEY>(c, p, grid); }
+    const uint32_t nblocks = (p.ring.count + kBlockSlots - 1u) / kBlockSlots, grid = std::min(nblocks, kMaxGroups);
+    dispatch_packed(c, [&](auto packed) {
+        constexpr bool P = decltype(packed)::value;
+        hipLaunchKernelGGL((u->mode == TH_HIST_LINEAR ? hist_tally_kernel<P, TH_HIST_LINEAR> : hist_tally_kernel<P, TH_HIST_KEY>), dim3(grid), dim3(256),
+                           (kTallyWords + p.bins) * sizeof(uint32_t), c->stream, p);
+    });
     TH_HIP(hipGetLastError());
     return TH_OK;
 }

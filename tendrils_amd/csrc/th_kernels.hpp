@@ -420,6 +420,9 @@ int loopback_init(void **comm, const Transport **transport, const void *id_bytes
 // exclusive scan of n u32 words in place (th_sort.hip: three launches); block_sums: exclusive_scan_sum_words(n) words of scratch
 uint32_t exclusive_scan_sum_words(uint32_t n);
 void launch_exclusive_scan_u32(uint32_t *data, uint32_t *block_sums, uint32_t n, hipStream_t stream);
+// a texel set's `nwords` mask words (th_ctx.hpp: TexelSet) cleared; and ranked - counts[w] = the members before word w: the words' popcounts (counted: the caller has left them) under the scan above
+void launch_texel_set_clear(unsigned long long *mask, uint32_t nwords, hipStream_t stream);
+void launch_texel_set_rank(const unsigned long long *mask, uint32_t *counts, uint32_t *block_sums, uint32_t nwords, bool counted, hipStream_t stream);
 // stable LSD radix sort of (key, u32 value) pairs by key bits [begin_bit, end_bit) (th_sort.hip): the passes ping-pong
 // between the (a) and (b) buffers; returns 0 when the result is in (a), 1 when it is in (b).  n = 0 returns 0 and writes
 // nothing.  end_bit > begin_bit: an empty range is outside the contract (no caller passes one; the plan would sort by one

@@ -9,7 +9,7 @@
 //
 // The caller's kernels leave the partials; the fold does not depend on the caller's source and lives here.  The same fold
 // kernel folds the ranks' result blocks of a row-band job (th_measure_global), in rank order.
-#include "th_ctx.hpp"
+#include "th_ring.hpp"           // RingView, TH_RING_BUFFER_OK: what the passes that read the ring where it lies share
 
 using namespace thi;
 
@@ -130,20 +130,18 @@ th_status measure_enqueue(th_context *c, th_program *prog, const char *entry, co
 {
     if (th_status s = use(c, true)) return s;             // read-only: the last draw's geometry and a fused launch's statistics stay valid
     if (th_status s = program_run_args(prog, kMeasureProgram, entry, uniforms, uniform_bytes)) return s;
-    TH_REQUIRE(buffer >= 0 && (size_t)buffer < c->ring.size(), "%s: buffer %d out of range (the ring has %zu)", entry, buffer, c->ring.size());
+    TH_RING_BUFFER_OK(c, buffer, entry);
     ProgramModule *m = nullptr;
     if (th_status s = program_loaded(c, prog, &m)) return s;
     if (th_status s = measure_storage(c)) return s;
-    const float4 *buf = c->ring[(size_t)buffer];
-    const int order = order_of(c, buf);                   // (the slot order stays: slot i holds texel perm[i])
+    const RingView ring = ring_read(c, buffer);
     KernArgs k{};
     MeasureArgs &a = k.a;
-    a.in = buf;
+    a.in = static_cast<const float4 *>(ring.in); a.perm = ring.perm;
     a.flow = c->flow; a.fw = c->fw; a.fh = c->fh;
-    a.perm = order >= 0 ? c->orders[(size_t)order].perm.get() : nullptr;
     a.part = c->measure_parts;
-    a.count = (uint32_t)c->texels(); a.width = (uint32_t)c->cfg.width; a.rows = (uint32_t)c->cfg.height;
-    a.row0 = (uint32_t)c->cfg.row0; a.global_height = (uint32_t)c->cfg.global_height;
+    a.count = ring.count; a.width = ring.width; a.rows = (uint32_t)c->cfg.height;
+    a.row0 = ring.row0; a.global_height = (uint32_t)c->cfg.global_height;
     k.set_uniforms(uniforms, uniform_bytes);
     const int grid = th::grid_for(c->texels(), 8);
     LaunchTimer timer;

@@ -9,19 +9,20 @@
 //                          predicate, and the particle's bit into the mask word of its TEXEL.  In texel order a wave's 64 slots are
 //                          one word: the wave's __ballot is that word, lane 0 stores it - and its popcount - with plain stores;
 //                          nothing is cleared, nothing atomic.  Over tile-sorted slots the mask is cleared first and every MATCHED
-//                          lane ORs its bit in (an integer atomic); select_count_kernel then takes the words' popcounts.  The live
-//                          particles: per lane, a butterfly per wave, one integer atomic per workgroup.
-//   (scan)                 th_sort.hip's exclusive scan over the words' counts, as it is; select_total_kernel leaves
-//                          matched = offsets[last] + popcount(mask[last]) and written = min(matched, capacity) in the info block
+//                          lane ORs its bit in (an integer atomic).  The live particles: per lane, th_ring.hpp's fold of a
+//                          workgroup's counters - a butterfly per wave, one integer atomic per workgroup.
+//   (rank)                 th_sort.hip's launch_texel_set_rank: the words' popcounts - over tile-sorted slots only - and the
+//                          exclusive scan over them, as it is; select_total_kernel leaves matched = offsets[last] +
+//                          popcount(mask[last]) and written = min(matched, capacity) in the info block
 //   select_gather_kernel   the slots again: a particle's bit is read from the MASK - the predicate is evaluated in one place
-//                          only -, its rank is offsets[word] + popcount(word below its bit), and below `capacity` the slot is
-//                          loaded and two 16-byte stores leave its record.  A slot whose bit is clear is not loaded.
+//                          only -, its rank is th_ring.hpp's texel_rank, and below `capacity` the slot is loaded and two
+//                          16-byte stores leave its record.  A slot whose bit is clear is not loaded.
 // Why the bits are indexed by texel and not by slot: the records come in increasing texel, and there is no inverse of perm to
 // walk a slot-indexed mask in that order; with texel-indexed bits the rank of a particle is a popcount below its own bit,
 // whatever slot holds it.  The price is the second walk over the slots (and, tile-sorted, the atomics).
 // No lane leaves the mark kernel before its wave-wide operations: the loop's bound is the workgroup's, a lane past the last
 // slot carries "no match, not live".  Every index that addresses memory comes from a value compared in range first.
-#include "th_select_match.hpp"   // Slot, SelectClauses, select_match, select_checks: shared with th_histogram.hip
+#include "th_select_match.hpp"   // SelectClauses, select_match, select_checks: shared with th_histogram.hip; th_ring.hpp behind it
 
 using namespace thi;
 
@@ -33,10 +34,8 @@ static_assert(sizeof(th_select_uniforms) == 40 && sizeof(th_selected) == 32 && s
 static_assert(offsetof(th_selected, index) == 16, "th_selected: the state, then index, x, y, reserved");
 
 struct SelectParams {
-    const void *in;                   // the ring buffer: float4 or, packed, uint2 per slot
-    const uint32_t *perm;             // slot -> local texel (tile-sorted slots), or null: texel order
-    uint32_t count, width, row0;      // this context's texels; the texture's width; the band's first row
-    uint32_t nwords;                  // mask words: (count + 63) / 64
+    RingView ring;                    // the buffer where it lies; ring.perm null: texel order
+    uint32_t nwords;                  // mask words: (ring.count + 63) / 64
     SelectClauses q;                  // the predicate's clauses
     uint32_t capacity;                // records the gather may write
     unsigned long long *mask;         // [nwords]: bit t & 63 of word t >> 6 is local texel t
@@ -45,9 +44,7 @@ struct SelectParams {
     th_selected *records;
 };
 
-TH_D uint32_t wave_sum(uint32_t v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
-
-// {0, 0, 0, 0} into the info block and, over tile-sorted slots, zero into the mask
+// {0, 0, 0, 0} into the info block and, over tile-sorted slots, zero into the mask (here, not by launch_texel_set_clear: one launch less)
 __global__ __launch_bounds__(256) void select_clear_kernel(unsigned long long *mask, uint32_t nwords, unsigned long long *info)
 {
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nwords; i += gridDim.x * 256u) mask[i] = 0ull;
@@ -62,18 +59,18 @@ __global__ __launch_bounds__(256) void select_mark_kernel(const SelectParams p)
     uint32_t live_n = 0u;
     // `base` is the workgroup's, a multiple of 256: every lane of the workgroup takes the same turns, a wave covers the 64
     // consecutive slots of ONE mask word
-    for (uint32_t base = blockIdx.x * 256u; base < p.count; base += gridDim.x * 256u) {
+    for (uint32_t base = blockIdx.x * 256u; base < p.ring.count; base += gridDim.x * 256u) {
         const uint32_t idx = base + tid;
         bool live = false, match = false;
         uint32_t t = idx;
-        if (idx < p.count) {
-            const v4f s = Slot<PACKED>::state(Slot<PACKED>::load(p.in, idx));
-            if (p.perm) t = __builtin_nontemporal_load(p.perm + idx);          // (wave-uniform test: the argument segment)
+        if (idx < p.ring.count) {
+            const v4f s = Slot<PACKED>::state(Slot<PACKED>::load(p.ring.in, idx));
+            if (p.ring.perm) t = __builtin_nontemporal_load(p.ring.perm + idx);          // (wave-uniform test: the argument segment)
             live = slot_live(s);
-            match = t < p.count && select_match(p.q, s, live, t);
+            match = t < p.ring.count && select_match(p.q, s, live, t);
         }
         live_n += live ? 1u : 0u;
-        if (!p.perm) {
+        if (!p.ring.perm) {
             const unsigned long long word = __ballot(match);                    // every lane of the wave is here
             const uint32_t w = idx >> 6;
             if ((tid & 63u) == 0u && w < p.nwords) { p.mask[w] = word; p.counts[w] = (uint32_t)__popcll(word); }
@@ -81,18 +78,7 @@ __global__ __launch_bounds__(256) void select_mark_kernel(const SelectParams p)
             atomicOr(&p.mask[t >> 6], 1ull << (t & 63u));                       // t < count: word t >> 6 < nwords
         }
     }
-    live_n = wave_sum(live_n);
-    if ((tid & 63u) == 0u) part[tid >> 6] = live_n;
-    __syncthreads();
-    if (tid == 0u) {
-        const uint32_t n = part[0] + part[1] + part[2] + part[3];
-        if (n) atomicAdd(&p.info[kLive], (unsigned long long)n);
-    }
-}
-
-__global__ __launch_bounds__(256) void select_count_kernel(const unsigned long long *mask, uint32_t *counts, uint32_t nwords)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nwords; i += gridDim.x * 256u) counts[i] = (uint32_t)__popcll(mask[i]);
+    fold_counters<kLive>(part, p.info, {live_n});                          // every lane of the workgroup is here
 }
 
 // behind the scan: counts[] holds the matches before each word
@@ -100,7 +86,7 @@ __global__ void select_total_kernel(const SelectParams p)
 {
     if (blockIdx.x || threadIdx.x) return;
     const unsigned long long matched = (unsigned long long)p.counts[p.nwords - 1u] + (unsigned long long)__popcll(p.mask[p.nwords - 1u]);
-    p.info[kParticles] = p.count;
+    p.info[kParticles] = p.ring.count;
     p.info[kMatched] = matched;
     p.info[kWritten] = matched < p.capacity ? matched : (unsigned long long)p.capacity;
 }
@@ -108,31 +94,19 @@ __global__ void select_total_kernel(const SelectParams p)
 template <bool PACKED>
 __global__ __launch_bounds__(256) void select_gather_kernel(const SelectParams p)
 {
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < p.count; idx += gridDim.x * 256u) {
-        const uint32_t t = p.perm ? __builtin_nontemporal_load(p.perm + idx) : idx;
-        if (t >= p.count) continue;
-        const unsigned long long word = p.mask[t >> 6], bit = 1ull << (t & 63u);
-        if (!(word & bit)) continue;
-        const uint32_t rank = p.counts[t >> 6] + (uint32_t)__popcll(word & (bit - 1ull));
-        if (rank >= p.capacity) continue;
-        const v4f s = Slot<PACKED>::state(Slot<PACKED>::load(p.in, idx));
-        const uint32_t row = t / p.width;
-        const v4u who = {t + p.row0 * p.width, t - row * p.width, row + p.row0, 0u};
+    const TexelSetView set{p.mask, p.counts};
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < p.ring.count; idx += gridDim.x * 256u) {
+        const uint32_t t = p.ring.perm ? __builtin_nontemporal_load(p.ring.perm + idx) : idx;
+        if (t >= p.ring.count) continue;
+        const uint32_t rank = texel_rank(set, t);
+        if (rank >= p.capacity) continue;                 // (kNoRank: its bit is clear)
+        const v4f s = Slot<PACKED>::state(Slot<PACKED>::load(p.ring.in, idx));
+        const uint32_t row = t / p.ring.width;
+        const v4u who = {t + p.ring.row0 * p.ring.width, t - row * p.ring.width, row + p.ring.row0, 0u};
         v4f *rec = reinterpret_cast<v4f *>(p.records + rank);
         rec[0] = s;
         *reinterpret_cast<v4u *>(rec + 1) = who;
     }
-}
-
-// the context's scratch, reserved by its first select (the texture's shape is the context's: only the records ever grow)
-th_status select_storage(th_context *c, uint32_t nwords)
-{
-    if (!c->select_info) if (th_status s = c->select_info.alloc(kInfoWords)) return s;
-    if (c->select_mask.size() < nwords) if (th_status s = c->select_mask.alloc(nwords)) return s;
-    if (c->select_counts.size() < nwords) if (th_status s = c->select_counts.alloc(nwords)) return s;
-    const size_t sums = th::exclusive_scan_sum_words(nwords);
-    if (c->select_sums.size() < sums) if (th_status s = c->select_sums.alloc(sums)) return s;
-    return TH_OK;
 }
 
 // `capacity` records of room; an earlier select's gather may still write the old ones
@@ -143,31 +117,28 @@ th_status select_records(th_context *c, uint32_t capacity)
     return c->select_records.alloc(capacity);
 }
 
-SelectParams select_params(th_context *c, const th_select_uniforms *u, int32_t buffer, uint32_t capacity)
+// the call's parameters, over the context's scratch: reserved by its first select (the texture's shape is the context's: only the records ever grow)
+th_status select_params(th_context *c, const th_select_uniforms *u, int32_t buffer, uint32_t capacity, SelectParams &p)
 {
-    SelectParams p{};
-    const float4 *buf = c->ring[(size_t)buffer];
-    const int order = order_of(c, buf);                   // (the slot order stays: slot i holds texel perm[i])
-    p.in = buf;
-    p.perm = order >= 0 ? c->orders[(size_t)order].perm.get() : nullptr;
-    p.count = (uint32_t)c->texels(); p.width = (uint32_t)c->cfg.width; p.row0 = (uint32_t)c->cfg.row0;
-    p.nwords = (p.count + 63u) / 64u;
+    p = SelectParams{};
+    p.ring = ring_read(c, buffer);
+    p.nwords = (p.ring.count + 63u) / 64u;
+    if (!c->select_info) if (th_status s = c->select_info.alloc(kInfoWords)) return s;
+    if (th_status s = c->select_set.reserve(p.nwords)) return s;
     p.q = select_clauses(c, u);
     p.capacity = capacity;
-    p.mask = c->select_mask; p.counts = c->select_counts; p.info = c->select_info;
+    p.mask = c->select_set.mask; p.counts = c->select_set.counts; p.info = c->select_info;
     p.records = c->select_records;
-    return p;
+    return TH_OK;
 }
 
-// mark, count, scan, total: enqueued, nothing more.  The info block is complete behind them (written = min(matched, capacity))
+// clear, mark, rank, total: enqueued, nothing more.  The info block is complete behind them (written = min(matched, capacity))
 th_status select_scan(th_context *c, const SelectParams &p)
 {
-    const int grid = th::grid_for(p.count, 8);
-    hipLaunchKernelGGL(select_clear_kernel, dim3(th::grid_for(p.perm ? p.nwords : 1u, 8)), dim3(256), 0, c->stream, p.mask, p.perm ? p.nwords : 0u, p.info);
-    if (c->packed) hipLaunchKernelGGL(select_mark_kernel<true>, dim3(grid), dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL(select_mark_kernel<false>, dim3(grid), dim3(256), 0, c->stream, p);
-    if (p.perm) hipLaunchKernelGGL(select_count_kernel, dim3(th::grid_for(p.nwords, 8)), dim3(256), 0, c->stream, p.mask, p.counts, p.nwords);
-    th::launch_exclusive_scan_u32(p.counts, c->select_sums, p.nwords, c->stream);
+    const int grid = th::grid_for(p.ring.count, 8);
+    hipLaunchKernelGGL(select_clear_kernel, dim3(th::grid_for(p.ring.perm ? p.nwords : 1u, 8)), dim3(256), 0, c->stream, p.mask, p.ring.perm ? p.nwords : 0u, p.info);
+    dispatch_packed(c, [&](auto packed) { hipLaunchKernelGGL(select_mark_kernel<decltype(packed)::value>, dim3(grid), dim3(256), 0, c->stream, p); });
+    th::launch_texel_set_rank(p.mask, p.counts, c->select_set.sums, p.nwords, !p.ring.perm, c->stream);      // (texel order: the mark kernel left the popcounts)
     hipLaunchKernelGGL(select_total_kernel, dim3(1), dim3(64), 0, c->stream, p);
     TH_HIP(hipGetLastError());
     return TH_OK;
@@ -175,9 +146,7 @@ th_status select_scan(th_context *c, const SelectParams &p)
 
 th_status select_gather(th_context *c, const SelectParams &p)
 {
-    const int grid = th::grid_for(p.count, 8);
-    if (c->packed) hipLaunchKernelGGL(select_gather_kernel<true>, dim3(grid), dim3(256), 0, c->stream, p);
-    else hipLaunchKernelGGL(select_gather_kernel<false>, dim3(grid), dim3(256), 0, c->stream, p);
+    dispatch_packed(c, [&](auto packed) { hipLaunchKernelGGL(select_gather_kernel<decltype(packed)::value>, dim3(th::grid_for(p.ring.count, 8)), dim3(256), 0, c->stream, p); });
     TH_HIP(hipGetLastError());
     return TH_OK;
 }
@@ -191,9 +160,9 @@ th_status th_select_async(th_context *c, const th_select_uniforms *u, int32_t bu
     if (th_status s = select_checks(c, u, buffer, "th_select_async")) return s;
     if (th_status s = use(c, true)) return s;             // read-only: the last draw's geometry and a fused launch's statistics stay valid
     const uint32_t room = (uint32_t)std::min<uint64_t>(capacity, c->texels());
-    if (th_status s = select_storage(c, (uint32_t)((c->texels() + 63) / 64))) return s;
     if (th_status s = select_records(c, room)) return s;
-    const SelectParams p = select_params(c, u, buffer, room);
+    SelectParams p;
+    if (th_status s = select_params(c, u, buffer, room, p)) return s;
     if (th_status s = select_scan(c, p)) return s;
     if (room) if (th_status s = select_gather(c, p)) return s;
     if (device_records) *device_records = room ? c->select_records.get() : nullptr;
@@ -207,8 +176,8 @@ th_status th_select(th_context *c, const th_select_uniforms *u, int32_t buffer, 
     TH_REQUIRE(info, "th_select: null info");
     if (th_status s = use(c, true)) return s;
     const uint32_t room = out ? (uint32_t)std::min<uint64_t>(capacity, c->texels()) : 0u;
-    if (th_status s = select_storage(c, (uint32_t)((c->texels() + 63) / 64))) return s;
-    SelectParams p = select_params(c, u, buffer, room);
+    SelectParams p;
+    if (th_status s = select_params(c, u, buffer, room, p)) return s;
     if (th_status s = select_scan(c, p)) return s;
     if (th_status s = read_back(c, info, c->select_info.get(), sizeof *info)) return s;      // the one wait: how many records there are
     const uint32_t written = (uint32_t)info->written;

@@ -1,15 +1,10 @@
-// th_select_match.hpp - what the built-in passes that ask WHICH particles share (th_select.hip, th_histogram.hip): a slot of the
-// ring as it lies in memory and the state it holds, the clauses of th_select_uniforms as a kernel carries them, the one
-// predicate both units evaluate, and the checks of the block on the host.  The header's words (include/tendrils_hip.h "select").
+// th_select_match.hpp - the predicate of the built-in passes that ask WHICH particles (th_select.hip, th_histogram.hip): the
+// clauses of th_select_uniforms as a kernel carries them, the one predicate both units evaluate, and the checks of the block on
+// the host.  The header's words (include/tendrils_hip.h "select").  The slot it is evaluated on is th_ring.hpp's.
 #pragma once
-#include "th_ctx.hpp"
-#include "th_logic.hpp"          // th::unpack_state (th_packed.inc)
+#include "th_ring.hpp"
 
 namespace thi {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kSelectFlags = TH_SELECT_BOX | TH_SELECT_SPEED | TH_SELECT_INERT;
 
@@ -19,21 +14,6 @@ struct SelectClauses {
     uint32_t stride, phase, flags;
     uint32_t width, row0;             // the texture's width; the band's first row
 };
-
-// a slot as it lies in memory - 16 bytes, or the 8 of a packed ring - and the state it holds
-template <bool PACKED> struct Slot;
-template <> struct Slot<false> {
-    using Raw = v4f;
-    TH_D static Raw load(const void *in, uint32_t idx) { return __builtin_nontemporal_load(static_cast<const Raw *>(in) + idx); }
-    TH_D static v4f state(Raw t) { return t; }
-};
-template <> struct Slot<true> {
-    using Raw = v2u;
-    TH_D static Raw load(const void *in, uint32_t idx) { return __builtin_nontemporal_load(static_cast<const Raw *>(in) + idx); }
-    TH_D static v4f state(Raw t) { const float4 s = th::unpack_state(make_uint2(t.x, t.y)); return v4f{s.x, s.y, s.z, s.w}; }
-};
-
-TH_D bool slot_live(v4f s) { return !(s.x == th::kInert && s.y == th::kInert); }
 
 // the clauses of the header, in its words: local texel t of a live-or-admitted particle with state s
 TH_D bool select_match(const SelectClauses &p, v4f s, bool live, uint32_t t)
@@ -63,14 +43,14 @@ inline th_status select_checks(th_context *c, const th_select_uniforms *u, int32
 {
     TH_REQUIRE(c, "%s: null context", entry);
     TH_REQUIRE(u, "%s: null uniforms", entry);
-    TH_REQUIRE(buffer >= 0 && (size_t)buffer < c->ring.size(), "%s: buffer %d out of range (the ring has %zu)", entry, buffer, c->ring.size());
+    TH_RING_BUFFER_OK(c, buffer, entry);
     TH_REQUIRE(u->stride >= 1u && u->phase < u->stride, "%s: stride %u, phase %u (stride >= 1, phase < stride)", entry, u->stride, u->phase);
     TH_REQUIRE(!(u->flags & ~kSelectFlags), "%s: flags 0x%x (TH_SELECT_BOX | _SPEED | _INERT)", entry, u->flags);
     TH_REQUIRE(u->reserved == 0u, "%s: reserved is %u, not 0", entry, u->reserved);
     if (u->flags & TH_SELECT_BOX)
         TH_REQUIRE(!(std::isnan(u->box[0]) || std::isnan(u->box[1]) || std::isnan(u->box[2]) || std::isnan(u->box[3])), "%s: a NaN in the box", entry);
     if (u->flags & TH_SELECT_SPEED) TH_REQUIRE(!(std::isnan(u->speed2[0]) || std::isnan(u->speed2[1])), "%s: a NaN in speed2", entry);
-    TH_REQUIRE(c->texels() > 0 && c->texels() <= (1ull << 28), "%s: %zu particles", entry, c->texels());
+    TH_RING_TEXELS_OK(c, entry);
     return TH_OK;
 }
 

@@ -190,6 +190,12 @@ __global__ __launch_bounds__(256) void sort_scan_add_kernel(uint32_t *data, cons
     for (int k = 0; k < 4; ++k) if (base + k < n) data[base + k] += add;
 }
 
+// ---- a set of texels, a bit per texel (th_ctx.hpp: TexelSet): its words' popcounts for the scan above ----
+__global__ __launch_bounds__(256) void texel_set_count_kernel(const unsigned long long *mask, uint32_t *counts, uint32_t nwords)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nwords; i += gridDim.x * 256u) counts[i] = (uint32_t)__popcll(mask[i]);
+}
+
 RadixPlan make_plan(int begin_bit, int end_bit)
 {
     RadixPlan p{};
@@ -219,6 +225,13 @@ void launch_exclusive_scan_u32(uint32_t *data, uint32_t *block_sums, uint32_t n,
     hipLaunchKernelGGL(sort_scan_local_kernel, dim3(blocks), dim3(256), 0, s, data, block_sums, n);
     hipLaunchKernelGGL(sort_scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, blocks);
     hipLaunchKernelGGL(sort_scan_add_kernel, dim3(blocks), dim3(256), 0, s, data, block_sums, n);
+}
+
+void launch_texel_set_clear(unsigned long long *mask, uint32_t nwords, hipStream_t s) { (void)hipMemsetAsync(mask, 0, (size_t)nwords * sizeof *mask, s); }
+void launch_texel_set_rank(const unsigned long long *mask, uint32_t *counts, uint32_t *block_sums, uint32_t nwords, bool counted, hipStream_t s)
+{
+    if (!counted) hipLaunchKernelGGL(texel_set_count_kernel, dim3(grid_for(nwords, 8)), dim3(256), 0, s, mask, counts, nwords);
+    launch_exclusive_scan_u32(counts, block_sums, nwords, s);
 }
 
 size_t radix_sort_temp_bytes(uint32_t n, int begin_bit, int end_bit)

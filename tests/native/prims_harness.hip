@@ -1,5 +1,5 @@
-// prims_harness.hip - test-only C entry points around the primitives every pipeline shares: the flat exclusive scan and the
-// radix sort of th_sort.hip, and block_scan (th_math.hpp).  This file holds no copy of them: it is linked against the object
+// prims_harness.hip - test-only C entry points around the primitives every pipeline shares: the flat exclusive scan, the rank
+// of a texel set and the radix sort of th_sort.hip, and block_scan (th_math.hpp).  This file holds no copy of them: it is linked against the object
 // the product library is linked from (tendrils_amd/lib/obj/th_sort.o), so the device code under test is the bytes that ship;
 // block_scan is a header template and is instantiated here at the product's (N, T) pairs.
 //
@@ -215,6 +215,29 @@ int thp_exclusive_scan_u32(uint32_t *data_inout, uint32_t n)
     th::launch_exclusive_scan_u32(reinterpret_cast<uint32_t *>(data.p), reinterpret_cast<uint32_t *>(sums.p), n, job.stream);
     THP_TRY(job.download(data_inout, data, data.bytes));
     THP_TRY(job.finish());
+    return job.guards();
+}
+
+// the members of a texel set before each of its nwords >= 1 mask words (launch_texel_set_rank), and how many there are: the last
+// word's count before and after.  counts_in: what a caller's kernel has left in the counts buffer (counted = true: the launcher
+// must scan THESE, whatever the mask says), or NULL: the buffer holds the fill pattern and the launcher counts the mask's bits.
+int thp_texel_set_rank(const unsigned long long *mask_in, uint32_t nwords, const uint32_t *counts_in, uint32_t *counts_out, unsigned long long *total_out)
+{
+    if (!mask_in || !counts_out || !total_out || nwords == 0) return fail(kArgument, "null array or no words");
+    const bool counted = counts_in != nullptr;
+    Job job;
+    THP_TRY(job.start());
+    Guarded mask, counts, sums;
+    THP_TRY(job.alloc(mask, "mask", (size_t)nwords * sizeof(unsigned long long), false));
+    THP_TRY(job.alloc(counts, "counts", (size_t)nwords * sizeof(uint32_t), !counted));
+    THP_TRY(job.alloc(sums, "block_sums", (size_t)th::exclusive_scan_sum_words(nwords) * sizeof(uint32_t), true));
+    THP_TRY(job.upload(mask, mask_in, mask.bytes));
+    if (counted) THP_TRY(job.upload(counts, counts_in, counts.bytes));
+    th::launch_texel_set_rank(reinterpret_cast<const unsigned long long *>(mask.p), reinterpret_cast<uint32_t *>(counts.p),
+                              reinterpret_cast<uint32_t *>(sums.p), nwords, counted, job.stream);
+    THP_TRY(job.download(counts_out, counts, counts.bytes));
+    THP_TRY(job.finish());
+    *total_out = (unsigned long long)counts_out[nwords - 1u] + (counted ? counts_in[nwords - 1u] : (uint32_t)__builtin_popcountll(mask_in[nwords - 1u]));
     return job.guards();
 }
 

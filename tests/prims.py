@@ -1,4 +1,4 @@
-"""The test-only harness around the shared primitives (tests/native/: exclusive scan, radix sort, block_scan - linked
+"""The test-only harness around the shared primitives (tests/native/: exclusive scan, texel-set rank, radix sort, block_scan - linked
 against the object the product library ships) as numpy-in / numpy-out functions, and the plain numpy references the GPU
 tests compare with: tests/test_gpu_prims.py, tests/test_gpu_statistics.py; the references themselves are pinned on
 hand-made inputs by tests/test_prims_build.py."""
@@ -14,13 +14,14 @@ NATIVE = os.path.join(ROOT, "tests", "native")
 LIB_PATH = os.environ.get("TH_PRIMS_LIB") or os.path.join(NATIVE, "_build", "libth_prims.so")   # TH_PRIMS_LIB: diagnostic builds
 SORT_OBJECT = os.path.join(ROOT, "tendrils_amd", "lib", "obj", "th_sort.o")
 ENTRY_POINTS = ["thp_block_scan", "thp_exclusive_scan_u32", "thp_last_error", "thp_radix_sort_empty", "thp_radix_sort_u32",
-                "thp_radix_sort_u64"]
+                "thp_radix_sort_u64", "thp_texel_set_rank"]
 RADIX_BITS = 8          # th_kernels.hpp: kRadixBits
 
 _u32p, _u64p, _i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int)
 _PROTOTYPES = {
     "thp_last_error": (C.c_char_p, []),
     "thp_exclusive_scan_u32": (C.c_int, [_u32p, C.c_uint32]),
+    "thp_texel_set_rank": (C.c_int, [_u64p, C.c_uint32, _u32p, _u32p, _u64p]),
     "thp_radix_sort_u32": (C.c_int, [_u32p, _u32p, C.c_uint32, C.c_int, C.c_int, _u32p, _u32p, _i32p]),
     "thp_radix_sort_u64": (C.c_int, [_u64p, _u32p, C.c_uint32, C.c_int, C.c_int, _u64p, _u32p, _i32p]),
     "thp_radix_sort_empty": (C.c_int, [C.c_int, C.c_uint32, C.c_int, C.c_int, _i32p]),
@@ -74,6 +75,18 @@ def exclusive_scan_u32(data):
     return out
 
 
+def texel_set_rank(mask, counts=None):
+    """mask: uint64 words, bit t & 63 of word t >> 6 is texel t; counts: what a caller's kernel left as the words' counts - the
+    launcher only scans them - or None: it counts the mask's bits.  -> (the members before each word, the members)"""
+    mask = np.ascontiguousarray(mask, np.uint64)
+    given = None if counts is None else np.ascontiguousarray(counts, np.uint32)
+    assert given is None or given.shape == mask.shape
+    out, total = np.empty(mask.size, np.uint32), C.c_uint64(0)
+    _call("thp_texel_set_rank", mask.ctypes.data_as(_u64p), mask.size, None if given is None else given.ctypes.data_as(_u32p),
+          out.ctypes.data_as(_u32p), C.byref(total))
+    return out, total.value
+
+
 def radix_sort(keys, vals, begin_bit, end_bit):
     """keys: uint32 or uint64 array; vals: uint32 array or None (iota).  -> (keys_out, vals_out, in_b)"""
     keys = np.ascontiguousarray(keys)
@@ -113,6 +126,12 @@ def scan_reference(data):
     out = np.zeros(running.size, np.uint64)
     out[1:] = running[:-1]
     return (out & np.uint64(0xffffffff)).astype(np.uint32)
+
+
+def texel_set_reference(mask):
+    """the members before each word - the exclusive scan of the words' popcounts - and the members"""
+    bits = np.unpackbits(np.ascontiguousarray(mask, np.uint64).view(np.uint8)).reshape(-1, 64)
+    return scan_reference(bits.sum(axis=1)), int(bits.sum())
 
 
 def block_scan_reference(values):

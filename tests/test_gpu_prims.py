@@ -1,5 +1,5 @@
-"""The primitives every pipeline shares - launch_exclusive_scan_u32, launch_radix_sort_u32 / _u64 (th_sort.hip) and
-block_scan (th_math.hpp) - against plain numpy, exactly, at the sizes where their regimes change.  They run through the
+"""The primitives every pipeline shares - launch_exclusive_scan_u32, launch_texel_set_rank, launch_radix_sort_u32 / _u64
+(th_sort.hip) and block_scan (th_math.hpp) - against plain numpy, exactly, at the sizes where their regimes change.  They run through the
 test-only harness of tests/native/, which is linked against the shipped object (tests/prims.py); every device
 buffer has guard words behind its stated size and a changed guard fails the call.
 
@@ -62,6 +62,44 @@ def test_exclusive_scan_equals_the_running_sum(n, kind):
     got = prims.exclusive_scan_u32(data)
     diff = first_difference(got, prims.scan_reference(data), [("block of 1024", 1024), ("run of 1024 blocks", 1024 * 1024)])
     assert not diff, "scan of %d words (%s): %s" % (n, kind, diff)
+
+
+# ---- the rank of a texel set ----------------------------------------------------------------------------------------------
+# either side of the scan's 1024-word block; the texel count is no multiple of 64: the last word holds 36 texels, the bits past
+# them are clear and must stay uncounted
+def texel_set_mask(kind, nwords):
+    texels = 64 * (nwords - 1) + 36
+    bits = np.zeros(64 * nwords, np.uint8)
+    if kind == "full":
+        bits[:texels] = 1
+    elif kind == "random":
+        bits[:texels] = np.random.default_rng(seed_of("texel set", nwords)).random(texels) < 0.3
+    elif kind == "last":                 # only the last valid bit
+        bits[texels - 1] = 1
+    elif kind != "empty":
+        raise KeyError(kind)
+    return np.packbits(bits.reshape(-1, 64), axis=1, bitorder="little").view(np.uint64).reshape(-1), texels
+
+
+@pytest.mark.parametrize("counted", [False, True], ids=["counts", "counted"])
+@pytest.mark.parametrize("kind", ["empty", "full", "random", "last"])
+@pytest.mark.parametrize("nwords", [1, 2, 1023, 1024, 1025])
+def test_texel_set_rank_is_the_scan_of_the_popcounts(nwords, kind, counted):
+    mask, texels = texel_set_mask(kind, nwords)
+    assert mask.shape == (nwords,) and int(mask[-1]) >> 36 == 0
+    want, members = prims.texel_set_reference(mask)
+    assert members == dict(empty=0, full=texels, last=1).get(kind, members)
+    given = None
+    if counted:
+        # counts that are NOT the mask's popcounts (each one more, the first 7 more): a launcher that counted all the same would
+        # scan the popcounts and differ in every word behind the first
+        given = (np.unpackbits(mask.view(np.uint8)).reshape(-1, 64).sum(axis=1) + 1).astype(np.uint32)
+        given[0] += 6
+        want, members = prims.scan_reference(given), int(given.sum())
+    got, total = prims.texel_set_rank(mask, given)
+    diff = first_difference(got, want, [("block of 1024", 1024)])
+    assert not diff, "rank of %d words (%s, %s): %s" % (nwords, kind, "counted" if counted else "to count", diff)
+    assert total == members
 
 
 # ---- radix sort -----------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ def test_harness_holds_the_shipped_sort_object(harness):
     """the launchers are defined inside the harness library (linked from lib/obj/th_sort.o: tests/native/Makefile names no
     other source of them), and the harness source holds no kernel of the sort or the scan"""
     defined = nm(harness, "--defined-only")
-    for launcher in ("th::launch_exclusive_scan_u32(", "th::launch_radix_sort_u32(", "th::launch_radix_sort_u64(",
+    for launcher in ("th::launch_exclusive_scan_u32(", "th::launch_texel_set_rank(", "th::launch_radix_sort_u32(", "th::launch_radix_sort_u64(",
                      "th::exclusive_scan_sum_words(", "th::radix_sort_temp_bytes("):
         assert re.search(r"^[0-9a-f]+ [Tt] %s" % re.escape(launcher), defined, flags=re.M), launcher
     in_object = nm(prims.SORT_OBJECT, "--defined-only")
@@ -45,7 +45,7 @@ def test_harness_holds_the_shipped_sort_object(harness):
     makefile = open(os.path.join(prims.NATIVE, "Makefile")).read()
     assert "lib/obj/th_sort.o" in makefile and "th_sort.hip" not in re.sub(r"#.*", "", makefile)
     source = open(os.path.join(prims.NATIVE, "prims_harness.hip")).read()
-    assert "sort_scan_" not in source and "radix_scatter" not in source and "radix_hist" not in source
+    assert "sort_scan_" not in source and "radix_scatter" not in source and "radix_hist" not in source and "texel_set_c" not in source
 
 
 def test_no_product_library_exports_a_harness_symbol(harness):
@@ -61,6 +61,16 @@ def test_scan_reference_by_hand():
     assert prims.scan_reference([0xfffffffe, 3, 5, 0xffffffff, 1]).tolist() == [0, 0xfffffffe, 1, 6, 5]
     out = prims.scan_reference([0xfffffffe, 3])
     assert out.dtype == np.uint32
+
+
+def test_texel_set_reference_by_hand():
+    # texels 0, 3 and 63 | none | texel 128 + 36 = 164 alone: 3, 0, 1 members, so 0, 3, 3 before the words
+    before, members = prims.texel_set_reference(np.array([(1 << 63) | 0b1001, 0, 1 << 36], np.uint64))
+    assert before.tolist() == [0, 3, 3] and before.dtype == np.uint32 and members == 4
+    before, members = prims.texel_set_reference(np.array([0xffffffffffffffff, 0xfffffffff], np.uint64))      # 100 texels, all members
+    assert before.tolist() == [0, 64] and members == 100
+    before, members = prims.texel_set_reference(np.zeros(1, np.uint64))
+    assert before.tolist() == [0] and members == 0
 
 
 def test_block_scan_reference_by_hand():
